@@ -22,7 +22,16 @@ At N = 1 both defaults are the same workload (100M rows on the one GPU = BASELIN
 carries `exchange_overhead`: one rank's share of configs[3] (12.5M rows) run unsharded and through the multi-GPU
 path on a 1-rank RCCL group -- the us per step the two exchanges + fold kernels add (--no-exchange-leg skips it).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run does only what the headline needs: set-up (inputs, the state's placement probe), warm-up, the timed steps, the
+outputs if --dump-outputs DIR is given, and the line.  Everything else below (the per-kernel second pass, the legs, the CPU
+baseline, the N > 1 weak sub-record) runs with --full only.
+
+  --dump-outputs DIR  after the timed steps, write what a caller of the timed path holds after its last step -- the
+                      preconditioned gradient and the updated U, V, d -- as DIR/{precond_grad,U,V,d}.npy (float32), on a fixed,
+                      seeded sample of rank 0's rows (at most 64 MB in all; all rows when they fit).  The inputs are seeded, so
+                      the same arguments give the same inputs on every run and two builds can be compared output for output.
+
+Rank 0 prints ONE JSON line.  With --full, besides the contract fields it carries
   roofline     -- the dominant kernel (update sweep 2), timed live with HIP events on the launch stream
                   (psgd_prof_*) in a SECOND pass (the headline pass runs with the hooks off); algorithmic bytes
                   per launch / average duration vs 8 TB/s.  `paths` holds the whole fused step and, at N = 1,
@@ -49,6 +58,9 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 TINY = 1.1754943508222875e-38  # psgd.py:22
 STEP = 0.01                    # psgd.py:664 (lr_preconditioner default)
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+DUMP_ROWS = 1 << 16            # ... and at most this many sampled rows
+DUMP_SEED = 0
 
 
 def make_inputs(n_local, n_global, r, dev, seed, arena=None):
@@ -673,6 +685,8 @@ def compact_line(res, limit=7800):
     line = _strip(res)
     for k in ("value", "ms_per_step"):           # the contract's own numbers: untouched
         line[k] = res[k]
+    if "roofline" not in line:                   # a plain run (no --full): the headline only
+        return line
     rf = line["roofline"]
     paths = rf.get("paths", {})
     hoist = {}
@@ -725,6 +739,25 @@ def compact_line(res, limit=7800):
     return line
 
 
+def sample_outputs(out, U, V, d):
+    """--dump-outputs: what a caller of the timed path holds after its last step (the preconditioned gradient, and U, V, d updated
+    in place) on a fixed, seeded sample of the rows, as float32 arrays of at most DUMP_BYTES in all."""
+    import numpy as np
+    n, r = U.shape
+    k = min(n, DUMP_ROWS, DUMP_BYTES // (4 * (2 * r + 2)))
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    idx = torch.from_numpy(rows).to(U.device)
+    return {name: t.index_select(0, idx).float().cpu().numpy()
+            for name, t in (("precond_grad", out), ("U", U), ("V", V), ("d", d))}
+
+
+def write_outputs(arrays, out_dir):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` from a plain shell: start the N ranks as a child torch.distributed.run job.  This
     parent never initialises a GPU (device_count() does not), so nothing that holds the device is ever replaced."""
@@ -754,9 +787,10 @@ def launch_ranks(args):
 
 
 def run_uvd(args, psgd, sharded, lib, dev, rank, world, use_dist, n_local, n_global, steps, warmup, keep_state=False,
-            placement_mode=None):
+            placement_mode=None, dump=False):
     """Warm-up + timed steps of the UVd update+apply on this rank's rows: `steps` steps between barrier + synchronize
-    (MAX over ranks), then a second pass of the same steps with the per-kernel HIP event hooks on."""
+    (MAX over ranks), then (--full) a second pass of the same steps with the per-kernel HIP event hooks on.  dump: sample the
+    last timed step's results (sample_outputs) before anything else touches the state."""
     import torch.distributed as dist
     r = args.rank_r
     # the state's owner places it (psgd_tf_amd/placement.py): one allocation for U, V, d, the workspace and the output, the layout
@@ -803,19 +837,22 @@ def run_uvd(args, psgd, sharded, lib, dev, rank, world, use_dist, n_local, n_glo
     fence()
     elapsed = time.perf_counter() - t0
     assert torch.isfinite(out).all().item(), "non-finite preconditioned gradient"
-    # ---- second pass: the same steps with a HIP event pair around every sweep launch (per-kernel durations)
-    lib.psgd_prof_enable(1)
-    for i in range(steps):
-        step(i)
-    fence()
-    slot_ms = prof_collect(lib)
-    lib.psgd_prof_enable(0)
+    dumped = sample_outputs(out, U, V, d) if dump else None
+    slot_ms = None
+    if args.full:
+        # ---- second pass: the same steps with a HIP event pair around every sweep launch (per-kernel durations)
+        lib.psgd_prof_enable(1)
+        for i in range(steps):
+            step(i)
+        fence()
+        slot_ms = prof_collect(lib)
+        lib.psgd_prof_enable(0)
     if use_dist:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     rec = {"elapsed": elapsed, "slot_ms": slot_ms, "n_local": n_local, "n_global": n_global,
-           "ms_per_step": elapsed / steps * 1e3, "value": n_global * steps / elapsed}
+           "ms_per_step": elapsed / steps * 1e3, "value": n_global * steps / elapsed, "outputs": dumped}
     if arena is not None:
         inf = arena.info
         rec["placement"] = {"mode": mode, "layout": inf.get("layout"), "held_gib": arena.bytes_held / 2**30,
@@ -913,6 +950,13 @@ def main():
                          "background), before the warm-up steps; untimed set-up")
     ap.add_argument("--force-sharded", action="store_true",
                     help="use the multi-GPU code path (process group + exchanges) even at world size 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the per-kernel second pass and `roofline`, the legs (apply / "
+                         "update alone, config 2, Kron, sparse LU, ranks 33..64, exchange_overhead), the CPU baseline and the N > 1 "
+                         "weak sub-record; the --no-* flags above skip single legs of it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's preconditioned gradient and updated U, V, d (rank 0, a fixed "
+                         "seeded sample of rows, <= 64 MB) to DIR/<name>.npy as float32")
     args = ap.parse_args()
     if args.rows is not None and args.global_rows is not None:
         raise SystemExit("--rows (weak) and --global-rows (strong) are exclusive")
@@ -959,15 +1003,18 @@ def main():
         n_global = args.global_rows if args.global_rows is not None else 100_000_000
         lo, hi = sharded.shard_rows(n_global, rank, world)
         scaling, n_local = ("strong" if world > 1 or args.global_rows is not None else "weak"), hi - lo
-        if args.global_rows is None and world > 1 and not args.no_weak_leg:
+        if args.global_rows is None and world > 1 and not args.no_weak_leg and args.full:
             weak_leg_rows = 100_000_000
     if n_local < 1:
         raise SystemExit("rank %d would hold no rows (global %d over %d ranks)" % (rank, n_global, world))
 
     main_rec = run_uvd(args, psgd, sharded, lib, dev, rank, world, use_dist, n_local, n_global, args.steps, args.warmup,
-                       keep_state=(world == 1 and not args.no_legs))
+                       keep_state=(world == 1 and args.full and not args.no_legs), dump=(rank == 0 and args.dump_outputs is not None))
     state = main_rec.pop("state", None)
     arena_keep = main_rec.pop("arena", None)      # (the legs below run on the same placed state)
+    outputs = main_rec.pop("outputs")
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
     weak_rec = None
     if weak_leg_rows:
         torch.cuda.empty_cache()
@@ -975,30 +1022,7 @@ def main():
                            args.steps, args.warmup)
 
     if rank == 0:
-        slot_ms, ms_per_step, value = main_rec["slot_ms"], main_rec["ms_per_step"], main_rec["value"]
-        kbytes = uvd_bytes(r, not args.unfused)
-        kern = {k: {"avg_ms": slot_ms[k], "achieved_GBs": kbytes[k] * n_local / (slot_ms[k] * 1e-3) / 1e9}
-                for k in kbytes if slot_ms[k]}
-        dom = "update_s2"
-        traffic, traffic_source = None, None
-        tp = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tp):
-            try:
-                rec = json.load(open(tp)).get("k_update_s2")
-                if rec and rec.get("rows") == n_local and rec.get("r") == r:
-                    traffic = rec["hbm_bytes_per_launch"]
-                    traffic_source = "profiles/pmc_traffic.json (rocprofv3 --pmc passes on an earlier box, NOT counters of this run)"
-            except Exception:
-                traffic = None
-        ach = kern[dom]["achieved_GBs"]
-        alg_step = 4 * (9 * r + 15)
-        moved_step = (4 * (5 * r + 10) + 4 * (3 * r + 8)) if args.unfused else \
-            (4 * (2 * r + 3) + 4 * (3 * r + 5) + 4 * (2 * r + 5))
-        gbs = lambda b: b * n_local / (ms_per_step * 1e-3) / 1e9
-        paths = {"fused": not args.unfused,
-                 "step": {"alg_bytes_per_param": alg_step, "moved_bytes_per_param": moved_step, "wall_ms": ms_per_step,
-                          "frac": gbs(alg_step) / HBM_PEAK_GBS, "frac_moved": gbs(moved_step) / HBM_PEAK_GBS,
-                          "kernel_ms": sum(slot_ms[k] or 0.0 for k in slot_ms)}}
+        ms_per_step, value = main_rec["ms_per_step"], main_rec["value"]
         if scaling == "strong":
             what = "N=%d rows global over %d GPU(s), contiguous blocks (%d on rank 0)" % (n_global, world, n_local)
         else:
@@ -1021,23 +1045,48 @@ def main():
                        "rccl_version": (".".join(str(x) for x in torch.cuda.nccl.version()) if (use_dist and backend == "nccl") else None),
                        "step": STEP, "branches": "balance=0, update_U alternating",
                        "placement": main_rec.get("placement")},
-            "roofline": {"bound": "hbm", "kernel": "k_update_s2 (update sweep 2, dominant kernel)",
-                         "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "alg_bytes_per_launch": kbytes[dom] * n_local,
-                         "avg_launch_ms": slot_ms[dom], "kernels": kern, "paths": paths,
-                         "timing": "headline pass without profiling hooks; kernel durations from a second pass of the "
-                                   "same steps with HIP event pairs on the launch stream"},
         }
-        if weak_rec is not None:
-            wk = weak_rec["slot_ms"]
-            res["weak"] = {"scaling": "weak", "value": weak_rec["value"], "unit": "params/s",
-                           "ms_per_step": weak_rec["ms_per_step"], "rows_per_gpu": weak_rec["n_local"],
-                           "rows_global": weak_rec["n_global"], "steps": args.steps, "warmup": args.warmup,
-                           "frac_of_hbm_roofline_per_gpu": alg_step * weak_rec["n_local"] /
-                           (weak_rec["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                           "kernels_ms": {k: wk[k] for k in kbytes if wk[k]}}
-        if world == 1:
+        if args.full:
+            slot_ms = main_rec["slot_ms"]
+            kbytes = uvd_bytes(r, not args.unfused)
+            kern = {k: {"avg_ms": slot_ms[k], "achieved_GBs": kbytes[k] * n_local / (slot_ms[k] * 1e-3) / 1e9}
+                    for k in kbytes if slot_ms[k]}
+            dom = "update_s2"
+            traffic, traffic_source = None, None
+            tp = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tp):
+                try:
+                    rec = json.load(open(tp)).get("k_update_s2")
+                    if rec and rec.get("rows") == n_local and rec.get("r") == r:
+                        traffic = rec["hbm_bytes_per_launch"]
+                        traffic_source = "profiles/pmc_traffic.json (rocprofv3 --pmc passes on an earlier box, NOT counters of this run)"
+                except Exception:
+                    traffic = None
+            ach = kern[dom]["achieved_GBs"]
+            alg_step = 4 * (9 * r + 15)
+            moved_step = (4 * (5 * r + 10) + 4 * (3 * r + 8)) if args.unfused else \
+                (4 * (2 * r + 3) + 4 * (3 * r + 5) + 4 * (2 * r + 5))
+            gbs = lambda b: b * n_local / (ms_per_step * 1e-3) / 1e9
+            paths = {"fused": not args.unfused,
+                     "step": {"alg_bytes_per_param": alg_step, "moved_bytes_per_param": moved_step, "wall_ms": ms_per_step,
+                              "frac": gbs(alg_step) / HBM_PEAK_GBS, "frac_moved": gbs(moved_step) / HBM_PEAK_GBS,
+                              "kernel_ms": sum(slot_ms[k] or 0.0 for k in slot_ms)}}
+            res["roofline"] = {"bound": "hbm", "kernel": "k_update_s2 (update sweep 2, dominant kernel)",
+                               "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                               "traffic": traffic, "traffic_source": traffic_source,
+                               "alg_bytes_per_launch": kbytes[dom] * n_local,
+                               "avg_launch_ms": slot_ms[dom], "kernels": kern, "paths": paths,
+                               "timing": "headline pass without profiling hooks; kernel durations from a second pass of the "
+                                         "same steps with HIP event pairs on the launch stream"}
+            if weak_rec is not None:
+                wk = weak_rec["slot_ms"]
+                res["weak"] = {"scaling": "weak", "value": weak_rec["value"], "unit": "params/s",
+                               "ms_per_step": weak_rec["ms_per_step"], "rows_per_gpu": weak_rec["n_local"],
+                               "rows_global": weak_rec["n_global"], "steps": args.steps, "warmup": args.warmup,
+                               "frac_of_hbm_roofline_per_gpu": alg_step * weak_rec["n_local"] /
+                               (weak_rec["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               "kernels_ms": {k: wk[k] for k in kbytes if wk[k]}}
+        if world == 1 and args.full:
             if state is not None:
                 legs = uvd_legs(dev, psgd, lib, state, r, max(5, min(args.steps, 20)), arena=arena_keep)
                 paths["apply"], paths["update"], paths["step_fused_events"] = legs["apply"], legs["update"], legs["step_fused"]

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -23,7 +24,7 @@ def _last_json(out):
 
 @pytest.mark.timeout(600)
 def test_bench_single_gpu_line(hip_lib):
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "4000000",
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "4000000", "--full",
                         "--no-kron", "--cpu-budget-s", "2", "--wide-rows", "2000000"], cwd=ROOT, capture_output=True, text=True,
                        timeout=580)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -70,6 +71,30 @@ def test_bench_single_gpu_line(hip_lib):
 
 
 @pytest.mark.timeout(600)
+def test_bench_plain_line_is_the_headline_and_dumps_outputs(hip_lib, tmp_path):
+    """A plain run (no --full) prints the headline and nothing that needs a run of its own; --dump-outputs writes what the last
+    timed step left to its caller (a seeded sample of rows), and two runs with the same arguments give the same arrays."""
+    outs = []
+    for k in range(2):
+        out_dir = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "1000000",
+                            "--dump-outputs", str(out_dir)], cwd=ROOT, capture_output=True, text=True, timeout=280)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _last_json(r.stdout)
+        assert d["metric"] == "uvd_update_apply_params_per_sec" and d["unit"] == "params/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 1
+        assert d["value"] > 0 and abs(d["value"] - 1000000 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+        assert not {"roofline", "cpu_baseline", "kron", "splu", "wide_rank", "config2_N1M_r10", "exchange_overhead", "weak"} & set(d)
+        arrs = {n: np.load(out_dir / (n + ".npy")) for n in ("precond_grad", "U", "V", "d")}
+        assert arrs["U"].shape == arrs["V"].shape == (65536, 20) and arrs["precond_grad"].shape == arrs["d"].shape == (65536, 1)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        outs.append(arrs)
+    for n, a in outs[0].items():
+        assert np.abs(outs[1][n] - a).max() <= 1e-5 * np.abs(a).max(), n
+
+
+@pytest.mark.timeout(600)
 def test_bench_two_ranks_self_launched(hip_lib):
     """`python bench.py --gpus 2` from a plain shell (as the driver's scaling run starts it): the parent launches the two
     ranks itself and relays rank 0's line.  Test mode: both ranks on the one GPU, gloo collectives."""
@@ -99,7 +124,7 @@ def test_bench_two_ranks_default_is_baseline_config3(hip_lib):
         env["PSGD_BENCH_SINGLE_DEVICE"] = "1"
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=880)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)

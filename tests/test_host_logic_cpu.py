@@ -177,6 +177,26 @@ def test_committed_pmc_traffic_file_is_what_bench_reads():
     assert 0.98 * alg < rec["hbm_bytes_per_launch"] < 1.10 * alg
 
 
+def test_bench_dump_sample_is_fixed_and_bounded():
+    """bench.py --dump-outputs: the same sorted rows on every call, every row when they fit, float32, and at most 64 MB in
+    all whatever the rank of modification."""
+    import bench
+    n = 300_000
+    U = torch.arange(n, dtype=torch.float64).view(n, 1).expand(n, 4)
+    col = torch.arange(n, dtype=torch.float32).view(n, 1)
+    a, b = bench.sample_outputs(col, U, U, col), bench.sample_outputs(col, U, U, col)
+    rows = a["precond_grad"][:, 0]
+    assert rows.shape == (bench.DUMP_ROWS,) and np.all(np.diff(rows) > 0) and rows.max() > n // 2
+    assert all(x.dtype == np.float32 and np.array_equal(x, b[k]) for k, x in a.items())
+    assert np.array_equal(a["U"][:, 0], rows) and np.array_equal(a["d"][:, 0], rows)
+    small = bench.sample_outputs(col[:1000], U[:1000], U[:1000], col[:1000])
+    assert np.array_equal(small["precond_grad"][:, 0], np.arange(1000))
+    r = 512
+    wide = torch.zeros(1, r).expand(n, r)
+    big = bench.sample_outputs(col, wide, wide, col)
+    assert 0 < big["U"].shape[0] < bench.DUMP_ROWS and sum(x.nbytes for x in big.values()) <= 64 << 20
+
+
 @pytest.mark.parametrize("sl,sr,sx", [((5, 5), (3, 3), (3, 5)),      # wrong-orientation data matrix
                                       ((4, 4), (3, 3), (5, 3)),      # left factor smaller than M
                                       ((5, 5), (2, 3), (5, 4)),      # (dense, normalization) with a short right factor
