@@ -46,7 +46,8 @@ extern "C" {
  * entry points of ranks 33 .. 64 added (building blocks, update, fused update -> apply); the sparse-LU entry points take ranks up to PSGD_SPLU_MAX_RANK = 64 and their workspace
  * regions have that capacity -- offsets from psgd_splu_ws_region changed; the fused strip kernels of small Kron layers and their
  * tuning key 21 removed: Kron workspaces of small layers shrink back by that scratch);
- * 7 = round 6 (psgd_kron_bf16_handoff_counter_offset added; bf16 tuning key 7: XCD patch of the fused pair; no layout change).
+ * 7 = round 6 (psgd_kron_bf16_handoff_counter_offset added; bf16 tuning key 7: XCD patch of the fused pair; no layout change);
+ *     later, additive: psgd_kron_dd_route_flags and the PSGD_KRON_ROUTE_* bits.
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -382,6 +383,23 @@ int psgd_kron_dd_apply_direct_f32(const float *Ql, const float *Qr, const float 
                                   int64_t ws_bytes, void *stream);
 /* 1 when the call above is a path of its own for this shape under the current tuning, 0 when it is psgd_kron_dd_apply_f32 */
 int psgd_kron_dd_apply_direct_distinct(int M, int N);
+
+/* The routes the Kron dense (x) dense calls take for an M x N layer under the current tuning keys (psgd_kron_set_tuning,
+ * psgd_kron_bf16_set_tuning), as a mask of the bits below; PSGD_ERR_SHAPE for M <= 0 or N <= 0.  Host only, no HIP call.
+ * Each bit is the predicate the launch code branches on, so a test can pin the shapes on either side of every threshold. */
+#define PSGD_KRON_ROUTE_SMALL          (1 << 0)   /* psgd_kron_dd_update_f32 runs as a batch of one (small layers)            */
+#define PSGD_KRON_ROUTE_PLANES_APPLY   (1 << 1)   /* the fp32 apply's products on operand planes                              */
+#define PSGD_KRON_ROUTE_PLANES_UPDATE  (1 << 2)   /* the fp32 update's products on operand planes                             */
+#define PSGD_KRON_ROUTE_INV_SOLVES     (1 << 3)   /* the fp32 update's solves through explicit inverses of diagonal blocks    */
+#define PSGD_KRON_ROUTE_INV_FIRST      (1 << 4)   /* ... with both inversions ahead of the products of psgd.py:173            */
+#define PSGD_KRON_ROUTE_BG_FRONT       (1 << 5)   /* ... and those products on a third stream from the fork point on          */
+#define PSGD_KRON_ROUTE_FACTOR_TS      (1 << 6)   /* ... with the fused prologue: the factors' planes at tile scales         */
+#define PSGD_KRON_ROUTE_GRAD_RECT      (1 << 7)   /* M != N: the smaller gradient's tiles split along their long K           */
+#define PSGD_KRON_ROUTE_APPLY_DIRECT   (1 << 8)   /* psgd_kron_dd_apply_direct_f32 is a path of its own                       */
+#define PSGD_KRON_ROUTE_BF16_INV       (1 << 9)   /* psgd_kron_dd_update_bf16's fp32 solves through explicit inverses        */
+#define PSGD_KRON_ROUTE_RECT_CHUNKS_SHIFT 12      /* bits 12-15: the K chunks per tile of PSGD_KRON_ROUTE_GRAD_RECT           */
+#define PSGD_KRON_ROUTE_RECT_CHUNKS_MASK  (15 << PSGD_KRON_ROUTE_RECT_CHUNKS_SHIFT)
+int psgd_kron_dd_route_flags(int M, int N);
 
 /* _update_precond_dense_dense(Ql, Qr, dX, dG, step)  psgd.py:156-179.
  * Pure: Ql, Qr are read, the new factors are written to QlOut, QrOut.      */

@@ -64,8 +64,10 @@ def update_precond_UVd_math_(U, V, d, v, h, step, tiny, balance=False, update_U=
     return None
 
 
-def _solve_ut_adjoint(Q, X):
-    return torch.linalg.solve_triangular(Q.t(), X, upper=False)
+def _solve_ut_adjoint(Q, X, cols=512):
+    """Q^-T X, in blocks of `cols` columns of X (the columns are independent): on the GPU the library's triangular solve asks
+    for a workspace that grows with the right-hand side, and a ragged 2049 x 8192 one no longer fits the workspace torch gives it."""
+    return torch.cat([torch.linalg.solve_triangular(Q.t(), X[:, j:j + cols], upper=False) for j in range(0, X.shape[1], cols)], 1)
 
 
 def update_precond_dense_dense(Ql, Qr, dX, dG, step, tiny):

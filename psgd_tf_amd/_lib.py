@@ -20,6 +20,12 @@ PSGD_WS_MAX_F32 = 1
 PSGD_WS_SEND_F64 = 2
 UVD_MAX_RANK = 32
 SPLU_MAX_RANK = 64       # PSGD_SPLU_MAX_RANK: the native sparse-LU entry points (round 5)
+# psgd_kron_dd_route_flags bits (PSGD_KRON_ROUTE_* of include/psgd_hip.h)
+KRON_ROUTE_SMALL, KRON_ROUTE_PLANES_APPLY, KRON_ROUTE_PLANES_UPDATE, KRON_ROUTE_INV_SOLVES = 1 << 0, 1 << 1, 1 << 2, 1 << 3
+KRON_ROUTE_INV_FIRST, KRON_ROUTE_BG_FRONT, KRON_ROUTE_FACTOR_TS, KRON_ROUTE_GRAD_RECT = 1 << 4, 1 << 5, 1 << 6, 1 << 7
+KRON_ROUTE_APPLY_DIRECT, KRON_ROUTE_BF16_INV = 1 << 8, 1 << 9
+KRON_ROUTE_RECT_CHUNKS_SHIFT = 12
+KRON_ROUTE_RECT_CHUNKS_MASK = 15 << KRON_ROUTE_RECT_CHUNKS_SHIFT
 
 
 class PsgdHipError(RuntimeError):
@@ -135,6 +141,7 @@ SIGNATURES = {
     "psgd_kron_dd_apply_bf16_prepared": (_int, [_c_f32p, _c_f32p, _int, _int, _c_ws, _i64, _strm]),
     "psgd_kron_dd_apply_direct_f32": (_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _int, _int, _c_ws, _i64, _strm]),
     "psgd_kron_dd_apply_direct_distinct": (_int, [_int, _int]),
+    "psgd_kron_dd_route_flags": (_int, [_int, _int]),
     "psgd_kron_dd_update_f32": (_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _int, _int, _flt, _flt,
                                        _c_ws, _i64, _strm]),
 }

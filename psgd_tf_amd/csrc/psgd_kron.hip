@@ -3992,6 +3992,16 @@ static int g_grad_split = 1;    // tuning key 6: 0 = no K split of the gradient 
 constexpr int g_grad_order = 1;    // (frozen in round 4, was tuning key 17) tile order of the gradient grid for M = N (see k_gemm_p3_grad; tools/grad_order_ab.py:
                                 // 4096^2 update 2.95-2.98 -> 2.87-2.88 ms, 6144^2 8.5 -> 8.3; patches of 4 x 4 tiles (2) are no better:
                                 // L2 locality is not what bounds this grid; 2048 x 4096 loses 9 % with either)
+// The rectangular split of the gradient grid (launch_p3_grad, M != N): the K chunks of every tile of the product with the longer K
+// (m_long: its output side), 0 = no split.  Also the route query's (psgd_kron_dd_route_flags).
+static int grad_rect_chunks(int m_long, int k_long, int k_short) {
+  if (!g_grad_split || !g_grad_rect || k_long == k_short) return 0;
+  const int Tl = (m_long + 127) / 128, nl = Tl * (Tl + 1) / 2;
+  const int ratio = (k_long + k_short / 2) / k_short;
+  if (ratio < 2 || nl > kGradSplitMax) return 0;
+  const int nchunk = ratio >= 7 ? 8 : ratio >= 5 ? 6 : ratio >= 3 ? 4 : 2;
+  return nchunk > kGradChunks ? kGradChunks : nchunk;
+}
 static int launch_p3_grad(const P3Args& a, const P3Args& b, float* scratch, unsigned* cnt, hipStream_t st, bool cnt_zeroed = false) {
   static int slots = 0;
   if (!slots) {
@@ -4003,12 +4013,10 @@ static int launch_p3_grad(const P3Args& a, const P3Args& b, float* scratch, unsi
   // M != N (round 6): the gradient of the SMALLER factor has few tiles with the longer side as its K -- a 1024 x 4096 layer: 36 tiles of 2 x 128
   // K steps beside 528 tiles of 2 x 32, and the launch took the long tiles' 246 us where the work is ~95 us of the chip.  That product goes
   // second and ALL its tiles are split into K chunks as long as the other product's tiles (the chunk count = the ratio of the sides, even, <= 8).
-  const bool rect_split = g_grad_split && g_grad_rect && scratch && a.e.K != b.e.K;
   const P3Args& lng = a.e.K > b.e.K ? a : b;          // (the longer K: the smaller output)
   const P3Args& sht = a.e.K > b.e.K ? b : a;
-  const int Tl = (lng.e.M + 127) / 128, nl = Tl * (Tl + 1) / 2;
-  const int ratio = (lng.e.K + sht.e.K / 2) / sht.e.K;
-  const bool rect = rect_split && ratio >= 2 && nl <= kGradSplitMax;
+  const int rect_chunks = scratch ? grad_rect_chunks(lng.e.M, lng.e.K, sht.e.K) : 0;
+  const bool rect = rect_chunks > 0;
   if (rect) { p.g[0] = sht; p.g[1] = lng; } else { p.g[0] = a; p.g[1] = b; }
   p.T0 = (p.g[0].e.M + 127) / 128; p.T1 = (p.g[1].e.M + 127) / 128;
   p.n0 = p.T0 * (p.T0 + 1) / 2; p.n1 = p.T1 * (p.T1 + 1) / 2;
@@ -4018,8 +4026,7 @@ static int launch_p3_grad(const P3Args& a, const P3Args& b, float* scratch, unsi
   p.nsplit = 0;
   if (rect) {
     p.nsplit = p.n1;
-    p.nchunk = ratio >= 7 ? 8 : ratio >= 5 ? 6 : ratio >= 3 ? 4 : 2;
-    if (p.nchunk > kGradChunks) p.nchunk = kGradChunks;
+    p.nchunk = rect_chunks;
   }
   // a short last round (at most an eighth of the slots): twice that many tiles become eighth-size items, which the idle
   // slots of the last full round and one short extra round absorb
@@ -4639,6 +4646,8 @@ static inline int inv_blk(int M, int N) {
   const int n = M > N ? M : N;
   return ((n + g_inv_blk - 1) / g_inv_blk > 4) ? 2048 : g_inv_blk;
 }
+// the blocked solves of the inverse route on tile-scale planes
+static inline bool kron_inv_ts(int M, int N) { return kron_tile_scales(M, N) && inv_blk(M, N) % 128 == 0; }
 static BlkSolve inv_solve_problem(const InvSolveWs& k, const float* QlS, const float* QrS, const float* dinv_r, const float* dinv_l,
                                   const float* X0, float* X1, float* Bt, int M, int N) {
   const long Mp = pad128(M), Np = pad128(N);
@@ -4753,7 +4762,7 @@ int kron_balance(const float* Ql, const float* Qr, int M, int N, float* QlS, flo
 }
 
 bool kron_fused_prologue_on(int M, int N) {
-  return g_fused_prologue && kron_inv_solves_on(M, N) && kron_tile_scales(M, N) && inv_blk(M, N) % 128 == 0;
+  return g_fused_prologue && kron_inv_solves_on(M, N) && kron_inv_ts(M, N);
 }
 int kron_balance_planes(const float* Ql, const float* Qr, int M, int N, float* QlS, float* QrS, hipStream_t st, float* dinv, void* inv_ws,
                         float* scal) {
@@ -4886,6 +4895,8 @@ int64_t psgd_kron_dd_workspace_bytes(int M, int N) {
   return kron_layout(nullptr, M, N).total;
 }
 
+static inline bool kron_apply_planes(int M, int N) { return kron_planes_apply(M, N) && g_planes && g_gemm_x3; }
+
 /* Factor-only half of the apply: the Gram(s) of the factors into the workspace (see plan_apply). */
 int psgd_kron_dd_prepare_f32(const float* Ql, const float* Qr, int M, int N, void* ws, int64_t ws_bytes, void* stream) {
   if (!Ql || !Qr) return PSGD_ERR_BAD_ARG;
@@ -4893,7 +4904,7 @@ int psgd_kron_dd_prepare_f32(const float* Ql, const float* Qr, int M, int N, voi
   if (kron_ws_check(ws, ws_bytes, kron_layout(nullptr, M, N).total)) return PSGD_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   KronWs k = kron_layout(static_cast<char*>(ws), M, N);
-  if (kron_planes_apply(M, N) && g_planes && g_gemm_x3) {
+  if (kron_apply_planes(M, N)) {
     KRON_LAUNCH(planes_prepare(Ql, Qr, M, N, k, st));
     return PSGD_OK;
   }
@@ -4913,7 +4924,7 @@ int psgd_kron_dd_apply_prepared_f32(const float* Ql, const float* Qr, const floa
   if (kron_ws_check(ws, ws_bytes, kron_layout(nullptr, M, N).total)) return PSGD_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   KronWs k = kron_layout(static_cast<char*>(ws), M, N);
-  if (kron_planes_apply(M, N) && g_planes && g_gemm_x3) {
+  if (kron_apply_planes(M, N)) {
     KRON_LAUNCH(planes_apply(G, out, M, N, k, st));
     return PSGD_OK;
   }
@@ -4935,7 +4946,7 @@ int psgd_kron_dd_apply_f32(const float* Ql, const float* Qr, const float* G, flo
  * apply; the same as psgd_kron_dd_apply_f32 elsewhere.  Leaves no prepared state: psgd_kron_dd_apply_prepared_f32 needs a
  * psgd_kron_dd_prepare_f32 (or psgd_kron_dd_apply_f32) for these factors first. */
 static bool apply_direct_is_distinct(int M, int N) {
-  return kron_planes_apply(M, N) && g_planes && g_gemm_x3 && g_planes_f16 && g_planes_exact;
+  return kron_apply_planes(M, N) && g_planes_f16 && g_planes_exact;
 }
 /* 1 when psgd_kron_dd_apply_direct_f32 is a path of its own for this shape under the current tuning (else it is psgd_kron_dd_apply_f32,
  * which leaves prepared state) */
@@ -4953,6 +4964,14 @@ int psgd_kron_dd_apply_direct_f32(const float* Ql, const float* Qr, const float*
   return psgd_kron_dd_apply_f32(Ql, Qr, G, out, M, N, ws, ws_bytes, stream);
 }
 
+// The route rules of psgd_kron_dd_update_f32 (and of psgd_kron_dd_route_flags, which reports them)
+static inline bool kron_update_small(int M, int N) { return M <= 512 && N <= 512 && (g_stage_mix & 2); }
+static inline bool kron_update_planes(int M, int N) { return kron_planes(M, N) && g_planes && g_gemm_x3; }
+static inline bool kron_update_inv_route(int M, int N) {        // (f16 x 2 planes: 6 levels of meta slots)
+  return kron_update_planes(M, N) && g_planes_f16 > 1 && g_trsm_inv && kron_inv_route(M, N) && M <= 8192 && N <= 8192;
+}
+static inline bool kron_update_factor_ts(int M, int N) { return kron_update_inv_route(M, N) && g_fused_prologue && kron_inv_ts(M, N); }
+
 int psgd_kron_dd_update_f32(const float* Ql, const float* Qr, const float* dX, const float* dG, float* QlOut,
                             float* QrOut, int M, int N, float step, float tiny, void* ws, int64_t ws_bytes,
                             void* stream) {
@@ -4960,17 +4979,17 @@ int psgd_kron_dd_update_f32(const float* Ql, const float* Qr, const float* dX, c
   if (M <= 0 || N <= 0) return PSGD_ERR_SHAPE;
   if (kron_ws_check(ws, ws_bytes, kron_layout(nullptr, M, N).total)) return PSGD_ERR_WORKSPACE;
   // small layers are launch-bound: the batch-of-one route with half the launches of the large-layer path (stages of independent chains share them)
-  if (M <= 512 && N <= 512 && (g_stage_mix & 2))
+  if (kron_update_small(M, N))
     return psgd_kron_dd_update_batched_f32(&Ql, &Qr, &dX, &dG, &QlOut, &QrOut, &M, &N, 1, step, tiny, ws, ws_bytes, stream);
   hipStream_t st = static_cast<hipStream_t>(stream);
   KronWs k = kron_layout(static_cast<char*>(ws), M, N);
-  const bool planes = kron_planes(M, N) && g_planes && g_gemm_x3;
+  const bool planes = kron_update_planes(M, N);
   PlaneMeta* pm = (planes && g_planes_f16 > 1) ? k.pmeta : nullptr;        // f16 x 2 planes of the update
   // K0: balance (:166-170); zeroes k.scal (and the update's plane maxima); the same launch inverts the diagonal blocks the
   // solves of K2 start from
-  const bool inv_route = pm && g_trsm_inv && kron_inv_route(M, N) && M <= 8192 && N <= 8192;    // (6 levels of meta slots)
+  const bool inv_route = pm && kron_update_inv_route(M, N);
   // (round 6) on the tile-scale route of the inverse solves the whole prologue is rho + ONE sweep (k_kron_balance_planes)
-  k.factor_ts = inv_route && g_fused_prologue && kron_tile_scales(M, N) && inv_blk(M, N) % 128 == 0;
+  k.factor_ts = kron_update_factor_ts(M, N);
   if (k.factor_ts)
     KRON_LAUNCH(kron_balance_planes(Ql, Qr, M, N, k, st, &pm[kPmL].scale, (kPmSlots - kPmL) * 4));
   else
@@ -5009,7 +5028,7 @@ int psgd_kron_dd_update_f32(const float* Ql, const float* Qr, const float* dX, c
     bs.X1 = k.X1; bs.Bt = k.Bt;
     bs.pa = P3Buf{k.Y0, Mp, Np, nullptr}; bs.pb = P3Buf{k.Y1, Mp, Np, nullptr};      // (transients of the apply: free during an update)
     bs.Br = P3Buf{k.U0, Mp, Np, pm + kPmBt}; bs.Bc = P3Buf{k.U1, Np, Mp, pm + kPmBt};
-    const bool ts = kron_tile_scales(M, N) && bs.h % 128 == 0;
+    const bool ts = kron_inv_ts(M, N);
     if (ts) {
       bs.L.Ir.te = k.te + kTeG1 * kTeTable; bs.L.Ic.te = k.te + kTeIcL * kTeTable; bs.L.Tp.te = k.te + kTeTpL * kTeTable;
       bs.R.Ir.te = k.te + kTeG2 * kTeTable; bs.R.Ic.te = k.te + kTeIcR * kTeTable; bs.R.Tp.te = k.te + kTeTpR * kTeTable;
@@ -5102,6 +5121,33 @@ int psgd_kron_dd_update_f32(const float* Ql, const float* Qr, const float* dX, c
   KRON_LAUNCH(launch_gemm_two(s[2], s[3], st));      // the two gradient products
   KRON_LAUNCH(launch_gemm_two(s[4], s[5], st));      // the two factor updates
   return PSGD_OK;
+}
+
+/* The route each Kron dense (x) dense call takes for this shape under the current tuning keys (PSGD_KRON_ROUTE_*): the very
+ * predicates the launch code branches on.  Host only.  (The stream order assumes the side streams exist, as they do outside a
+ * first call under capture.) */
+int psgd_kron_dd_route_flags(int M, int N) {
+  if (M <= 0 || N <= 0) return PSGD_ERR_SHAPE;
+  int f = 0;
+  if (kron_apply_planes(M, N)) f |= PSGD_KRON_ROUTE_PLANES_APPLY;
+  if (apply_direct_is_distinct(M, N)) f |= PSGD_KRON_ROUTE_APPLY_DIRECT;
+  if (kron_inv_solves_on(M, N)) f |= PSGD_KRON_ROUTE_BF16_INV;
+  if (kron_update_small(M, N)) return f | PSGD_KRON_ROUTE_SMALL;
+  if (kron_update_planes(M, N)) {
+    f |= PSGD_KRON_ROUTE_PLANES_UPDATE;
+    const int lo = M < N ? M : N, hi = M < N ? N : M;
+    const int nchunk = grad_rect_chunks(lo, hi, lo);      // (the gradient products: M x M over K = N, N x N over K = M)
+    if (nchunk) f |= PSGD_KRON_ROUTE_GRAD_RECT | (nchunk << PSGD_KRON_ROUTE_RECT_CHUNKS_SHIFT);
+  }
+  if (kron_update_inv_route(M, N)) {
+    f |= PSGD_KRON_ROUTE_INV_SOLVES;
+    if (kron_update_factor_ts(M, N)) f |= PSGD_KRON_ROUTE_FACTOR_TS;
+    if (kron_inv_first(M, N) && kron_overlap_chains(M, N)) {
+      f |= PSGD_KRON_ROUTE_INV_FIRST;
+      if (kron_inv_ts(M, N) && kron_bg_front(M, N)) f |= PSGD_KRON_ROUTE_BG_FRONT;
+    }
+  }
+  return f;
 }
 
 /* ---- batched forms: the same stage of every layer in one launch (LeNet5-size layers are

@@ -26,6 +26,28 @@ def tri(n, g, off):
     return torch.triu(torch.randn(n, n, device=dev, generator=g) * off, 1) + torch.diag(torch.exp(0.3 * torch.randn(n, device=dev, generator=g)))
 
 
+def randint(lo, hi, g):
+    return int(torch.randint(lo, hi, (1,), generator=g, device=dev))
+
+
+def long_side_shape(g, it, mult=1):
+    """Rarely, a layer with one long side ([2048, 8200] x [64, 1100], either way round: the inverse tiers, the 8192 cap, the
+    rectangular gradient split) or, more rarely still, both sides in [3000, 6200] (the inverse route with the products first);
+    else None.  Sides rounded down to `mult`."""
+    if it % 61 == 40:
+        M, N = randint(3000, 6201, g), randint(3000, 6201, g)
+    elif it % 23 == 11:
+        M, N = randint(2048, 8201, g), randint(64, 1101, g)
+        if it % 2:
+            M, N = N, M
+    else:
+        return None
+    return M // mult * mult, N // mult * mult
+
+
+LARGE_KRON = [0]      # Kron cases with a side >= 4096 (reported by the command line)
+
+
 def fuzz_kron(g, it):
     big = it % 7 == 0
     M = int(torch.randint(1, 2600 if big else 700, (1,), generator=g, device=dev))
@@ -33,6 +55,8 @@ def fuzz_kron(g, it):
     if it % 28 == 27 or (os.environ.get("FUZZ_BIG") == "1" and it % 3 == 2):   # both factors from 2048 on: the solves through explicit inverses
         M = int(torch.randint(2048, 3000, (1,), generator=g, device=dev))
         N = int(torch.randint(2049, 3000, (1,), generator=g, device=dev))
+    M, N = long_side_shape(g, it) or (M, N)
+    LARGE_KRON[0] += max(M, N) >= 4096
     off = 0.5 / max(M, N) ** 0.5
     Ql, Qr = tri(M, g, off) * 1.7, tri(N, g, off)
     dX = torch.randn(M, N, device=dev, generator=g)
@@ -75,6 +99,10 @@ def fuzz_kron_bf16_update(g, it):
         M = 256 * int(torch.randint(1, 10, (1,), generator=g, device=dev))
         N = M if it % 8 == 1 else 256 * int(torch.randint(1, 10, (1,), generator=g, device=dev))
         sk = 2 + (it // 4) % 2                        # 2: whole-tile rounds + ranges, 3: ranges only
+    big = long_side_shape(g, it, 8)
+    if big:
+        M, N, sk = big[0], big[1], 0
+        LARGE_KRON[0] += max(M, N) >= 4096
     off = 0.5 / max(M, N) ** 0.5
     Ql, Qr = tri(M, g, off) * 1.7, tri(N, g, off)
     dX = torch.randn(M, N, device=dev, generator=g)
@@ -242,7 +270,7 @@ def run(budget, seed=1):
 
 if __name__ == "__main__":
     cases, bad, worst = run(float(sys.argv[1]) if len(sys.argv) > 1 else 120.0, int(os.environ.get("FUZZ_SEED", "1")))
-    print("cases", cases, "failures", len(bad))
+    print("cases", cases, "failures", len(bad), "kron cases with a side >= 4096:", LARGE_KRON[0])
     for fam, (e, n) in worst.items():
         print("worst %-10s %.3e  (%s)" % (fam, e, n))
     sys.exit(1 if bad else 0)

@@ -92,6 +92,28 @@ def test_kron_workspace_layout_rules(lib):
     assert sp(1, 30000, 1000) > sp(1, 30000, 500) and sp(2, 30000, 1000) < sp(1, 30000, 1000)      # (norm, dense) vs (norm, scaling)
 
 
+def test_kron_route_flags_anchor_the_route_table(lib):
+    """psgd_kron_dd_route_flags reports the predicates the Kron launch code branches on (no GPU needed): a few anchors of the
+    route table, and a tuning key that moves the route moves the flag."""
+    R = lambda m, n: lib.psgd_kron_dd_route_flags(m, n)
+    inv = _lib.KRON_ROUTE_INV_SOLVES
+    assert R(0, 4) == R(4, -1) == _lib.PSGD_ERR_SHAPE
+    assert R(1024, 4096) & inv and R(4096, 1024) & inv
+    assert not R(1023, 2048) & inv and not R(256, 8193) & inv
+    assert R(6144, 6144) & inv and not R(6144, 6144) & _lib.KRON_ROUTE_INV_FIRST
+    assert R(4096, 4096) & _lib.KRON_ROUTE_BG_FRONT
+    assert R(512, 512) & _lib.KRON_ROUTE_SMALL and not R(513, 512) & _lib.KRON_ROUTE_SMALL
+    chunks = lambda f: (f & _lib.KRON_ROUTE_RECT_CHUNKS_MASK) >> _lib.KRON_ROUTE_RECT_CHUNKS_SHIFT
+    assert R(1024, 1536) & _lib.KRON_ROUTE_GRAD_RECT and chunks(R(1024, 1536)) == 2
+    assert not R(1024, 1535) & _lib.KRON_ROUTE_GRAD_RECT and chunks(R(1024, 1535)) == 0
+    try:
+        assert lib.psgd_kron_set_tuning(11, 0) == 0
+        assert not R(1024, 4096) & inv and R(1024, 4096) & _lib.KRON_ROUTE_PLANES_UPDATE
+    finally:
+        lib.psgd_kron_set_tuning(11, 1)
+    assert R(1024, 4096) & inv
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))

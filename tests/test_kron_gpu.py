@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import psgd_oracle as orc
+from tests.kron_cases import illcond_factor
 from tests.uvd_cases import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -646,12 +647,7 @@ def test_bf16_update_solves_with_ill_conditioned_factors(psgd, hip_lib, M, N):
     cond(Q) ~ 1e4 factors (the conditioning multiplies whatever the products lose) the default must agree with the
     all-six-terms solve far inside the bf16 bars, and both with the fp64 oracle on the bf16-rounded data."""
     rng = np.random.default_rng(M + 13 * N)
-
-    def illcond(n):
-        d = np.exp(np.linspace(0.0, -np.log(1e4), n))
-        rng.shuffle(d)
-        return np.triu(rng.standard_normal((n, n)) * (0.3 / n ** 0.5), 1) * d[None, :] + np.diag(d)
-    Ql, Qr = illcond(M).astype(np.float32), illcond(N).astype(np.float32)
+    Ql, Qr = illcond_factor(rng, M).astype(np.float32), illcond_factor(rng, N).astype(np.float32)
     assert 3e3 < np.linalg.cond(Ql.astype(np.float64)) < 1e6 and 3e3 < np.linalg.cond(Qr.astype(np.float64)) < 1e6
     dX = rng.standard_normal((M, N))
     dG = np.linalg.solve(Ql.T.astype(np.float64) @ Ql, dX) @ np.linalg.inv(Qr.T.astype(np.float64) @ Qr) \
@@ -1397,13 +1393,7 @@ def test_update_with_ill_conditioned_factors(psgd, M, N):
     psgd.py:174 carry the conditioning.  Updated factors within 1e-5 of the fp64 oracle, increments within 2e-3 -- the
     bar any faster (e.g. inverse-based) solve has to keep."""
     rng = np.random.default_rng(M + 13 * N)
-
-    def illcond(n):
-        d = np.exp(np.linspace(0.0, -np.log(1e4), n))
-        rng.shuffle(d)
-        Q = np.triu(rng.standard_normal((n, n)) * (0.3 / n ** 0.5), 1) * d[None, :] + np.diag(d)
-        return Q
-    Ql, Qr = illcond(M), illcond(N)
+    Ql, Qr = illcond_factor(rng, M), illcond_factor(rng, N)
     assert 3e3 < np.linalg.cond(Ql) < 1e6 and 3e3 < np.linalg.cond(Qr) < 1e6
     dX = rng.standard_normal((M, N))
     dG = np.linalg.solve(Ql.T @ Ql, dX) @ np.linalg.inv(Qr.T @ Qr) * np.exp(rng.uniform(-0.5, 0.5, (1, N)))   # near the fixed point: A ~ Bt
