@@ -47,7 +47,8 @@ extern "C" {
  * regions have that capacity -- offsets from psgd_splu_ws_region changed; the fused strip kernels of small Kron layers and their
  * tuning key 21 removed: Kron workspaces of small layers shrink back by that scratch);
  * 7 = round 6 (psgd_kron_bf16_handoff_counter_offset added; bf16 tuning key 7: XCD patch of the fused pair; no layout change);
- *     later, additive: psgd_kron_dd_route_flags and the PSGD_KRON_ROUTE_* bits.
+ *     later, additive: psgd_kron_dd_route_flags and the PSGD_KRON_ROUTE_* bits; the dense preconditioner's
+ *     psgd_dense_workspace_bytes, psgd_dense_update_f32 and psgd_dense_apply_f32 (new symbols only: the version stays 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -519,6 +520,22 @@ int psgd_kron_bf16_handoff_reset(void *ws, int M, int N, void *stream);
  * synchronising copies the word to pinned host memory asynchronously now and then (psgd_tf_amd/kron.py does, and switches to the
  * hand-off-free kernels by itself after three recoveries).  < 0 on a bad shape.                                                     */
 int64_t psgd_kron_bf16_handoff_counter_offset(int M, int N);
+
+/* ---------------------------------------------------------------- dense ---
+ * One dense N x N preconditioner factor Q, P = Q'Q (psgd.py:26-63).  Q is row-major [N, N]; dx, dg, g are the
+ * concatenated columns [N].  Q is used as a full matrix in the products; the triangular solve of :39 reads its upper
+ * triangle only.  The update never forms G = triu(a a' - b b') nor an N^3 product: (G Q)[i,j] = a_i A[i,j] - b_i B[i,j]
+ * with A, B the suffix sums sum_{k>=i} a_k Q[k,j], sum_{k>=i} b_k Q[k,j] down each column.  Results are bit-identical
+ * from call to call.  The workspace (>= psgd_dense_workspace_bytes(N), 256-byte aligned) serves both calls.         */
+int64_t psgd_dense_workspace_bytes(int64_t N);   /* PSGD_ERR_BAD_ARG for N <= 0 */
+/* update_precond_dense (psgd.py:26-42): a = Q dg, Q' b = dx, mu = step / (max_{i<=j} |a_i a_j - b_i b_j| + tiny),
+ * Qout = Q - mu G Q.  Pure: Qout == Q is PSGD_ERR_BAD_ARG.                                                   */
+int psgd_dense_update_f32(const float *Q, const float *dx, const float *dg, float *Qout, int64_t N,
+                          float step, float tiny, void *ws, int64_t ws_bytes, void *stream);
+/* precond_grad_dense (psgd.py:55): out = Q' (Q g) */
+int psgd_dense_apply_f32(const float *Q, const float *g, float *out, int64_t N, void *ws, int64_t ws_bytes,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

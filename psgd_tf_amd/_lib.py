@@ -144,6 +144,9 @@ SIGNATURES = {
     "psgd_kron_dd_route_flags": (_int, [_int, _int]),
     "psgd_kron_dd_update_f32": (_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _int, _int, _flt, _flt,
                                        _c_ws, _i64, _strm]),
+    "psgd_dense_workspace_bytes": (_i64, [_i64]),
+    "psgd_dense_update_f32": (_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64, _flt, _flt, _c_ws, _i64, _strm]),
+    "psgd_dense_apply_f32": (_int, [_c_f32p, _c_f32p, _c_f32p, _i64, _c_ws, _i64, _strm]),
 }
 
 _lib = None

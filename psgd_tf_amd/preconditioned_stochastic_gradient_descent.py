@@ -20,8 +20,9 @@ The UVd, sparse-LU and Kron arithmetic runs in hand-written HIP kernels behind t
 C ABI of include/psgd_hip.h (bound in _lib.py).  Tensors must be fp32 and resident on a ROCm
 device; anything else raises -- there is no CPU fallback for the hot path.  Strided views are
 accepted (copied on the way in, in-place state written back on the way out); the kernels work on
-contiguous memory.  The dense preconditioner (psgd.py:26-63) is host-side plumbing on torch ops
-(2x2 matrices, never a kernel target).
+contiguous memory.  The dense preconditioner (psgd.py:26-63) runs in HIP kernels too when Q and its
+operands are fp32 on one ROCm device (psgd_dense.hip, O(N^2) per call); on the CPU (hello_psgd's 2x2),
+in fp64 or bf16, or after ``set_dense_route("torch")``, it is the torch-op plumbing of the reference.
 
 The reference draws its two branch decisions (psgd.py:562, :588) from TensorFlow's
 global RNG; here they come from a torch.Generator (module default, or ``generator=``)
@@ -120,9 +121,80 @@ def _uvd_shapes(name, U, V, *cols):
     return N, r
 
 
-# --------------------------------------------------------------------------- dense (plumbing)
+# --------------------------------------------------------------------------- dense
+_dense_route = "native"
+
+
+def set_dense_route(route):
+    """"native" (default): fp32 operands on one ROCm device run the HIP kernels of psgd_dense.hip; "torch": the torch-op
+    plumbing below for every operand (A/B runs).  CPU, fp64 and bf16 operands take the torch ops under either route."""
+    global _dense_route
+    if route not in ("native", "torch"):
+        raise ValueError("set_dense_route: route must be 'native' or 'torch', got %r" % (route,))
+    _dense_route = route
+
+
+def _dense_native(Q, *lists):
+    """True when the call goes to the kernels: route "native", Q and every list entry fp32 tensors on one ROCm device."""
+    if _dense_route != "native" or not isinstance(Q, torch.Tensor) or not Q.is_cuda or Q.dtype != torch.float32:
+        return False
+    return all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == Q.device for xs in lists for t in xs)
+
+
+def _dense_workspace(device, N):
+    key = ("dense", device.index if device.index is not None else torch.cuda.current_device(), int(N),
+           torch.cuda.current_stream(device).cuda_stream)
+
+    def make():
+        nbytes = int(_lib.load().psgd_dense_workspace_bytes(N))
+        if nbytes <= 0:
+            _lib.check(nbytes, "psgd_dense_workspace_bytes")
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _ws_cache.get(key, make)
+
+
+def _dense_n(name, Q):
+    if Q.dim() != 2 or Q.shape[0] != Q.shape[1]:
+        raise ValueError("%s: Q must be N x N, got %s" % (name, tuple(Q.shape)))
+    return Q.shape[0]
+
+
+def _update_dense_native(Q, dxs, dgs, step):
+    Q = _c(Q)
+    N = _dense_n("update_precond_dense", Q)
+    dx, dg = _tall("update_precond_dense", dxs, N), _tall("update_precond_dense", dgs, N)
+    dev = _require_hip("update_precond_dense", Q, dx, dg)
+    out = torch.empty((N, N), dtype=Q.dtype, device=dev)
+    ws = _dense_workspace(dev, N)
+    rc = _lib.load().psgd_dense_update_f32(Q.data_ptr(), dx.data_ptr(), dg.data_ptr(), out.data_ptr(), N, float(step),
+                                           float(_tiny), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    _lib.check(rc, "psgd_dense_update_f32")
+    return out
+
+
+def _precond_grad_dense_native(Q, grads):
+    Q = _c(Q)
+    N = _dense_n("precond_grad_dense", Q)
+    g = _tall("precond_grad_dense", grads, N)
+    dev = _require_hip("precond_grad_dense", Q, g)
+    out = torch.empty(N, dtype=Q.dtype, device=dev)
+    ws = _dense_workspace(dev, N)
+    rc = _lib.load().psgd_dense_apply_f32(Q.data_ptr(), g.data_ptr(), out.data_ptr(), N, ws.data_ptr(), ws.numel(),
+                                          _stream_ptr(dev))
+    _lib.check(rc, "psgd_dense_apply_f32")
+    pre_grads, idx = [], 0
+    for x in grads:
+        n = x.numel()
+        pre_grads.append(torch.reshape(out[idx:idx + n], x.shape))
+        idx = idx + n
+    return pre_grads
+
+
 def update_precond_dense(Q, dxs, dgs, step=0.01):
-    """psgd.py:26-42.  Host-side plumbing on torch ops (config 1, hello_psgd: 2x2 on CPU)."""
+    """psgd.py:26-42.  fp32 on a ROCm device: psgd_dense_update_f32 (O(N^2), never forms G; Q is not modified).  Anything else
+    (hello_psgd's 2x2 on the CPU, fp64, bf16), or set_dense_route("torch"): the torch ops below."""
+    if _dense_native(Q, dxs, dgs):
+        return _update_dense_native(Q, dxs, dgs, step)
     dx = torch.cat([torch.reshape(x, [-1, 1]) for x in dxs], 0)
     dg = torch.cat([torch.reshape(g, [-1, 1]) for g in dgs], 0)
     a = Q @ dg
@@ -133,7 +205,9 @@ def update_precond_dense(Q, dxs, dgs, step=0.01):
 
 
 def precond_grad_dense(Q, grads):
-    """psgd.py:45-63: list in, list out with the original shapes."""
+    """psgd.py:45-63: list in, list out with the original shapes.  Routes as update_precond_dense (psgd_dense_apply_f32)."""
+    if _dense_native(Q, grads):
+        return _precond_grad_dense_native(Q, grads)
     cols = [torch.reshape(g, [-1, 1]) for g in grads]
     lens = [c.shape[0] for c in cols]
     grad = torch.cat(cols, 0)
