@@ -48,7 +48,8 @@ extern "C" {
  * tuning key 21 removed: Kron workspaces of small layers shrink back by that scratch);
  * 7 = round 6 (psgd_kron_bf16_handoff_counter_offset added; bf16 tuning key 7: XCD patch of the fused pair; no layout change);
  *     later, additive: psgd_kron_dd_route_flags and the PSGD_KRON_ROUTE_* bits; the dense preconditioner's
- *     psgd_dense_workspace_bytes, psgd_dense_update_f32 and psgd_dense_apply_f32 (new symbols only: the version stays 7).
+ *     psgd_dense_workspace_bytes, psgd_dense_update_f32 and psgd_dense_apply_f32 (new symbols only: the version stays 7);
+ *     the psgd_uvd_*_bf16 entry points of a bf16-stored UVd state (new symbols only).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -255,6 +256,33 @@ int psgd_uvd_rank2_update_ld_f32(float *M, int64_t ld, const float *a, const flo
 int psgd_uvd_update_sweep1_ld_f32(const float *U, int64_t ldU, const float *V, int64_t ldV, const float *d,
                                   const float *v, const float *h, int64_t N, int r, void *ws, int64_t ws_bytes,
                                   void *stream);
+
+/* ------------------------------------------------------ UVd, bf16 state ---
+ * The same preconditioner with U, V ([N, r]) and d ([N]) STORED as bf16 (psgd.py:671, :688-690: the state in the
+ * parameters' type); v, h, g and out are fp32 and all arithmetic is fp32 / fp64 -- only the HBM image of the state is
+ * narrow (psgd_uvd_bf16.hip).  1 <= r <= PSGD_UVD_MAX_RANK (PSGD_ERR_RANK above), any N >= 1.  U, V, d must be 16-byte
+ * aligned (PSGD_ERR_ALIGN).  The workspace (psgd_uvd_bf16_workspace_bytes, 256-byte aligned, about 16 MiB + 4 N) has a
+ * layout of its own and needs no initialisation.  Results are bit-identical from call to call.
+ *   rounding 0: round to nearest even.
+ *   rounding 1: stochastic -- a finite fp32 value with bits b is stored as (b + u) >> 16, u uniform in [0, 2^16) from a
+ *               counter hash of (seed, tensor, flat element index): the result depends on the seed and the element only.
+ *               NaN and Inf are stored as they are.  Applies to every state tensor the call writes.
+ *   any other value: PSGD_ERR_BAD_ARG.
+ * balance = 1 (psgd.py:562-567) rewrites both factors; the rescaling happens in registers, so every stored element is
+ * rounded once.  psgd_uvd_update_apply_bf16 = the update followed by precond_grad_UVd_math ON THE STORED (rounded) STATE:
+ * five sweeps (the d update rides on the apply's first sweep); out must not alias g, v or h.                          */
+int64_t psgd_uvd_bf16_workspace_bytes(int64_t N, int r);
+/* The 64-bit key of the stochastic-rounding stream of one state tensor (0 = U, 1 = V, 2 = d) under `seed`; host only.  The
+ * seed is hashed before the tensor id enters, so related seeds (seed + c, ...) never alias one tensor's stream to another's. */
+uint64_t psgd_uvd_bf16_rounding_key(uint64_t seed, int tensor);
+int psgd_uvd_apply_bf16(const void *U, const void *V, const void *d, const float *g, float *out,
+                        int64_t N, int r, void *ws, int64_t ws_bytes, void *stream);
+int psgd_uvd_update_bf16(void *U, void *V, void *d, const float *v, const float *h, int64_t N, int r,
+                         float step, float tiny, int balance, int update_U,
+                         int rounding, uint64_t seed, void *ws, int64_t ws_bytes, void *stream);
+int psgd_uvd_update_apply_bf16(void *U, void *V, void *d, const float *v, const float *h, const float *g, float *out,
+                               int64_t N, int r, float step, float tiny, int balance, int update_U,
+                               int rounding, uint64_t seed, void *ws, int64_t ws_bytes, void *stream);
 
 /* Tuning knobs for experiments (not part of the stable ABI).
  * key 0: streaming policy (0 = automatic: non-temporal when U,V exceed the Infinity Cache,

@@ -97,6 +97,12 @@ SIGNATURES = {
     "psgd_uvd_rank2_update_ld_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _i64, _int, _c_ws, _i64, _strm]),
     "psgd_uvd_update_sweep1_ld_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _i64, _int, _c_ws, _i64,
                                              _strm]),
+    "psgd_uvd_bf16_workspace_bytes": (_i64, [_i64, _int]),
+    "psgd_uvd_bf16_rounding_key": (ctypes.c_uint64, [ctypes.c_uint64, _int]),
+    "psgd_uvd_apply_bf16": (_int, [_c_f32p] * 5 + [_i64, _int, _c_ws, _i64, _strm]),
+    "psgd_uvd_update_bf16": (_int, [_c_f32p] * 5 + [_i64, _int, _flt, _flt, _int, _int, _int, ctypes.c_uint64, _c_ws, _i64, _strm]),
+    "psgd_uvd_update_apply_bf16": (_int, [_c_f32p] * 7 + [_i64, _int, _flt, _flt, _int, _int, _int, ctypes.c_uint64, _c_ws, _i64,
+                                          _strm]),
     "psgd_splu_workspace_bytes": (_i64, [_i64, _int]),
     "psgd_splu_apply_f32": (_int, [_c_f32p] * 6 + [_i64, _int, _c_ws, _i64, _strm]),
     "psgd_splu_update_f32": (_int, [_c_f32p] * 10 + [_i64, _int, ctypes.c_float, ctypes.c_float, _c_ws, _i64, _strm]),

@@ -111,6 +111,100 @@ def uvd_workspace(device, N, r):
     return _ws_cache.get(key, make)
 
 
+def uvd_bf16_workspace(device, N, r):
+    """Cached workspace of the bf16-state kernels (psgd_uvd_bf16_workspace_bytes: a layout of its own), per stream."""
+    key = ("uvd_bf16", device.index if device.index is not None else torch.cuda.current_device(), int(N), int(r),
+           torch.cuda.current_stream(device).cuda_stream)
+
+    def make():
+        nbytes = _lib.load().psgd_uvd_bf16_workspace_bytes(N, r)
+        if nbytes < 0:
+            _lib.check(int(nbytes), "psgd_uvd_bf16_workspace_bytes")
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    return _ws_cache.get(key, make)
+
+
+_ROUNDINGS = {"nearest": 0, "stochastic": 1}
+
+
+def _bf16_state(name, U, V, d, *cols):
+    """True when U, V, d are a bf16-stored state (psgd_uvd_bf16.hip); raises for the combinations that path does not cover.
+    Its limits: U, V, d all bfloat16 (float16 is not supported), fp32 column vectors, rank <= 32."""
+    state = (U, V, d)
+    if not all(isinstance(t, torch.Tensor) for t in state):
+        return False
+    dts = {t.dtype for t in state}
+    if dts == {torch.float32} or not (dts & {torch.bfloat16, torch.float16}):
+        return False
+    if torch.float16 in dts:
+        raise TypeError("%s: a float16 state is not supported (the native narrow state is bfloat16 only)" % name)
+    if dts != {torch.bfloat16}:
+        raise TypeError("%s: mixed state dtypes %s; U, V and d must all be bfloat16 (or all float32)"
+                        % (name, sorted(str(x) for x in dts)))
+    for t in state + cols:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: expected torch tensors, got %r" % (name, type(t)))
+        if not t.is_cuda:
+            raise _lib.PsgdHipError("%s runs on the HIP device only (tensor is on %s); no CPU fallback" % (name, t.device))
+        if t.device != U.device:
+            raise ValueError("%s: all tensors must be on one device" % name)
+    for c in cols:
+        if c.dtype != torch.float32:
+            raise TypeError("%s: with a bfloat16 state the vectors v, h, g and out stay float32, got %s" % (name, c.dtype))
+    if U.dim() == 2 and U.shape[1] > _lib.UVD_MAX_RANK:
+        raise ValueError("%s: a bfloat16 state supports ranks up to %d, got %d" % (name, _lib.UVD_MAX_RANK, U.shape[1]))
+    return True
+
+
+def _rounding_args(name, rounding, rounding_seed, generator):
+    if rounding not in _ROUNDINGS:
+        raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (name, rounding))
+    if rounding_seed is None:
+        if rounding == "stochastic":     # from the branch generator, never from the global CUDA generator
+            gen = generator if generator is not None else _branch_rng
+            rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=gen).item())
+        else:
+            rounding_seed = 0
+    return _ROUNDINGS[rounding], int(rounding_seed) & (2 ** 64 - 1)
+
+
+def _mix64(z):
+    """the splitmix64 finaliser (step seeds of class UVd)"""
+    z &= 2 ** 64 - 1
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & (2 ** 64 - 1)
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & (2 ** 64 - 1)
+    return z ^ (z >> 31)
+
+
+def uvd_step_rounding_seed(seed0, k):
+    """rounding seed of step k (0, 1, ...) of a UVd optimizer whose construction seed is seed0: a hash of both, not a sum, and the
+    kernels hash it again before the tensor id enters (psgd_uvd_bf16_rounding_key) -- no two (step, tensor) streams coincide"""
+    return _mix64(_mix64(int(seed0)) + 0x9E3779B97F4A7C15 * (int(k) + 1))
+
+
+def _bf16_call(name, U, V, d, g, out, balance, update_U, rounding, rounding_seed, generator, cols):
+    """what the three bf16-state calls share: shape checks, the branch draws (reference order), rounding mode and seed, the
+    output and the workspace.  balance is None for the apply (no draws, no rounding)."""
+    if g is not None and g.dim() == 2 and g.shape[1] > 1:
+        raise ValueError("%s: a matrix g is not supported with a bfloat16 state (column vectors only)" % name)
+    N, r = _uvd_shapes(name, U, V, d, *cols)
+    mode = seed = 0
+    if rounding is not None:
+        if balance is None:
+            balance = _draw_branch(0.01, generator)
+        if update_U is None:
+            update_U = _draw_branch(0.5, generator)
+        mode, seed = _rounding_args(name, rounding, rounding_seed, generator)
+    if g is not None:
+        if out is None:
+            out = torch.empty_like(g)
+        elif out.shape != g.shape or not out.is_contiguous():
+            raise ValueError("%s: out must be contiguous and shaped like g" % name)
+    ws = uvd_bf16_workspace(U.device, N, r)
+    tail = (ws.data_ptr(), ws.numel(), _stream_ptr(U.device))
+    return N, r, int(bool(balance)), int(bool(update_U)), mode, seed, out, tail
+
+
 def _uvd_shapes(name, U, V, *cols):
     if U.dim() != 2 or V.shape != U.shape:
         raise ValueError("%s: U and V must both be [N, r]" % name)
@@ -377,6 +471,13 @@ def precond_grad_UVd_math(U, V, d, g, *, out=None):
     the columns and U, V are swept once per group of four columns (psgd_uvd_apply_cols_f32).
     out (extension; column-vector g, r <= 32): a contiguous fp32 tensor shaped like g to write the result to (placement.UVdArena.out)."""
     U, V, d = _c(U), _c(V), _c(d)
+    if _bf16_state("precond_grad_UVd_math", U, V, d, *([g] if out is None else [g, out])):
+        # bf16-stored state (psgd_uvd_bf16.hip): fp32 column vector g, r <= 32
+        g = _c(g)
+        N, r, _, _, _, _, out, tail = _bf16_call("precond_grad_UVd_math", U, V, d, g, out, None, None, None, None, None, (g,))
+        rc = _lib.load().psgd_uvd_apply_bf16(U.data_ptr(), V.data_ptr(), d.data_ptr(), g.data_ptr(), out.data_ptr(), N, r, *tail)
+        _lib.check(rc, "psgd_uvd_apply_bf16")
+        return out
     if isinstance(g, torch.Tensor) and g.dim() == 2 and g.shape[1] > 1:
         dev = _require_hip("precond_grad_UVd_math", U, V, d)
         if not g.is_cuda or g.dtype != torch.float32 or g.device != dev:
@@ -417,14 +518,33 @@ def _draw_branch(p, generator):
     return bool(torch.rand((), generator=gen).item() < p)
 
 
-def update_precond_UVd_math_(U, V, d, v, h, step, tiny, *, balance=None, update_U=None, generator=None):
+def update_precond_UVd_math_(U, V, d, v, h, step, tiny, *, balance=None, update_U=None, generator=None,
+                             rounding="nearest", rounding_seed=None):
     """psgd.py:554-617.  Updates U or V, and d, IN PLACE; returns None.
 
     balance / update_U fix the two random branches of the reference (:562 p=0.01, :588 p=0.5);
     left at None they are drawn from `generator` (a CPU torch.Generator; module default otherwise),
-    in the reference's order."""
+    in the reference's order.
+
+    A bfloat16 U, V, d (all three; fp32 v, h; r <= 32) is updated by the bf16-state kernels: fp32 arithmetic, each written
+    element narrowed once -- rounding="nearest" or "stochastic" (seeded by rounding_seed; None draws one from `generator` /
+    the module's branch generator after the branch draws).  An fp32 state is not rounded: any rounding other than the default, or
+    a rounding_seed, raises ValueError there."""
     state = _InPlace(U, V, d)
     (U, V, d), v, h = state.work, _c(v), _c(h)
+    if rounding not in _ROUNDINGS:
+        raise ValueError("update_precond_UVd_math_: rounding must be 'nearest' or 'stochastic', got %r" % (rounding,))
+    if _bf16_state("update_precond_UVd_math_", U, V, d, v, h):
+        N, r, bal, upd, mode, seed, _, tail = _bf16_call("update_precond_UVd_math_", U, V, d, None, None, balance, update_U,
+                                                          rounding, rounding_seed, generator, (v, h))
+        rc = _lib.load().psgd_uvd_update_bf16(U.data_ptr(), V.data_ptr(), d.data_ptr(), v.data_ptr(), h.data_ptr(), N, r,
+                                               float(step), float(tiny), bal, upd, mode, seed, *tail)
+        _lib.check(rc, "psgd_uvd_update_bf16")
+        state.writeback()
+        return None
+    if rounding != "nearest" or rounding_seed is not None:
+        raise ValueError("update_precond_UVd_math_: rounding / rounding_seed apply to a bfloat16 state only; an fp32 state is not "
+                         "rounded")
     dev = _require_hip("update_precond_UVd_math_", U, V, d, v, h)
     N, r = _uvd_shapes("update_precond_UVd_math_", U, V, d, v, h)
     if balance is None:
@@ -445,7 +565,7 @@ def update_precond_UVd_math_(U, V, d, v, h, step, tiny, *, balance=None, update_
 
 
 def update_precond_UVd_math_and_precond_grad(U, V, d, v, h, g, step, tiny, *, balance=None, update_U=None,
-                                             generator=None, out=None):
+                                             generator=None, out=None, rounding="nearest", rounding_seed=None):
     """Extension: update_precond_UVd_math_(U, V, d, v, h, step, tiny) followed by
     precond_grad_UVd_math(U, V, d, g) on the updated state -- the UVd.step pattern (psgd.py:732 -> :748) --
     as one fused call that saves a pass over V.  U or V, and d, are updated in place; returns the
@@ -453,6 +573,22 @@ def update_precond_UVd_math_and_precond_grad(U, V, d, v, h, g, step, tiny, *, ba
     where the output stream lives is worth 4 % of the last sweep); ranks above 32 ignore it."""
     state = _InPlace(U, V, d)
     (U, V, d), v, h, g = state.work, _c(v), _c(h), _c(g)
+    name = "update_precond_UVd_math_and_precond_grad"
+    if rounding not in _ROUNDINGS:
+        raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (name, rounding))
+    if _bf16_state(name, U, V, d, *([v, h, g] if out is None else [v, h, g, out])):
+        # bf16-stored state: rounding / rounding_seed as in update_precond_UVd_math_; the gradient is preconditioned with the
+        # state as it was stored (rounded)
+        N, r, bal, upd, mode, seed, out, tail = _bf16_call(name, U, V, d, g, out, balance, update_U, rounding, rounding_seed,
+                                                            generator, (v, h, g))
+        rc = _lib.load().psgd_uvd_update_apply_bf16(U.data_ptr(), V.data_ptr(), d.data_ptr(), v.data_ptr(), h.data_ptr(),
+                                                     g.data_ptr(), out.data_ptr(), N, r, float(step), float(tiny), bal, upd, mode,
+                                                     seed, *tail)
+        _lib.check(rc, "psgd_uvd_update_apply_bf16")
+        state.writeback()
+        return out
+    if rounding != "nearest" or rounding_seed is not None:
+        raise ValueError("%s: rounding / rounding_seed apply to a bfloat16 state only; an fp32 state is not rounded" % name)
     dev = _require_hip("update_precond_UVd_math_and_precond_grad", U, V, d, v, h, g)
     N, r = _uvd_shapes("update_precond_UVd_math_and_precond_grad", U, V, d, v, h, g)
     if balance is None:
@@ -544,7 +680,7 @@ class UVd:
                  lr_params=0.01, lr_preconditioner=0.01,
                  grad_clip_max_norm=None, preconditioner_update_probability=1.0,
                  exact_hessian_vector_product: bool = True, generator=None, state_dtype=None, group=None,
-                 stage_backend=None, placement="auto"):
+                 stage_backend=None, placement="auto", state_route="widen", state_rounding=None):
         # group (extension): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
         # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the
         # concatenation of the ranks' vectors in rank order, and U, V, d hold this rank's rows only.  A step then costs three
@@ -577,6 +713,32 @@ class UVd:
         r = int(rank_of_modification)
         if r < 1:
             raise ValueError("UVd: rank_of_modification must be >= 1, got %d" % r)
+        # state_route (extension): "widen" (default) = the behaviour above for a narrow state_dtype; "native" = a bfloat16 state is
+        # read and written by the bf16-state kernels themselves (psgd_uvd_bf16.hip): no fp32 copies of U, V, d exist at any time.
+        # state_rounding: how those kernels narrow what they write, "stochastic" (default of the native route: under round to
+        # nearest a bf16 d practically stops learning, its increments are below half a spacing) or "nearest".  The seed of step k
+        # is a hash of one seed fixed here (drawn from `generator` when given, the module's branch generator otherwise) and k
+        # (uvd_step_rounding_seed).
+        if state_route not in ("widen", "native"):
+            raise ValueError("UVd: state_route must be 'widen' or 'native', got %r" % (state_route,))
+        self._native = state_route == "native"
+        if self._native:
+            if self._store_dtype != torch.bfloat16:
+                raise ValueError("UVd: state_route='native' needs a bfloat16 state (state_dtype=torch.bfloat16, or 'param' with "
+                                 "bfloat16 parameters), got %s" % (self._store_dtype,))
+            if r > _lib.UVD_MAX_RANK:
+                raise ValueError("UVd: state_route='native' supports ranks up to %d, got %d" % (_lib.UVD_MAX_RANK, r))
+            if group is not None or stage_backend is not None:
+                raise ValueError("UVd: state_route='native' does not support the row-sharded optimizer (group= / stage_backend=)")
+            state_rounding = "stochastic" if state_rounding is None else state_rounding
+            if state_rounding not in _ROUNDINGS:
+                raise ValueError("UVd: state_rounding must be 'stochastic' or 'nearest', got %r" % (state_rounding,))
+            gen = generator if generator is not None else _branch_rng
+            self._round_seed0 = int(torch.randint(0, 2 ** 62, (), generator=gen).item())
+            self._round_step = 0
+        elif state_rounding is not None:
+            raise ValueError("UVd: state_rounding applies to state_route='native' only")
+        self._state_rounding = state_rounding
         self.lr_params = _Hyper(lr_params)                                                   # :673
         self.lr_preconditioner = _Hyper(lr_preconditioner)                                   # :674
         self.grad_clip_max_norm = _Hyper(math.inf if grad_clip_max_norm is None else grad_clip_max_norm)  # :675-678
@@ -624,13 +786,14 @@ class UVd:
             self._U, self._V, self._d = (x.to(self._store_dtype) for x in (self._U, self._V, self._d))
 
     def _state_fp32(self):
-        """the state the kernels work on: the stored tensors themselves, or fp32 copies of a half-precision state"""
-        if self._store_dtype == torch.float32:
+        """the state the kernels work on: the stored tensors themselves (fp32, or bf16 on the native route), or fp32 copies of a
+        half-precision state"""
+        if self._store_dtype == torch.float32 or self._native:
             return self._U, self._V, self._d
         return self._U.float(), self._V.float(), self._d.float()
 
     def _state_store(self, U, V, d):
-        if self._store_dtype != torch.float32:
+        if self._store_dtype != torch.float32 and not self._native:
             self._U.copy_(U)
             self._V.copy_(V)
             self._d.copy_(d)
@@ -683,7 +846,13 @@ class UVd:
             grad = self._flat(grads, "g")                                                     # :747
             # :732-733 then :748 as one fused call (same results, three sweeps instead of six)
             U, V, d = self._state_fp32()
-            if self._group is None:
+            if self._native:                       # the stored bf16 tensors go straight to the fused call
+                seed = uvd_step_rounding_seed(self._round_seed0, self._round_step)
+                self._round_step += 1
+                pre_grad = update_precond_UVd_math_and_precond_grad(
+                    U, V, d, v[:, None], h[:, None], grad[:, None], step=float(self.lr_preconditioner), tiny=self._tiny,
+                    generator=self._generator, rounding=self._state_rounding, rounding_seed=seed)
+            elif self._group is None:
                 pre_grad = update_precond_UVd_math_and_precond_grad(
                     U, V, d, v[:, None].contiguous(), h[:, None].contiguous(),
                     grad[:, None].contiguous(), step=float(self.lr_preconditioner), tiny=self._tiny,
