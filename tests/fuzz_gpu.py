@@ -1,6 +1,8 @@
 """Randomised parity sweep on the GPU: many random shapes per entry-point family against independent fp64 torch
 restatements (oracle/psgd_oracle_torch.py and local block formulas).  TEST INFRASTRUCTURE (it imports oracle/).
-tests/test_fuzz_gpu.py runs it for a few seconds; longer sweeps: python tests/fuzz_gpu.py [seconds]"""
+tests/test_fuzz_gpu.py runs the six-family rotation of run() for a few seconds; tests/test_fuzz_families_gpu.py runs a fixed
+number of cases of the other families through run_cases(); longer sweeps over all of them: python tests/fuzz_gpu.py [seconds]"""
+import hashlib
 import os
 import sys
 import time
@@ -193,8 +195,8 @@ def fuzz_uvd(g, it):
                 rel(U, U64), rel(V, V64), rel(d, d64))
         X = torch.cat([gr, v, d], 1).contiguous()
         e = max(e, rel(psgd.IpUVtmatvec(U, V, X), ref64.IpUVtmatvec(U.double(), V.double(), X.double())))
-        if r > 32:                                    # precond_grad_UVd_math on a matrix g (three columns)
-            e = max(e, rel(psgd.precond_grad_UVd_math(U, V, d, X), ref64.precond_grad_UVd_math(U64, V64, d64, X.double())))
+        # precond_grad_UVd_math on a matrix g (three columns): psgd_uvd_apply_cols_f32 up to rank 32, the column chunks above
+        e = max(e, rel(psgd.precond_grad_UVd_math(U, V, d, X), ref64.precond_grad_UVd_math(U64, V64, d64, X.double())))
     tol = 2e-5 if r > 32 else 1e-5
     if not e < tol:
         # Before calling it a failure: how far does the fp64 update itself move when its fp32 inputs are perturbed by
@@ -224,6 +226,12 @@ def splu_apply64(L12, l3, U12, u3, x, r):
     return torch.cat([U1.t() @ Lt1, U2.t() @ Lt1 + u3 * (l3 * Qg2)], 0)
 
 
+def _rel_np(a, b):
+    import numpy as np
+    den = np.linalg.norm(b)
+    return float(np.linalg.norm(a - b) / (den if den > 0 else 1.0))
+
+
 def fuzz_splu(g, it):
     r = int(torch.randint(1, 33, (1,), generator=g, device=dev))
     if it % 5 == 2:                                   # ranks 33 .. 64: the native kernels on 64-row tiles (round 5); above: column chunks
@@ -245,7 +253,193 @@ def fuzz_splu(g, it):
     new = psgd.update_precond_splu(L12, l3, U12, u3, [x], [dg], 0.05)
     # the updated factors must still give a symmetric positive P consistent with their own fp64 apply
     e2 = rel(psgd.precond_grad_splu(*new, [gr])[0], splu_apply64(*[t.double() for t in new], gr.double(), r))
-    return "splu N=%d r=%d" % (N, r), max(e1, e2), 1e-5
+    # the four factors against the numpy fp64 oracle, bars of tests/test_splu_gpu.py: 1e-5 on each non-empty factor, 2e-3 on its
+    # increment over the rho-balanced base (reported on the 1e-5 scale), exact zeros in the strict triangles of L1 / U1
+    import numpy as np
+    from oracle import psgd_oracle as orc
+    n64 = lambda t: t.cpu().numpy().astype(np.float64)
+    q = [n64(t) for t in (L12, l3, U12, u3)]
+    ref = orc.update_precond_splu(*q, [n64(x)], [n64(dg)], 0.05)
+    rho = np.sqrt(max(np.max(np.diag(q[0][:r])), np.max(q[1], initial=-np.inf)) /
+                  max(np.max(np.diag(q[2][:, :r])), np.max(q[3], initial=-np.inf)))
+    base = (q[0] / rho, q[1] / rho, q[2] * rho, q[3] * rho)
+    e3 = e4 = 0.0
+    for got, want, b0 in zip(new, ref, base):
+        if want.size == 0:
+            continue
+        got = n64(got)
+        e3 = max(e3, _rel_np(got, want))
+        e4 = max(e4, _rel_np(got - b0, want - b0))
+    if bool(torch.triu(new[0][:r], 1).any()) or bool(torch.tril(new[2][:, :r], -1).any()):
+        print("splu N=%d r=%d: a strict triangle of L1 / U1 is not zero" % (N, r), flush=True)
+        e3 = float("inf")
+    return "splu N=%d r=%d" % (N, r), max(e1, e2, e3, e4 * (1e-5 / 2e-3)), 1e-5
+
+
+# ------------------------------------------------------------------------------------------------ dense (psgd_dense.hip)
+_DENSE_EDGES = (("edge64", 64, 47), ("edge256", 256, 12), ("edge1024", 1024, 3), ("route64", 64, 2))   # class, multiple, k < this
+
+
+def _split_list(flat, g):
+    """flat [N] as a list of 1 .. 4 tensors of random shapes (the list arguments of psgd.py:34-35 / :48-53)"""
+    n = flat.numel()
+    k = min(randint(1, 5, g), n)
+    cuts = sorted(set([0, n] + [randint(1, n, g) for _ in range(k - 1)])) if n > 1 else [0, n]
+    parts = []
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        m, kind = hi - lo, randint(0, 4, g)
+        p = [q for q in (2, 3, 4, 5) if m % q == 0]
+        shape = ((m,), (m, 1), (1, m), (p[0], m // p[0]) if p else (m,))[kind]
+        parts.append(flat[lo:hi].reshape(shape).clone())
+    return parts
+
+
+def dense_update64(Q, dx, dg, step):
+    """psgd.py:34-42 in fp64 torch ops (G formed, O(N^3)); the solve reads the upper triangle of Q only, as the reference's does"""
+    a = Q @ dg
+    b = torch.linalg.solve_triangular(Q.t(), dx, upper=False)
+    grad = torch.triu(a @ a.t() - b @ b.t())
+    return Q - ((step / (grad.abs().max() + TINY)) * grad) @ Q
+
+
+DENSE_RATIOS = []      # (case, err_native / err_torch on Q_new, on the increment, on the apply) of the c = 2.0 cases
+
+
+def fuzz_dense(g, it):
+    """update_precond_dense and precond_grad_dense on N in [1, 3000]: tile, workgroup and route edges, an upper-triangular or a full
+    Q, Q at an unaligned address, list arguments, data of any magnitude; bars of tests/test_dense_gpu.py (Q_new 1e-5, its increment
+    2e-3, the apply 1e-5, exact zeros below the diagonal of an upper-triangular Q).  Reported: the largest error / bar."""
+    N = randint(1, 3001, g)
+    tags = []
+    if it % 3 == 0:                                   # on a tile / workgroup / route edge, or up to four off it
+        name, mult, khi = _DENSE_EDGES[(it // 3) % 4]
+        N = mult * randint(1, khi, g) + randint(-4, 5, g)
+        tags.append(name)
+    unaligned = it % 4 == 1
+    if unaligned:                                     # N % 4 == 0 at an address that is not: update_large<1> / apply_large<1>
+        N = max(4, N // 4 * 4)
+        tags.append("unaligned")
+    upper = it % 2 == 0
+    c = (0.3, 1.0, 2.0)[randint(0, 3, g)]
+    step = (0.01, 0.1)[randint(0, 2, g)]
+    Q = torch.triu(torch.randn(N, N, device=dev, generator=g) * (c / N ** 0.5), 1) \
+        + torch.diag(torch.exp(torch.empty(N, device=dev).uniform_(-1.6, 1.6, generator=g)))
+    if not upper:
+        Q = Q + torch.tril(torch.randn(N, N, device=dev, generator=g) * (0.3 / N ** 0.5), -1)
+    dx, dg, gr = (torch.randn(N, device=dev, generator=g) for _ in range(3))
+    if (it + it // 3) % 3 == 1:                       # one case in three, moving through the residues of the other switches
+        s = 10.0 ** float(torch.empty(1, device=dev).uniform_(-12, 12, generator=g))
+        dx, dg = dx * s, dg / s * torch.exp(torch.empty(N, device=dev).uniform_(-2, 2, generator=g))
+        tags.append("s=%.0e" % s)
+    if unaligned:
+        buf = torch.zeros(N * N + 4, device=dev)
+        off = randint(1, 4, g)
+        Qv = buf[off:off + N * N].view(N, N)
+        Qv.copy_(Q)
+        Q = Qv
+        if Q.data_ptr() % 16 == 0 or not Q.is_contiguous():
+            raise RuntimeError("fuzz_dense: the view at offset %d is aligned" % off)
+    dxs, dgs, grs = _split_list(dx, g), _split_list(dg, g), _split_list(gr, g)
+    Q0 = Q.clone()
+    Q64, dx64, dg64, gr64 = Q.double(), dx.double()[:, None], dg.double()[:, None], gr.double()[:, None]
+    ref_q, ref_p = dense_update64(Q64, dx64, dg64, step), Q64.t() @ (Q64 @ gr64)
+
+    def errs(route):
+        psgd.set_dense_route(route)
+        try:
+            qn = psgd.update_precond_dense(Q, dxs, dgs, step)
+            pg = psgd.precond_grad_dense(Q, grs)
+        finally:
+            psgd.set_dense_route("native")
+        if [tuple(p.shape) for p in pg] != [tuple(t.shape) for t in grs] or qn.shape != Q.shape:
+            return qn, (float("inf"),) * 3
+        return qn, (rel(qn, ref_q), rel(qn.double() - Q64, ref_q - Q64), rel(torch.cat([p.reshape(-1) for p in pg]), ref_p))
+    bars = (1e-5, 2e-3, 1e-5)
+    qn, e_nat = errs("native")
+    worst = max(e / b for e, b in zip(e_nat, bars))
+    name = "dense N=%d %s c=%.1f step=%.2f%s" % (N, "upper" if upper else "full", c, step, "".join(" " + t for t in tags))
+    if upper and bool(torch.tril(qn, -1).any()):
+        print(name + ": the strict lower triangle is not zero", flush=True)
+        worst = float("inf")
+    if not torch.equal(Q, Q0):
+        print(name + ": Q was modified", flush=True)
+        worst = float("inf")
+    if c == 2.0:
+        # The least benign Q, where the blocked solve's explicit block inverses matter most: the torch-op route on the same inputs.
+        # err_native <= 2 err_torch + bar is implied by the bars above (its floor IS the bar), so it cannot fail on its own: what
+        # it adds is the record of err_native / err_torch in DENSE_RATIOS (profiles/fuzz_families.txt).
+        _, e_tor = errs("torch")
+        DENSE_RATIOS.append((name,) + tuple(n / t if t > 0 else float("inf") for n, t in zip(e_nat, e_tor)))
+        worst = max([worst] + [n / (2 * t + b) for n, t, b in zip(e_nat, e_tor, bars)])
+    return name + " [Q %.1e inc %.1e apply %.1e]" % e_nat, worst, 1.0
+
+
+# ------------------------------------------------------------------------------------------------ bf16-state UVd (psgd_uvd_bf16.hip)
+def uvd_bf16_tile_rows(r):
+    """rows per tile of psgd_uvd_bf16.hip at rank r (make_geo): 256 at ranks 1 .. 8, 16 and 29 .. 32; 136 .. 240 at the others"""
+    m = min(256 // r, 32)
+    return 256 // (8 * m) * (8 * m)
+
+
+def fuzz_uvd_bf16(g, it):
+    """The apply, the update and the fused call on a bf16-stored state, inputs as in fuzz_uvd with U, V, d rounded to bf16 first, the
+    fp64 oracle on the widened values; bars of tests/test_uvd_bf16_gpu.py.  Reported: the largest error / bar."""
+    import numpy as np
+    from tests.uvd_cases import check_bf16_state
+    r = randint(1, 33, g)
+    hi = 400000 if it % 4 == 0 else 20000
+    N = randint(max(r, 2), hi, g)
+    edge = ""
+    if it % 3 == 1:                                   # a partial last tile of 1 .. 63 rows behind whole tiles of 64, 256 and the family's own
+        mult = (64, 256, uvd_bf16_tile_rows(r))[(it // 3) % 3]
+        N = mult * randint(1, max(2, hi // mult), g) + randint(1, 64, g)
+        edge = " edge%s" % ("TR%d" % mult if (it // 3) % 3 == 2 else mult)
+    gain = 2.0 if it % 3 else float(torch.empty(1, device=dev).uniform_(0.5, 1.5, generator=g)) * r ** 0.5
+    sc = gain * (1.0 / (N * r)) ** 0.5
+    U, V = torch.randn(N, r, device=dev, generator=g) * sc, torch.randn(N, r, device=dev, generator=g) * sc
+    if it % 3 == 0 and N > 4 * r:
+        V = (0.5 * U @ torch.linalg.qr(torch.randn(r, r, device=dev, generator=g))[0] + 0.7 * V).contiguous()
+    d = torch.exp(0.3 * torch.randn(N, 1, device=dev, generator=g))
+    gr, v = torch.randn(N, 1, device=dev, generator=g), torch.randn(N, 1, device=dev, generator=g)
+    h = v * torch.exp(torch.empty(N, 1, device=dev).uniform_(-4.6, 4.6, generator=g))
+    upd, bal = bool(it % 2), it % 5 == 0
+    rounding = "stochastic" if (it // 2) % 2 else "nearest"
+    fused = (it // 4) % 2 == 0
+    seed = randint(0, 2 ** 31, g)
+    bf = torch.bfloat16
+    Ub, Vb, db = U.to(bf), V.to(bf), d.to(bf)
+    name = "uvd-bf16 N=%d r=%d %s%s %s %s%s" % (N, r, "U" if upd else "V", " bal" if bal else "", rounding,
+                                               "fused" if fused else "two-call", edge)
+    e_apply = rel(psgd.precond_grad_UVd_math(Ub, Vb, db, gr), ref64.precond_grad_UVd_math(Ub.double(), Vb.double(), db.double(), gr.double()))
+    U64, V64, d64 = Ub.double(), Vb.double(), db.double()
+    ref64.update_precond_UVd_math_(U64, V64, d64, v.double(), h.double(), 0.01, TINY, balance=bal, update_U=upd)
+    Uw, Vw, dw = Ub.float(), Vb.float(), db.float()   # the yardstick of the code shares: the fp32 kernels on the widened inputs
+    psgd.update_precond_UVd_math_(Uw, Vw, dw, v, h, 0.01, TINY, balance=bal, update_U=upd)
+    Ut, Vt, dt = Ub.clone(), Vb.clone(), db.clone()
+    kw = dict(balance=bal, update_U=upd, rounding=rounding, rounding_seed=seed)
+    if fused:
+        out = psgd.update_precond_UVd_math_and_precond_grad(Ut, Vt, dt, v, h, gr, 0.01, TINY, **kw)
+    else:
+        psgd.update_precond_UVd_math_(Ut, Vt, dt, v, h, 0.01, TINY, **kw)
+        out = psgd.precond_grad_UVd_math(Ut, Vt, dt, gr)
+    e_grad = rel(out, ref64.precond_grad_UVd_math(Ut.double(), Vt.double(), dt.double(), gr.double()))
+    worst = max(e_apply, e_grad) / 1e-5
+    written = {"d", "U" if upd else "V"} | ({"U", "V"} if bal else set())
+    for k, a, b in (("U", Ut, Ub), ("V", Vt, Vb)):
+        if k not in written and not torch.equal(a.view(torch.int16), b.view(torch.int16)):
+            print(name + ": %s was written" % k, flush=True)
+            worst = float("inf")
+    if any(t.dtype != bf for t in (Ut, Vt, dt)):
+        worst = float("inf")
+    n64 = lambda t: t.double().cpu().numpy()
+    try:
+        pn, pw, w = check_bf16_state(name, dict(U=n64(Ut), V=n64(Vt), d=n64(dt)), dict(U=n64(U64), V=n64(V64), d=n64(d64)),
+                                     dict(U=Uw.cpu().numpy(), V=Vw.cpu().numpy(), d=dw.cpu().numpy()), written, rounding)
+        worst = max(worst, w, pn / (2 * pw + 1e-4))   # nearest: codes off RNE(y64); stochastic: codes that are neither floor nor ceil
+    except AssertionError as ex:
+        print(name + ": element bound missed: %s" % (ex,), flush=True)
+        worst = float("inf")
+    return name + " [apply %.1e grad %.1e]" % (e_apply, e_grad), worst, 1.0
 
 
 def run(budget, seed=1):
@@ -268,8 +462,52 @@ def run(budget, seed=1):
     return it, bad, worst
 
 
+FAMILIES = {"kron": fuzz_kron, "kron-bf16": fuzz_kron_bf16, "kron-bf16-upd": fuzz_kron_bf16_update, "uvd": fuzz_uvd, "splu": fuzz_splu,
+            "kron-sparse": fuzz_kron_sparse, "dense": fuzz_dense, "uvd-bf16": fuzz_uvd_bf16}
+
+
+def _tally(name, err, tol, worst, bad):
+    """the bookkeeping of run()'s loop body (run() itself stays as it was: earlier recorded sweeps remain comparable)"""
+    fam = name.split()[0]
+    if err > worst.get(fam, (0, ""))[0]:
+        worst[fam] = (err, name)
+    if not (err < tol):
+        bad.append((name, err))
+        print("FAIL", name, err, flush=True)
+
+
+def run_cases(families, n_per_family, seed, log=None):
+    """Exactly n_per_family cases of each family (names of FAMILIES), each family on a generator of its own seeded from (seed, name)
+    and its own counter it = 0 .. n - 1: which cases run depends on nothing but the arguments.  Returns (cases, bad, worst) as run()
+    does; log (a list) receives every case's (name, err, tol)."""
+    _lib.load()
+    cases, worst, bad = 0, {}, []
+    for fam in families:
+        key = int.from_bytes(hashlib.sha256(("%d/%s" % (seed, fam)).encode()).digest()[:7], "little")
+        g = torch.Generator(device=dev).manual_seed(key)
+        for it in range(n_per_family):
+            name, err, tol = FAMILIES[fam](g, it)
+            _tally(name, err, tol, worst, bad)
+            if log is not None:
+                log.append((name, err, tol))
+            cases += 1
+    return cases, bad, worst
+
+
+def run_all(budget, seed=1):
+    """the command line's sweep: run()'s rotation over every family of FAMILIES"""
+    _lib.load()
+    g = torch.Generator(device=dev).manual_seed(seed)
+    fams = [fuzz_uvd, fuzz_splu] if _WIDE_ONLY else list(FAMILIES.values())
+    t0, it, worst, bad = time.time(), 0, {}, []
+    while time.time() - t0 < budget:
+        _tally(*fams[it % len(fams)](g, it // len(fams)), worst, bad)
+        it += 1
+    return it, bad, worst
+
+
 if __name__ == "__main__":
-    cases, bad, worst = run(float(sys.argv[1]) if len(sys.argv) > 1 else 120.0, int(os.environ.get("FUZZ_SEED", "1")))
+    cases, bad, worst = run_all(float(sys.argv[1]) if len(sys.argv) > 1 else 120.0, int(os.environ.get("FUZZ_SEED", "1")))
     print("cases", cases, "failures", len(bad), "kron cases with a side >= 4096:", LARGE_KRON[0])
     for fam, (e, n) in worst.items():
         print("worst %-10s %.3e  (%s)" % (fam, e, n))

@@ -8,7 +8,7 @@ from tests.uvd_cases import rel_err
 
 pytestmark = pytest.mark.gpu
 
-SIZES = (1, 2, 3, 31, 64, 65, 127, 128, 129, 400, 1000, 1021, 4096)
+SIZES = (1, 2, 3, 31, 64, 65, 66, 68, 127, 128, 129, 192, 255, 256, 257, 400, 1000, 1021, 1023, 1024, 1025, 1028, 4096)
 
 
 @pytest.fixture
@@ -54,6 +54,90 @@ def test_update_and_apply_match_fp64(psgd, n, dense):
     assert rel_err(pg.cpu().numpy(), ref_pg) < 1e-5
     if not dense:
         assert not np.tril(got, -1).any()                      # an upper-triangular Q stays upper-triangular, exactly
+
+
+def _unaligned(t):
+    """t as a contiguous view 1 .. 3 floats into a larger buffer: its address is not a multiple of 16 bytes"""
+    n = t.numel()
+    for off in (1, 2, 3):
+        v = torch.zeros(n + 4, device=t.device, dtype=t.dtype)[off:off + n].view(t.shape)
+        if v.data_ptr() % 16:
+            v.copy_(t)
+            return v
+    raise AssertionError("no unaligned view")
+
+
+@pytest.mark.parametrize("dense", [False, True], ids=["upper", "dense"])
+@pytest.mark.parametrize("n", [68, 256, 1024])
+def test_unaligned_q_view(psgd, n, dense):
+    """N % 4 == 0 with Q at an address that is not 16-byte aligned: the scalar instantiations (update_large<1>, apply_large<1>) at
+    sizes that otherwise only see the float4 ones.  Same fp64 bars as the aligned call, equal to it within 1e-5, bit-identical on
+    repeat."""
+    Q, dx, dg, g = _problem(n, dense, seed=n + 13 * dense)
+    tQ, tdx, tdg, tg = _dev(Q, dx, dg, g)
+    vQ = _unaligned(tQ)
+    assert vQ.is_contiguous() and vQ.data_ptr() % 16 != 0 and tQ.data_ptr() % 16 == 0 and torch.equal(vQ, tQ)
+    Qa, pa = psgd.update_precond_dense(tQ, [tdx], [tdg], step=0.01), psgd.precond_grad_dense(tQ, [tg])[0]
+    Qu, pu = psgd.update_precond_dense(vQ, [tdx], [tdg], step=0.01), psgd.precond_grad_dense(vQ, [tg])[0]
+    assert torch.equal(vQ, tQ)                                    # the view is not modified
+    assert torch.equal(Qu, psgd.update_precond_dense(vQ, [tdx], [tdg], step=0.01))
+    assert torch.equal(pu, psgd.precond_grad_dense(vQ, [tg])[0])
+    Q64 = Q.astype(np.float64)
+    ref = orc.update_precond_dense(Q64, [dx.astype(np.float64)], [dg.astype(np.float64)], step=0.01)
+    ref_pg = orc.precond_grad_dense(Q64, [g.astype(np.float64)])[0]
+    for got, pg in ((Qu, pu), (Qa, pa)):
+        got = got.cpu().numpy()
+        assert rel_err(got, ref) < 1e-5
+        assert rel_err(got.astype(np.float64) - Q64, ref - Q64) < 2e-3
+        assert rel_err(pg.cpu().numpy(), ref_pg) < 1e-5
+        if not dense:
+            assert not np.tril(got, -1).any()
+    assert rel_err(Qu.cpu().numpy(), Qa.cpu().numpy()) < 1e-5
+    assert rel_err(pu.cpu().numpy(), pa.cpu().numpy()) < 1e-5
+
+
+def _solve_direction(Q64, Qn, step):
+    """With dg = 0 the update is Q_new - Q = mu triu(b b') Q with mu = step / (max_i b_i^2 + tiny): T = (Q_new - Q) Q^-1 (fp64) holds
+    mu b_i b_j at [i, j], j >= i.  Through the row and column of p = argmax T[i, i]: u_j = mu b_p b_j / sqrt(mu b_p^2) =
+    sqrt(step) b_j / max|b| up to the sign of b_p -- the solve's b up to the scale the update normalises away.  Q^-1 amplifies the
+    rounding of Q_new; the diagonal of an upper-triangular Q needs no inverse: (Q_new - Q)[i, i] / (step Q[i, i]) = (b_i / max|b|)^2.
+    Returns (u / sqrt(step), p, those squares)."""
+    D = Qn.astype(np.float64) - Q64
+    T = np.linalg.solve(Q64.T, D.T).T
+    p = int(np.argmax(np.diag(T)))
+    u = np.concatenate([T[:p, p], T[p, p:]]) / np.sqrt(T[p, p])
+    return u / np.sqrt(step), p, np.diag(D) / (step * np.diag(Q64))
+
+
+@pytest.mark.parametrize("n", [129, 1000])
+def test_blocked_solve_residual_on_a_less_benign_q(psgd, n):
+    """The blocked solve through explicit 64 x 64 block inverses on the least benign Q of the randomised sweep's domain (diagonal
+    exp(U(-1.6, 1.6)), strictly upper part 2 / sqrt(N): condition ~1e3 .. 1e5).  b = Q^-T dx is read back out of an update with
+    dg = 0 (_solve_direction; the step is free here and any value is a valid call: step = 1, against the 0.01 / 0.1 of the other
+    tests, makes the increment largest against the rounding of Q_new, which both routes share) and compared with the fp64 solve,
+    both normalised to max|b| = 1, and so are the squares (b_i / max|b|)^2 off the diagonal, which carry less of Q_new's rounding.  Bar
+    for each: twice the error of the torch-op route (torch's fp32 triangular solve) read back the same way, plus 1e-5."""
+    rng = np.random.default_rng(100 + n)
+    Q = (np.triu(rng.standard_normal((n, n)) * (2.0 / np.sqrt(n)), 1) + np.diag(np.exp(rng.uniform(-1.6, 1.6, n)))).astype(np.float32)
+    dx = rng.standard_normal(n).astype(np.float32)
+    Q64 = Q.astype(np.float64)
+    b64 = np.linalg.solve(Q64.T, dx.astype(np.float64))
+    tQ, tdx = _dev(Q, dx)
+    zero = torch.zeros(n, device="cuda")
+    err, err2 = {}, {}
+    for route in ("native", "torch"):
+        psgd.set_dense_route(route)
+        Qn = psgd.update_precond_dense(tQ, [tdx], [zero], step=1.0).cpu().numpy()
+        b, p, sq = _solve_direction(Q64, Qn, 1.0)
+        want = b64 / np.max(np.abs(b64)) * np.sign(b64[p])
+        assert abs(b64[p]) == np.max(np.abs(b64))                # the pivot is the largest entry of the true solution
+        err[route] = rel_err(b, want)
+        err2[route] = rel_err(sq, want * want)
+    psgd.set_dense_route("native")
+    print("solve n=%d cond %.1e: b native %.2e torch %.2e, b^2 native %.2e torch %.2e"
+          % (n, np.linalg.cond(Q64), err["native"], err["torch"], err2["native"], err2["torch"]))
+    assert err["native"] <= 2 * err["torch"] + 1e-5, err
+    assert err2["native"] <= 2 * err2["torch"] + 1e-5, err2
 
 
 def test_kat_r_rosenbrock_first_step(psgd):

@@ -20,7 +20,7 @@ import pytest
 import torch
 
 from oracle import psgd_oracle as orc
-from tests.uvd_cases import TINY32, make_uvd_problem, rel_err
+from tests.uvd_cases import TINY32, bf16_grid, check_bf16_state, make_uvd_problem, rel_err, to_bf16_np
 
 pytestmark = pytest.mark.gpu
 
@@ -36,20 +36,6 @@ def psgd(hip_lib):
 
 def _dev():
     return torch.device("cuda:0")
-
-
-def bf16_grid(y):
-    """(floor, ceil, round-to-nearest-even, spacing) of fp64 values on the bf16 grid (normal range)"""
-    y = np.asarray(y, dtype=np.float64)
-    _, ex = np.frexp(np.where(y == 0, 1.0, y))
-    s = np.ldexp(1.0, ex - 1 - 7)
-    q = y / s
-    return np.floor(q) * s, np.ceil(q) * s, np.round(q) * s, s
-
-
-def to_bf16_np(x):
-    """fp32 array -> the fp32 array of its bf16 roundings (round to nearest even)"""
-    return torch.from_numpy(np.ascontiguousarray(x)).to(torch.bfloat16).float().numpy()
 
 
 def problem(N, r, seed, d_spread=0.3):
@@ -93,27 +79,6 @@ def test_apply(psgd, N, r):
 
 
 # ------------------------------------------------------------------------------------------------ update, fused call
-def _check_state(tag, stored, y64, widen32, written, rounding):
-    """the element bound on every tensor; returns the pooled shares (p_native, p_widen) over the written tensors"""
-    bad_n = bad_w = total = 0
-    for k in ("U", "V", "d"):
-        s, y = stored[k], y64[k]
-        rms = float(np.sqrt(np.mean(y * y)))
-        err = np.abs(s - y)
-        bound = 2.0 ** -7 * np.abs(y) + 1e-5 * rms
-        assert np.all(err <= bound), (tag, k, float(np.max(err - bound)))
-        if k not in written:
-            continue
-        lo, hi, rne, _ = bf16_grid(y)
-        if rounding == "nearest":
-            bad_n += int(np.sum(s != rne))
-        else:
-            bad_n += int(np.sum((s != lo) & (s != hi)))
-        bad_w += int(np.sum(to_bf16_np(widen32[k]).astype(np.float64) != rne))
-        total += y.size
-    return bad_n / total, bad_w / total
-
-
 def _run_update_case(psgd, N, r, update_U, balance, fused, rounding, seed=1234):
     p = problem(N, r, seed=3 * r + N % 89 + 2 * update_U + balance)
     q = {k: v.astype(np.float64) for k, v in p.items()}
@@ -135,7 +100,7 @@ def _run_update_case(psgd, N, r, update_U, balance, fused, rounding, seed=1234):
         if k not in written:
             assert np.array_equal(stored[k], p[k].astype(np.float64)), k      # the other factor is not touched
     tag = "%s N=%d r=%d update_U=%d balance=%d %s" % ("fused" if fused else "update", N, r, update_U, balance, rounding)
-    pn, pw = _check_state(tag, stored, {k: q[k] for k in ("U", "V", "d")}, widen32, written, rounding)
+    pn, pw, _ = check_bf16_state(tag, stored, {k: q[k] for k in ("U", "V", "d")}, widen32, written, rounding)
     line = "%s p_native=%.3e p_widen=%.3e" % (tag, pn, pw)
     print(line)
     _record(line)
