@@ -49,7 +49,8 @@ extern "C" {
  * 7 = round 6 (psgd_kron_bf16_handoff_counter_offset added; bf16 tuning key 7: XCD patch of the fused pair; no layout change);
  *     later, additive: psgd_kron_dd_route_flags and the PSGD_KRON_ROUTE_* bits; the dense preconditioner's
  *     psgd_dense_workspace_bytes, psgd_dense_update_f32 and psgd_dense_apply_f32 (new symbols only: the version stays 7);
- *     the psgd_uvd_*_bf16 entry points of a bf16-stored UVd state (new symbols only).
+ *     the psgd_uvd_*_bf16 entry points of a bf16-stored UVd state (new symbols only);
+ *     psgd_uvd_pack_f32, psgd_uvd_sumsq_f32 and psgd_uvd_param_update_multi, the tail of UVd.step (new symbols only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -283,6 +284,42 @@ int psgd_uvd_update_bf16(void *U, void *V, void *d, const float *v, const float 
 int psgd_uvd_update_apply_bf16(void *U, void *V, void *d, const float *v, const float *h, const float *g, float *out,
                                int64_t N, int r, float step, float tiny, int balance, int update_U,
                                int rounding, uint64_t seed, void *ws, int64_t ws_bytes, void *stream);
+
+/* ------------------------------------------------- UVd, tail of the step ---
+ * What class UVd does around the preconditioner call (psgd.py:729-730, :747, :750-762), for any number k of parameter tensors
+ * in a fixed number of launches (psgd_uvd_tail.hip).  All k tensors of one call have one dtype (PSGD_DTYPE_*).
+ *
+ * Two DEVICE tables describe the work:
+ *   segments: k entries {uint64_t ptr; int64_t start; int64_t count} -- a tensor's device pointer (aligned to its element), its
+ *             start offset in the flat vector and its element count (0 allowed);
+ *   chunks:   nchunks entries {int64_t seg; int64_t off} -- elements [off, min(off + PSGD_UVD_TAIL_CHUNK, count)) of segment seg.
+ *             Built by the caller from the sizes alone: for every segment in order, off = 0, CHUNK, 2 CHUNK, ... while off < count,
+ *             so every flat element belongs to exactly one chunk and no chunk crosses a segment.  Entries that do not fit the
+ *             segment table (seg outside [0, k), off outside [0, count)) are skipped.
+ * Null pointers, k < 0, nchunks < 0 and an unknown dtype return PSGD_ERR_BAD_ARG before any HIP call; nchunks == 0 is a no-op.  */
+#define PSGD_DTYPE_F32   0
+#define PSGD_DTYPE_BF16  1
+#define PSGD_DTYPE_F16   2
+#define PSGD_UVD_TAIL_CHUNK      4096   /* elements per chunk */
+#define PSGD_UVD_SUMSQ_WS_BYTES  8192   /* workspace of psgd_uvd_sumsq_f32 (8-byte aligned, needs no initialisation) */
+
+/* out[start + i] = fl32(float(tensor[i]) * scale) for every segment: torch.cat([...]).float() * scale (psgd.py:729-730, :747;
+ * scale = 1 / delta_param_scale on the finite-difference branch, :734-736).  out: flat fp32, 4-byte aligned.                     */
+int psgd_uvd_pack_f32(const void *segs, int k, const void *chunks, int64_t nchunks, int dtype, float scale, float *out,
+                      void *stream);
+
+/* out[0] = sum_i fl32(x[i] * x[i]), summed in fp64 in a fixed order (the square of the clip norm of psgd.py:753): two launches,
+ * no floating-point atomics, the same bits on every call.  N >= 0; x 4-byte aligned.                                             */
+int psgd_uvd_sumsq_f32(const float *x, int64_t N, double *out, void *ws, int64_t ws_bytes, void *stream);
+
+/* psgd.py:757-762 for all parameters in ONE launch, T = the parameters' type, every operation rounded to nearest even on its own:
+ *     delta = T(fl32(lr_eff * pre_grad[start + i]));   vs_segs given: delta = T(delta + v[i]);   p[i] = T(p[i] - delta)
+ * lr_eff = lr when sumsq is NULL; otherwise lr_eff = fl32(lr * min(max_norm / (sqrt(*sumsq) + tiny), 1)) (:753-754), evaluated in
+ * fp64 on the device from the double psgd_uvd_sumsq_f32 left (all-reduced first when the vector is sharded): no host read.
+ * pre_grad == NULL (vs_segs required, sumsq must be NULL): p[i] = T(p[i] + v[i]), the perturbation of :723.
+ * vs_segs: the segment table of the vs tensors (same sizes and dtype as the parameters), or NULL.                              */
+int psgd_uvd_param_update_multi(const void *param_segs, const void *vs_segs, int k, const void *chunks, int64_t nchunks, int dtype,
+                                const float *pre_grad, float lr, const double *sumsq, float max_norm, float tiny, void *stream);
 
 /* Tuning knobs for experiments (not part of the stable ABI).
  * key 0: streaming policy (0 = automatic: non-temporal when U,V exceed the Infinity Cache,

@@ -19,6 +19,9 @@ PSGD_WS_SUMS_F64 = 0
 PSGD_WS_MAX_F32 = 1
 PSGD_WS_SEND_F64 = 2
 UVD_MAX_RANK = 32
+UVD_TAIL_CHUNK = 4096    # PSGD_UVD_TAIL_CHUNK: elements per entry of the chunk table of the step-tail kernels
+UVD_SUMSQ_WS_BYTES = 8192
+DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2     # PSGD_DTYPE_*
 SPLU_MAX_RANK = 64       # PSGD_SPLU_MAX_RANK: the native sparse-LU entry points (round 5)
 # psgd_kron_dd_route_flags bits (PSGD_KRON_ROUTE_* of include/psgd_hip.h)
 KRON_ROUTE_SMALL, KRON_ROUTE_PLANES_APPLY, KRON_ROUTE_PLANES_UPDATE, KRON_ROUTE_INV_SOLVES = 1 << 0, 1 << 1, 1 << 2, 1 << 3
@@ -103,6 +106,9 @@ SIGNATURES = {
     "psgd_uvd_update_bf16": (_int, [_c_f32p] * 5 + [_i64, _int, _flt, _flt, _int, _int, _int, ctypes.c_uint64, _c_ws, _i64, _strm]),
     "psgd_uvd_update_apply_bf16": (_int, [_c_f32p] * 7 + [_i64, _int, _flt, _flt, _int, _int, _int, ctypes.c_uint64, _c_ws, _i64,
                                           _strm]),
+    "psgd_uvd_pack_f32": (_int, [_c_f32p, _int, _c_f32p, _i64, _int, _flt, _c_f32p, _strm]),
+    "psgd_uvd_sumsq_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_ws, _i64, _strm]),
+    "psgd_uvd_param_update_multi": (_int, [_c_f32p, _c_f32p, _int, _c_f32p, _i64, _int, _c_f32p, _flt, _c_f32p, _flt, _flt, _strm]),
     "psgd_splu_workspace_bytes": (_i64, [_i64, _int]),
     "psgd_splu_apply_f32": (_int, [_c_f32p] * 6 + [_i64, _int, _c_ws, _i64, _strm]),
     "psgd_splu_update_f32": (_int, [_c_f32p] * 10 + [_i64, _int, ctypes.c_float, ctypes.c_float, _c_ws, _i64, _strm]),

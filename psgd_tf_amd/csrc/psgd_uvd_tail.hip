@@ -1,0 +1,343 @@
+// psgd_uvd_tail.hip -- the tail of UVd.step (psgd.py:729-730, :747, :750-762) on gfx950, whatever the number of parameter tensors.
+//
+//   psgd_uvd_pack_f32            k tensors of one dtype (fp32 / bf16 / fp16) -> one flat fp32 vector, times a scale      (:729-736, :747)
+//   psgd_uvd_sumsq_f32           sum x^2 of a flat fp32 vector -> one device double (the clip norm's square)              (:753)
+//   psgd_uvd_param_update_multi  p <- T(p - [T(T(fl32(lr_eff pre_grad)) + v)])  for every element of every parameter      (:757-762)
+//
+// The work of pack and update is described by two device tables.  A SEGMENT is one tensor: {pointer, start offset in the flat vector,
+// element count}.  A CHUNK is one piece of at most kChunk consecutive elements of one segment: {segment index, offset inside it}; the
+// host builds the chunk table once from the sizes, every flat element belongs to exactly one chunk, and a workgroup takes whole chunks
+// (grid-stride): nothing searches.  One launch serves any k.
+//
+// HBM-bound streaming: inside a chunk the stored side (the flat vector for pack, the parameters for the update) is brought to a
+// 16-byte boundary by a scalar head, the body moves 16 bytes of the narrowest type per lane and access (4 fp32 or 8 half-precision
+// elements), a scalar tail finishes.  The other streams of the body are read through vector types whose declared alignment is the
+// element's, so tensors that start at any element (offset views, odd sizes in front of them) still take wide loads.
+//
+// The sum of squares rounds each product to fp32 (as the torch expression it replaces does), accumulates in fp64 per lane, folds
+// lanes -> waves -> workgroup in a fixed order into one fp64 partial per workgroup, and a second one-workgroup launch folds the
+// partials in index order: no floating-point atomics, the same bits on every call.
+//
+// No entry point allocates or synchronises; argument checks return before any HIP call.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "psgd_hip.h"
+
+// The roundings of this file are its contract (bit-equal to the torch expressions it replaces): no product may be fused into a
+// following sum.  hipcc contracts by default, and the header's __fmul_rn / __fadd_rn are compiled under that default: plain
+// operators under this pragma are what stays unfused (checked in the ISA: no v_fma / v_fmac / v_pk_fma on fp32).
+#pragma clang fp contract(off)
+
+namespace psgdt {
+
+constexpr int kT = 256;                    // threads per workgroup
+constexpr int kChunk = PSGD_UVD_TAIL_CHUNK;
+constexpr int kMaxGrid = 2048;             // 8 workgroups per CU; the rest is grid-stride
+constexpr int kSumsqBlocks = 1024;         // partials of the sum of squares: PSGD_UVD_SUMSQ_WS_BYTES / 8
+static_assert(kSumsqBlocks * 8 == PSGD_UVD_SUMSQ_WS_BYTES, "workspace constant of the header");
+
+struct Seg {
+  uint64_t ptr;
+  int64_t start, count;
+};
+struct Chunk {
+  int64_t seg, off;
+};
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));       // 16 bytes from any fp32 element
+typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
+typedef uint16_t u16x8_u __attribute__((ext_vector_type(8), aligned(2)));    // 16 bytes from any 16-bit element
+
+// dtype codes of the C ABI
+struct F32 {
+  using raw = float;
+  static constexpr int E = 4;
+  static __device__ __forceinline__ float widen(float x) { return x; }
+  static __device__ __forceinline__ float narrow(float x) { return x; }
+};
+struct BF16 {
+  using raw = uint16_t;
+  static constexpr int E = 8;
+  static __device__ __forceinline__ float widen(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
+  static __device__ __forceinline__ uint16_t narrow(float x) {          // round to nearest even, NaN -> quiet NaN
+    const uint32_t u = __float_as_uint(x);
+    if (x != x) return 0x7FC0;
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+  }
+};
+struct F16 {
+  using raw = uint16_t;
+  static constexpr int E = 8;
+  static __device__ __forceinline__ float widen(uint16_t b) {
+    union { uint16_t u; _Float16 h; } c;
+    c.u = b;
+    return (float)c.h;
+  }
+  static __device__ __forceinline__ uint16_t narrow(float x) {          // v_cvt_f16_f32: round to nearest even
+    union { uint16_t u; _Float16 h; } c;
+    c.h = (_Float16)x;
+    return c.u;
+  }
+};
+
+// E consecutive elements of type T from an address aligned to the element only
+template <class T>
+__device__ __forceinline__ void load_any(const typename T::raw* p, float (&x)[T::E]) {
+  if constexpr (T::E == 4) {
+    const f32x4_u v = *reinterpret_cast<const f32x4_u*>(p);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = v[e];
+  } else {
+    const u16x8_u v = *reinterpret_cast<const u16x8_u*>(p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = T::widen(v[e]);
+  }
+}
+// ... from / to a 16-byte aligned address
+template <class T>
+__device__ __forceinline__ void load_16(const typename T::raw* p, float (&x)[T::E]) {
+  if constexpr (T::E == 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = v[e];
+  } else {
+    const u16x8 v = *reinterpret_cast<const u16x8*>(p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = T::widen(v[e]);
+  }
+}
+template <class T>
+__device__ __forceinline__ void store_16(typename T::raw* p, const float (&x)[T::E]) {
+  if constexpr (T::E == 4) {
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = x[e];
+    *reinterpret_cast<f32x4*>(p) = v;
+  } else {
+    u16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = T::narrow(x[e]);
+    *reinterpret_cast<u16x8*>(p) = v;
+  }
+}
+
+// elements in front of the first 16-byte boundary at or after p (elements of `bytes` bytes), at most n
+__device__ __forceinline__ int head_of(const void* p, int bytes, int n) {
+  const int h = (int)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) / bytes;
+  return h < n ? h : n;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------- pack
+template <class T>
+__global__ __launch_bounds__(kT) void k_uvd_pack(const Seg* __restrict__ segs, const Chunk* __restrict__ chunks, int64_t nchunks,
+                                                 int k, float scale, float* __restrict__ out) {
+  using raw = typename T::raw;
+  constexpr int E = T::E;
+  const int t = threadIdx.x;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Chunk ch = chunks[c];
+    if ((uint64_t)ch.seg >= (uint64_t)k) continue;              // a table that does not belong to these segments moves nothing
+    const Seg s = segs[ch.seg];
+    const int64_t left = s.count - ch.off;
+    if (ch.off < 0 || left <= 0) continue;
+    const int n = (int)(left < kChunk ? left : kChunk);
+    const raw* src = reinterpret_cast<const raw*>(s.ptr) + ch.off;
+    float* dst = out + s.start + ch.off;
+    const int head = head_of(dst, 4, n);
+    const int nvec = (n - head) / E;
+    if (t < head) dst[t] = T::widen(src[t]) * scale;
+#pragma unroll 2
+    for (int g = t; g < nvec; g += kT) {
+      const int i = head + g * E;
+      float x[E];
+      load_any<T>(src + i, x);
+#pragma unroll
+      for (int e = 0; e < E; ++e) x[e] = x[e] * scale;
+#pragma unroll
+      for (int q = 0; q < E / 4; ++q) {
+        f32x4 v = {x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]};
+        *reinterpret_cast<f32x4*>(dst + i + 4 * q) = v;
+      }
+    }
+    const int i = head + nvec * E + t;
+    if (i < n) dst[i] = T::widen(src[i]) * scale;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- sum of squares
+__device__ __forceinline__ double block_sum(double v, double* lds) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) lds[w] = v;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < kT / 64; ++k) s += lds[k];
+  return s;
+}
+
+__global__ __launch_bounds__(kT) void k_uvd_sumsq_partial(const float* __restrict__ x, int64_t N, double* __restrict__ partial) {
+  __shared__ double lds[kT / 64];
+  const int64_t nvec = N / 4;
+  double acc = 0.0;
+#pragma unroll 4
+  for (int64_t g = (int64_t)blockIdx.x * kT + threadIdx.x; g < nvec; g += (int64_t)gridDim.x * kT) {
+    const f32x4_u v = *reinterpret_cast<const f32x4_u*>(x + 4 * g);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc += (double)(v[e] * v[e]);
+  }
+  if (blockIdx.x == 0) {
+    const int64_t i = 4 * nvec + threadIdx.x;
+    if (i < N) acc += (double)(x[i] * x[i]);
+  }
+  const double s = block_sum(acc, lds);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kT) void k_uvd_sumsq_fold(const double* __restrict__ partial, int n, double* __restrict__ out) {
+  __shared__ double lds[kT / 64];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += kT) acc += partial[i];
+  const double s = block_sum(acc, lds);
+  if (threadIdx.x == 0) out[0] = s;
+}
+
+// ------------------------------------------------------------------------------------------------------------ parameter update
+// psgd.py:757-762 with the roundings of the torch expressions:  delta = T(fl32(lr_eff * pre_grad));  [delta = T(delta + v)];
+// p = T(p - delta).  No contraction: every product, sum and difference is rounded on its own.
+template <class T, bool kPre, bool kVs>
+__device__ __forceinline__ float update_one(float p, float g, float v, float lr_eff) {
+  if constexpr (!kPre) {
+    return p + v;                                     // p.add_(v) of the finite-difference branch (:723)
+  } else {
+    float delta = T::widen(T::narrow(lr_eff * g));
+    if constexpr (kVs) delta = T::widen(T::narrow(delta + v));
+    return p - delta;
+  }
+}
+
+template <class T, bool kPre, bool kVs>
+__global__ __launch_bounds__(kT) void k_uvd_param_update(const Seg* __restrict__ psegs, const Seg* __restrict__ vsegs,
+                                                         const Chunk* __restrict__ chunks, int64_t nchunks, int k,
+                                                         const float* __restrict__ pre_grad, float lr, const double* __restrict__ sumsq,
+                                                         float max_norm, float tiny) {
+  using raw = typename T::raw;
+  constexpr int E = T::E;
+  const int t = threadIdx.x;
+  float lr_eff = lr;
+  if (kPre && sumsq) {        // psgd.py:753-754, one rounding: lr_eff = fl32(lr * min(max_norm / (sqrt(sumsq) + tiny), 1))
+    const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
+    lr_eff = (float)((double)lr * (ratio < 1.0 ? ratio : 1.0));
+  }
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Chunk ch = chunks[c];
+    if ((uint64_t)ch.seg >= (uint64_t)k) continue;
+    const Seg s = psegs[ch.seg];
+    const int64_t left = s.count - ch.off;
+    if (ch.off < 0 || left <= 0) continue;
+    const int n = (int)(left < kChunk ? left : kChunk);
+    raw* p = reinterpret_cast<raw*>(s.ptr) + ch.off;
+    const float* g = kPre ? pre_grad + s.start + ch.off : nullptr;
+    const raw* v = kVs ? reinterpret_cast<const raw*>(vsegs[ch.seg].ptr) + ch.off : nullptr;
+    const int head = head_of(p, (int)sizeof(raw), n);
+    const int nvec = (n - head) / E;
+    if (t < head)
+      p[t] = T::narrow(update_one<T, kPre, kVs>(T::widen(p[t]), kPre ? g[t] : 0.f, kVs ? T::widen(v[t]) : 0.f, lr_eff));
+#pragma unroll 2
+    for (int q = t; q < nvec; q += kT) {
+      const int i = head + q * E;
+      float x[E], gg[E], vv[E];
+      load_16<T>(p + i, x);
+      if constexpr (kPre) {
+#pragma unroll
+        for (int b = 0; b < E / 4; ++b) {
+          const f32x4_u w = *reinterpret_cast<const f32x4_u*>(g + i + 4 * b);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) gg[4 * b + e] = w[e];
+        }
+      }
+      if constexpr (kVs) load_any<T>(v + i, vv);
+#pragma unroll
+      for (int e = 0; e < E; ++e) x[e] = update_one<T, kPre, kVs>(x[e], kPre ? gg[e] : 0.f, kVs ? vv[e] : 0.f, lr_eff);
+      store_16<T>(p + i, x);
+    }
+    const int i = head + nvec * E + t;
+    if (i < n)
+      p[i] = T::narrow(update_one<T, kPre, kVs>(T::widen(p[i]), kPre ? g[i] : 0.f, kVs ? T::widen(v[i]) : 0.f, lr_eff));
+  }
+}
+
+static int grid_for(int64_t nchunks) { return (int)(nchunks < kMaxGrid ? nchunks : kMaxGrid); }
+static bool bad_dtype(int dtype) { return dtype < PSGD_DTYPE_F32 || dtype > PSGD_DTYPE_F16; }
+static int launched() { return hipGetLastError() == hipSuccess ? PSGD_OK : PSGD_ERR_LAUNCH; }
+
+template <class T>
+static void launch_update(bool pre, bool vs, int grid, hipStream_t st, const Seg* ps, const Seg* vsg, const Chunk* ch, int64_t nchunks,
+                          int k, const float* pre_grad, float lr, const double* sumsq, float max_norm, float tiny) {
+  if (!pre)
+    hipLaunchKernelGGL((k_uvd_param_update<T, false, true>), dim3(grid), dim3(kT), 0, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq,
+                       max_norm, tiny);
+  else if (vs)
+    hipLaunchKernelGGL((k_uvd_param_update<T, true, true>), dim3(grid), dim3(kT), 0, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq,
+                       max_norm, tiny);
+  else
+    hipLaunchKernelGGL((k_uvd_param_update<T, true, false>), dim3(grid), dim3(kT), 0, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq,
+                       max_norm, tiny);
+}
+
+}  // namespace psgdt
+
+using namespace psgdt;
+
+extern "C" {
+
+int psgd_uvd_pack_f32(const void* segs, int k, const void* chunks, int64_t nchunks, int dtype, float scale, float* out,
+                      void* stream) {
+  if (!segs || !chunks || !out || k < 0 || nchunks < 0 || bad_dtype(dtype)) return PSGD_ERR_BAD_ARG;
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const Seg* sg = (const Seg*)segs;
+  const Chunk* ch = (const Chunk*)chunks;
+  const int grid = grid_for(nchunks);
+  if (dtype == PSGD_DTYPE_F32)
+    hipLaunchKernelGGL(k_uvd_pack<F32>, dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, out);
+  else if (dtype == PSGD_DTYPE_BF16)
+    hipLaunchKernelGGL(k_uvd_pack<BF16>, dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, out);
+  else
+    hipLaunchKernelGGL(k_uvd_pack<F16>, dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, out);
+  return launched();
+}
+
+int psgd_uvd_sumsq_f32(const float* x, int64_t N, double* out, void* ws, int64_t ws_bytes, void* stream) {
+  if (!x || !out || !ws || N < 0) return PSGD_ERR_BAD_ARG;
+  if (ws_bytes < PSGD_UVD_SUMSQ_WS_BYTES || ((uintptr_t)ws & 7)) return PSGD_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t tiles = (N + kChunk - 1) / kChunk;
+  const int nb = (int)(tiles < kSumsqBlocks ? tiles : kSumsqBlocks);        // a function of N alone: the partition never changes
+  if (nb > 0) hipLaunchKernelGGL(k_uvd_sumsq_partial, dim3(nb), dim3(kT), 0, st, x, N, (double*)ws);
+  hipLaunchKernelGGL(k_uvd_sumsq_fold, dim3(1), dim3(kT), 0, st, (const double*)ws, nb, out);
+  return launched();
+}
+
+int psgd_uvd_param_update_multi(const void* param_segs, const void* vs_segs, int k, const void* chunks, int64_t nchunks, int dtype,
+                                const float* pre_grad, float lr, const double* sumsq, float max_norm, float tiny, void* stream) {
+  if (!param_segs || !chunks || k < 0 || nchunks < 0 || bad_dtype(dtype)) return PSGD_ERR_BAD_ARG;
+  if (!pre_grad && (!vs_segs || sumsq)) return PSGD_ERR_BAD_ARG;            // nothing to do, or a clip norm without a gradient
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const Seg* ps = (const Seg*)param_segs;
+  const Seg* vsg = (const Seg*)vs_segs;
+  const Chunk* ch = (const Chunk*)chunks;
+  const int grid = grid_for(nchunks);
+  const bool pre = pre_grad != nullptr, vs = vs_segs != nullptr;
+  if (dtype == PSGD_DTYPE_F32)
+    launch_update<F32>(pre, vs, grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny);
+  else if (dtype == PSGD_DTYPE_BF16)
+    launch_update<BF16>(pre, vs, grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny);
+  else
+    launch_update<F16>(pre, vs, grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny);
+  return launched();
+}
+
+}  // extern "C"

@@ -615,6 +615,171 @@ def update_precond_UVd_math_and_precond_grad(U, V, d, v, h, g, step, tiny, *, ba
     return out
 
 
+# --------------------------------------------------------------------------- UVd step tail (psgd_uvd_tail.hip)
+# What class UVd does around the preconditioner call -- psgd.py:729-730 / :747 (lists of tensors -> flat vectors), :753-754 (clip norm)
+# and :757-762 (parameter update) -- in a number of launches that does not depend on how many parameter tensors there are.
+_TAIL_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+
+
+def uvd_tail_chunks(sizes):
+    """The chunk table of the step-tail kernels for tensors of these element counts (include/psgd_hip.h): an int64 numpy array
+    [nchunks, 2] of (segment, offset inside the segment), one row per piece of at most _lib.UVD_TAIL_CHUNK elements, segments in
+    order.  Every element of every segment is in exactly one chunk; a segment of 0 elements has none."""
+    import numpy as np
+    sizes = np.asarray(list(sizes), dtype=np.int64).reshape(-1)
+    if (sizes < 0).any():
+        raise ValueError("uvd_tail_chunks: negative size")
+    per = (sizes + (_lib.UVD_TAIL_CHUNK - 1)) // _lib.UVD_TAIL_CHUNK
+    seg = np.repeat(np.arange(len(sizes), dtype=np.int64), per)
+    first = np.cumsum(per) - per
+    off = (np.arange(int(per.sum()), dtype=np.int64) - np.repeat(first, per)) * _lib.UVD_TAIL_CHUNK
+    return np.stack([seg, off], axis=1)
+
+
+class _SegTable:
+    """The device segment table {pointer, start, count} of one list of tensors.  The host copy lives in pinned memory; the table is
+    uploaded (one asynchronous copy on the current stream) only when a pointer differs from the last upload."""
+
+    def __init__(self, starts, sizes, device):
+        k = len(sizes)
+        self.host = torch.zeros((k, 3), dtype=torch.int64).pin_memory()
+        self.rows = self.host.numpy()
+        self.rows[:, 1] = starts
+        self.rows[:, 2] = sizes
+        self.dev = torch.zeros((k, 3), dtype=torch.int64, device=device)
+        self.ptrs, self.uploaded = None, None
+
+    def refresh(self, ptrs):
+        if ptrs != self.ptrs:
+            if self.uploaded is not None:
+                self.uploaded.synchronize()                     # the previous upload has read the pinned rows (long ago, normally)
+            self.rows[:, 0] = ptrs
+            self.dev.copy_(self.host, non_blocking=True)
+            self.uploaded = torch.cuda.Event()
+            self.uploaded.record()
+            self.ptrs = ptrs
+        return self.dev.data_ptr()
+
+
+class UVdTailPlan:
+    """Everything about a list of parameter tensors that the step-tail kernels need and that does not change from step to step:
+    sizes, start offsets, the chunk table on the device, one segment table per role ("params", "vs", "v", "h", "g", ...), the
+    device double of the clip norm and the workspace of its reduction.  Calls that share a plan must run on one stream."""
+
+    def __init__(self, sizes, dtype, device):
+        if dtype not in _TAIL_DTYPES:
+            raise TypeError("UVd step tail: tensors must be float32, bfloat16 or float16, got %s" % (dtype,))
+        self.sizes = tuple(int(n) for n in sizes)
+        self.dtype, self.code, self.device = dtype, _TAIL_DTYPES[dtype], torch.device(device)
+        self.starts, acc = [], 0
+        for n in self.sizes:
+            self.starts.append(acc)
+            acc += n
+        self.total = acc
+        chunks = uvd_tail_chunks(self.sizes)
+        self.nchunks = int(chunks.shape[0])
+        self.chunks = torch.from_numpy(chunks).to(self.device) if self.nchunks else None
+        self.sumsq = torch.zeros(1, dtype=torch.float64, device=self.device)
+        self.ws = torch.empty(_lib.UVD_SUMSQ_WS_BYTES, dtype=torch.uint8, device=self.device)
+        self._tables = {}
+
+    def table(self, role, tensors, what):
+        """device pointer of the segment table of `tensors` in this role (uploaded when a pointer changed)"""
+        if len(tensors) != len(self.sizes):
+            raise ValueError("%s: %d tensors, the plan has %d" % (what, len(tensors), len(self.sizes)))
+        dt, dev = self.dtype, self.device
+        for t, n in zip(tensors, self.sizes):
+            if t.dtype != dt or t.device != dev or t.numel() != n or not t.is_contiguous():
+                raise ValueError("%s: every tensor must be a contiguous %s tensor on %s with the plan's element count (%d), got %s %s "
+                                 "%s%s" % (what, dt, dev, n, t.dtype, t.device, tuple(t.shape), "" if t.is_contiguous() else " strided"))
+        tab = self._tables.get(role)
+        if tab is None:
+            tab = self._tables[role] = _SegTable(self.starts, self.sizes, dev)
+        return tab.refresh([t.data_ptr() for t in tensors])
+
+
+_tail_plans = {}     # (device, dtype, sizes) -> UVdTailPlan of the calls that bring none (a model has one or two such keys)
+
+
+def _tail_plan(tensors, what):
+    if not tensors:
+        raise ValueError("%s: empty tensor list" % what)
+    t0 = tensors[0]
+    if not isinstance(t0, torch.Tensor) or not t0.is_cuda:
+        raise _lib.PsgdHipError("%s runs on the HIP device only; no CPU fallback" % what)
+    key = (t0.device, t0.dtype, tuple(int(t.numel()) for t in tensors))
+    plan = _tail_plans.get(key)
+    if plan is None:
+        while len(_tail_plans) >= 16:
+            _tail_plans.pop(next(iter(_tail_plans)))
+        plan = _tail_plans[key] = UVdTailPlan(key[2], t0.dtype, t0.device)
+    return plan
+
+
+def uvd_pack(tensors, out, scale=1.0, *, plan=None, role="pack"):
+    """out[:n] = torch.cat([t.reshape(-1) for t in tensors]).float() * scale in ONE launch whatever len(tensors) (psgd.py:729-730, :747;
+    scale: the 1 / delta_param_scale of :734-736).  tensors: contiguous device tensors of one dtype (float32, bfloat16 or float16),
+    empty ones allowed; out: a contiguous fp32 device tensor of at least n elements.  Returns out's first n elements, flat."""
+    tensors = list(tensors)
+    plan = plan if plan is not None else _tail_plan(tensors, "uvd_pack")
+    dev = _require_hip("uvd_pack", out)
+    if out.numel() < plan.total:
+        raise ValueError("uvd_pack: out has %d elements, the tensors have %d" % (out.numel(), plan.total))
+    segs = plan.table(role, tensors, "uvd_pack")
+    if plan.nchunks:
+        rc = _lib.load().psgd_uvd_pack_f32(segs, len(tensors), plan.chunks.data_ptr(), plan.nchunks, plan.code, float(scale),
+                                           out.data_ptr(), _stream_ptr(dev))
+        _lib.check(rc, "psgd_uvd_pack_f32")
+    return out.view(-1)[:plan.total]
+
+
+def uvd_sumsq(x, *, plan):
+    """plan.sumsq[0] = sum of fl32(x * x) in fp64, fixed order (the square of the clip norm of psgd.py:753); returns that tensor"""
+    dev = _require_hip("uvd_sumsq", x)
+    rc = _lib.load().psgd_uvd_sumsq_f32(x.data_ptr(), x.numel(), plan.sumsq.data_ptr(), plan.ws.data_ptr(), plan.ws.numel(),
+                                        _stream_ptr(dev))
+    _lib.check(rc, "psgd_uvd_sumsq_f32")
+    return plan.sumsq
+
+
+def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group=None, *, plan=None):
+    """psgd.py:750-762 on all parameters in place, in launches that do not depend on len(params):
+        lr_eff = lr                                                         (max_norm None or inf, :750-751)
+                 lr * min(max_norm / (||pre_grad|| + tiny), 1)              (:753-754; the norm never reaches the host)
+        p <- T(p - delta),  delta = T(fl32(lr_eff * pre_grad slice)),  with vs: delta = T(delta + v)        (:757-762)
+    with T the parameters' dtype: the roundings of the torch expressions of class UVd.  params (and vs): contiguous device tensors
+    of one dtype; pre_grad: the flat fp32 preconditioned gradient of their concatenation.  tiny defaults to the dtype's smallest
+    normal (:682).  group: pre_grad holds this rank's rows of a row-sharded vector -- the sum of squares is all-reduced (one fp64
+    scalar, the collective sharded.global_norm uses).  pre_grad None (vs required): p <- T(p + v), the perturbation of :723.
+    The parameters are written through their pointers: autograd's version counters do not move."""
+    params = list(params)
+    plan = plan if plan is not None else _tail_plan(params, "uvd_step_tail")
+    dev = plan.device
+    psegs = plan.table("params", params, "uvd_step_tail")
+    vsegs = plan.table("vs", list(vs), "uvd_step_tail (vs)") if vs is not None else None
+    clip = max_norm is not None and not math.isinf(float(max_norm))
+    sumsq = None
+    if pre_grad is None:
+        if vsegs is None or clip:
+            raise ValueError("uvd_step_tail: pre_grad=None adds vs to the parameters; it needs vs and takes no max_norm")
+    else:
+        _require_hip("uvd_step_tail", pre_grad)
+        if pre_grad.device != dev or pre_grad.numel() != plan.total:
+            raise ValueError("uvd_step_tail: pre_grad must hold the %d elements of the parameters on %s" % (plan.total, dev))
+        if clip:
+            sumsq = uvd_sumsq(pre_grad, plan=plan)
+            if group is not None:
+                from . import sharded as _sharded
+                _sharded.all_reduce_sum_f64_(sumsq, group)
+    if plan.nchunks:
+        tiny = torch.finfo(plan.dtype).tiny if tiny is None else tiny
+        rc = _lib.load().psgd_uvd_param_update_multi(
+            psegs, vsegs, len(params), plan.chunks.data_ptr(), plan.nchunks, plan.code,
+            None if pre_grad is None else pre_grad.data_ptr(), float(lr), None if sumsq is None else sumsq.data_ptr(),
+            float(max_norm) if clip else 0.0, float(tiny), _stream_ptr(dev))
+        _lib.check(rc, "psgd_uvd_param_update_multi")
+
+
 # --------------------------------------------------------------------------- UVd optimizer wrapper
 class _Hyper:
     """Stand-in for the non-trainable tf.Variable hyper-parameters of psgd.py:673-680:
@@ -680,7 +845,7 @@ class UVd:
                  lr_params=0.01, lr_preconditioner=0.01,
                  grad_clip_max_norm=None, preconditioner_update_probability=1.0,
                  exact_hessian_vector_product: bool = True, generator=None, state_dtype=None, group=None,
-                 stage_backend=None, placement="auto", state_route="widen", state_rounding=None):
+                 stage_backend=None, placement="auto", state_route="widen", state_rounding=None, step_tail="torch"):
         # group (extension): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
         # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the
         # concatenation of the ranks' vectors in rank order, and U, V, d hold this rank's rows only.  A step then costs three
@@ -749,6 +914,22 @@ class UVd:
         self._param_sizes, self._param_cumsizes = uvd_param_index(self._params_with_grad)    # :684-685
         num_params = self._param_cumsizes[-1]                                                # :686
         self._generator = generator
+        # step_tail (extension): "torch" (default) = the tail of step() as torch expressions, a handful of launches per parameter tensor;
+        # "fused" = the step-tail kernels (uvd_pack, uvd_step_tail): the lists of :729-730, :747 packed into flat vectors that this
+        # object owns (the arena's when the state is placed), the clip norm of :753 and the update of :757-762 in a number of launches
+        # that does not depend on the number of tensors -- the same roundings, so without clipping the same bits.  Parameters that
+        # are not contiguous, or not of one dtype, keep the torch tail for the life of the object (one warning).
+        if step_tail not in ("torch", "fused"):
+            raise ValueError("UVd: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
+        self._tail, self._flat_bufs = None, {}
+        if step_tail == "fused":
+            if all(p.is_contiguous() and p.dtype == self._dtype for p in self._params_with_grad):
+                self._tail = UVdTailPlan(self._param_sizes, self._dtype, self._device)
+                import numpy as np
+                self._fd_inv_scale = float(np.float32(1.0) / np.float32(self._delta_param_scale))   # what torch's `/ scale` multiplies by
+            else:
+                import warnings
+                warnings.warn("UVd: step_tail='fused' needs contiguous parameters of one dtype; this optimizer keeps the torch tail")
         self._group, self._stage_backend, self._num_params_global = group, stage_backend, num_params
         if group is not None:
             from . import sharded as _sharded
@@ -798,9 +979,15 @@ class UVd:
             self._V.copy_(V)
             self._d.copy_(d)
 
-    def _flat(self, tensors, name):
+    def _flat(self, tensors, name, fd_scaled=False):
         """psgd.py:729-730, :747: the per-parameter tensors as one flat vector in the state's type -- concatenated straight into
-        the arena's region for it when the state is placed (no second copy, and the vector sits where the sweeps read it)"""
+        the arena's region for it when the state is placed (no second copy, and the vector sits where the sweeps read it).
+        fd_scaled (fused tail only): the division of :734-736 rides on the pack."""
+        if self._tail is not None:
+            out = getattr(self._arena, name).view(-1) if self._arena is not None else self._flat_bufs.get(name)
+            if out is None:
+                out = self._flat_bufs[name] = torch.empty(self._tail.total, dtype=torch.float32, device=self._device)
+            return uvd_pack([_c(x) for x in tensors], out, self._fd_inv_scale if fd_scaled else 1.0, plan=self._tail, role=name)
         parts = [torch.reshape(x, [-1]) for x in tensors]
         if self._arena is not None and all(x.dtype == self._state_dtype for x in parts):
             return torch.cat(parts, 0, out=getattr(self._arena, name).view(-1))
@@ -833,14 +1020,17 @@ class UVd:
                     grads = torch.autograd.grad(self._loss_of(closure_returns), params)
                 vs = [_randn_like(p) * self._delta_param_scale for p in params]
                 with torch.no_grad():
-                    for p, v in zip(params, vs):
-                        p.add_(v)
+                    if self._tail is not None:
+                        uvd_step_tail(params, None, 0.0, vs=vs, plan=self._tail)
+                    else:
+                        for p, v in zip(params, vs):
+                            p.add_(v)
                 with torch.enable_grad():
                     perturbed_grads = torch.autograd.grad(self._loss_of(closure()), params)
                 Hvs = [pg - g for pg, g in zip(perturbed_grads, grads)]
-            v = self._flat(vs, "v")                                                           # :729
-            h = self._flat(Hvs, "h")                                                          # :730
-            if not exact:                                                                     # :734-736
+            v = self._flat(vs, "v", not exact)                                                # :729
+            h = self._flat(Hvs, "h", not exact)                                               # :730
+            if not exact and self._tail is None:                                              # :734-736
                 v = v / self._delta_param_scale
                 h = h / self._delta_param_scale
             grad = self._flat(grads, "g")                                                     # :747
@@ -876,6 +1066,10 @@ class UVd:
                 pre_grad = self._sharded.precond_grad_UVd_math(*self._state_fp32(), grad[:, None].contiguous(),
                                                                group=self._group, backend=self._stage_backend)
         max_norm = float(self.grad_clip_max_norm)
+        if self._tail is not None:                                                            # :750-762 in the step-tail kernels
+            uvd_step_tail(params, pre_grad, float(self.lr_params), max_norm, self._tiny, vs if (not exact) and update_Q else None,
+                          self._group, plan=self._tail)
+            return closure_returns
         if math.isinf(max_norm):                                                              # :750-751
             lr = float(self.lr_params)
         else:                                                                                 # :753-754

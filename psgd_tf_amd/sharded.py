@@ -189,12 +189,19 @@ def global_norm(x, group=None):
     """2-norm of the global vector whose rows on this rank are x (the clip norm of psgd.py:753): the local sum of squares in fp64,
     ONE scalar all-reduce (every rank receives the same bits), the root as a device tensor of x's dtype -- no host read."""
     sq = torch.sum(x.to(torch.float64) ** 2).reshape(1)
+    all_reduce_sum_f64_(sq, group)
+    return torch.sqrt(sq[0]).to(x.dtype)
+
+
+def all_reduce_sum_f64_(sq, group=None):
+    """in-place SUM over the ranks of a contiguous fp64 tensor, on the current stream: the one scalar collective of the clip norm
+    (global_norm above, and the fused step tail, which hands the kernel the reduced sum of squares)"""
     comm = _direct_comm(group, sq.device) if sq.is_cuda else None
     if comm is not None:
         comm.all_reduce_sum_f64(sq, torch.cuda.current_stream(sq.device).cuda_stream)
     else:
         dist.all_reduce(sq, op=dist.ReduceOp.SUM, group=group)
-    return torch.sqrt(sq[0]).to(x.dtype)
+    return sq
 
 
 class BranchRng:

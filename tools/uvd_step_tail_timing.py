@@ -1,0 +1,133 @@
+#!/usr/bin/env python
+"""Time class UVd's step with the torch tail and with the fused tail (step_tail="fused") on a closure that costs next to nothing.
+
+The closure is 0.5 ||w||^2 over all parameter tensors, so a step is: the closure with its gradient and Hessian-vector product (a few
+launches per tensor, the same on both routes -- timed alone as "closure"), the fused update -> apply call, and the tail this tool is
+about: lists of tensors -> flat vectors, the clip norm, the parameter update.
+
+Protocol: warm up until the device has been busy for --warm-seconds (and at least 5 steps), then --chunks chunks of --steps steps,
+each chunk timed by the host clock between two device synchronisations; the figure is the median over chunks, with the spread.
+Peak memory: torch.cuda.max_memory_allocated over three further steps minus what was allocated before them.
+
+    python tools/uvd_step_tail_timing.py                      # the table: N = 1M (1, 16, 256 tensors) and N = 100M (256 tensors)
+    python tools/uvd_step_tail_timing.py --quick              # N = 1M only
+    python tools/uvd_step_tail_timing.py --tail torch         # one route only (also runs on a checkout that has no step_tail)
+    python tools/uvd_step_tail_timing.py --trace N K TAIL     # 20 steps of one configuration and nothing else, for
+                                                              # rocprofv3 --kernel-trace --stats -- python tools/... --trace 1000000 256 fused
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import preconditioned_stochastic_gradient_descent as psgd  # noqa: E402
+
+
+def split(N, k):
+    """k sizes that sum to N, none a multiple of 4 where that can be avoided (starts land on odd elements, as in a real model)"""
+    base = N // k
+    sizes = [base + (1 if i % 2 else -1) * (i % 7) for i in range(k)] if base > 16 else [base] * k
+    sizes[-1] += N - sum(sizes)
+    assert sum(sizes) == N and min(sizes) >= 0
+    return sizes
+
+
+def build(N, r, k, dtype, clip, tail, seed=0):
+    dev = torch.device("cuda:0")
+    torch.manual_seed(seed)
+    psgd.manual_seed(seed)
+    params = [(torch.randn(n, device=dev) * 0.1).to(dtype).requires_grad_(True) for n in split(N, k)]
+    kw = {} if tail == "torch" else {"step_tail": tail}
+    opt = psgd.UVd(params, rank_of_modification=r, lr_params=1e-3, lr_preconditioner=0.01,
+                   grad_clip_max_norm=1.0 if clip else None, **kw)
+
+    def closure():
+        sq = torch._foreach_mul(params, params)
+        return 0.5 * torch.stack([s.sum() for s in sq]).float().sum()
+    return params, opt, closure
+
+
+def closure_only(params, closure):
+    """what a step spends outside the optimizer's own code: loss, gradient, Hessian-vector product (psgd.py:706-714)"""
+    with torch.enable_grad():
+        grads = torch.autograd.grad(closure(), params, create_graph=True)
+        vs = [torch.randn_like(p) for p in params]
+        torch.autograd.grad(grads, params, vs)
+
+
+def timed(fn, steps, chunks, warm_seconds):
+    torch.cuda.synchronize()
+    busy, n = 0.0, 0
+    while busy < warm_seconds or n < 5:
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        busy += time.perf_counter() - t0
+        n += 1
+    out = []
+    for _ in range(chunks):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) / steps)
+    return statistics.median(out), min(out), max(out)
+
+
+def peak_delta(fn):
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - before
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tail", choices=["torch", "fused", "both"], default="both")
+    ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--chunks", type=int, default=7)
+    ap.add_argument("--warm-seconds", type=float, default=0.3)
+    ap.add_argument("--trace", nargs=3, metavar=("N", "K", "TAIL"))
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "this tool measures on the GPU"
+    if a.trace:
+        N, k, tail = int(a.trace[0]), int(a.trace[1]), a.trace[2]
+        params, opt, closure = build(N, 10 if N <= 1_000_000 else 20, k, torch.float32, True, tail)
+        for _ in range(20):
+            opt.step(closure)
+        torch.cuda.synchronize()
+        print("trace: 20 steps, N=%d k=%d tail=%s clip=on fp32" % (N, k, tail))
+        return
+    assert a.chunks >= 7
+    tails = ["torch", "fused"] if a.tail == "both" else [a.tail]
+    shapes = [(1_000_000, 10, 1), (1_000_000, 10, 16), (1_000_000, 10, 256)] + ([] if a.quick else [(100_000_000, 20, 256)])
+    print("# N r k dtype clip | route: median step [min .. max] us, peak bytes over 3 steps | closure alone us")
+    for N, r, k in shapes:
+        steps = a.steps if N <= 1_000_000 else max(5, a.steps // 4)
+        for dtype in (torch.float32, torch.bfloat16):
+            for clip in (False, True):
+                row = "N=%d r=%d k=%d %s clip=%s |" % (N, r, k, str(dtype).replace("torch.", ""), "on" if clip else "off")
+                for tail in tails:
+                    params, opt, closure = build(N, r, k, dtype, clip, tail)
+                    med, lo, hi = timed(lambda: opt.step(closure), steps, a.chunks, a.warm_seconds)
+                    peak = peak_delta(lambda: opt.step(closure))
+                    row += " %s: %.1f [%.1f .. %.1f] us, peak +%d B |" % (tail, med * 1e6, lo * 1e6, hi * 1e6, peak)
+                    if tail == tails[-1]:
+                        c, _, _ = timed(lambda: closure_only(params, closure), steps, a.chunks, a.warm_seconds)
+                        row += " closure: %.1f us" % (c * 1e6)
+                    del params, opt, closure
+                    torch.cuda.empty_cache()
+                print(row, flush=True)
+
+
+if __name__ == "__main__":
+    main()
