@@ -51,6 +51,7 @@ extern "C" {
  *     psgd_dense_workspace_bytes, psgd_dense_update_f32 and psgd_dense_apply_f32 (new symbols only: the version stays 7);
  *     the psgd_uvd_*_bf16 entry points of a bf16-stored UVd state (new symbols only);
  *     psgd_uvd_pack_f32, psgd_uvd_sumsq_f32 and psgd_uvd_param_update_multi, the tail of UVd.step (new symbols only: still 7).
+ *     the stage forms of the bf16-state UVd calls, psgd_uvd_bf16_ws_region and psgd_uvd_bf16_fold_gathered_f64 (new symbols only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -284,6 +285,51 @@ int psgd_uvd_update_bf16(void *U, void *V, void *d, const float *v, const float 
 int psgd_uvd_update_apply_bf16(void *U, void *V, void *d, const float *v, const float *h, const float *g, float *out,
                                int64_t N, int r, float step, float tiny, int balance, int update_U,
                                int rounding, uint64_t seed, void *ws, int64_t ws_bytes, void *stream);
+
+/* Stage forms of the three calls above for a ROW-SHARDED bf16 state (one process per GPU; every rank passes its rows, N = its
+ * row count).  Same conventions: bf16 U, V, d (16-byte aligned), fp32 v, h, g, out, the workspace of
+ * psgd_uvd_bf16_workspace_bytes(N, r), rounding and seed as above; argument checks return before any HIP call.  Every stage
+ * leaves this rank's contribution to the following exchange as fp64 in the send region psgd_uvd_bf16_ws_region reports
+ * (`which` must be PSGD_WS_SEND_F64: protocol (a), all-gather + fold, is the only one; stages 10, 11, 12, 1, 2 as in the fp32
+ * family).  psgd_uvd_bf16_fold_gathered_f64 folds the gathered copies ([world][count] doubles, rank order) in rank order --
+ * sums in fp64, maxima with the NaN-propagating maximum -- and leaves the workspace exactly as the next kernel of the one-call
+ * sequence expects it.  The fold is not optional: with world = 1 it is what publishes the values.
+ *   stage 10: 2 maxima (max|U|, max|V|)        11: the folded Gram, the 16 ceil((2r + 6) / 16) rows of the fp64 [.][80] matrix
+ *         12: 1 maximum (max|nablaD|)               in use (at most 80 x 80 = 50 KB, never the block partials)
+ *          1: r sums V'(d .* g)                2: r sums U'g1
+ * Sequences (X = exchange):
+ *   apply:   apply_sweep1 -> X(1) -> apply_sweep2 -> X(2) -> apply_sweep3                                       2 exchanges
+ *   update:  [balance_max -> X(10)] update_gram -> X(11) -> update_rewrite -> X(12) -> update_d                 2 (+1)
+ *   fused:   [balance_max -> X(10)] update_gram -> X(11) -> update_rewrite -> X(12) -> apply_sweep1_d -> X(1)
+ *            -> apply_sweep2 -> X(2) -> apply_sweep3                                                            4 (+1)
+ * The fused step needs FOUR exchanges where the fp32 family needs two: that family derives the apply's reductions from sums
+ * over the unrounded d and factor, and here the apply must see the STORED (rounded) state, which exists only after the
+ * rewrite and the d update.  Exchanges must not be merged by algebra on the unrounded state.
+ * row0: the global index of this rank's first row.  The stochastic-rounding index of element (row, c) of U / V is
+ * (row0 + row) * r + c and of d it is row0 + row, so no two ranks share random numbers and the stored codes do not depend on
+ * the split (up to the fp64 fold order of the sums).  The one-call functions are row0 = 0.
+ * balance (update_rewrite) must be what the call decided for balance_max: 1 rescales and rewrites both factors.          */
+int psgd_uvd_bf16_ws_region(int which, int stage, int64_t N, int r, int64_t *offset_bytes, int64_t *count);
+int psgd_uvd_bf16_fold_gathered_f64(int stage, const double *gathered, int world, int64_t N, int r,
+                                    void *ws, int64_t ws_bytes, void *stream);
+int psgd_uvd_balance_max_bf16(const void *U, const void *V, int64_t N, int r, void *ws, int64_t ws_bytes, void *stream);
+int psgd_uvd_update_gram_bf16(const void *U, const void *V, const void *d, const float *v, const float *h,
+                              int64_t N, int r, void *ws, int64_t ws_bytes, void *stream);
+int psgd_uvd_update_rewrite_bf16(void *U, void *V, const void *d, const float *v, const float *h, int64_t N, int r,
+                                 float step, float tiny, int balance, int update_U, int rounding, uint64_t seed,
+                                 int64_t row0, void *ws, int64_t ws_bytes, void *stream);
+/* d <- d - mu_d d nablaD on its own (the plain update) ... */
+int psgd_uvd_update_d_bf16(void *d, int64_t N, int r, float step, float tiny, int rounding, uint64_t seed,
+                           int64_t row0, void *ws, int64_t ws_bytes, void *stream);
+int psgd_uvd_apply_sweep1_bf16(const void *V, const void *d, const float *g, int64_t N, int r,
+                               void *ws, int64_t ws_bytes, void *stream);
+/* ... or riding on the apply's first sweep (the fused step) */
+int psgd_uvd_apply_sweep1_d_bf16(const void *V, void *d, const float *g, int64_t N, int r, float step, float tiny,
+                                 int rounding, uint64_t seed, int64_t row0, void *ws, int64_t ws_bytes, void *stream);
+int psgd_uvd_apply_sweep2_bf16(const void *U, const void *d, const float *g, float *out, int64_t N, int r,
+                               void *ws, int64_t ws_bytes, void *stream);
+int psgd_uvd_apply_sweep3_bf16(const void *V, const void *d, float *out, int64_t N, int r,
+                               void *ws, int64_t ws_bytes, void *stream);
 
 /* ------------------------------------------------- UVd, tail of the step ---
  * What class UVd does around the preconditioner call (psgd.py:729-730, :747, :750-762), for any number k of parameter tensors

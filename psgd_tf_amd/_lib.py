@@ -106,6 +106,17 @@ SIGNATURES = {
     "psgd_uvd_update_bf16": (_int, [_c_f32p] * 5 + [_i64, _int, _flt, _flt, _int, _int, _int, ctypes.c_uint64, _c_ws, _i64, _strm]),
     "psgd_uvd_update_apply_bf16": (_int, [_c_f32p] * 7 + [_i64, _int, _flt, _flt, _int, _int, _int, ctypes.c_uint64, _c_ws, _i64,
                                           _strm]),
+    "psgd_uvd_bf16_ws_region": (_int, [_int, _int, _i64, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "psgd_uvd_bf16_fold_gathered_f64": (_int, [_int, _c_f32p, _int, _i64, _int, _c_ws, _i64, _strm]),
+    "psgd_uvd_balance_max_bf16": (_int, [_c_f32p, _c_f32p, _i64, _int, _c_ws, _i64, _strm]),
+    "psgd_uvd_update_gram_bf16": (_int, [_c_f32p] * 5 + [_i64, _int, _c_ws, _i64, _strm]),
+    "psgd_uvd_update_rewrite_bf16": (_int, [_c_f32p] * 5 + [_i64, _int, _flt, _flt, _int, _int, _int, ctypes.c_uint64, _i64, _c_ws,
+                                            _i64, _strm]),
+    "psgd_uvd_update_d_bf16": (_int, [_c_f32p, _i64, _int, _flt, _flt, _int, ctypes.c_uint64, _i64, _c_ws, _i64, _strm]),
+    "psgd_uvd_apply_sweep1_bf16": (_int, [_c_f32p] * 3 + [_i64, _int, _c_ws, _i64, _strm]),
+    "psgd_uvd_apply_sweep1_d_bf16": (_int, [_c_f32p] * 3 + [_i64, _int, _flt, _flt, _int, ctypes.c_uint64, _i64, _c_ws, _i64, _strm]),
+    "psgd_uvd_apply_sweep2_bf16": (_int, [_c_f32p] * 4 + [_i64, _int, _c_ws, _i64, _strm]),
+    "psgd_uvd_apply_sweep3_bf16": (_int, [_c_f32p] * 3 + [_i64, _int, _c_ws, _i64, _strm]),
     "psgd_uvd_pack_f32": (_int, [_c_f32p, _int, _c_f32p, _i64, _int, _flt, _c_f32p, _strm]),
     "psgd_uvd_sumsq_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_ws, _i64, _strm]),
     "psgd_uvd_param_update_multi": (_int, [_c_f32p, _c_f32p, _int, _c_f32p, _i64, _int, _c_f32p, _flt, _c_f32p, _flt, _flt, _strm]),
@@ -215,6 +226,12 @@ def check(code, what):
 def ws_region(which, stage, N, r):
     off, cnt = _i64(0), _i64(0)
     check(load().psgd_uvd_ws_region(which, stage, N, r, ctypes.byref(off), ctypes.byref(cnt)), "psgd_uvd_ws_region")
+    return off.value, cnt.value
+
+
+def uvd_bf16_ws_region(which, stage, N, r):
+    off, cnt = _i64(0), _i64(0)
+    check(load().psgd_uvd_bf16_ws_region(which, stage, N, r, ctypes.byref(off), ctypes.byref(cnt)), "psgd_uvd_bf16_ws_region")
     return off.value, cnt.value
 
 

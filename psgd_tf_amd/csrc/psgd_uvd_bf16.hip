@@ -20,6 +20,16 @@
 // The stored state is what the apply must see, so the fused update -> apply does NOT use the algebraic short cut of the
 // fp32 path (its reductions are linear in the unrounded d and factor): it is the update's sweeps followed by the apply's,
 // with the d update folded into the apply's first sweep -- five sweeps, about (8r + 4) * 2 + 52 bytes per parameter.
+//
+// Row-sharded state (one process per GPU, psgd_tf_amd/sharded.py): every sweep already ends in a small fold kernel, so the
+// staged entry points stop there, leave this rank's contribution as fp64 in a send region of the workspace
+// (psgd_uvd_bf16_ws_region) and psgd_uvd_bf16_fold_gathered_f64 folds the all-gathered copies in rank order into exactly
+// what the next kernel of the one-call sequence reads.  Exchanges per call -- one more on the balance branch (stage 10):
+//     apply 2 (stages 1, 2)      update 2 (11, 12)      fused update -> apply 4 (11, 12, 1, 2)
+// Four, not the two of the fp32 family: its short cut derives the apply's reductions from sums over the UNROUNDED d and
+// factor, and here the apply must see the stored codes.  The stochastic-rounding stream of a shard is keyed by the GLOBAL
+// element index (row0 + row), so ranks never round their rows with the same random numbers and the stored state does not
+// depend on how the rows are split.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -51,6 +61,11 @@ constexpr int64_t kOffMax = kOffG + kGS * kGS * 8;                // float[2 * k
 constexpr int64_t kOffVec = kOffMax + 2 * kMaxBlocks * 4;         // double[kMaxBlocks * 32]
 constexpr int64_t kOffGram = kOffVec + kMaxBlocks * 32 * 8;       // double[kGramBlocks * kPairs * 256]
 constexpr int64_t kOffNabla = kOffGram + (int64_t)kGramBlocks * kPairs * 256 * 8;   // float[N]
+// fp64 send regions of the staged entry points, in the unused tail of the header (floats 320 .. 1023 are free)
+constexpr int64_t kOffSend10 = 2048;   // double[2]: max|U|, max|V|
+constexpr int64_t kOffSend12 = 2064;   // double[1]: max|nablaD|
+constexpr int64_t kOffSend1 = 2304;    // double[32]: V'(d .* g)
+constexpr int64_t kOffSend2 = 2560;    // double[32]: U'g1
 // header floats
 constexpr int kHScaleU = 0, kHScaleV = 1, kHMuD = 2, kHCo = 8, kHS1 = 256, kHS2 = 288;
 // coefficient r-vectors inside the header (32 floats each, from kHCo)
@@ -521,7 +536,8 @@ __global__ __launch_bounds__(64) void k_small(const double* __restrict__ G, int 
 __global__ __launch_bounds__(kT, 2) void k_rewrite(u16* __restrict__ U, u16* __restrict__ V, const u16* __restrict__ d,
                                                     const float* __restrict__ v, const float* __restrict__ h, long N, Geo g,
                                                     const float* __restrict__ hdr, int update_U, int write_both, int mode,
-                                                    SrKey keyU, SrKey keyV, float* __restrict__ nabla, float* maxpart) {
+                                                    SrKey keyU, SrKey keyV, long grow0, float* __restrict__ nabla,
+                                                    float* maxpart) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ float red[4];
   float* A = lds;
@@ -561,7 +577,7 @@ __global__ __launch_bounds__(kT, 2) void k_rewrite(u16* __restrict__ U, u16* __r
       const float nab = Ph * hh - vv * invPv;                // :581
       nabla[row] = nab;
       lmax = amaxf(lmax, fabsf(nab));
-      const unsigned long long e0 = (unsigned long long)row * (unsigned)r;
+      const unsigned long long e0 = (unsigned long long)(grow0 + row) * (unsigned)r;   // grow0: first row of a shard
       if (update_U) {
 #pragma unroll 4
         for (int k = 0; k < r; ++k) {
@@ -591,21 +607,60 @@ __global__ __launch_bounds__(kT, 2) void k_rewrite(u16* __restrict__ U, u16* __r
 }
 
 // mu_d = step / (max |nablaD| + tiny)   (psgd.py:582)
-__global__ __launch_bounds__(64) void k_mu_d(const float* maxpart, int nblk, float step, float tiny, float* hdr) {
+__device__ __forceinline__ float wave_fold_max(const float* maxpart, int nblk) {
   float m = 0.f;
   for (int b = threadIdx.x; b < nblk; b += 64) m = amaxf(m, maxpart[b]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = amaxf(m, __shfl_xor(m, o));
+  return m;
+}
+
+__global__ __launch_bounds__(64) void k_mu_d(const float* maxpart, int nblk, float step, float tiny, float* hdr) {
+  const float m = wave_fold_max(maxpart, nblk);
   if (threadIdx.x == 0) hdr[kHMuD] = step / (m + tiny);
+}
+
+// staged form: this rank's max |nablaD|, as the double it is sent as
+__global__ __launch_bounds__(64) void k_max_fold(const float* maxpart, int nblk, double* send) {
+  const float m = wave_fold_max(maxpart, nblk);
+  if (threadIdx.x == 0) send[0] = (double)m;
+}
+
+// staged form of the fold inside k_scales (the same order): this rank's max|U|, max|V|
+__global__ void k_bmax_fold(const float* maxpart, int nblk, double* send) {
+  if (threadIdx.x != 0) return;
+  float mu = 0.f, mv = 0.f;
+  for (int b = 0; b < nblk; ++b) { mu = amaxf(mu, maxpart[2 * b]); mv = amaxf(mv, maxpart[2 * b + 1]); }
+  send[0] = (double)mu;
+  send[1] = (double)mv;
+}
+
+// Exchange, second half: `gathered` = the send regions of all ranks, [world][count] doubles in rank order.  Every rank
+// folds them in that order (is_max: NaN-propagating maximum, else +), so all ranks hold the same bits.  dst: the fp64
+// region itself; fdst (optional): the fp32 words the next kernel reads.  ncols > 0: dst is the [.][kGS] Gram and only its
+// first ncols columns are in use (the rest is never written by k_gram_fold and never read by k_small).
+__global__ void k_fold_gathered_b(const double* __restrict__ gathered, int world, int count, int is_max, int ncols,
+                                  double* __restrict__ dst, float* __restrict__ fdst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  if (ncols > 0 && i % kGS >= ncols) return;
+  double a = gathered[i];
+  if (is_max) {
+    for (int k = 1; k < world; ++k) a = psgd::nmax(a, gathered[(long)k * count + i]);
+  } else {
+    for (int k = 1; k < world; ++k) a += gathered[(long)k * count + i];
+  }
+  dst[i] = a;
+  if (fdst) fdst[i] = (float)a;
 }
 
 // d <- d - mu_d d nablaD   (psgd.py:584), on its own (the update without the apply)
 __global__ __launch_bounds__(kT) void k_d_update(u16* __restrict__ d, const float* __restrict__ nabla, long N,
-                                                  const float* __restrict__ hdr, int mode, SrKey keyD) {
+                                                  const float* __restrict__ hdr, int mode, SrKey keyD, long grow0) {
   const float mu = hdr[kHMuD];
   for (long i = (long)blockIdx.x * kT + threadIdx.x; i < N; i += (long)gridDim.x * kT) {
     const float dd = widen(d[i]);
-    d[i] = (u16)narrow(dd - mu * dd * nabla[i], mode, keyD, (unsigned long long)i);
+    d[i] = (u16)narrow(dd - mu * dd * nabla[i], mode, keyD, (unsigned long long)(grow0 + i));
   }
 }
 
@@ -617,7 +672,8 @@ __global__ __launch_bounds__(kT) void k_d_update(u16* __restrict__ d, const floa
 template <int MODE>
 __global__ __launch_bounds__(kT, 2) void k_apply(const u16* __restrict__ M, u16* d, const float* __restrict__ g, float* out,
                                                   long N, Geo geo, const float* __restrict__ hdr,
-                                                  const float* __restrict__ nabla, int mode, SrKey keyD, double* vecpart) {
+                                                  const float* __restrict__ nabla, int mode, SrKey keyD, long grow0,
+                                                  double* vecpart) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* A = lds;
   float* X = A + kT * geo.rp;   // [kT][4]: three pieces of the reduced column
@@ -653,7 +709,7 @@ __global__ __launch_bounds__(kT, 2) void k_apply(const u16* __restrict__ M, u16*
       float dd = widen(d[row]);
       float x;
       if (MODE == 1) {
-        const unsigned code = narrow(dd - mu_d * dd * nabla[row], mode, keyD, (unsigned long long)row);
+        const unsigned code = narrow(dd - mu_d * dd * nabla[row], mode, keyD, (unsigned long long)(grow0 + row));
         d[row] = (u16)code;
         dd = widen(code);
       }
@@ -721,8 +777,9 @@ __global__ __launch_bounds__(kT, 2) void k_apply(const u16* __restrict__ M, u16*
   }
 }
 
-// eight interleaved partial folds per column, then their sum: a fixed order
-__global__ __launch_bounds__(kT) void k_vec_fold(const double* vecpart, int nblk, int r, float* dst) {
+// eight interleaved partial folds per column, then their sum: a fixed order.  dst64 (staged form): the sums stay fp64,
+// this rank's contribution to the exchange; the fold over ranks then writes the fp32 words of dst.
+__global__ __launch_bounds__(kT) void k_vec_fold(const double* vecpart, int nblk, int r, float* dst, double* dst64) {
   __shared__ double sh[8][32];
   const int i = threadIdx.x & 31, part = threadIdx.x >> 5;
   double s = 0.0;
@@ -733,7 +790,8 @@ __global__ __launch_bounds__(kT) void k_vec_fold(const double* vecpart, int nblk
   if ((int)threadIdx.x < r) {
     double t = 0.0;
     for (int p = 0; p < 8; ++p) t += sh[p][threadIdx.x];
-    dst[threadIdx.x] = (float)t;
+    if (dst64) dst64[threadIdx.x] = t;
+    else dst[threadIdx.x] = (float)t;
   }
 }
 
@@ -798,30 +856,33 @@ constexpr size_t kRewriteLdsMax = (size_t)kT * 2 * kMaxRp * 4;
 
 int launch_ok() { return hipGetLastError() == hipSuccess ? PSGD_OK : PSGD_ERR_LAUNCH; }
 
+// send: nullptr = the one-call form (the sums go straight to the header as fp32); otherwise the staged form, which leaves
+// them as fp64 in `send` for the exchange
 template <int MODE>
 int run_apply_sweep(const u16* M, u16* d, const float* g, float* out, int64_t N, const Geo& geo, const Ws& w, int mode,
-                    SrKey keyD, hipStream_t st) {
+                    SrKey keyD, int64_t row0, double* send, hipStream_t st) {
   const size_t lds = (size_t)kT * (geo.rp + 4) * 4 < 4 * 32 * 3 * 8 ? 4 * 32 * 3 * 8 : (size_t)kT * (geo.rp + 4) * 4;
   const int grid = grid_for(N, geo, lds, kMaxBlocks);
   hipLaunchKernelGGL(k_apply<MODE>, dim3(grid), dim3(kT), lds, st, M, d, g, out, (long)N, geo, w.hdr, w.nabla, mode, keyD,
-                     w.vecpart);
+                     (long)row0, w.vecpart);
   if (MODE != 3)
-    hipLaunchKernelGGL(k_vec_fold, dim3(1), dim3(kT), 0, st, w.vecpart, grid, geo.r, w.hdr + (MODE == 2 ? kHS2 : kHS1));
+    hipLaunchKernelGGL(k_vec_fold, dim3(1), dim3(kT), 0, st, w.vecpart, grid, geo.r, w.hdr + (MODE == 2 ? kHS2 : kHS1), send);
   return launch_ok();
 }
 
-// update without its d sweep: [balance maxima] scales, Gram, fold, r x r algebra, rewrite, mu_d
-int run_update_front(u16* U, u16* V, const u16* d, const float* v, const float* h, int64_t N, const Geo& geo, float step,
-                     float tiny, int balance, int update_U, int mode, uint64_t seed, const Ws& w, hipStream_t st) {
+// block maxima of |U|, |V| (the balance branch); returns the number of blocks
+int run_bmax(const u16* U, const u16* V, int64_t N, int r, const Ws& w, hipStream_t st) {
+  const int64_t nch = (N * r + 7) / 8;
+  const int64_t want = (nch + kT - 1) / kT;
+  const int bgrid = (int)(want < kMaxBlocks ? want : kMaxBlocks);
+  hipLaunchKernelGGL(k_bmax, dim3(bgrid), dim3(kT), 0, st, U, V, (long)(N * r), w.maxpart);
+  return bgrid;
+}
+
+// Gram sweep and the fold of its block partials
+int run_gram(const u16* U, const u16* V, const u16* d, const float* v, const float* h, int64_t N, const Geo& geo, const Ws& w,
+             hipStream_t st) {
   const int r = geo.r;
-  int bgrid = 1;
-  if (balance) {
-    const int64_t nch = (N * r + 7) / 8;
-    const int64_t want = (nch + kT - 1) / kT;
-    bgrid = (int)(want < kMaxBlocks ? want : kMaxBlocks);
-    hipLaunchKernelGGL(k_bmax, dim3(bgrid), dim3(kT), 0, st, U, V, (long)(N * r), w.maxpart);
-  }
-  hipLaunchKernelGGL(k_scales, dim3(1), dim3(64), 0, st, w.maxpart, bgrid, balance, w.hdr);
   const int nb = (2 * r + 6 + 15) / 16;
   const size_t lds = (size_t)kT * (2 * geo.rp + 7) * 4;
   const int ggrid = grid_for(N, geo, lds, kGramBlocks);
@@ -836,14 +897,53 @@ int run_update_front(u16* U, u16* V, const u16* d, const float* v, const float* 
     default: return PSGD_ERR_RANK;
   }
   hipLaunchKernelGGL(k_gram_fold, dim3(kPairs), dim3(kT), 0, st, w.grampart, ggrid, nb, w.G);
-  hipLaunchKernelGGL(k_small, dim3(1), dim3(64), 0, st, w.G, r, step, tiny, update_U, w.hdr);
+  return PSGD_OK;
+}
+
+// r x r algebra and the rewrite sweep; *grid_out = the number of block maxima of |nablaD| it leaves
+int run_rewrite(u16* U, u16* V, const u16* d, const float* v, const float* h, int64_t N, const Geo& geo, float step,
+                float tiny, int balance, int update_U, int mode, uint64_t seed, int64_t row0, const Ws& w, hipStream_t st,
+                int* grid_out) {
+  hipLaunchKernelGGL(k_small, dim3(1), dim3(64), 0, st, w.G, geo.r, step, tiny, update_U, w.hdr);
   const size_t lds2 = (size_t)kT * 2 * geo.rp * 4;
   const int grid = grid_for(N, geo, lds2, kMaxBlocks);
   if (int rc = set_lds<k_rewrite>(kRewriteLdsMax)) return rc;
   hipLaunchKernelGGL(k_rewrite, dim3(grid), dim3(kT), lds2, st, U, V, d, v, h, (long)N, geo, w.hdr, update_U, balance, mode,
-                     make_key(seed, 0), make_key(seed, 1), w.nabla, w.maxpart);
+                     make_key(seed, 0), make_key(seed, 1), (long)row0, w.nabla, w.maxpart);
+  *grid_out = grid;
+  return PSGD_OK;
+}
+
+// update without its d sweep: [balance maxima] scales, Gram, fold, r x r algebra, rewrite, mu_d
+int run_update_front(u16* U, u16* V, const u16* d, const float* v, const float* h, int64_t N, const Geo& geo, float step,
+                     float tiny, int balance, int update_U, int mode, uint64_t seed, const Ws& w, hipStream_t st) {
+  const int bgrid = balance ? run_bmax(U, V, N, geo.r, w, st) : 1;
+  hipLaunchKernelGGL(k_scales, dim3(1), dim3(64), 0, st, w.maxpart, bgrid, balance, w.hdr);
+  if (int rc = run_gram(U, V, d, v, h, N, geo, w, st)) return rc;
+  int grid = 0;
+  if (int rc = run_rewrite(U, V, d, v, h, N, geo, step, tiny, balance, update_U, mode, seed, 0, w, st, &grid)) return rc;
   hipLaunchKernelGGL(k_mu_d, dim3(1), dim3(64), 0, st, w.maxpart, grid, step, tiny, w.hdr);
   return launch_ok();
+}
+
+void run_d_update(u16* d, int64_t N, int mode, uint64_t seed, int64_t row0, const Ws& w, hipStream_t st) {
+  const int64_t want = (N + kT - 1) / kT;
+  const int grid = (int)(want < 2048 ? want : 2048);
+  hipLaunchKernelGGL(k_d_update, dim3(grid), dim3(kT), 0, st, d, w.nabla, (long)N, w.hdr, mode, make_key(seed, 2), (long)row0);
+}
+
+double* send_ptr(void* ws, int64_t off) { return reinterpret_cast<double*>(static_cast<char*>(ws) + off); }
+
+// offset (bytes) and count (doubles) of the send region of `stage`; false for an unknown stage
+bool send_region(int stage, int r, int64_t* off, int64_t* count) {
+  switch (stage) {
+    case 1: *off = kOffSend1; *count = r; return true;
+    case 2: *off = kOffSend2; *count = r; return true;
+    case 10: *off = kOffSend10; *count = 2; return true;
+    case 11: *off = kOffG; *count = (int64_t)16 * ((2 * r + 6 + 15) / 16) * kGS; return true;   // the rows of G in use
+    case 12: *off = kOffSend12; *count = 1; return true;
+    default: return false;
+  }
 }
 
 }  // namespace
@@ -857,22 +957,27 @@ int64_t psgd_uvd_bf16_workspace_bytes(int64_t N, int r) {
   return ws_bytes_for(N);
 }
 
-int psgd_uvd_apply_bf16(const void* U, const void* V, const void* d, const float* g, float* out, int64_t N, int r, void* ws,
-                        int64_t ws_bytes, void* stream) {
+static int check_apply(const void* U, const void* V, const void* d, const float* g, float* out, int64_t N, int r) {
   if (!U || !V || !d || !g || !out) return PSGD_ERR_BAD_ARG;
   if (int rc = check_common(N, r)) return rc;
   if (out == g) return PSGD_ERR_BAD_ARG;
   if (misaligned(U, 16) || misaligned(V, 16) || misaligned(d, 16) || misaligned(g, 4) || misaligned(out, 4))
     return PSGD_ERR_ALIGN;
+  return PSGD_OK;
+}
+
+int psgd_uvd_apply_bf16(const void* U, const void* V, const void* d, const float* g, float* out, int64_t N, int r, void* ws,
+                        int64_t ws_bytes, void* stream) {
+  if (int rc = check_apply(U, V, d, g, out, N, r)) return rc;
   Ws w;
   if (int rc = carve(ws, ws_bytes, N, w)) return rc;
   const Geo geo = make_geo(r);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const SrKey k0{0, 0};
   u16* dd = const_cast<u16*>(static_cast<const u16*>(d));   // MODE 0, 2, 3 only read d
-  if (int rc = run_apply_sweep<0>(static_cast<const u16*>(V), dd, g, out, N, geo, w, 0, k0, st)) return rc;
-  if (int rc = run_apply_sweep<2>(static_cast<const u16*>(U), dd, g, out, N, geo, w, 0, k0, st)) return rc;
-  return run_apply_sweep<3>(static_cast<const u16*>(V), dd, g, out, N, geo, w, 0, k0, st);
+  if (int rc = run_apply_sweep<0>(static_cast<const u16*>(V), dd, g, out, N, geo, w, 0, k0, 0, nullptr, st)) return rc;
+  if (int rc = run_apply_sweep<2>(static_cast<const u16*>(U), dd, g, out, N, geo, w, 0, k0, 0, nullptr, st)) return rc;
+  return run_apply_sweep<3>(static_cast<const u16*>(V), dd, g, out, N, geo, w, 0, k0, 0, nullptr, st);
 }
 
 static int check_update(const void* U, const void* V, const void* d, const float* v, const float* h, int64_t N, int r,
@@ -896,10 +1001,7 @@ int psgd_uvd_update_bf16(void* U, void* V, void* d, const float* v, const float*
   if (int rc = run_update_front(static_cast<u16*>(U), static_cast<u16*>(V), static_cast<const u16*>(d), v, h, N, geo, step,
                                 tiny, balance != 0, update_U != 0, rounding, seed, w, st))
     return rc;
-  const int64_t want = (N + kT - 1) / kT;
-  const int grid = (int)(want < 2048 ? want : 2048);
-  hipLaunchKernelGGL(k_d_update, dim3(grid), dim3(kT), 0, st, static_cast<u16*>(d), w.nabla, (long)N, w.hdr, rounding,
-                     make_key(seed, 2));
+  run_d_update(static_cast<u16*>(d), N, rounding, seed, 0, w, st);
   return launch_ok();
 }
 
@@ -918,9 +1020,143 @@ int psgd_uvd_update_apply_bf16(void* U, void* V, void* d, const float* v, const 
   if (int rc = run_update_front(Uq, Vq, dq, v, h, N, geo, step, tiny, balance != 0, update_U != 0, rounding, seed, w, st))
     return rc;
   const SrKey kd = make_key(seed, 2);
-  if (int rc = run_apply_sweep<1>(Vq, dq, g, out, N, geo, w, rounding, kd, st)) return rc;
-  if (int rc = run_apply_sweep<2>(Uq, dq, g, out, N, geo, w, rounding, kd, st)) return rc;
-  return run_apply_sweep<3>(Vq, dq, g, out, N, geo, w, rounding, kd, st);
+  if (int rc = run_apply_sweep<1>(Vq, dq, g, out, N, geo, w, rounding, kd, 0, nullptr, st)) return rc;
+  if (int rc = run_apply_sweep<2>(Uq, dq, g, out, N, geo, w, rounding, kd, 0, nullptr, st)) return rc;
+  return run_apply_sweep<3>(Vq, dq, g, out, N, geo, w, rounding, kd, 0, nullptr, st);
+}
+
+// ------------------------------------------------------------------ staged forms (row-sharded state)
+int psgd_uvd_bf16_ws_region(int which, int stage, int64_t N, int r, int64_t* offset_bytes, int64_t* count) {
+  if (!offset_bytes || !count) return PSGD_ERR_BAD_ARG;
+  if (int rc = check_common(N, r)) return rc;
+  if (which != PSGD_WS_SEND_F64) return PSGD_ERR_BAD_ARG;
+  return send_region(stage, r, offset_bytes, count) ? PSGD_OK : PSGD_ERR_BAD_ARG;
+}
+
+int psgd_uvd_bf16_fold_gathered_f64(int stage, const double* gathered, int world, int64_t N, int r, void* ws,
+                                    int64_t ws_bytes, void* stream) {
+  if (!gathered || world < 1 || misaligned(gathered, 8)) return PSGD_ERR_BAD_ARG;
+  if (int rc = check_common(N, r)) return rc;
+  int64_t off = 0, count = 0;
+  if (!send_region(stage, r, &off, &count)) return PSGD_ERR_BAD_ARG;
+  Ws w;
+  if (int rc = carve(ws, ws_bytes, N, w)) return rc;
+  float* fdst = nullptr;
+  int is_max = 0, ncols = 0;
+  if (stage == 1) fdst = w.hdr + kHS1;
+  else if (stage == 2) fdst = w.hdr + kHS2;
+  else if (stage == 11) ncols = 16 * ((2 * r + 6 + 15) / 16);
+  else { is_max = 1; fdst = w.maxpart; }   // 10: what k_scales folds (one "block"); 12: what k_mu_d folds
+  hipLaunchKernelGGL(k_fold_gathered_b, dim3(((int)count + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     gathered, world, (int)count, is_max, ncols, send_ptr(ws, off), fdst);
+  return launch_ok();
+}
+
+int psgd_uvd_balance_max_bf16(const void* U, const void* V, int64_t N, int r, void* ws, int64_t ws_bytes, void* stream) {
+  if (!U || !V) return PSGD_ERR_BAD_ARG;
+  if (int rc = check_common(N, r)) return rc;
+  if (misaligned(U, 16) || misaligned(V, 16)) return PSGD_ERR_ALIGN;
+  Ws w;
+  if (int rc = carve(ws, ws_bytes, N, w)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int bgrid = run_bmax(static_cast<const u16*>(U), static_cast<const u16*>(V), N, r, w, st);
+  hipLaunchKernelGGL(k_bmax_fold, dim3(1), dim3(64), 0, st, w.maxpart, bgrid, send_ptr(ws, kOffSend10));
+  return launch_ok();
+}
+
+int psgd_uvd_update_gram_bf16(const void* U, const void* V, const void* d, const float* v, const float* h, int64_t N, int r,
+                              void* ws, int64_t ws_bytes, void* stream) {
+  if (int rc = check_update(U, V, d, v, h, N, r, 0)) return rc;
+  Ws w;
+  if (int rc = carve(ws, ws_bytes, N, w)) return rc;
+  if (int rc = run_gram(static_cast<const u16*>(U), static_cast<const u16*>(V), static_cast<const u16*>(d), v, h, N,
+                        make_geo(r), w, static_cast<hipStream_t>(stream)))
+    return rc;
+  return launch_ok();
+}
+
+int psgd_uvd_update_rewrite_bf16(void* U, void* V, const void* d, const float* v, const float* h, int64_t N, int r,
+                                 float step, float tiny, int balance, int update_U, int rounding, uint64_t seed,
+                                 int64_t row0, void* ws, int64_t ws_bytes, void* stream) {
+  if (int rc = check_update(U, V, d, v, h, N, r, rounding)) return rc;
+  if (row0 < 0) return PSGD_ERR_BAD_ARG;
+  Ws w;
+  if (int rc = carve(ws, ws_bytes, N, w)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // after the fold of stage 10 the maxima of the whole problem are the one "block" of the scales kernel
+  hipLaunchKernelGGL(k_scales, dim3(1), dim3(64), 0, st, w.maxpart, 1, balance != 0, w.hdr);
+  int grid = 0;
+  if (int rc = run_rewrite(static_cast<u16*>(U), static_cast<u16*>(V), static_cast<const u16*>(d), v, h, N, make_geo(r), step,
+                           tiny, balance != 0, update_U != 0, rounding, seed, row0, w, st, &grid))
+    return rc;
+  hipLaunchKernelGGL(k_max_fold, dim3(1), dim3(64), 0, st, w.maxpart, grid, send_ptr(ws, kOffSend12));
+  return launch_ok();
+}
+
+static int check_d(const void* d, int64_t N, int r, int rounding, int64_t row0) {
+  if (!d) return PSGD_ERR_BAD_ARG;
+  if (int rc = check_common(N, r)) return rc;
+  if ((rounding != 0 && rounding != 1) || row0 < 0) return PSGD_ERR_BAD_ARG;
+  if (misaligned(d, 16)) return PSGD_ERR_ALIGN;
+  return PSGD_OK;
+}
+
+int psgd_uvd_update_d_bf16(void* d, int64_t N, int r, float step, float tiny, int rounding, uint64_t seed, int64_t row0,
+                           void* ws, int64_t ws_bytes, void* stream) {
+  if (int rc = check_d(d, N, r, rounding, row0)) return rc;
+  Ws w;
+  if (int rc = carve(ws, ws_bytes, N, w)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_mu_d, dim3(1), dim3(64), 0, st, w.maxpart, 1, step, tiny, w.hdr);
+  run_d_update(static_cast<u16*>(d), N, rounding, seed, row0, w, st);
+  return launch_ok();
+}
+
+int psgd_uvd_apply_sweep1_bf16(const void* V, const void* d, const float* g, int64_t N, int r, void* ws, int64_t ws_bytes,
+                               void* stream) {
+  if (!V || !d || !g) return PSGD_ERR_BAD_ARG;
+  if (int rc = check_common(N, r)) return rc;
+  if (misaligned(V, 16) || misaligned(d, 16) || misaligned(g, 4)) return PSGD_ERR_ALIGN;
+  Ws w;
+  if (int rc = carve(ws, ws_bytes, N, w)) return rc;
+  u16* dd = const_cast<u16*>(static_cast<const u16*>(d));   // MODE 0 only reads d
+  return run_apply_sweep<0>(static_cast<const u16*>(V), dd, g, nullptr, N, make_geo(r), w, 0, SrKey{0, 0}, 0,
+                            send_ptr(ws, kOffSend1), static_cast<hipStream_t>(stream));
+}
+
+int psgd_uvd_apply_sweep1_d_bf16(const void* V, void* d, const float* g, int64_t N, int r, float step, float tiny,
+                                 int rounding, uint64_t seed, int64_t row0, void* ws, int64_t ws_bytes, void* stream) {
+  if (!V || !g) return PSGD_ERR_BAD_ARG;
+  if (int rc = check_d(d, N, r, rounding, row0)) return rc;
+  if (misaligned(V, 16) || misaligned(g, 4)) return PSGD_ERR_ALIGN;
+  Ws w;
+  if (int rc = carve(ws, ws_bytes, N, w)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_mu_d, dim3(1), dim3(64), 0, st, w.maxpart, 1, step, tiny, w.hdr);
+  return run_apply_sweep<1>(static_cast<const u16*>(V), static_cast<u16*>(d), g, nullptr, N, make_geo(r), w, rounding,
+                            make_key(seed, 2), row0, send_ptr(ws, kOffSend1), st);
+}
+
+int psgd_uvd_apply_sweep2_bf16(const void* U, const void* d, const float* g, float* out, int64_t N, int r, void* ws,
+                               int64_t ws_bytes, void* stream) {
+  if (int rc = check_apply(U, U, d, g, out, N, r)) return rc;
+  Ws w;
+  if (int rc = carve(ws, ws_bytes, N, w)) return rc;
+  u16* dd = const_cast<u16*>(static_cast<const u16*>(d));
+  return run_apply_sweep<2>(static_cast<const u16*>(U), dd, g, out, N, make_geo(r), w, 0, SrKey{0, 0}, 0,
+                            send_ptr(ws, kOffSend2), static_cast<hipStream_t>(stream));
+}
+
+int psgd_uvd_apply_sweep3_bf16(const void* V, const void* d, float* out, int64_t N, int r, void* ws, int64_t ws_bytes,
+                               void* stream) {
+  if (!V || !d || !out) return PSGD_ERR_BAD_ARG;
+  if (int rc = check_common(N, r)) return rc;
+  if (misaligned(V, 16) || misaligned(d, 16) || misaligned(out, 4)) return PSGD_ERR_ALIGN;
+  Ws w;
+  if (int rc = carve(ws, ws_bytes, N, w)) return rc;
+  u16* dd = const_cast<u16*>(static_cast<const u16*>(d));
+  return run_apply_sweep<3>(static_cast<const u16*>(V), dd, nullptr, out, N, make_geo(r), w, 0, SrKey{0, 0}, 0, nullptr,
+                            static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -893,12 +893,23 @@ class UVd:
                                  "bfloat16 parameters), got %s" % (self._store_dtype,))
             if r > _lib.UVD_MAX_RANK:
                 raise ValueError("UVd: state_route='native' supports ranks up to %d, got %d" % (_lib.UVD_MAX_RANK, r))
-            if group is not None or stage_backend is not None:
-                raise ValueError("UVd: state_route='native' does not support the row-sharded optimizer (group= / stage_backend=)")
+            # row-sharded (group=): this rank's rows in bf16, the staged bf16 kernels of sharded.py -- 4 exchanges per step.  The
+            # bf16 stages exist in the HIP backend only, and the group must be a real process group.
+            if stage_backend is not None:
+                raise ValueError("UVd: state_route='native' runs the HIP stages of its group= only (stage_backend= is not supported)")
+            if group is not None:
+                import torch.distributed as _dist
+                if not (_dist.is_available() and isinstance(group, _dist.ProcessGroup)):
+                    raise ValueError("UVd: state_route='native' needs group= to be a torch.distributed process group, got %r"
+                                     % (type(group),))
             state_rounding = "stochastic" if state_rounding is None else state_rounding
             if state_rounding not in _ROUNDINGS:
                 raise ValueError("UVd: state_rounding must be 'stochastic' or 'nearest', got %r" % (state_rounding,))
-            gen = generator if generator is not None else _branch_rng
+            if group is None:
+                gen = generator if generator is not None else _branch_rng
+            else:       # the generator whose state rank 0 broadcasts: one seed for all ranks
+                from . import sharded as _sharded
+                gen = _sharded.branch_rng_for(generator, group, p0.device).gen
             self._round_seed0 = int(torch.randint(0, 2 ** 62, (), generator=gen).item())
             self._round_step = 0
         elif state_rounding is not None:
@@ -1036,7 +1047,14 @@ class UVd:
             grad = self._flat(grads, "g")                                                     # :747
             # :732-733 then :748 as one fused call (same results, three sweeps instead of six)
             U, V, d = self._state_fp32()
-            if self._native:                       # the stored bf16 tensors go straight to the fused call
+            if self._native and self._group is not None:     # this rank's bf16 rows; 4 exchanges (sharded.py)
+                seed = uvd_step_rounding_seed(self._round_seed0, self._round_step)
+                self._round_step += 1
+                pre_grad = self._sharded.update_precond_UVd_math_and_precond_grad(
+                    U, V, d, v[:, None].contiguous(), h[:, None].contiguous(), grad[:, None].contiguous(),
+                    float(self.lr_preconditioner), self._tiny, generator=self._generator, group=self._group,
+                    rounding=self._state_rounding, rounding_seed=seed)
+            elif self._native:                     # the stored bf16 tensors go straight to the fused call
                 seed = uvd_step_rounding_seed(self._round_seed0, self._round_step)
                 self._round_step += 1
                 pre_grad = update_precond_UVd_math_and_precond_grad(

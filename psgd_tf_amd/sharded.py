@@ -16,6 +16,18 @@ whatever algorithm RCCL picks), so the r x r solves and step sizes redone on eve
     fused update -> apply:     sweep1 -> X(Gram) -> sweep2 -> X([pU | pV | qU | qV | max]) ->
                                r x r algebra -> last sweep (d update + whole apply)             2 exchanges
 
+A bf16-stored state (U, V, d all bfloat16, r <= 32; psgd_uvd_bf16.hip) runs the staged forms of the bf16 kernels.  Its fused
+step cannot use the algebraic short cut above -- the apply must see the STORED, rounded state, which exists only after the
+rewrite sweep and the d update -- so it is the update's exchanges followed by the apply's:
+
+    apply:                     sweep1 -> X(1) -> sweep2 -> X(2) -> sweep3                        2 exchanges
+    update:                    [max -> X(10)] gram -> X(11) -> rewrite -> X(12) -> d update      2 exchanges
+    fused update -> apply:     [max -> X(10)] gram -> X(11) -> rewrite -> X(12) ->
+                               sweep1 (+ d update) -> X(1) -> sweep2 -> X(2) -> sweep3           4 exchanges
+
+The stochastic-rounding stream is keyed by the GLOBAL element index: every rank passes row0, the number of rows on the ranks
+before it (one set-up collective per (group, local row count), cached).
+
 The two random branches of the reference (psgd.py:562, :588) must agree across ranks as well:
 pass them explicitly, or let them be drawn from a branch generator whose state is synchronised
 from rank 0 ONCE (first use); afterwards every rank draws the same numbers locally -- no
@@ -148,15 +160,93 @@ class HipStages:
                                                        wp, wn, st), "update_sweep3")
 
 
+class HipStagesBf16:
+    """Stage functions of the bf16-state kernels (psgd_uvd_*_bf16) on this rank's shard: U, V, d bfloat16, vectors fp32.  The
+    send regions are views into the device workspace (psgd_uvd_bf16_ws_region); the fold after every stage is what publishes
+    the reduced values to the next one (with one rank as well)."""
+
+    def __init__(self, device, n_local, r):
+        self.device, self.N, self.r = device, int(n_local), int(r)
+        if self.r > _lib.UVD_MAX_RANK:
+            raise ValueError("a bfloat16 state supports ranks up to %d, got r = %d" % (_lib.UVD_MAX_RANK, self.r))
+        self.lib = _lib.load()
+        self.ws = _psgd.uvd_bf16_workspace(device, self.N, self.r)
+        self._views = {}
+        self._out = None
+
+    def _w(self):
+        return self.ws.data_ptr(), self.ws.numel(), torch.cuda.current_stream(self.device).cuda_stream
+
+    def send(self, stage):
+        if stage not in self._views:
+            off, cnt = _lib.uvd_bf16_ws_region(_lib.PSGD_WS_SEND_F64, stage, self.N, self.r)
+            self._views[stage] = self.ws[off:off + cnt * 8].view(torch.float64)
+        return self._views[stage]
+
+    def gather_buf(self, stage, world):
+        key = ("gather", stage, world)
+        if key not in self._views:
+            self._views[key] = torch.empty(world * self.send(stage).numel(), dtype=torch.float64, device=self.device)
+        return self._views[key]
+
+    def fold(self, stage, gathered, world):
+        wp, wn, st = self._w()
+        _lib.check(self.lib.psgd_uvd_bf16_fold_gathered_f64(stage, gathered.data_ptr(), world, self.N, self.r, wp, wn, st),
+                   "bf16 fold_gathered")
+
+    def coefficients(self):
+        """the r-vectors of the last r x r algebra (fp32 header words 8 .. 8 + 224: identical on every rank)"""
+        return self.ws[32:32 + 224 * 4].view(torch.float32)
+
+    def balance_max(self, U, V):
+        _lib.check(self.lib.psgd_uvd_balance_max_bf16(U.data_ptr(), V.data_ptr(), self.N, self.r, *self._w()), "bf16 balance_max")
+
+    def update_gram(self, U, V, d, v, h):
+        _lib.check(self.lib.psgd_uvd_update_gram_bf16(U.data_ptr(), V.data_ptr(), d.data_ptr(), v.data_ptr(), h.data_ptr(),
+                                                      self.N, self.r, *self._w()), "bf16 update_gram")
+
+    def update_rewrite(self, U, V, d, v, h, step, tiny, balance, update_U, mode, seed, row0):
+        wp, wn, st = self._w()
+        _lib.check(self.lib.psgd_uvd_update_rewrite_bf16(U.data_ptr(), V.data_ptr(), d.data_ptr(), v.data_ptr(), h.data_ptr(),
+                                                         self.N, self.r, float(step), float(tiny), int(bool(balance)),
+                                                         int(bool(update_U)), mode, seed, row0, wp, wn, st), "bf16 update_rewrite")
+
+    def update_d(self, d, step, tiny, mode, seed, row0):
+        wp, wn, st = self._w()
+        _lib.check(self.lib.psgd_uvd_update_d_bf16(d.data_ptr(), self.N, self.r, float(step), float(tiny), mode, seed, row0,
+                                                   wp, wn, st), "bf16 update_d")
+
+    def apply_sweep1(self, V, d, g):
+        _lib.check(self.lib.psgd_uvd_apply_sweep1_bf16(V.data_ptr(), d.data_ptr(), g.data_ptr(), self.N, self.r, *self._w()),
+                   "bf16 apply_sweep1")
+
+    def apply_sweep1_d(self, V, d, g, step, tiny, mode, seed, row0):
+        wp, wn, st = self._w()
+        _lib.check(self.lib.psgd_uvd_apply_sweep1_d_bf16(V.data_ptr(), d.data_ptr(), g.data_ptr(), self.N, self.r, float(step),
+                                                         float(tiny), mode, seed, row0, wp, wn, st), "bf16 apply_sweep1_d")
+
+    def apply_sweep2(self, U, d, g, out=None):
+        self._out = torch.empty_like(g) if out is None else out           # holds g1 = d.*g + U s1 until sweep 3
+        _lib.check(self.lib.psgd_uvd_apply_sweep2_bf16(U.data_ptr(), d.data_ptr(), g.data_ptr(), self._out.data_ptr(),
+                                                       self.N, self.r, *self._w()), "bf16 apply_sweep2")
+
+    def apply_sweep3(self, V, d):
+        out, self._out = self._out, None
+        _lib.check(self.lib.psgd_uvd_apply_sweep3_bf16(V.data_ptr(), d.data_ptr(), out.data_ptr(), self.N, self.r, *self._w()),
+                   "bf16 apply_sweep3")
+        return out
+
+
 _backends = {}
 
 
 def hip_backend_for(U):
     if not U.is_cuda:
         raise _lib.PsgdHipError("sharded UVd runs on HIP devices only (tensor is on %s); no CPU fallback" % U.device)
-    key = (U.device.index, U.shape[0], U.shape[1], torch.cuda.current_stream(U.device).cuda_stream)
+    key = (U.device.index, U.shape[0], U.shape[1], torch.cuda.current_stream(U.device).cuda_stream, U.dtype)
     if key not in _backends:
-        _backends[key] = HipStages(U.device, U.shape[0], U.shape[1])
+        cls = HipStagesBf16 if U.dtype == torch.bfloat16 else HipStages
+        _backends[key] = cls(U.device, U.shape[0], U.shape[1])
     return _backends[key]
 
 
@@ -406,8 +496,98 @@ def _check_explicit_branches_agree(balance, update_U, device, group):
         raise ValueError("sharded UVd: ranks passed different explicit balance / update_U values")
 
 
+_row0s = {}
+
+
+def global_row0(n_local, device=None, group=None):
+    """Rows on the ranks before this one = the global index of this rank's first row (the exclusive prefix of the ranks' row
+    counts).  One all-gather and a host read the first time a (group, local row count) is seen; cached afterwards."""
+    key = (id(group) if group is not None else None, int(n_local))
+    ent = _row0s.get(key)
+    if ent is None or ent[0] is not group:
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+        on_host = _host_collectives(group) or device is None or torch.device(device).type == "cpu"
+        dev = "cpu" if on_host else device
+        counts = torch.empty(world, dtype=torch.int64, device=dev)
+        dist.all_gather_into_tensor(counts, torch.tensor([int(n_local)], dtype=torch.int64, device=dev), group=group)
+        ent = (group, int(counts.cpu()[:rank].sum().item()))              # (the strong reference keeps id() unique)
+        _row0s[key] = ent
+    return ent[1]
+
+
+def _bf16_sharded(name, U, V, d, cols, backend):
+    """True when U, V, d are a bf16-stored state; raises for a mixed state, ranks above 32 and (product backend) everything the
+    single-GPU bf16 entry points refuse."""
+    if backend is None:
+        if not _psgd._bf16_state(name, U, V, d, *cols):
+            return False
+        if not all(t.is_contiguous() for t in (U, V, d) + tuple(cols)):
+            raise ValueError("%s: contiguous tensors required" % name)
+        _psgd._uvd_shapes(name, U, V, d, *cols)
+        return True
+    dts = {t.dtype for t in (U, V, d)}
+    if torch.bfloat16 not in dts:
+        return False
+    if dts != {torch.bfloat16}:
+        raise TypeError("%s: mixed state dtypes %s; U, V and d must all be bfloat16 (or all float32)"
+                        % (name, sorted(str(x) for x in dts)))
+    if U.shape[1] > _lib.UVD_MAX_RANK:
+        raise ValueError("%s: a bfloat16 state supports ranks up to %d, got %d" % (name, _lib.UVD_MAX_RANK, U.shape[1]))
+    return True
+
+
+def _no_rounding(name, rounding, rounding_seed, row0):
+    if rounding not in _psgd._ROUNDINGS:
+        raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (name, rounding))
+    if rounding != "nearest" or rounding_seed is not None or row0 is not None:
+        raise ValueError("%s: rounding / rounding_seed / row0 apply to a bfloat16 state only; an fp32 state is not rounded" % name)
+
+
+def _bf16_update_args(name, U, balance, update_U, generator, rounding, rounding_seed, row0, group, backend):
+    """what the two updating bf16 calls share: the branches, the rounding mode, ONE seed for all ranks (drawn, when none is given,
+    from the synchronised branch generator after the branch draws) and this rank's first global row"""
+    if rounding not in _psgd._ROUNDINGS:
+        raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (name, rounding))
+    device = U.device if backend is None else None
+    balance, update_U = _agree_on_branches(balance, update_U, generator, device, group)
+    if rounding_seed is None:
+        rounding_seed = 0
+        if rounding == "stochastic":
+            gen = branch_rng_for(generator, group, device).gen
+            rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=gen).item())
+    if row0 is None:
+        row0 = global_row0(U.shape[0], device, group)
+    if int(row0) < 0:
+        raise ValueError("%s: row0 must be >= 0, got %r" % (name, row0))
+    return balance, update_U, _psgd._ROUNDINGS[rounding], int(rounding_seed) & (2 ** 64 - 1), int(row0)
+
+
+def _bf16_update_front(be, U, V, d, v, h, step, tiny, balance, update_U, mode, seed, row0, group):
+    if balance:
+        be.balance_max(U, V)
+        _exchange(be, 10, group)
+    be.update_gram(U, V, d, v, h)
+    _exchange(be, 11, group)
+    be.update_rewrite(U, V, d, v, h, step, tiny, balance, update_U, mode, seed, row0)
+    _exchange(be, 12, group)
+
+
+def _bf16_apply_tail(be, U, V, d, g, group, out=None):
+    _exchange(be, 1, group)
+    if out is None:
+        be.apply_sweep2(U, d, g)
+    else:
+        be.apply_sweep2(U, d, g, out=out)
+    _exchange(be, 2, group)
+    return be.apply_sweep3(V, d)
+
+
 def precond_grad_UVd_math(U, V, d, g, group=None, backend=None):
-    """Sharded psgd.py:619-627 on this rank's rows; returns this rank's rows of the result.  2 exchanges."""
+    """Sharded psgd.py:619-627 on this rank's rows; returns this rank's rows of the result.  2 exchanges (fp32 and bf16 state)."""
+    if _bf16_sharded("sharded precond_grad_UVd_math", U, V, d, (g,), backend):
+        be = backend if backend is not None else hip_backend_for(U)
+        be.apply_sweep1(V, d, g)
+        return _bf16_apply_tail(be, U, V, d, g, group)
     if backend is None:
         _check_local("sharded precond_grad_UVd_math", U, V, d, g)
     if _is_wide(U, backend):
@@ -421,8 +601,20 @@ def precond_grad_UVd_math(U, V, d, g, group=None, backend=None):
 
 
 def update_precond_UVd_math_(U, V, d, v, h, step, tiny, *, balance=None, update_U=None, generator=None,
-                             group=None, backend=None):
-    """Sharded psgd.py:554-617 on this rank's rows (in place, returns None).  2 exchanges (+1 on the balance branch)."""
+                             group=None, backend=None, rounding="nearest", rounding_seed=None, row0=None):
+    """Sharded psgd.py:554-617 on this rank's rows (in place, returns None).  2 exchanges (+1 on the balance branch).
+    A bfloat16 U, V, d (fp32 v, h; r <= 32) is updated by the bf16-state kernels: rounding / rounding_seed as in the single-GPU
+    function (every rank must use the same seed: None draws it from the synchronised branch generator); row0 = the global index
+    of this rank's first row (None: the exclusive prefix of the ranks' row counts, one set-up collective)."""
+    name = "sharded update_precond_UVd_math_"
+    if _bf16_sharded(name, U, V, d, (v, h), backend):
+        balance, update_U, mode, seed, row0 = _bf16_update_args(name, U, balance, update_U, generator, rounding, rounding_seed,
+                                                                row0, group, backend)
+        be = backend if backend is not None else hip_backend_for(U)
+        _bf16_update_front(be, U, V, d, v, h, step, tiny, balance, update_U, mode, seed, row0, group)
+        be.update_d(d, step, tiny, mode, seed, row0)
+        return None
+    _no_rounding(name, rounding, rounding_seed, row0)
     if backend is None:
         _check_local("sharded update_precond_UVd_math_", U, V, d, v, h)
     if _is_wide(U, backend):
@@ -444,10 +636,24 @@ def update_precond_UVd_math_(U, V, d, v, h, step, tiny, *, balance=None, update_
 
 
 def update_precond_UVd_math_and_precond_grad(U, V, d, v, h, g, step, tiny, *, balance=None, update_U=None,
-                                             generator=None, group=None, backend=None, out=None):
+                                             generator=None, group=None, backend=None, out=None, rounding="nearest",
+                                             rounding_seed=None, row0=None):
     """Sharded fused update -> apply; returns this rank's rows of the preconditioned gradient.
     2 exchanges: the Gram; the 4r column sums of sweep 2 with max|nablaD| in one buffer (every rank, r > 32 included since
-    round 6)."""
+    round 6).  A bfloat16 state takes 4 exchanges (11, 12, 1, 2): the gradient is preconditioned with the state as it was
+    STORED, so the apply's reductions cannot be derived from sums over the unrounded one; rounding, rounding_seed and row0 as in
+    update_precond_UVd_math_."""
+    name = "sharded update_precond_UVd_math_and_precond_grad"
+    if _bf16_sharded(name, U, V, d, (v, h, g) if out is None or backend is not None else (v, h, g, out), backend):
+        balance, update_U, mode, seed, row0 = _bf16_update_args(name, U, balance, update_U, generator, rounding, rounding_seed,
+                                                                row0, group, backend)
+        be = backend if backend is not None else hip_backend_for(U)
+        if out is not None and (out.shape != g.shape or not out.is_contiguous()):
+            raise ValueError("%s: out must be contiguous and shaped like g" % name)
+        _bf16_update_front(be, U, V, d, v, h, step, tiny, balance, update_U, mode, seed, row0, group)
+        be.apply_sweep1_d(V, d, g, step, tiny, mode, seed, row0)
+        return _bf16_apply_tail(be, U, V, d, g, group, out=out)
+    _no_rounding(name, rounding, rounding_seed, row0)
     if backend is None:
         _check_local("sharded update_precond_UVd_math_and_precond_grad", U, V, d, v, h, g)
     if _is_wide(U, backend):
