@@ -52,6 +52,7 @@ extern "C" {
  *     the psgd_uvd_*_bf16 entry points of a bf16-stored UVd state (new symbols only);
  *     psgd_uvd_pack_f32, psgd_uvd_sumsq_f32 and psgd_uvd_param_update_multi, the tail of UVd.step (new symbols only: still 7).
  *     the stage forms of the bf16-state UVd calls, psgd_uvd_bf16_ws_region and psgd_uvd_bf16_fold_gathered_f64 (new symbols only: still 7).
+ *     psgd_uvd_bf16_narrow_f32, the fp32 -> stored bf16 narrowing of a checkpoint load (new symbol only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -285,6 +286,15 @@ int psgd_uvd_update_bf16(void *U, void *V, void *d, const float *v, const float 
 int psgd_uvd_update_apply_bf16(void *U, void *V, void *d, const float *v, const float *h, const float *g, float *out,
                                int64_t N, int r, float step, float tiny, int balance, int update_U,
                                int rounding, uint64_t seed, void *ws, int64_t ws_bytes, void *stream);
+/* fp32 values into the stored form (loading an fp32 checkpoint into a bf16 state): dst[i] = the bf16 code of src[i], i < count,
+ * narrowed exactly as the calls above narrow what they write (rounding 0 / 1; NaN and Inf stored as they are).  tensor: 0 = U,
+ * 1 = V, 2 = d -- the stream is that of psgd_uvd_bf16_rounding_key(seed, tensor).  index0: the flat GLOBAL element index of
+ * src[0], (row0 + first row) * r for a factor and row0 + first row for d, so the codes depend on neither the chunks a caller
+ * copies in nor the row split.  Streaming: no workspace, no atomics, no synchronisation; src needs 4-byte and dst 2-byte
+ * alignment only (PSGD_ERR_ALIGN), 16-byte stores and loads from any such addresses.  count = 0 is a no-op (PSGD_OK); null
+ * pointers, count < 0, index0 < 0, tensor outside 0 .. 2 and rounding outside 0 .. 1 return PSGD_ERR_BAD_ARG before any HIP call. */
+int psgd_uvd_bf16_narrow_f32(const float *src, void *dst, int64_t count, int64_t index0, int tensor, int rounding,
+                             uint64_t seed, void *stream);
 
 /* Stage forms of the three calls above for a ROW-SHARDED bf16 state (one process per GPU; every rank passes its rows, N = its
  * row count).  Same conventions: bf16 U, V, d (16-byte aligned), fp32 v, h, g, out, the workspace of

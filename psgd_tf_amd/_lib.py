@@ -106,6 +106,7 @@ SIGNATURES = {
     "psgd_uvd_update_bf16": (_int, [_c_f32p] * 5 + [_i64, _int, _flt, _flt, _int, _int, _int, ctypes.c_uint64, _c_ws, _i64, _strm]),
     "psgd_uvd_update_apply_bf16": (_int, [_c_f32p] * 7 + [_i64, _int, _flt, _flt, _int, _int, _int, ctypes.c_uint64, _c_ws, _i64,
                                           _strm]),
+    "psgd_uvd_bf16_narrow_f32": (_int, [_c_f32p, _c_f32p, _i64, _i64, _int, _int, ctypes.c_uint64, _strm]),
     "psgd_uvd_bf16_ws_region": (_int, [_int, _int, _i64, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "psgd_uvd_bf16_fold_gathered_f64": (_int, [_int, _c_f32p, _int, _i64, _int, _c_ws, _i64, _strm]),
     "psgd_uvd_balance_max_bf16": (_int, [_c_f32p, _c_f32p, _i64, _int, _c_ws, _i64, _strm]),

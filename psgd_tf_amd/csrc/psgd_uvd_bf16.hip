@@ -30,6 +30,9 @@
 // factor, and here the apply must see the stored codes.  The stochastic-rounding stream of a shard is keyed by the GLOBAL
 // element index (row0 + row), so ranks never round their rows with the same random numbers and the stored state does not
 // depend on how the rows are split.
+//
+// psgd_uvd_bf16_narrow_f32 (k_narrow_f32) brings fp32 values into this stored form with the same narrow() and the same
+// global-index stream: what loading an fp32 checkpoint into a bf16 state runs, chunk by chunk, with no workspace.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -664,6 +667,41 @@ __global__ __launch_bounds__(kT) void k_d_update(u16* __restrict__ d, const floa
   }
 }
 
+// ------------------------------------------------------------------ fp32 -> stored bf16 (loading an fp32 checkpoint)
+// dst[i] = narrow(src[i]) for i < count, the rounding index of element i being idx0 + i (its flat GLOBAL index in the tensor the
+// key belongs to: the codes depend on neither how the caller chunks the copy nor the row split).  HBM-bound streaming, the shape
+// of psgd_uvd_tail.hip: a scalar head brings dst to a 16-byte boundary, the body stores 16 bytes (8 codes) per lane from two
+// 16-byte loads, a scalar tail finishes.  src is read through a vector type whose declared alignment is the element's, so an
+// odd idx0 or an src that starts at any fp32 element still takes wide loads.
+typedef float f32x4_e __attribute__((ext_vector_type(4), aligned(4)));       // 16 bytes from any fp32 element
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+
+__global__ __launch_bounds__(kT) void k_narrow_f32(const float* __restrict__ src, u16* __restrict__ dst, long count, int mode,
+                                                   SrKey key, unsigned long long idx0) {
+  long head = (long)(((16u - (unsigned)((uintptr_t)dst & 15u)) & 15u) / 2u);
+  if (head > count) head = count;
+  const long nvec = (count - head) / 8;
+  const long tid = (long)blockIdx.x * kT + threadIdx.x;
+  const long nthr = (long)gridDim.x * kT;
+  if (tid < head) dst[tid] = (u16)narrow(src[tid], mode, key, idx0 + (unsigned long long)tid);
+#pragma unroll 2
+  for (long q = tid; q < nvec; q += nthr) {
+    const long i = head + q * 8;
+    const f32x4_e a = *reinterpret_cast<const f32x4_e*>(src + i);
+    const f32x4_e b = *reinterpret_cast<const f32x4_e*>(src + i + 4);
+    const unsigned long long e0 = idx0 + (unsigned long long)i;
+    u16x8 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = (u16)narrow(a[e], mode, key, e0 + e);
+      v[e + 4] = (u16)narrow(b[e], mode, key, e0 + 4 + e);
+    }
+    *reinterpret_cast<u16x8*>(dst + i) = v;
+  }
+  const long i = head + nvec * 8 + tid;
+  if (i < count) dst[i] = (u16)narrow(src[i], mode, key, idx0 + (unsigned long long)i);
+}
+
 // ------------------------------------------------------------------ the three sweeps of the apply (psgd.py:619-627)
 // MODE 0: s1 = M'(d .* g)                                   (M = V)
 // MODE 1: the same after d <- d - mu_d d nablaD (written)   (M = V; the fused call)
@@ -955,6 +993,21 @@ uint64_t psgd_uvd_bf16_rounding_key(uint64_t seed, int tensor) { return key64(se
 int64_t psgd_uvd_bf16_workspace_bytes(int64_t N, int r) {
   if (int rc = check_common(N, r)) return rc;
   return ws_bytes_for(N);
+}
+
+int psgd_uvd_bf16_narrow_f32(const float* src, void* dst, int64_t count, int64_t index0, int tensor, int rounding, uint64_t seed,
+                             void* stream) {
+  if (!src || !dst || count < 0 || index0 < 0) return PSGD_ERR_BAD_ARG;
+  if (tensor < 0 || tensor > 2 || (rounding != 0 && rounding != 1)) return PSGD_ERR_BAD_ARG;
+  if (misaligned(src, 4) || misaligned(dst, 2)) return PSGD_ERR_ALIGN;
+  if (count == 0) return PSGD_OK;
+  // two 8-element groups per thread before the grid-stride loop takes over
+  int64_t blocks = (count / 8 + 2 * kT - 1) / (2 * kT);
+  if (blocks < 1) blocks = 1;
+  if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+  hipLaunchKernelGGL(k_narrow_f32, dim3((unsigned)blocks), dim3(kT), 0, static_cast<hipStream_t>(stream), src, static_cast<u16*>(dst),
+                     (long)count, rounding, make_key(seed, (unsigned)tensor), (unsigned long long)index0);
+  return launch_ok();
 }
 
 static int check_apply(const void* U, const void* V, const void* d, const float* g, float* out, int64_t N, int r) {

@@ -182,6 +182,41 @@ def uvd_step_rounding_seed(seed0, k):
     return _mix64(_mix64(int(seed0)) + 0x9E3779B97F4A7C15 * (int(k) + 1))
 
 
+_UVD_TENSOR_IDS = {"U": 0, "V": 1, "d": 2}           # the tensor ids of psgd_uvd_bf16_rounding_key
+_NARROW_STAGING_BYTES = 64 << 20                     # UVd.load_state_dict: the fp32 staging buffer of an fp32 -> native bf16 load
+
+
+def uvd_bf16_narrow_(dst, src, *, tensor, index0=0, rounding="nearest", rounding_seed=0):
+    """dst <- the bf16 codes of the fp32 values src, narrowed as the bf16-state kernels narrow what they write
+    (psgd_uvd_bf16_narrow_f32): dst bfloat16 and src float32 on one ROCm device, contiguous, of one size.  tensor: "U", "V" or "d"
+    (the rounding stream of that state tensor under rounding_seed); index0: the flat GLOBAL element index of src[0] in it --
+    (row0 + first row) * r for a factor, row0 + first row for d -- so the codes depend on neither the chunks nor the row split.
+    Returns dst."""
+    name = "uvd_bf16_narrow_"
+    if tensor not in _UVD_TENSOR_IDS:
+        raise ValueError("%s: tensor must be 'U', 'V' or 'd', got %r" % (name, tensor))
+    if rounding not in _ROUNDINGS:
+        raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (name, rounding))
+    for t, want in ((dst, torch.bfloat16), (src, torch.float32)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: expected torch tensors, got %r" % (name, type(t)))
+        if not t.is_cuda:
+            raise _lib.PsgdHipError("%s runs on the HIP device only (tensor is on %s); no CPU fallback" % (name, t.device))
+        if t.dtype != want:
+            raise TypeError("%s: dst must be bfloat16 and src float32, got %s and %s" % (name, dst.dtype, src.dtype))
+        if not t.is_contiguous():
+            raise ValueError("%s: contiguous tensors required" % name)
+    if dst.device != src.device or dst.numel() != src.numel():
+        raise ValueError("%s: dst and src must be on one device and of one size" % name)
+    if int(index0) < 0:
+        raise ValueError("%s: index0 must be >= 0, got %r" % (name, index0))
+    if dst.numel():
+        rc = _lib.load().psgd_uvd_bf16_narrow_f32(src.data_ptr(), dst.data_ptr(), dst.numel(), int(index0), _UVD_TENSOR_IDS[tensor],
+                                                  _ROUNDINGS[rounding], int(rounding_seed) & (2 ** 64 - 1), _stream_ptr(dst.device))
+        _lib.check(rc, "psgd_uvd_bf16_narrow_f32")
+    return dst
+
+
 def _bf16_call(name, U, V, d, g, out, balance, update_U, rounding, rounding_seed, generator, cols):
     """what the three bf16-state calls share: shape checks, the branch draws (reference order), rounding mode and seed, the
     output and the workspace.  balance is None for the apply (no draws, no rounding)."""
@@ -1006,6 +1041,158 @@ class UVd:
 
     def _loss_of(self, closure_returns):
         return closure_returns if isinstance(closure_returns, torch.Tensor) else closure_returns[0]
+
+    # ------------------------------------------------------------------------------------------------- checkpoint / resume
+    _HYPER_KEYS = ("lr_params", "lr_preconditioner", "grad_clip_max_norm", "preconditioner_update_probability",
+                   "exact_hessian_vector_product")
+
+    def _coin_generator(self):
+        """the generator behind the coins of :703, :562, :588 (and the construction seed of the native route)"""
+        if self._group is not None:
+            return self._coins.gen
+        return self._generator if self._generator is not None else _branch_rng
+
+    def _row0(self):
+        if self._group is None:
+            return 0
+        return self._sharded.global_row0(self._U.shape[0], self._device, self._group)
+
+    def state_dict(self):
+        """Everything a bit-faithful resume of this optimizer needs, as a flat dict of CPU tensors and plain Python values (safe
+        for torch.save / torch.load(weights_only=True)):
+
+            format                   1
+            U, V, d                  this rank's rows in the STORED dtype (clones on the CPU, never views of an arena)
+            rank                     the rank of the modification r
+            num_params, row0         this rank's row count and the global index of its first row (unsharded: row0 = 0)
+            num_params_global        rows of the global vector (unsharded: num_params)
+            param_sizes              the element counts of this rank's parameter tensors
+            state_dtype, state_route, state_rounding    strings ("torch.bfloat16", "native" / "widen", "stochastic" / "nearest" / "none")
+            round_seed0, round_step  native route only: together they fix every stored code of every later step
+            hyper                    lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability (floats),
+                                     exact_hessian_vector_product (bool)
+            branch_rng               get_state() of the generator behind the coin flips: the generator= argument, else the
+                                     module's branch generator; row-sharded, the synchronised generator all ranks draw from
+
+        NOT saved: the parameters (they are the caller's), and the global CUDA generator that draws the probe vectors of
+        :713 / :721 -- it belongs to the caller; save torch.cuda.get_rng_state() next to this dict and restore it with
+        torch.cuda.set_rng_state() where the resumed run must draw the same vectors.
+
+        Row-sharded: every rank calls it (row0 is one set-up collective the first time, sharded.global_row0) and saves its own dict."""
+        def host(t):
+            return t.detach().to("cpu", copy=True).contiguous()
+        n = int(self._U.shape[0])
+        sd = {"format": 1, "U": host(self._U), "V": host(self._V), "d": host(self._d),
+              "rank": int(self._U.shape[1]), "num_params": n, "num_params_global": int(self._num_params_global),
+              "row0": int(self._row0()), "param_sizes": [int(s) for s in self._param_sizes],
+              "state_dtype": str(self._store_dtype), "state_route": "native" if self._native else "widen",
+              "state_rounding": self._state_rounding if self._state_rounding is not None else "none",
+              "hyper": {k: (bool if k == "exact_hessian_vector_product" else float)(getattr(self, k)) for k in self._HYPER_KEYS},
+              "branch_rng": self._coin_generator().get_state().clone()}
+        if self._native:
+            sd["round_seed0"], sd["round_step"] = int(self._round_seed0), int(self._round_step)
+        return sd
+
+    def load_state_dict(self, sd, *, strict=True, narrow_rounding=None, narrow_seed=None):
+        """Restore what state_dict() saved, IN PLACE: U, V, d are written into the tensors this object already holds (a placed
+        state stays in its arena; every pointer the tail plan and the workspaces cache stays valid), the hyper-parameters are
+        assigned, the generator behind the coins gets the saved state (row-sharded: every rank loads the same bytes into the
+        synchronised generator; nothing is broadcast again) and, on the native route, so do round_seed0 / round_step.
+
+        Checked against this object (ValueError naming the key): format, rank, num_params, param_sizes (skipped when the dict
+        holds None, as a resharded one does); with strict=True also num_params_global and row0.  strict=False is for loading a
+        slice of a global state into an object that does not know where its rows sit (rows of a resharded checkpoint).
+
+        Dtypes: the same stored dtype is a bitwise copy; a bfloat16 checkpoint into a float32 state widens exactly; a float32
+        checkpoint into a NATIVE bfloat16 state is streamed -- host -> pinned staging -> device staging (64 MiB at most, the only
+        fp32 image of the state that ever exists on the device) -> psgd_uvd_bf16_narrow_f32 -- with narrow_rounding (default: this
+        object's state_rounding) and narrow_seed (default: uvd_step_rounding_seed(round_seed0, 2**40 + round_step), a stream
+        disjoint from every step's); the rounding index is the GLOBAL element index (from the dict's row0), so the codes depend
+        on neither the chunking nor the row split.  Such a checkpoint carries no round_seed0 / round_step: the object keeps
+        its own.  Any other pair of dtypes raises TypeError.  The parameters and the global CUDA generator are the caller's."""
+        name = "UVd.load_state_dict"
+
+        def need(key):
+            if key not in sd:
+                raise ValueError("%s: the state dict has no %r" % (name, key))
+            return sd[key]
+
+        def same(key, mine):
+            got = need(key)
+            if got != mine:
+                raise ValueError("%s: %r is %r in the state dict, %r in this optimizer" % (name, key, got, mine))
+        if need("format") != 1:
+            raise ValueError("%s: 'format' is %r; this version reads format 1" % (name, sd["format"]))
+        if narrow_rounding is not None and narrow_rounding not in _ROUNDINGS:
+            raise ValueError("%s: narrow_rounding must be 'stochastic' or 'nearest', got %r" % (name, narrow_rounding))
+        n, r = int(self._U.shape[0]), int(self._U.shape[1])
+        same("rank", r)
+        same("num_params", n)
+        if need("param_sizes") is not None and [int(s) for s in sd["param_sizes"]] != [int(s) for s in self._param_sizes]:
+            raise ValueError("%s: 'param_sizes' is %r in the state dict, %r in this optimizer"
+                             % (name, list(sd["param_sizes"]), list(self._param_sizes)))
+        if strict:
+            same("num_params_global", int(self._num_params_global))
+            same("row0", int(self._row0()))
+        row0 = int(need("row0"))
+        src = {k: need(k) for k in ("U", "V", "d")}
+        for k, mine in (("U", self._U), ("V", self._V), ("d", self._d)):
+            if not isinstance(src[k], torch.Tensor) or tuple(src[k].shape) != tuple(mine.shape):
+                raise ValueError("%s: %r must be a tensor of shape %s" % (name, k, tuple(mine.shape)))
+        have = {src[k].dtype for k in src}
+        if len(have) != 1:
+            raise TypeError("%s: U, V and d of the state dict have different dtypes %s" % (name, sorted(str(x) for x in have)))
+        have = have.pop()
+        if have == self._store_dtype:
+            how = "copy"
+        elif have == torch.bfloat16 and self._store_dtype == torch.float32:
+            how = "copy"                                   # exact: every bfloat16 value is a float32 value
+        elif have == torch.float32 and self._native:
+            how = "narrow"
+        else:
+            raise TypeError("%s: a %s checkpoint cannot be loaded into a %s state (state_route=%r): the same dtype, bfloat16 into "
+                            "float32 and float32 into a native bfloat16 state are supported"
+                            % (name, have, self._store_dtype, "native" if self._native else "widen"))
+        hyper = need("hyper")
+        for k in self._HYPER_KEYS:
+            if k not in hyper:
+                raise ValueError("%s: 'hyper' has no %r" % (name, k))
+        rng_state = need("branch_rng")
+        try:
+            self._coin_generator().set_state(rng_state)
+        except (RuntimeError, TypeError) as e:
+            raise ValueError("%s: 'branch_rng' does not fit this optimizer's generator: %s" % (name, e))
+        for k in self._HYPER_KEYS:
+            getattr(self, k).assign(hyper[k])
+        if self._native and "round_seed0" in sd:
+            self._round_seed0, self._round_step = int(sd["round_seed0"]), int(need("round_step"))
+        with torch.no_grad():
+            if how == "copy":
+                for k, mine in (("U", self._U), ("V", self._V), ("d", self._d)):
+                    mine.copy_(src[k])
+                return
+            rounding = narrow_rounding if narrow_rounding is not None else self._state_rounding
+            seed = uvd_step_rounding_seed(self._round_seed0, 2 ** 40 + self._round_step) if narrow_seed is None else int(narrow_seed)
+            self._load_narrowed(src, row0, r, rounding, seed)
+
+    def _load_narrowed(self, src, row0, r, rounding, seed):
+        """fp32 host tensors -> this object's native bf16 state, through ONE pinned and ONE device staging buffer of at most
+        _NARROW_STAGING_BYTES (reused chunk after chunk: the stream is drained before a buffer is refilled)"""
+        chunk = max(1, int(_NARROW_STAGING_BYTES) // 4)
+        cap = min(chunk, max(int(t.numel()) for t in src.values()))
+        pinned = torch.empty(cap, dtype=torch.float32, pin_memory=True)
+        staged = torch.empty(cap, dtype=torch.float32, device=self._device)
+        stream = torch.cuda.current_stream(self._device)
+        for k, mine, index0 in (("U", self._U, row0 * r), ("V", self._V, row0 * r), ("d", self._d, row0)):
+            if not mine.is_contiguous():
+                raise ValueError("UVd.load_state_dict: the native state must be contiguous")
+            flat, host = mine.view(-1), src[k].detach().contiguous().view(-1)
+            for lo in range(0, int(host.numel()), chunk):
+                m = min(chunk, int(host.numel()) - lo)
+                pinned[:m].copy_(host[lo:lo + m])
+                staged[:m].copy_(pinned[:m], non_blocking=True)
+                uvd_bf16_narrow_(flat[lo:lo + m], staged[:m], tensor=k, index0=index0 + lo, rounding=rounding, rounding_seed=seed)
+                stream.synchronize()
 
     def step(self, closure):
         """psgd.py:692-764."""

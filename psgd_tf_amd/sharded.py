@@ -261,6 +261,63 @@ def shard_rows(n_global, rank, world):
     return lo, hi
 
 
+def reshard_uvd_state(state_dicts, new_row_counts):
+    """The W state dicts of ONE row-sharded checkpoint (UVd.state_dict() of every rank, in any order) as W' dicts whose row
+    counts are new_row_counts: offline, on the CPU, no process group.  The inputs must tile [0, num_params_global) without gap
+    or overlap and agree on format, rank, dtypes, route, rounding, hyper, round_seed0 / round_step and branch_rng (ValueError
+    naming what does not).  new_row_counts must sum to num_params_global, and every entry but the last must be a multiple of 64
+    (shards start at multiples of 64 rows, see shard_rows).  Output k holds rows [row0', row0' + n') with its own num_params
+    and row0; its param_sizes is None (the new ranks' parameter lists are not known here), which UVd.load_state_dict skips.
+
+    The stochastic-rounding stream is keyed by the global element index, so the resharded run stores the same codes up to the
+    fp64 fold order of the exchanges."""
+    name = "reshard_uvd_state"
+    sds = sorted(state_dicts, key=lambda s: int(s["row0"]))
+    if not sds:
+        raise ValueError("%s: no state dicts" % name)
+    first = sds[0]
+    if first.get("format") != 1:
+        raise ValueError("%s: 'format' is %r; this version reads format 1" % (name, first.get("format")))
+    for key in ("format", "rank", "num_params_global", "state_dtype", "state_route", "state_rounding", "hyper", "round_seed0",
+                "round_step"):
+        for s in sds[1:]:
+            if s.get(key) != first.get(key):
+                raise ValueError("%s: the state dicts disagree on %r (%r and %r)" % (name, key, first.get(key), s.get(key)))
+    for s in sds:
+        if not torch.equal(s["branch_rng"], first["branch_rng"]):
+            raise ValueError("%s: the state dicts disagree on 'branch_rng'" % name)
+        for k in ("U", "V", "d"):
+            if s[k].dtype != first["U"].dtype:
+                raise ValueError("%s: the state dicts disagree on the dtype of %r (%s and %s)" % (name, k, first["U"].dtype, s[k].dtype))
+            if s[k].shape[0] != int(s["num_params"]):
+                raise ValueError("%s: %r has %d rows where 'num_params' says %d" % (name, k, s[k].shape[0], int(s["num_params"])))
+    total, pos = int(first["num_params_global"]), 0
+    for s in sds:
+        if int(s["row0"]) != pos:
+            raise ValueError("%s: 'row0' = %d where the rows before it end at %d (%s)"
+                             % (name, int(s["row0"]), pos, "a gap" if int(s["row0"]) > pos else "an overlap"))
+        pos += int(s["num_params"])
+    if pos != total:
+        raise ValueError("%s: the rows end at %d but 'num_params_global' is %d" % (name, pos, total))
+    counts = [int(c) for c in new_row_counts]
+    if not counts or any(c < 1 for c in counts) or sum(counts) != total:
+        raise ValueError("%s: new_row_counts %r must be positive and sum to num_params_global = %d" % (name, counts, total))
+    if any(c % 64 for c in counts[:-1]):
+        raise ValueError("%s: every entry of new_row_counts but the last must be a multiple of 64, got %r" % (name, counts))
+    whole = {k: torch.cat([s[k] for s in sds], 0) for k in ("U", "V", "d")}
+    out, lo = [], 0
+    for c in counts:
+        new = {k: v for k, v in first.items() if k not in ("U", "V", "d")}
+        new["hyper"] = dict(first["hyper"])
+        new["branch_rng"] = first["branch_rng"].clone()
+        for k in ("U", "V", "d"):
+            new[k] = whole[k][lo:lo + c].clone()
+        new["num_params"], new["row0"], new["param_sizes"] = c, lo, None
+        out.append(new)
+        lo += c
+    return out
+
+
 def _host_collectives(group):
     """gloo groups reduce host tensors (set-up-time scalars only; the per-step exchanges take device tensors on either backend)"""
     return dist.get_backend(group) == "gloo"
