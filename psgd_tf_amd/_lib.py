@@ -224,22 +224,23 @@ def check(code, what):
         raise PsgdHipError("%s failed: %s (code %d)" % (what, msg, code))
 
 
-def ws_region(which, stage, N, r):
+def _region(fn_name, which, stage, N, r):
+    """(byte offset, element count) of one reduced buffer of a stage in the workspace of an [N, r] shard"""
     off, cnt = _i64(0), _i64(0)
-    check(load().psgd_uvd_ws_region(which, stage, N, r, ctypes.byref(off), ctypes.byref(cnt)), "psgd_uvd_ws_region")
+    check(getattr(load(), fn_name)(which, stage, N, r, ctypes.byref(off), ctypes.byref(cnt)), fn_name)
     return off.value, cnt.value
+
+
+def ws_region(which, stage, N, r):
+    return _region("psgd_uvd_ws_region", which, stage, N, r)
 
 
 def uvd_bf16_ws_region(which, stage, N, r):
-    off, cnt = _i64(0), _i64(0)
-    check(load().psgd_uvd_bf16_ws_region(which, stage, N, r, ctypes.byref(off), ctypes.byref(cnt)), "psgd_uvd_bf16_ws_region")
-    return off.value, cnt.value
+    return _region("psgd_uvd_bf16_ws_region", which, stage, N, r)
 
 
 def splu_ws_region(which, stage, N, r):
-    off, cnt = _i64(0), _i64(0)
-    check(load().psgd_splu_ws_region(which, stage, N, r, ctypes.byref(off), ctypes.byref(cnt)), "psgd_splu_ws_region")
-    return off.value, cnt.value
+    return _region("psgd_splu_ws_region", which, stage, N, r)
 
 
 class WorkspaceCache:

@@ -59,19 +59,23 @@ def _stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def _require_hip(name, *tensors):
-    for t in tensors:
+def _require_hip(name, *tensors, dtypes=(), dtype_msg="fp32 tensors required"):
+    """The one tensor check of the HIP entry points: every operand a torch tensor, on the HIP device, of the dtype wanted --
+    dtypes[i] for tensor i, float32 for those past its end; dtype_msg: what a wrong one is told -- contiguous (the kernels take
+    raw pointers), all on one device.  Returns that device."""
+    dev = None
+    for t, want in zip(tensors, dtypes + (torch.float32,) * (len(tensors) - len(dtypes))):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s: expected torch tensors, got %r" % (name, type(t)))
         if not t.is_cuda:
             raise _lib.PsgdHipError("%s runs on the HIP device only (tensor is on %s); no CPU fallback" % (name, t.device))
-        if t.dtype != torch.float32:
-            raise TypeError("%s: fp32 tensors required, got %s" % (name, t.dtype))
+        if t.dtype != want:
+            raise TypeError("%s: %s, got %s" % (name, dtype_msg, t.dtype))
         if not t.is_contiguous():
             raise ValueError("%s: contiguous tensors required" % name)
-    dev = tensors[0].device
-    for t in tensors:
-        if t.device != dev:
+        if dev is None:
+            dev = t.device
+        elif t.device != dev:
             raise ValueError("%s: all tensors must be on one device" % name)
     return dev
 
@@ -96,40 +100,43 @@ class _InPlace:
                 o.copy_(w)
 
 
-def uvd_workspace(device, N, r):
-    """Cached device workspace for a shard of N rows at rank r (see psgd_uvd_workspace_bytes).  Keyed by the current
-    stream as well: a workspace carries the reduced vectors between the sweeps of one call, so calls issued on two
-    streams must not share one (the C ABI itself is safe on several streams as long as each has its own workspace)."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(), int(N), int(r),
-           torch.cuda.current_stream(device).cuda_stream)
+def _workspace(kind, device, bytes_fn, *shape, limits=""):
+    """Cached device workspace of `bytes_fn(*shape)` bytes, keyed by ([kind,] device index, *shape, current stream): a workspace
+    carries the reduced vectors between the sweeps of one call, so calls issued on two streams must not share one (the C ABI itself
+    is safe on several streams as long as each has its own workspace).  A shape the kernels do not support raises: most of the
+    size functions answer with an error code, the sparse-LU one with 0 bytes (limits: what that message adds)."""
+    key = kind + (device.index if device.index is not None else torch.cuda.current_device(), *map(int, shape),
+                  torch.cuda.current_stream(device).cuda_stream)
 
     def make():
-        nbytes = _lib.load().psgd_uvd_workspace_bytes(N, r)
+        nbytes = int(getattr(_lib.load(), bytes_fn)(*shape))
         if nbytes < 0:
-            _lib.check(int(nbytes), "psgd_uvd_workspace_bytes")
-        return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+            _lib.check(nbytes, bytes_fn)
+        if nbytes == 0:
+            raise _lib.PsgdHipError("%s: unsupported shape %r%s" % (bytes_fn, shape, limits))
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
     return _ws_cache.get(key, make)
+
+
+def uvd_workspace(device, N, r):
+    """Cached workspace for a shard of N rows at rank r (psgd_uvd_workspace_bytes); its key has no kind: placement.UVdArena
+    installs its own block under (device index, N, r, stream)."""
+    return _workspace((), device, "psgd_uvd_workspace_bytes", N, r)
 
 
 def uvd_bf16_workspace(device, N, r):
-    """Cached workspace of the bf16-state kernels (psgd_uvd_bf16_workspace_bytes: a layout of its own), per stream."""
-    key = ("uvd_bf16", device.index if device.index is not None else torch.cuda.current_device(), int(N), int(r),
-           torch.cuda.current_stream(device).cuda_stream)
-
-    def make():
-        nbytes = _lib.load().psgd_uvd_bf16_workspace_bytes(N, r)
-        if nbytes < 0:
-            _lib.check(int(nbytes), "psgd_uvd_bf16_workspace_bytes")
-        return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-    return _ws_cache.get(key, make)
+    """Cached workspace of the bf16-state kernels (psgd_uvd_bf16_workspace_bytes: a layout of its own)."""
+    return _workspace(("uvd_bf16",), device, "psgd_uvd_bf16_workspace_bytes", N, r)
 
 
 _ROUNDINGS = {"nearest": 0, "stochastic": 1}
+_FP32_STATE = {}                                     # _require_hip(name, U, V, d, *vectors, **_BF16_STATE or **_FP32_STATE)
+_BF16_STATE = {"dtypes": (torch.bfloat16,) * 3, "dtype_msg": "with a bfloat16 state the vectors v, h, g and out stay float32"}
 
 
-def _bf16_state(name, U, V, d, *cols):
-    """True when U, V, d are a bf16-stored state (psgd_uvd_bf16.hip); raises for the combinations that path does not cover.
-    Its limits: U, V, d all bfloat16 (float16 is not supported), fp32 column vectors, rank <= 32."""
+def _bf16_state(name, U, V, d):
+    """Classifies the state: True for a bf16-stored one (psgd_uvd_bf16.hip: U, V, d all bfloat16, rank <= 32), False for anything
+    the fp32 entry points judge; raises for a float16 or mixed state and for a bfloat16 state of rank above 32."""
     state = (U, V, d)
     if not all(isinstance(t, torch.Tensor) for t in state):
         return False
@@ -141,31 +148,45 @@ def _bf16_state(name, U, V, d, *cols):
     if dts != {torch.bfloat16}:
         raise TypeError("%s: mixed state dtypes %s; U, V and d must all be bfloat16 (or all float32)"
                         % (name, sorted(str(x) for x in dts)))
-    for t in state + cols:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s: expected torch tensors, got %r" % (name, type(t)))
-        if not t.is_cuda:
-            raise _lib.PsgdHipError("%s runs on the HIP device only (tensor is on %s); no CPU fallback" % (name, t.device))
-        if t.device != U.device:
-            raise ValueError("%s: all tensors must be on one device" % name)
-    for c in cols:
-        if c.dtype != torch.float32:
-            raise TypeError("%s: with a bfloat16 state the vectors v, h, g and out stay float32, got %s" % (name, c.dtype))
     if U.dim() == 2 and U.shape[1] > _lib.UVD_MAX_RANK:
         raise ValueError("%s: a bfloat16 state supports ranks up to %d, got %d" % (name, _lib.UVD_MAX_RANK, U.shape[1]))
     return True
 
 
-def _rounding_args(name, rounding, rounding_seed, generator):
+def _rounding_mode(name, bf16, rounding, rounding_seed=None, row0=None):
+    """The rounding arguments of an updating call, judged before a tensor is looked at, a workspace made or a number drawn:
+    returns the mode.  An fp32 state (bf16 False) is not rounded: rounding arguments, row0 (row-sharded) among them, raise."""
     if rounding not in _ROUNDINGS:
         raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (name, rounding))
-    if rounding_seed is None:
-        if rounding == "stochastic":     # from the branch generator, never from the global CUDA generator
-            gen = generator if generator is not None else _branch_rng
-            rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=gen).item())
-        else:
-            rounding_seed = 0
-    return _ROUNDINGS[rounding], int(rounding_seed) & (2 ** 64 - 1)
+    mode = _ROUNDINGS[rounding]
+    if not bf16 and (mode or rounding_seed is not None or row0 is not None):
+        raise ValueError("%s: rounding / rounding_seed / row0 apply to a bfloat16 state only; an fp32 state is not rounded" % name)
+    return mode
+
+
+def _draw_branch(p, generator):
+    gen = generator if generator is not None else _branch_rng
+    return bool(torch.rand((), generator=gen).item() < p)
+
+
+def _resolve_branches(balance, update_U, generator, mode, rounding_seed, synced=None):
+    """The two branches (psgd.py:562, :588) and the rounding seed of one updating call, single-GPU or row-sharded, whose rounding
+    arguments _rounding_mode has judged: (balance, update_U, seed).  Whatever is None is drawn, in the reference's order --
+    balance (p = 0.01), update_U (p = 0.5), then the seed, the last only for rounding="stochastic" -- from `generator` (the
+    module's branch generator when None), never from the global CUDA generator.  synced (row-sharded): () -> the
+    sharded.BranchRng all ranks draw from in place of `generator`; it is synchronised by a collective the first time, so it is
+    asked for only when something is drawn."""
+    draw_seed = bool(mode) and rounding_seed is None
+    rng = synced() if synced is not None and (balance is None or update_U is None or draw_seed) else None
+    if balance is None:
+        balance = _draw_branch(0.01, generator) if rng is None else rng.draw(0.01)
+    if update_U is None:
+        update_U = _draw_branch(0.5, generator) if rng is None else rng.draw(0.5)
+    seed = 0 if rounding_seed is None else int(rounding_seed) & (2 ** 64 - 1)
+    if draw_seed:
+        gen = rng.gen if rng is not None else generator if generator is not None else _branch_rng
+        seed = int(torch.randint(0, 2 ** 62, (), generator=gen).item())
+    return bool(balance), bool(update_U), seed
 
 
 def _mix64(z):
@@ -195,49 +216,17 @@ def uvd_bf16_narrow_(dst, src, *, tensor, index0=0, rounding="nearest", rounding
     name = "uvd_bf16_narrow_"
     if tensor not in _UVD_TENSOR_IDS:
         raise ValueError("%s: tensor must be 'U', 'V' or 'd', got %r" % (name, tensor))
-    if rounding not in _ROUNDINGS:
-        raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (name, rounding))
-    for t, want in ((dst, torch.bfloat16), (src, torch.float32)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s: expected torch tensors, got %r" % (name, type(t)))
-        if not t.is_cuda:
-            raise _lib.PsgdHipError("%s runs on the HIP device only (tensor is on %s); no CPU fallback" % (name, t.device))
-        if t.dtype != want:
-            raise TypeError("%s: dst must be bfloat16 and src float32, got %s and %s" % (name, dst.dtype, src.dtype))
-        if not t.is_contiguous():
-            raise ValueError("%s: contiguous tensors required" % name)
-    if dst.device != src.device or dst.numel() != src.numel():
-        raise ValueError("%s: dst and src must be on one device and of one size" % name)
+    mode = _rounding_mode(name, True, rounding)
+    _require_hip(name, dst, src, dtypes=(torch.bfloat16,), dtype_msg="dst must be bfloat16 and src float32")
+    if dst.numel() != src.numel():
+        raise ValueError("%s: dst and src must be of one size" % name)
     if int(index0) < 0:
         raise ValueError("%s: index0 must be >= 0, got %r" % (name, index0))
     if dst.numel():
         rc = _lib.load().psgd_uvd_bf16_narrow_f32(src.data_ptr(), dst.data_ptr(), dst.numel(), int(index0), _UVD_TENSOR_IDS[tensor],
-                                                  _ROUNDINGS[rounding], int(rounding_seed) & (2 ** 64 - 1), _stream_ptr(dst.device))
+                                                  mode, int(rounding_seed) & (2 ** 64 - 1), _stream_ptr(dst.device))
         _lib.check(rc, "psgd_uvd_bf16_narrow_f32")
     return dst
-
-
-def _bf16_call(name, U, V, d, g, out, balance, update_U, rounding, rounding_seed, generator, cols):
-    """what the three bf16-state calls share: shape checks, the branch draws (reference order), rounding mode and seed, the
-    output and the workspace.  balance is None for the apply (no draws, no rounding)."""
-    if g is not None and g.dim() == 2 and g.shape[1] > 1:
-        raise ValueError("%s: a matrix g is not supported with a bfloat16 state (column vectors only)" % name)
-    N, r = _uvd_shapes(name, U, V, d, *cols)
-    mode = seed = 0
-    if rounding is not None:
-        if balance is None:
-            balance = _draw_branch(0.01, generator)
-        if update_U is None:
-            update_U = _draw_branch(0.5, generator)
-        mode, seed = _rounding_args(name, rounding, rounding_seed, generator)
-    if g is not None:
-        if out is None:
-            out = torch.empty_like(g)
-        elif out.shape != g.shape or not out.is_contiguous():
-            raise ValueError("%s: out must be contiguous and shaped like g" % name)
-    ws = uvd_bf16_workspace(U.device, N, r)
-    tail = (ws.data_ptr(), ws.numel(), _stream_ptr(U.device))
-    return N, r, int(bool(balance)), int(bool(update_U)), mode, seed, out, tail
 
 
 def _uvd_shapes(name, U, V, *cols):
@@ -271,15 +260,7 @@ def _dense_native(Q, *lists):
 
 
 def _dense_workspace(device, N):
-    key = ("dense", device.index if device.index is not None else torch.cuda.current_device(), int(N),
-           torch.cuda.current_stream(device).cuda_stream)
-
-    def make():
-        nbytes = int(_lib.load().psgd_dense_workspace_bytes(N))
-        if nbytes <= 0:
-            _lib.check(nbytes, "psgd_dense_workspace_bytes")
-        return torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return _ws_cache.get(key, make)
+    return _workspace(("dense",), device, "psgd_dense_workspace_bytes", N)
 
 
 def _dense_n(name, Q):
@@ -370,16 +351,11 @@ def precond_grad_kron_batched(Qls, Qrs, Grads):
 
 
 # --------------------------------------------------------------------------- sparse LU
-def _splu_workspace(device, N, r):
-    key = ("splu", device.index if device.index is not None else torch.cuda.current_device(), int(N), int(r),
-           torch.cuda.current_stream(device).cuda_stream)
+_SPLU_LIMITS = " (1 <= r <= %d, N >= r)" % _lib.SPLU_MAX_RANK
 
-    def make():
-        nbytes = int(_lib.load().psgd_splu_workspace_bytes(N, r))
-        if nbytes <= 0:
-            raise _lib.PsgdHipError("psgd_splu_workspace_bytes: unsupported shape N=%d r=%d (1 <= r <= 32, N >= r)" % (N, r))
-        return torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return _ws_cache.get(key, make)
+
+def _splu_workspace(device, N, r):
+    return _workspace(("splu",), device, "psgd_splu_workspace_bytes", N, r, limits=_SPLU_LIMITS)
 
 
 def _splu_shapes(name, L12, l3, U12, u3):
@@ -500,25 +476,40 @@ def _cols_of(name, x, N):
     return xt if xt.is_contiguous() else xt.contiguous()
 
 
+def _vector_call(name, bf16, U, V, d, cols, out=None):
+    """what the vector forms of the three UVd calls share once the state is classified: the tensor check (a bf16 state keeps
+    fp32 vectors), the shapes and the (workspace pointer, bytes, stream) tail of the kernels' argument lists -- the bf16-state
+    kernels have a workspace layout of their own; None above rank 32, where uvd_wide.py brings its own and `out` is ignored.
+    Returns (N, r, tail)."""
+    dev = _require_hip(name, U, V, d, *cols, **(_BF16_STATE if bf16 else _FP32_STATE))
+    N, r = _uvd_shapes(name, U, V, d, *cols)
+    if r > _lib.UVD_MAX_RANK:
+        return N, r, None
+    if out is not None:
+        _require_hip(name, out, cols[-1])
+        if out.shape != cols[-1].shape:
+            raise ValueError("%s: out must be shaped like g" % name)
+    ws = (uvd_bf16_workspace if bf16 else uvd_workspace)(dev, N, r)
+    return N, r, (ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+
+
 def precond_grad_UVd_math(U, V, d, g, *, out=None):
     """psgd.py:619-627: d .* (I + V U')(I + U V')(d .* g); returns a new tensor shaped like g.
     g is a column vector ([N] or [N, 1]) or, as the reference's docstring allows (:623), a matrix [N, k]: d broadcasts over
     the columns and U, V are swept once per group of four columns (psgd_uvd_apply_cols_f32).
-    out (extension; column-vector g, r <= 32): a contiguous fp32 tensor shaped like g to write the result to (placement.UVdArena.out)."""
+    out (extension; column-vector g, r <= 32): a contiguous fp32 tensor shaped like g to write the result to (placement.UVdArena.out).
+    A bfloat16 U, V, d (psgd_uvd_bf16.hip): fp32 column vector g, r <= 32."""
+    name = "precond_grad_UVd_math"
     U, V, d = _c(U), _c(V), _c(d)
-    if _bf16_state("precond_grad_UVd_math", U, V, d, *([g] if out is None else [g, out])):
-        # bf16-stored state (psgd_uvd_bf16.hip): fp32 column vector g, r <= 32
-        g = _c(g)
-        N, r, _, _, _, _, out, tail = _bf16_call("precond_grad_UVd_math", U, V, d, g, out, None, None, None, None, None, (g,))
-        rc = _lib.load().psgd_uvd_apply_bf16(U.data_ptr(), V.data_ptr(), d.data_ptr(), g.data_ptr(), out.data_ptr(), N, r, *tail)
-        _lib.check(rc, "psgd_uvd_apply_bf16")
-        return out
+    bf16 = _bf16_state(name, U, V, d)
     if isinstance(g, torch.Tensor) and g.dim() == 2 and g.shape[1] > 1:
-        dev = _require_hip("precond_grad_UVd_math", U, V, d)
+        if bf16:
+            raise ValueError("%s: a matrix g is not supported with a bfloat16 state (column vectors only)" % name)
+        dev = _require_hip(name, U, V, d)
         if not g.is_cuda or g.dtype != torch.float32 or g.device != dev:
-            _require_hip("precond_grad_UVd_math", U, g)
-        N, r = _uvd_shapes("precond_grad_UVd_math", U, V, d)
-        gt = _cols_of("precond_grad_UVd_math", g, N)
+            _require_hip(name, U, g)
+        N, r = _uvd_shapes(name, U, V, d)
+        gt = _cols_of(name, g, N)
         k = gt.shape[0]
         if r > _lib.UVD_MAX_RANK:
             return _wide.precond_grad(U, V, d, [gt[j] for j in range(k)], uvd_workspace).t().contiguous()
@@ -531,26 +522,15 @@ def precond_grad_UVd_math(U, V, d, g, *, out=None):
         _lib.check(rc, "psgd_uvd_apply_cols_f32")
         return ot.t().contiguous()
     g = _c(g)
-    dev = _require_hip("precond_grad_UVd_math", U, V, d, g)
-    N, r = _uvd_shapes("precond_grad_UVd_math", U, V, d, g)
-    if r > _lib.UVD_MAX_RANK:                      # wide rank: column chunks through the same kernels (uvd_wide.py)
+    N, r, tail = _vector_call(name, bf16, U, V, d, (g,), out)
+    if tail is None:                               # wide rank: column chunks through the same kernels (uvd_wide.py)
         return _wide.precond_grad(U, V, d, g, uvd_workspace)
-    if out is None:
-        out = torch.empty_like(g)
-    else:
-        _require_hip("precond_grad_UVd_math", out, U)
-        if out.shape != g.shape:
-            raise ValueError("precond_grad_UVd_math: out must be shaped like g")
-    ws = uvd_workspace(dev, N, r)
-    rc = _lib.load().psgd_uvd_apply_f32(U.data_ptr(), V.data_ptr(), d.data_ptr(), g.data_ptr(), out.data_ptr(),
-                                         N, r, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "psgd_uvd_apply_f32")
+    out = torch.empty_like(g) if out is None else out
+    lib = _lib.load()
+    rc = (lib.psgd_uvd_apply_bf16 if bf16 else lib.psgd_uvd_apply_f32)(
+        U.data_ptr(), V.data_ptr(), d.data_ptr(), g.data_ptr(), out.data_ptr(), N, r, *tail)
+    _lib.check(rc, "psgd_uvd_apply_bf16" if bf16 else "psgd_uvd_apply_f32")
     return out
-
-
-def _draw_branch(p, generator):
-    gen = generator if generator is not None else _branch_rng
-    return bool(torch.rand((), generator=gen).item() < p)
 
 
 def update_precond_UVd_math_(U, V, d, v, h, step, tiny, *, balance=None, update_U=None, generator=None,
@@ -565,36 +545,23 @@ def update_precond_UVd_math_(U, V, d, v, h, step, tiny, *, balance=None, update_
     element narrowed once -- rounding="nearest" or "stochastic" (seeded by rounding_seed; None draws one from `generator` /
     the module's branch generator after the branch draws).  An fp32 state is not rounded: any rounding other than the default, or
     a rounding_seed, raises ValueError there."""
+    name = "update_precond_UVd_math_"
     state = _InPlace(U, V, d)
     (U, V, d), v, h = state.work, _c(v), _c(h)
-    if rounding not in _ROUNDINGS:
-        raise ValueError("update_precond_UVd_math_: rounding must be 'nearest' or 'stochastic', got %r" % (rounding,))
-    if _bf16_state("update_precond_UVd_math_", U, V, d, v, h):
-        N, r, bal, upd, mode, seed, _, tail = _bf16_call("update_precond_UVd_math_", U, V, d, None, None, balance, update_U,
-                                                          rounding, rounding_seed, generator, (v, h))
+    bf16 = _bf16_state(name, U, V, d)
+    mode = _rounding_mode(name, bf16, rounding, rounding_seed)
+    N, r, tail = _vector_call(name, bf16, U, V, d, (v, h))
+    balance, update_U, seed = _resolve_branches(balance, update_U, generator, mode, rounding_seed)
+    if tail is None:
+        _wide.update(U, V, d, v, h, float(step), float(tiny), balance, update_U, uvd_workspace)
+    elif bf16:
         rc = _lib.load().psgd_uvd_update_bf16(U.data_ptr(), V.data_ptr(), d.data_ptr(), v.data_ptr(), h.data_ptr(), N, r,
-                                               float(step), float(tiny), bal, upd, mode, seed, *tail)
+                                               float(step), float(tiny), balance, update_U, mode, seed, *tail)
         _lib.check(rc, "psgd_uvd_update_bf16")
-        state.writeback()
-        return None
-    if rounding != "nearest" or rounding_seed is not None:
-        raise ValueError("update_precond_UVd_math_: rounding / rounding_seed apply to a bfloat16 state only; an fp32 state is not "
-                         "rounded")
-    dev = _require_hip("update_precond_UVd_math_", U, V, d, v, h)
-    N, r = _uvd_shapes("update_precond_UVd_math_", U, V, d, v, h)
-    if balance is None:
-        balance = _draw_branch(0.01, generator)
-    if update_U is None:
-        update_U = _draw_branch(0.5, generator)
-    if r > _lib.UVD_MAX_RANK:
-        _wide.update(U, V, d, v, h, float(step), float(tiny), bool(balance), bool(update_U), uvd_workspace)
-        state.writeback()
-        return None
-    ws = uvd_workspace(dev, N, r)
-    rc = _lib.load().psgd_uvd_update_f32(U.data_ptr(), V.data_ptr(), d.data_ptr(), v.data_ptr(), h.data_ptr(), N, r,
-                                          float(step), float(tiny), int(bool(balance)), int(bool(update_U)),
-                                          ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "psgd_uvd_update_f32")
+    else:
+        rc = _lib.load().psgd_uvd_update_f32(U.data_ptr(), V.data_ptr(), d.data_ptr(), v.data_ptr(), h.data_ptr(), N, r,
+                                              float(step), float(tiny), balance, update_U, *tail)
+        _lib.check(rc, "psgd_uvd_update_f32")
     state.writeback()
     return None
 
@@ -605,47 +572,31 @@ def update_precond_UVd_math_and_precond_grad(U, V, d, v, h, g, step, tiny, *, ba
     precond_grad_UVd_math(U, V, d, g) on the updated state -- the UVd.step pattern (psgd.py:732 -> :748) --
     as one fused call that saves a pass over V.  U or V, and d, are updated in place; returns the
     preconditioned gradient.  out (optional): a contiguous fp32 tensor shaped like g to write it to (placement.UVdArena.out:
-    where the output stream lives is worth 4 % of the last sweep); ranks above 32 ignore it."""
+    where the output stream lives is worth 4 % of the last sweep); ranks above 32 ignore it.
+    A bfloat16 state: rounding / rounding_seed as in update_precond_UVd_math_; the gradient is preconditioned with the state as
+    it was stored (rounded)."""
+    name = "update_precond_UVd_math_and_precond_grad"
     state = _InPlace(U, V, d)
     (U, V, d), v, h, g = state.work, _c(v), _c(h), _c(g)
-    name = "update_precond_UVd_math_and_precond_grad"
-    if rounding not in _ROUNDINGS:
-        raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (name, rounding))
-    if _bf16_state(name, U, V, d, *([v, h, g] if out is None else [v, h, g, out])):
-        # bf16-stored state: rounding / rounding_seed as in update_precond_UVd_math_; the gradient is preconditioned with the
-        # state as it was stored (rounded)
-        N, r, bal, upd, mode, seed, out, tail = _bf16_call(name, U, V, d, g, out, balance, update_U, rounding, rounding_seed,
-                                                            generator, (v, h, g))
+    bf16 = _bf16_state(name, U, V, d)
+    mode = _rounding_mode(name, bf16, rounding, rounding_seed)
+    N, r, tail = _vector_call(name, bf16, U, V, d, (v, h, g), out)
+    balance, update_U, seed = _resolve_branches(balance, update_U, generator, mode, rounding_seed)
+    if tail is None:                               # ranks 33 .. 64: the fused sequence of uvd_wide.update_apply; above: update, then apply
+        out = _wide.update_apply(U, V, d, v, h, g, float(step), float(tiny), balance, update_U, uvd_workspace)
+        state.writeback()
+        return out
+    out = torch.empty_like(g) if out is None else out
+    if bf16:
         rc = _lib.load().psgd_uvd_update_apply_bf16(U.data_ptr(), V.data_ptr(), d.data_ptr(), v.data_ptr(), h.data_ptr(),
-                                                     g.data_ptr(), out.data_ptr(), N, r, float(step), float(tiny), bal, upd, mode,
-                                                     seed, *tail)
+                                                     g.data_ptr(), out.data_ptr(), N, r, float(step), float(tiny), balance,
+                                                     update_U, mode, seed, *tail)
         _lib.check(rc, "psgd_uvd_update_apply_bf16")
-        state.writeback()
-        return out
-    if rounding != "nearest" or rounding_seed is not None:
-        raise ValueError("%s: rounding / rounding_seed apply to a bfloat16 state only; an fp32 state is not rounded" % name)
-    dev = _require_hip("update_precond_UVd_math_and_precond_grad", U, V, d, v, h, g)
-    N, r = _uvd_shapes("update_precond_UVd_math_and_precond_grad", U, V, d, v, h, g)
-    if balance is None:
-        balance = _draw_branch(0.01, generator)
-    if update_U is None:
-        update_U = _draw_branch(0.5, generator)
-    if r > _lib.UVD_MAX_RANK:                      # ranks 33 .. 64: the fused sequence of uvd_wide.update_apply; above: update, then apply
-        out = _wide.update_apply(U, V, d, v, h, g, float(step), float(tiny), bool(balance), bool(update_U), uvd_workspace)
-        state.writeback()
-        return out
-    if out is None:
-        out = torch.empty_like(g)
     else:
-        _require_hip("update_precond_UVd_math_and_precond_grad", out, U)
-        if out.shape != g.shape:
-            raise ValueError("update_precond_UVd_math_and_precond_grad: out must be shaped like g")
-    ws = uvd_workspace(dev, N, r)
-    rc = _lib.load().psgd_uvd_update_apply_f32(U.data_ptr(), V.data_ptr(), d.data_ptr(), v.data_ptr(), h.data_ptr(),
-                                                g.data_ptr(), out.data_ptr(), N, r, float(step), float(tiny),
-                                                int(bool(balance)), int(bool(update_U)), ws.data_ptr(), ws.numel(),
-                                                _stream_ptr(dev))
-    _lib.check(rc, "psgd_uvd_update_apply_f32")
+        rc = _lib.load().psgd_uvd_update_apply_f32(U.data_ptr(), V.data_ptr(), d.data_ptr(), v.data_ptr(), h.data_ptr(),
+                                                    g.data_ptr(), out.data_ptr(), N, r, float(step), float(tiny), balance,
+                                                    update_U, *tail)
+        _lib.check(rc, "psgd_uvd_update_apply_f32")
     state.writeback()
     return out
 
@@ -999,6 +950,10 @@ class UVd:
             from . import placement as _placement
             self._arena = (_placement.UVdArena.probe if placement == "probe" else _placement.UVdArena.packed)(
                 num_params, r, self._device)
+        # the keywords of the two calls of step() (_precondition) that never change
+        out = None if self._arena is None else self._arena.out
+        self._apply_kw = dict(group=group, backend=stage_backend) if group is not None else dict(out=out)
+        self._update_kw = dict(self._apply_kw, out=out, generator=generator, rounding=state_rounding or "nearest")
         if self._arena is not None:
             self._arena.install_workspace()
             self._U, self._V, self._d = self._arena.U, self._arena.V, self._arena.d
@@ -1194,6 +1149,27 @@ class UVd:
                 uvd_bf16_narrow_(flat[lo:lo + m], staged[:m], tensor=k, index0=index0 + lo, rounding=rounding, rounding_seed=seed)
                 stream.synchronize()
 
+    def _precondition(self, v, h, grad):
+        """psgd.py:748 on the flat gradient; with v and h (None on a step that leaves the preconditioner alone) after :732-733,
+        as one fused call: the same results in three sweeps instead of six.  Row-sharded: this rank's rows, 2 exchanges (4 for
+        a native bf16 state), :562 and :588 from the synchronised generator.  A native state gets the rounding seed of this step."""
+        U, V, d = self._state_fp32()
+        g = grad[:, None].contiguous()
+        if self._group is not None:          # (looked up at the call, as a global is: a spy on the module attribute sees the call)
+            apply, fused = self._sharded.precond_grad_UVd_math, self._sharded.update_precond_UVd_math_and_precond_grad
+        else:
+            apply, fused = precond_grad_UVd_math, update_precond_UVd_math_and_precond_grad
+        if v is None:
+            return apply(U, V, d, g, **self._apply_kw)
+        seed = None
+        if self._native:
+            seed = uvd_step_rounding_seed(self._round_seed0, self._round_step)
+            self._round_step += 1
+        pre_grad = fused(U, V, d, v[:, None].contiguous(), h[:, None].contiguous(), g, step=float(self.lr_preconditioner),
+                         tiny=self._tiny, rounding_seed=seed, **self._update_kw)
+        self._state_store(U, V, d)
+        return pre_grad
+
     def step(self, closure):
         """psgd.py:692-764."""
         params = self._params_with_grad
@@ -1232,44 +1208,12 @@ class UVd:
                 v = v / self._delta_param_scale
                 h = h / self._delta_param_scale
             grad = self._flat(grads, "g")                                                     # :747
-            # :732-733 then :748 as one fused call (same results, three sweeps instead of six)
-            U, V, d = self._state_fp32()
-            if self._native and self._group is not None:     # this rank's bf16 rows; 4 exchanges (sharded.py)
-                seed = uvd_step_rounding_seed(self._round_seed0, self._round_step)
-                self._round_step += 1
-                pre_grad = self._sharded.update_precond_UVd_math_and_precond_grad(
-                    U, V, d, v[:, None].contiguous(), h[:, None].contiguous(), grad[:, None].contiguous(),
-                    float(self.lr_preconditioner), self._tiny, generator=self._generator, group=self._group,
-                    rounding=self._state_rounding, rounding_seed=seed)
-            elif self._native:                     # the stored bf16 tensors go straight to the fused call
-                seed = uvd_step_rounding_seed(self._round_seed0, self._round_step)
-                self._round_step += 1
-                pre_grad = update_precond_UVd_math_and_precond_grad(
-                    U, V, d, v[:, None], h[:, None], grad[:, None], step=float(self.lr_preconditioner), tiny=self._tiny,
-                    generator=self._generator, rounding=self._state_rounding, rounding_seed=seed)
-            elif self._group is None:
-                pre_grad = update_precond_UVd_math_and_precond_grad(
-                    U, V, d, v[:, None].contiguous(), h[:, None].contiguous(),
-                    grad[:, None].contiguous(), step=float(self.lr_preconditioner), tiny=self._tiny,
-                    generator=self._generator, out=None if self._arena is None else self._arena.out)
-            else:                                  # this rank's rows; 2 exchanges; :562, :588 from the synchronised generator
-                pre_grad = self._sharded.update_precond_UVd_math_and_precond_grad(
-                    U, V, d, v[:, None].contiguous(), h[:, None].contiguous(),
-                    grad[:, None].contiguous(), float(self.lr_preconditioner), self._tiny,
-                    generator=self._generator, group=self._group, backend=self._stage_backend,
-                    out=None if self._arena is None else self._arena.out)
-            self._state_store(U, V, d)
+            pre_grad = self._precondition(v, h, grad)                                         # :732-733, :748
         else:                                                                                 # :737-744
             with torch.enable_grad():
                 closure_returns = closure()
                 grads = torch.autograd.grad(self._loss_of(closure_returns), params)
-            grad = self._flat(grads, "g")                                                     # :747
-            if self._group is None:
-                pre_grad = precond_grad_UVd_math(*self._state_fp32(), grad[:, None].contiguous(),      # :748
-                                                 out=None if self._arena is None else self._arena.out)
-            else:
-                pre_grad = self._sharded.precond_grad_UVd_math(*self._state_fp32(), grad[:, None].contiguous(),
-                                                               group=self._group, backend=self._stage_backend)
+            pre_grad = self._precondition(None, None, self._flat(grads, "g"))                 # :747-748
         max_norm = float(self.grad_clip_max_norm)
         if self._tail is not None:                                                            # :750-762 in the step-tail kernels
             uvd_step_tail(params, pre_grad, float(self.lr_params), max_norm, self._tiny, vs if (not exact) and update_Q else None,

@@ -48,34 +48,29 @@ from . import uvd_wide as _wide
 from . import splu_wide as _splu_wide
 
 
-class HipStages:
-    """Stage functions of the C ABI on this rank's shard; the reduced buffers are views into the
-    device workspace (psgd_uvd_ws_region)."""
+class _HipStageBase:
+    """What the HIP stage backends share: this rank's shard shape, the library, the device workspace, the reduced buffers as
+    cached views into it and the exchange half of the stage interface (send / gather_buf / fold).  A subclass names the region
+    query of its workspace layout (_region) and the fold kernel of its send regions (_fold)."""
+    _region = _fold = None
 
-    def __init__(self, device, n_local, r):
+    def __init__(self, device, n_local, r, workspace):
         self.device, self.N, self.r = device, int(n_local), int(r)
-        if self.r > _lib.UVD_MAX_RANK:
-            raise _lib.PsgdHipError("the stage kernels take ranks up to %d; wider preconditioners go through uvd_wide.py "
-                                    "(the sharded entry points route them there), got r = %d" % (_lib.UVD_MAX_RANK, self.r))
         self.lib = _lib.load()
-        self.ws = _psgd.uvd_workspace(device, self.N, self.r)
+        self.ws = workspace(device, self.N, self.r)
+        self._fold_fn = getattr(self.lib, self._fold)
         self._views = {}
+        self._out = None
 
-    def _st(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+    def _w(self):
+        return self.ws.data_ptr(), self.ws.numel(), torch.cuda.current_stream(self.device).cuda_stream
 
     def _view(self, which, stage, dtype, itemsize):
         key = (which, stage)
         if key not in self._views:
-            off, cnt = _lib.ws_region(which, stage, self.N, self.r)
+            off, cnt = self._region(which, stage, self.N, self.r)
             self._views[key] = self.ws[off:off + cnt * itemsize].view(dtype)
         return self._views[key]
-
-    def sums(self, stage):
-        return self._view(_lib.PSGD_WS_SUMS_F64, stage, torch.float64, 8)
-
-    def maxbuf(self, stage):
-        return self._view(_lib.PSGD_WS_MAX_F32, stage, torch.float32, 4)
 
     def send(self, stage):
         """This rank's fp64 contribution to the exchange after `stage` (a view into the workspace)."""
@@ -89,12 +84,25 @@ class HipStages:
 
     def fold(self, stage, gathered, world):
         """Fold the all-gathered send regions ([world][count], rank order) into this rank's workspace."""
-        wp, wn, st = self._w()
-        _lib.check(self.lib.psgd_uvd_fold_gathered_f64(stage, gathered.data_ptr(), world, self.N, self.r, wp, wn, st),
-                   "fold_gathered")
+        _lib.check(self._fold_fn(stage, gathered.data_ptr(), world, self.N, self.r, *self._w()), self._fold)
 
-    def _w(self):
-        return self.ws.data_ptr(), self.ws.numel(), self._st()
+
+class HipStages(_HipStageBase):
+    """Stage functions of the C ABI on this rank's shard; the reduced buffers are views into the
+    device workspace (psgd_uvd_ws_region)."""
+    _region, _fold = staticmethod(_lib.ws_region), "psgd_uvd_fold_gathered_f64"
+
+    def __init__(self, device, n_local, r):
+        if int(r) > _lib.UVD_MAX_RANK:
+            raise _lib.PsgdHipError("the stage kernels take ranks up to %d; wider preconditioners go through uvd_wide.py "
+                                    "(the sharded entry points route them there), got r = %d" % (_lib.UVD_MAX_RANK, int(r)))
+        super().__init__(device, n_local, r, _psgd.uvd_workspace)
+
+    def sums(self, stage):
+        return self._view(_lib.PSGD_WS_SUMS_F64, stage, torch.float64, 8)
+
+    def maxbuf(self, stage):
+        return self._view(_lib.PSGD_WS_MAX_F32, stage, torch.float32, 4)
 
     def apply_sweep1(self, V, d, g):
         _lib.check(self.lib.psgd_uvd_apply_sweep1_f32(V.data_ptr(), d.data_ptr(), g.data_ptr(), self.N, self.r,
@@ -160,39 +168,16 @@ class HipStages:
                                                        wp, wn, st), "update_sweep3")
 
 
-class HipStagesBf16:
+class HipStagesBf16(_HipStageBase):
     """Stage functions of the bf16-state kernels (psgd_uvd_*_bf16) on this rank's shard: U, V, d bfloat16, vectors fp32.  The
     send regions are views into the device workspace (psgd_uvd_bf16_ws_region); the fold after every stage is what publishes
     the reduced values to the next one (with one rank as well)."""
+    _region, _fold = staticmethod(_lib.uvd_bf16_ws_region), "psgd_uvd_bf16_fold_gathered_f64"
 
     def __init__(self, device, n_local, r):
-        self.device, self.N, self.r = device, int(n_local), int(r)
-        if self.r > _lib.UVD_MAX_RANK:
-            raise ValueError("a bfloat16 state supports ranks up to %d, got r = %d" % (_lib.UVD_MAX_RANK, self.r))
-        self.lib = _lib.load()
-        self.ws = _psgd.uvd_bf16_workspace(device, self.N, self.r)
-        self._views = {}
-        self._out = None
-
-    def _w(self):
-        return self.ws.data_ptr(), self.ws.numel(), torch.cuda.current_stream(self.device).cuda_stream
-
-    def send(self, stage):
-        if stage not in self._views:
-            off, cnt = _lib.uvd_bf16_ws_region(_lib.PSGD_WS_SEND_F64, stage, self.N, self.r)
-            self._views[stage] = self.ws[off:off + cnt * 8].view(torch.float64)
-        return self._views[stage]
-
-    def gather_buf(self, stage, world):
-        key = ("gather", stage, world)
-        if key not in self._views:
-            self._views[key] = torch.empty(world * self.send(stage).numel(), dtype=torch.float64, device=self.device)
-        return self._views[key]
-
-    def fold(self, stage, gathered, world):
-        wp, wn, st = self._w()
-        _lib.check(self.lib.psgd_uvd_bf16_fold_gathered_f64(stage, gathered.data_ptr(), world, self.N, self.r, wp, wn, st),
-                   "bf16 fold_gathered")
+        if int(r) > _lib.UVD_MAX_RANK:
+            raise ValueError("a bfloat16 state supports ranks up to %d, got r = %d" % (_lib.UVD_MAX_RANK, int(r)))
+        super().__init__(device, n_local, r, _psgd.uvd_bf16_workspace)
 
     def coefficients(self):
         """the r-vectors of the last r x r algebra (fp32 header words 8 .. 8 + 224: identical on every rank)"""
@@ -389,17 +374,6 @@ CHECK_EXPLICIT_BRANCHES = False     # debugging aid: verify (one all-reduce + a 
                                     # same explicit balance / update_U values; drawn values agree by construction
 
 
-def _agree_on_branches(balance, update_U, generator, device, group):
-    if balance is not None and update_U is not None:
-        if CHECK_EXPLICIT_BRANCHES:
-            _check_explicit_branches_agree(balance, update_U, device, group)
-        return bool(balance), bool(update_U)
-    rng = branch_rng_for(generator, group, device)
-    b = rng.draw(0.01) if balance is None else bool(balance)            # reference order: :562 then :588
-    u = rng.draw(0.5) if update_U is None else bool(update_U)
-    return b, u
-
-
 class _RcclDirect:
     """An RCCL communicator of our own for the exchanges, used through ctypes so that the all-gather is enqueued on the CALLER'S
     stream -- sweep, collective and fold are then one stream-ordered sequence.  torch.distributed runs NCCL / RCCL collectives on a
@@ -532,13 +506,6 @@ def _is_wide(U, backend):
     return backend is None and U.dim() == 2 and U.shape[1] > _lib.UVD_MAX_RANK
 
 
-def _check_local(name, U, V, *cols):
-    """The single-GPU entry points' checks on this rank's tensors (device, dtype, contiguity, shapes): the stage kernels
-    and the wide-rank chunks take raw pointers.  Only for the product backend (the CPU test backend takes CPU tensors)."""
-    _psgd._require_hip(name, U, V, *cols)
-    _psgd._uvd_shapes(name, U, V, *cols)
-
-
 def _check_explicit_branches_agree(balance, update_U, device, group):
     """Explicit branch values must be the same on every rank (drawn ones are, by construction): the ranks would otherwise
     run different stage sequences and hang or mix branches.  One tiny MAX/MIN pair rides on a single all-reduce."""
@@ -572,54 +539,46 @@ def global_row0(n_local, device=None, group=None):
     return ent[1]
 
 
-def _bf16_sharded(name, U, V, d, cols, backend):
-    """True when U, V, d are a bf16-stored state; raises for a mixed state, ranks above 32 and (product backend) everything the
-    single-GPU bf16 entry points refuse."""
+def _classify(name, U, V, d, cols, backend):
+    """True when U, V, d are a bf16-stored state, False for an fp32 one (raises for a float16 or mixed state and for a bfloat16
+    one of rank above 32).  Product backend: also the single-GPU entry points' checks on this rank's tensors (device, dtype,
+    contiguity -- a strided operand is refused, not copied: a copy of a shard helps nobody -- and shapes): the stage kernels and
+    the wide-rank chunks take raw pointers.  A backend passed in (the CPU doubles of tests/) takes CPU tensors as they come."""
+    bf16 = _psgd._bf16_state(name, U, V, d)
     if backend is None:
-        if not _psgd._bf16_state(name, U, V, d, *cols):
-            return False
-        if not all(t.is_contiguous() for t in (U, V, d) + tuple(cols)):
-            raise ValueError("%s: contiguous tensors required" % name)
+        _psgd._require_hip(name, U, V, d, *cols, **(_psgd._BF16_STATE if bf16 else _psgd._FP32_STATE))
         _psgd._uvd_shapes(name, U, V, d, *cols)
-        return True
-    dts = {t.dtype for t in (U, V, d)}
-    if torch.bfloat16 not in dts:
-        return False
-    if dts != {torch.bfloat16}:
-        raise TypeError("%s: mixed state dtypes %s; U, V and d must all be bfloat16 (or all float32)"
-                        % (name, sorted(str(x) for x in dts)))
-    if U.shape[1] > _lib.UVD_MAX_RANK:
-        raise ValueError("%s: a bfloat16 state supports ranks up to %d, got %d" % (name, _lib.UVD_MAX_RANK, U.shape[1]))
-    return True
+    return bf16
 
 
-def _no_rounding(name, rounding, rounding_seed, row0):
-    if rounding not in _psgd._ROUNDINGS:
-        raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (name, rounding))
-    if rounding != "nearest" or rounding_seed is not None or row0 is not None:
-        raise ValueError("%s: rounding / rounding_seed / row0 apply to a bfloat16 state only; an fp32 state is not rounded" % name)
+def _resolve(name, bf16, U, balance, update_U, generator, rounding, rounding_seed, row0, group):
+    """(balance, update_U, rounding mode, seed, row0) of an updating call, the same on every rank: what is None is drawn from the
+    synchronised branch generator (psgd's _resolve_branches: one order of draws for the single-GPU and the sharded calls); row0
+    (bf16 state only) defaults to the rows on the ranks before this one"""
+    mode = _psgd._rounding_mode(name, bf16, rounding, rounding_seed, row0)
+    if CHECK_EXPLICIT_BRANCHES and balance is not None and update_U is not None:
+        _check_explicit_branches_agree(balance, update_U, U.device, group)
+    balance, update_U, seed = _psgd._resolve_branches(balance, update_U, generator, mode, rounding_seed,
+                                                      lambda: branch_rng_for(generator, group, U.device))
+    if bf16:
+        row0 = global_row0(U.shape[0], U.device, group) if row0 is None else int(row0)
+        if row0 < 0:
+            raise ValueError("%s: row0 must be >= 0, got %r" % (name, row0))
+    return balance, update_U, mode, seed, row0
 
 
-def _bf16_update_args(name, U, balance, update_U, generator, rounding, rounding_seed, row0, group, backend):
-    """what the two updating bf16 calls share: the branches, the rounding mode, ONE seed for all ranks (drawn, when none is given,
-    from the synchronised branch generator after the branch draws) and this rank's first global row"""
-    if rounding not in _psgd._ROUNDINGS:
-        raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (name, rounding))
-    device = U.device if backend is None else None
-    balance, update_U = _agree_on_branches(balance, update_U, generator, device, group)
-    if rounding_seed is None:
-        rounding_seed = 0
-        if rounding == "stochastic":
-            gen = branch_rng_for(generator, group, device).gen
-            rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=gen).item())
-    if row0 is None:
-        row0 = global_row0(U.shape[0], device, group)
-    if int(row0) < 0:
-        raise ValueError("%s: row0 must be >= 0, got %r" % (name, row0))
-    return balance, update_U, _psgd._ROUNDINGS[rounding], int(rounding_seed) & (2 ** 64 - 1), int(row0)
+def _update_front(be, U, V, d, v, h, balance, group):
+    """what the fp32 update and fused step start with: [max -> X(10) -> scale] -> sweep1 -> X(Gram)"""
+    if balance:
+        be.balance_max(U, V)
+        _exchange(be, 10, group)
+        be.balance_scale(U, V)
+    be.update_sweep1(U, V, d, v, h)
+    _exchange(be, 11, group)
 
 
 def _bf16_update_front(be, U, V, d, v, h, step, tiny, balance, update_U, mode, seed, row0, group):
+    """... and the bf16 ones: [max -> X(10)] -> Gram -> X(11) -> rewrite (which applies the balancing factors) -> X(12)"""
     if balance:
         be.balance_max(U, V)
         _exchange(be, 10, group)
@@ -631,26 +590,20 @@ def _bf16_update_front(be, U, V, d, v, h, step, tiny, balance, update_U, mode, s
 
 def _bf16_apply_tail(be, U, V, d, g, group, out=None):
     _exchange(be, 1, group)
-    if out is None:
-        be.apply_sweep2(U, d, g)
-    else:
-        be.apply_sweep2(U, d, g, out=out)
+    be.apply_sweep2(U, d, g, out=out)
     _exchange(be, 2, group)
     return be.apply_sweep3(V, d)
 
 
 def precond_grad_UVd_math(U, V, d, g, group=None, backend=None):
     """Sharded psgd.py:619-627 on this rank's rows; returns this rank's rows of the result.  2 exchanges (fp32 and bf16 state)."""
-    if _bf16_sharded("sharded precond_grad_UVd_math", U, V, d, (g,), backend):
-        be = backend if backend is not None else hip_backend_for(U)
-        be.apply_sweep1(V, d, g)
-        return _bf16_apply_tail(be, U, V, d, g, group)
-    if backend is None:
-        _check_local("sharded precond_grad_UVd_math", U, V, d, g)
+    bf16 = _classify("sharded precond_grad_UVd_math", U, V, d, (g,), backend)
     if _is_wide(U, backend):
         return _wide.precond_grad(U, V, d, g, _psgd.uvd_workspace, reduce=_wide_reduce(group))
     be = backend if backend is not None else hip_backend_for(U)
     be.apply_sweep1(V, d, g)
+    if bf16:
+        return _bf16_apply_tail(be, U, V, d, g, group)
     _exchange(be, 1, group)
     be.apply_sweep2(U, d, g)
     _exchange(be, 2, group)
@@ -664,28 +617,17 @@ def update_precond_UVd_math_(U, V, d, v, h, step, tiny, *, balance=None, update_
     function (every rank must use the same seed: None draws it from the synchronised branch generator); row0 = the global index
     of this rank's first row (None: the exclusive prefix of the ranks' row counts, one set-up collective)."""
     name = "sharded update_precond_UVd_math_"
-    if _bf16_sharded(name, U, V, d, (v, h), backend):
-        balance, update_U, mode, seed, row0 = _bf16_update_args(name, U, balance, update_U, generator, rounding, rounding_seed,
-                                                                row0, group, backend)
-        be = backend if backend is not None else hip_backend_for(U)
-        _bf16_update_front(be, U, V, d, v, h, step, tiny, balance, update_U, mode, seed, row0, group)
-        be.update_d(d, step, tiny, mode, seed, row0)
-        return None
-    _no_rounding(name, rounding, rounding_seed, row0)
-    if backend is None:
-        _check_local("sharded update_precond_UVd_math_", U, V, d, v, h)
+    bf16 = _classify(name, U, V, d, (v, h), backend)
+    balance, update_U, mode, seed, row0 = _resolve(name, bf16, U, balance, update_U, generator, rounding, rounding_seed, row0, group)
     if _is_wide(U, backend):
-        balance, update_U = _agree_on_branches(balance, update_U, generator, U.device, group)
         return _wide.update(U, V, d, v, h, float(step), float(tiny), balance, update_U, _psgd.uvd_workspace,
                             reduce=_wide_reduce(group))
     be = backend if backend is not None else hip_backend_for(U)
-    balance, update_U = _agree_on_branches(balance, update_U, generator, U.device, group)
-    if balance:
-        be.balance_max(U, V)
-        _exchange(be, 10, group)
-        be.balance_scale(U, V)
-    be.update_sweep1(U, V, d, v, h)
-    _exchange(be, 11, group)
+    if bf16:
+        _bf16_update_front(be, U, V, d, v, h, step, tiny, balance, update_U, mode, seed, row0, group)
+        be.update_d(d, step, tiny, mode, seed, row0)
+        return None
+    _update_front(be, U, V, d, v, h, balance, group)
     be.update_sweep2(U, V, d, v, h, step, tiny, update_U)
     _exchange(be, 12, group)
     be.update_sweep3(d, step, tiny)
@@ -699,82 +641,46 @@ def update_precond_UVd_math_and_precond_grad(U, V, d, v, h, g, step, tiny, *, ba
     2 exchanges: the Gram; the 4r column sums of sweep 2 with max|nablaD| in one buffer (every rank, r > 32 included since
     round 6).  A bfloat16 state takes 4 exchanges (11, 12, 1, 2): the gradient is preconditioned with the state as it was
     STORED, so the apply's reductions cannot be derived from sums over the unrounded one; rounding, rounding_seed and row0 as in
-    update_precond_UVd_math_."""
+    update_precond_UVd_math_.  out (a placed state passes its arena's output region): where to write the result; ranks above 32
+    and an fp32 stage backend passed in ignore it."""
     name = "sharded update_precond_UVd_math_and_precond_grad"
-    if _bf16_sharded(name, U, V, d, (v, h, g) if out is None or backend is not None else (v, h, g, out), backend):
-        balance, update_U, mode, seed, row0 = _bf16_update_args(name, U, balance, update_U, generator, rounding, rounding_seed,
-                                                                row0, group, backend)
-        be = backend if backend is not None else hip_backend_for(U)
+    bf16 = _classify(name, U, V, d, (v, h, g) if out is None else (v, h, g, out), backend)
+    balance, update_U, mode, seed, row0 = _resolve(name, bf16, U, balance, update_U, generator, rounding, rounding_seed, row0, group)
+    if _is_wide(U, backend):
+        # r > 32: the fused sequence on the wide-rank building blocks, 2 exchanges (+ 1 on the balance branch) like the ranks below
+        return _wide.update_apply(U, V, d, v, h, g, float(step), float(tiny), balance, update_U, _psgd.uvd_workspace,
+                                  reduce=_wide_reduce(group))
+    be = backend if backend is not None else hip_backend_for(U)
+    if bf16:
         if out is not None and (out.shape != g.shape or not out.is_contiguous()):
             raise ValueError("%s: out must be contiguous and shaped like g" % name)
         _bf16_update_front(be, U, V, d, v, h, step, tiny, balance, update_U, mode, seed, row0, group)
         be.apply_sweep1_d(V, d, g, step, tiny, mode, seed, row0)
-        return _bf16_apply_tail(be, U, V, d, g, group, out=out)
-    _no_rounding(name, rounding, rounding_seed, row0)
-    if backend is None:
-        _check_local("sharded update_precond_UVd_math_and_precond_grad", U, V, d, v, h, g)
-    if _is_wide(U, backend):
-        # r > 32: the fused sequence on the wide-rank building blocks, 2 exchanges (+ 1 on the balance branch) like the ranks below
-        balance, update_U = _agree_on_branches(balance, update_U, generator, U.device, group)
-        return _wide.update_apply(U, V, d, v, h, g, float(step), float(tiny), balance, update_U, _psgd.uvd_workspace,
-                                  reduce=_wide_reduce(group))
-    be = backend if backend is not None else hip_backend_for(U)
-    balance, update_U = _agree_on_branches(balance, update_U, generator, U.device, group)
-    if balance:
-        be.balance_max(U, V)
-        _exchange(be, 10, group)
-        be.balance_scale(U, V)
-    be.update_sweep1(U, V, d, v, h)
-    _exchange(be, 11, group)
+        return _bf16_apply_tail(be, U, V, d, g, group, out)
+    _update_front(be, U, V, d, v, h, balance, group)
     be.update_sweep2_fused(U, V, d, v, h, g, step, tiny, update_U)
     _exchange(be, 13, group)
     be.fused_post(step, tiny, update_U)
-    if out is not None and backend is None:                # (the product backend; a placed state passes its arena's output region)
-        return be.fused_final(U, V, d, g, step, tiny, out=out)
-    return be.fused_final(U, V, d, g, step, tiny)
+    if backend is not None:                                # (the fp32 stage interface of a backend passed in has no out)
+        return be.fused_final(U, V, d, g, step, tiny)
+    return be.fused_final(U, V, d, g, step, tiny, out=out)
 
 
 # --------------------------------------------------------------------------- sparse LU (psgd.py:396-524), tail rows sharded
-class HipSpluStages:
+class HipSpluStages(_HipStageBase):
     """Stage functions of the C ABI on this rank's shard of the sparse-LU preconditioner: local tensors
     L12 = [L1; local rows of L2] ([r + n_local, r]), U12 = [U1, local columns of U2], local slices of l3 / u3, flat
     vectors [r corner entries (replicated); local slice of the tail].  Reduced buffers are views into the workspace."""
+    _region, _fold = staticmethod(_lib.splu_ws_region), "psgd_splu_fold_gathered_f64"
 
     def __init__(self, device, n_local_total, r):
-        self.device, self.N, self.r = device, int(n_local_total), int(r)
-        self.lib = _lib.load()
-        self.ws = _psgd._splu_workspace(device, self.N, self.r)
-        self._views = {}
-
-    def _w(self):
-        return self.ws.data_ptr(), self.ws.numel(), torch.cuda.current_stream(self.device).cuda_stream
-
-    def _view(self, which, stage, dtype, itemsize):
-        key = (which, stage)
-        if key not in self._views:
-            off, cnt = _lib.splu_ws_region(which, stage, self.N, self.r)
-            self._views[key] = self.ws[off:off + cnt * itemsize].view(dtype)
-        return self._views[key]
+        super().__init__(device, n_local_total, r, _psgd._splu_workspace)
 
     def sums(self, stage):
         return self._view(0, stage, torch.float64, 8)
 
     def maxbuf(self):
         return self._view(1, 3, torch.float32, 4)
-
-    def send(self, stage):
-        return self._view(_lib.PSGD_WS_SEND_F64, stage, torch.float64, 8)
-
-    def gather_buf(self, stage, world):
-        key = ("gather", stage, world)
-        if key not in self._views:
-            self._views[key] = torch.empty(world * self.send(stage).numel(), dtype=torch.float64, device=self.device)
-        return self._views[key]
-
-    def fold(self, stage, gathered, world):
-        wp, wn, st = self._w()
-        _lib.check(self.lib.psgd_splu_fold_gathered_f64(stage, gathered.data_ptr(), world, self.N, self.r, wp, wn, st),
-                   "splu fold_gathered")
 
     def stage1(self, U12, x):
         _lib.check(self.lib.psgd_splu_stage1_f32(U12.data_ptr(), x.data_ptr(), self.N, self.r, *self._w()), "splu stage1")
