@@ -21,6 +21,8 @@ PSGD_WS_SEND_F64 = 2
 UVD_MAX_RANK = 32
 UVD_TAIL_CHUNK = 4096    # PSGD_UVD_TAIL_CHUNK: elements per entry of the chunk table of the step-tail kernels
 UVD_SUMSQ_WS_BYTES = 8192
+UVD_TAIL_MAX_GRID = 2048                         # kMaxGrid of psgd_uvd_tail.hip: workgroups of pack / update; further chunks are grid-stride
+UVD_SUMSQ_PARTIALS = UVD_SUMSQ_WS_BYTES // 8     # kSumsqBlocks: workgroups (one fp64 partial each) of the sum of squares
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2     # PSGD_DTYPE_*
 SPLU_MAX_RANK = 64       # PSGD_SPLU_MAX_RANK: the native sparse-LU entry points (round 5)
 # psgd_kron_dd_route_flags bits (PSGD_KRON_ROUTE_* of include/psgd_hip.h)

@@ -206,12 +206,17 @@ __global__ __launch_bounds__(kT) void k_uvd_sumsq_fold(const double* __restrict_
 // ------------------------------------------------------------------------------------------------------------ parameter update
 // psgd.py:757-762 with the roundings of the torch expressions:  delta = T(fl32(lr_eff * pre_grad));  [delta = T(delta + v)];
 // p = T(p - delta).  No contraction: every product, sum and difference is rounded on its own.
-template <class T, bool kPre, bool kVs>
+// kOpaque (the scalar head and tail of a chunk): the product reaches the narrowing as a rounded fp32 value in a register.  Left to
+// itself hipcc selects v_fma_mixlo_f16 lr_eff, g, 0 for the float16 narrow(lr_eff * g) there, and the +0 addend turns a -0 product
+// into +0: a parameter -0 then stays -0 where the torch tail gives -0 - (-0) = +0.  (The 16-byte body converts with v_cvt_pk_f16_f32.)
+template <class T, bool kPre, bool kVs, bool kOpaque = false>
 __device__ __forceinline__ float update_one(float p, float g, float v, float lr_eff) {
   if constexpr (!kPre) {
     return p + v;                                     // p.add_(v) of the finite-difference branch (:723)
   } else {
-    float delta = T::widen(T::narrow(lr_eff * g));
+    float prod = lr_eff * g;
+    if constexpr (kOpaque) asm("" : "+v"(prod));
+    float delta = T::widen(T::narrow(prod));
     if constexpr (kVs) delta = T::widen(T::narrow(delta + v));
     return p - delta;
   }
@@ -227,8 +232,10 @@ __global__ __launch_bounds__(kT) void k_uvd_param_update(const Seg* __restrict__
   const int t = threadIdx.x;
   float lr_eff = lr;
   if (kPre && sumsq) {        // psgd.py:753-754, one rounding: lr_eff = fl32(lr * min(max_norm / (sqrt(sumsq) + tiny), 1))
+    // the minimum propagates NaN as tf.minimum and torch.clamp do: a NaN norm makes lr_eff, and with it every parameter, NaN
+    // (ratio < 1.0 alone is false for a NaN and would take the full unclipped step)
     const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
-    lr_eff = (float)((double)lr * (ratio < 1.0 ? ratio : 1.0));
+    lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
   }
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const Chunk ch = chunks[c];
@@ -243,7 +250,7 @@ __global__ __launch_bounds__(kT) void k_uvd_param_update(const Seg* __restrict__
     const int head = head_of(p, (int)sizeof(raw), n);
     const int nvec = (n - head) / E;
     if (t < head)
-      p[t] = T::narrow(update_one<T, kPre, kVs>(T::widen(p[t]), kPre ? g[t] : 0.f, kVs ? T::widen(v[t]) : 0.f, lr_eff));
+      p[t] = T::narrow(update_one<T, kPre, kVs, true>(T::widen(p[t]), kPre ? g[t] : 0.f, kVs ? T::widen(v[t]) : 0.f, lr_eff));
 #pragma unroll 2
     for (int q = t; q < nvec; q += kT) {
       const int i = head + q * E;
@@ -264,7 +271,7 @@ __global__ __launch_bounds__(kT) void k_uvd_param_update(const Seg* __restrict__
     }
     const int i = head + nvec * E + t;
     if (i < n)
-      p[i] = T::narrow(update_one<T, kPre, kVs>(T::widen(p[i]), kPre ? g[i] : 0.f, kVs ? T::widen(v[i]) : 0.f, lr_eff));
+      p[i] = T::narrow(update_one<T, kPre, kVs, true>(T::widen(p[i]), kPre ? g[i] : 0.f, kVs ? T::widen(v[i]) : 0.f, lr_eff));
   }
 }
 

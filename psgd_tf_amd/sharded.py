@@ -477,7 +477,8 @@ def _exchange(be, stage, group):
 
 def _wide_reduce(group):
     """Exchange of the wide-rank path (r > 32, uvd_wide.py): an all-reduce of one small stacked tensor per exchange point.
-    Every rank receives the same bits (the collective computes each element once and distributes it).  "summax" (the fused step's
+    Every rank receives the same bits (the collective computes each element once and distributes it).  "max": an all-gather and a
+    NaN-propagating fold in rank order (a NaN maximum on any rank reaches every rank).  "summax" (the fused step's
     second exchange: 4r sums and one maximum in one buffer): an all-gather and a fold in rank order on every rank."""
     def reduce(t, op):
         if op == "summax":
@@ -497,8 +498,22 @@ def _wide_reduce(group):
                 out[-1] = torch.maximum(out[-1], g2[k][-1])
             return out
         EXCHANGES["count"] += 1
-        dist.all_reduce(t, op=dist.ReduceOp.SUM if op == "sum" else dist.ReduceOp.MAX, group=group)
-        return t
+        if op == "sum":
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+            return t
+        # "max": a floating-point MAX all-reduce promises nothing about NaN (gloo's keeps the NaN of one operand and drops that of
+        # the other: one rank's state would turn NaN while the other's stays finite).  All-gather and fold in rank order with
+        # torch.maximum, which propagates NaN like tf.reduce_max: one collective, the same bits on every rank, signed operands
+        # (the sparse-LU diagonals) included.
+        world = dist.get_world_size(group)
+        t = t.contiguous()
+        gathered = torch.empty(world * t.numel(), dtype=t.dtype, device=t.device)
+        dist.all_gather_into_tensor(gathered, t.reshape(-1), group=group)
+        g2 = gathered.view(world, *t.shape)
+        out = g2[0].clone()
+        for k in range(1, world):
+            out = torch.maximum(out, g2[k])
+        return out
     return reduce
 
 

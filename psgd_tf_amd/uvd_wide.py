@@ -375,9 +375,10 @@ def update(U, V, d, v, h, step, tiny, balance, update_U, workspace_fn, reduce=_n
     K = torch.eye(R, **f64) + VU                                               # :575  (padded rows/columns: identity)
     s1 = Vt                                                                    # V't
     s2 = Ut + UU @ s1                                                          # U'Qh
-    x1 = torch.linalg.solve(K.t(), Uw)                                         # :577 (adjoint)
+    # solve_ex: no error check -- a NaN (or singular) K gives NaN / Inf, not an exception (the error convention), and nothing reads back
+    x1 = torch.linalg.solve_ex(K.t(), Uw)[0]                                   # :577 (adjoint)
     p2 = Vw - VV @ x1
-    x2 = torch.linalg.solve(K, p2)                                             # :578
+    x2 = torch.linalg.solve_ex(K, p2)[0]                                       # :578
     cs1 = VU @ s1
     aa = tt + 2 * (s1 @ Ut) + s1 @ (UU @ s1)
     bb = ww - 2 * (x1 @ Vw) + x1 @ (VV @ x1)

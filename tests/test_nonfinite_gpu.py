@@ -1,5 +1,17 @@
 """Error convention of the hot path (reference README.md:56): no exceptions, NaN/Inf propagate silently --
-and zero inputs give exact zeros.  Checked for every HIP entry point family."""
+and zero inputs give exact zeros.  Checked for every HIP entry point family; this file holds the first three rows:
+
+    UVd, r <= 32 (r = 10): apply, update, the NaN-propagating maxima     here; the balance branch at r = 10: test_nonfinite_families_gpu.py
+    sparse LU, r <= 32 (r = 7)                                           here
+    Kron (small, large and bf16-operand routes, its balance branch)      here
+    UVd ranks 33 .. 64 (whole-matrix kernels) and above (column chunks), N < r, the matrix-g apply, the balance branch,
+      the fused update -> apply; sparse LU ranks 33 .. 65                 test_nonfinite_families_gpu.py (masks against the oracle)
+    fold entry points of the row-sharded routes (fp32 UVd, sparse LU,
+      bf16 UVd), a NaN in one rank's slot                                test_nonfinite_families_gpu.py::test_fold_gathered
+    dense preconditioner                                                 test_dense_gpu.py::test_nan_propagates
+    bf16-state UVd kernels                                               test_uvd_bf16_gpu.py::test_nan_in_h_propagates
+    step-tail kernels (pack, sum of squares, parameter update, clip)     test_uvd_tail_gpu.py (special values, NaN clip norm)
+    row-sharded wide ranks, a NaN that one rank alone owns               test_sharded_cpu.py (gloo), test_sharded_2proc_gpu.py"""
 import numpy as np
 import pytest
 import torch

@@ -76,7 +76,16 @@ def _worker(rank, port, outdir, N, r, two_devices):
     pre1 = sharded.precond_grad_splu(*new, loc["g"])
     if sb is not None:
         red["splu_apply_s2"] = sb.sums(2).cpu().numpy().copy()
-    np.savez(os.path.join(outdir, "r%d.npz" % rank), U=t["U"].cpu().numpy(), V=t["V"].cpu().numpy(), d=t["d"].cpu().numpy(),
+    nan = {}
+    if r > _lib.UVD_MAX_RANK:
+        # a NaN in rows of U that rank 1 owns, balance branch (psgd.py:563-564): max|U| is NaN on rank 1 ONLY and must win the
+        # "max" exchange of the wide route on both ranks -- both factors and d entirely NaN everywhere, as in the unsharded oracle
+        b = {k: v.clone() for k, v in t.items()}
+        if rank == 1:
+            b["U"][b["U"].shape[0] // 2, 7] = float("nan")
+        sharded.update_precond_UVd_math_(b["U"], b["V"], b["d"], b["v"], b["h"], 0.01, TINY32, balance=True, update_U=True)
+        nan = {"nan_" + k: torch.isnan(b[k]).cpu().numpy() for k in ("U", "V", "d")}
+    np.savez(os.path.join(outdir, "r%d.npz" % rank), **nan, U=t["U"].cpu().numpy(), V=t["V"].cpu().numpy(), d=t["d"].cpu().numpy(),
              out=out.cpu().numpy(), outf=outf.cpu().numpy(), pre0=pre0.cpu().numpy(), pre1=pre1.cpu().numpy(),
              L12=new[0].cpu().numpy(), l3=new[1].cpu().numpy(), U12=new[2].cpu().numpy(), u3=new[3].cpu().numpy(),
              backend=np.array(dist.get_backend()), device=np.array(dev.index), fused_exchanges=np.array(fused_exchanges),
@@ -127,6 +136,18 @@ def test_two_processes_real_kernels_real_collectives(hip_lib, N, r, transport):
         assert rel_err(got[k], a[k].cpu().numpy()) < 1e-5, k
     assert rel_err(got["outf"], orc.precond_grad_UVd_math(q["U"], q["V"], q["d"], q["g"])) < 1e-5
     assert rel_err(got["outf"], outf.cpu().numpy()) < 1e-5
+    if r > 32:                     # the one-sided NaN of the balance branch: the oracle's mask is all NaN, on both ranks' rows
+        w = {k: v.astype(np.float64) for k, v in p.items()}
+        from psgd_tf_amd import sharded
+        lo1, hi1 = sharded.shard_rows(N, 1, WORLD)
+        w["U"][lo1 + (hi1 - lo1) // 2, 7] = np.nan
+        with np.errstate(invalid="ignore"):
+            orc.update_precond_UVd_math_(w["U"], w["V"], w["d"], w["v"], w["h"], 0.01, TINY32, balance=True, update_U=True)
+        for k in ("U", "V", "d"):
+            got_mask = np.concatenate([s["nan_" + k] for s in sh], 0)
+            assert np.array_equal(got_mask, np.isnan(w[k])), "%s: NaN on rank 0 %d of %d, on rank 1 %d of %d, oracle %d of %d" % (
+                k, sh[0]["nan_" + k].sum(), sh[0]["nan_" + k].size, sh[1]["nan_" + k].sum(), sh[1]["nan_" + k].size,
+                np.isnan(w[k]).sum(), w[k].size)
     # sparse LU: apply, update, apply with the updated factors
     n, rr = N // 4, (7 if r <= 32 else 40)
     s = make_splu_problem(n, rr, seed=5)

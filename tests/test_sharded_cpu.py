@@ -333,3 +333,107 @@ def test_sharded_uvd_class_equals_unsharded_oracle_and_counts_collectives():
     assert rel_err(got["p"], want_p) < 2e-5
     for k, ref in (("U", U), ("V", V), ("d", d)):
         assert rel_err(got[k], ref) < 2e-5, k
+
+
+# ----------------------------------------------------------------------------- wide ranks (r > 32): a NaN on ONE rank only
+WIDE_N, WIDE_R = 1003, 40
+
+
+class _TorchWideCtx:
+    """A torch double of uvd_wide._Ctx in its whole-matrix form (one "chunk"): what the HIP building blocks of ranks 33 .. 64
+    compute, on CPU tensors.  Under test is everything around them: the row-sharded sequence of uvd_wide.update and the
+    exchanges of sharded._wide_reduce over a real gloo group."""
+
+    def __init__(self, U, workspace_fn, full=False):
+        self.dev, (self.N, self.r) = U.device, U.shape
+        self.full, self.c, self.rc, self.views = True, 1, U.shape[1], True
+
+    def split(self, M, copy=False):
+        return [M]
+
+    def scatter(self, M, chunks):
+        pass
+
+    def colsums(self, M, xs):
+        return torch.stack([M.double().t() @ x.double() for x in xs])
+
+    def axpy(self, M, xs, S):
+        for x, s in zip(xs, S.to(torch.float32)):
+            x.add_(M @ s)
+
+    def rank2(self, M, a, b, c1, c2):
+        M.sub_(torch.outer(a, c1.to(torch.float32)) - torch.outer(b, c2.to(torch.float32)))
+
+    def gram_wide(self, U, V, d, v, h):
+        W = torch.cat([U, V, (d * h)[:, None], (v / d)[:, None]], 1).double()
+        return W.t() @ W
+
+
+WIDE_CASES = {                       # name -> (balance, what gets the NaN, its global row): rank 0 owns rows [0, 512)
+    "h_rank1": (False, "h", 700), "h_rank0": (False, "h", 100), "balance_U_rank1": (True, "U", 900)}
+
+
+def _wide_problem(case):
+    balance, key, row = WIDE_CASES[case]
+    p = make_uvd_problem(WIDE_N, WIDE_R, seed=41)
+    if key == "h":
+        p["h"][row] = np.nan
+    else:
+        p["U"][row, 7] = np.nan
+    return p, balance
+
+
+def _wide_worker(rank, world, port, outdir):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from psgd_tf_amd import sharded, uvd_wide
+        uvd_wide._Ctx = _TorchWideCtx
+        reduce = sharded._wide_reduce(None)
+        lo, hi = sharded.shard_rows(WIDE_N, rank, world)
+        res = {}
+        # the exchange on its own: a NaN maximum on one rank only must come out NaN on BOTH ranks (first and last operand)
+        for owner in range(world):
+            t = torch.tensor([3.0 + rank, float("nan") if rank == owner else 1.0 + rank, 0.5], dtype=torch.float32)
+            res["max_owner%d" % owner] = reduce(t, "max").numpy().copy()
+        for case in WIDE_CASES:
+            p, balance = _wide_problem(case)
+            t = {k: torch.from_numpy(p[k][lo:hi].copy()) for k in p}
+            assert bool(torch.isnan(t["h"]).any() or torch.isnan(t["U"]).any()) == ((rank == 1) == case.endswith("rank1"))
+            ex0 = sharded.EXCHANGES["count"]
+            uvd_wide.update(t["U"], t["V"], t["d"], t["v"], t["h"], 0.01, TINY, balance, True, None, reduce=reduce)
+            assert sharded.EXCHANGES["count"] - ex0 == 2 + int(balance)
+            for k in ("U", "V", "d"):
+                res["%s_%s" % (case, k)] = np.isnan(t[k].numpy())
+        np.savez(os.path.join(outdir, "wide%d.npz" % rank), lo=lo, hi=hi, **res)
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+def test_sharded_wide_rank_nan_on_one_rank_reaches_both():
+    """r = 40, two ranks over gloo: a NaN in rows that ONE rank owns.  The maxima of the wide route (max|U|, max|V| of the balance
+    branch, max|nablaD|) cross the ranks in sharded._wide_reduce(..., "max"); if the NaN lost there, one rank's state would turn
+    NaN and the other's stay finite.  Both ranks' NaN masks must be the unsharded oracle's, sliced to their rows.
+    (A NaN in h reaches both ranks' nablaD through the SUM exchange of the Gram already; on the balance branch the NaN maximum
+    exists on one rank only, and so it does in the bare exchange checked first.)"""
+    with tempfile.TemporaryDirectory() as outdir:
+        mp.spawn(_wide_worker, args=(WORLD, _free_port(), outdir), nprocs=WORLD, join=True)
+        sh = [dict(np.load(os.path.join(outdir, "wide%d.npz" % k))) for k in range(WORLD)]
+    for owner in range(WORLD):
+        for k in range(WORLD):
+            got = sh[k]["max_owner%d" % owner]
+            assert got[0] == 4.0 and got[2] == 0.5 and np.isnan(got[1]), (owner, k, got)
+    for case in WIDE_CASES:
+        p, balance = _wide_problem(case)
+        q = {k: v.astype(np.float64) for k, v in p.items()}
+        with np.errstate(invalid="ignore"):
+            orc.update_precond_UVd_math_(q["U"], q["V"], q["d"], q["v"], q["h"], 0.01, TINY, balance=balance, update_U=True)
+        assert np.isnan(q["d"]).all() and np.isnan(q["U"]).all()
+        for k in ("U", "V", "d"):
+            for s in sh:
+                want = np.isnan(q[k][int(s["lo"]):int(s["hi"])])
+                got = s["%s_%s" % (case, k)]
+                assert np.array_equal(got, want), "%s %s rows from %d: NaN in got %d, in the oracle %d of %d" % (
+                    case, k, int(s["lo"]), int(got.sum()), int(want.sum()), want.size)
