@@ -53,6 +53,8 @@ extern "C" {
  *     psgd_uvd_pack_f32, psgd_uvd_sumsq_f32 and psgd_uvd_param_update_multi, the tail of UVd.step (new symbols only: still 7).
  *     the stage forms of the bf16-state UVd calls, psgd_uvd_bf16_ws_region and psgd_uvd_bf16_fold_gathered_f64 (new symbols only: still 7).
  *     psgd_uvd_bf16_narrow_f32, the fp32 -> stored bf16 narrowing of a checkpoint load (new symbol only: still 7).
+ *     psgd_splu_bf16_workspace_bytes, psgd_splu_apply_bf16 and psgd_splu_update_bf16, the sparse-LU preconditioner on a bf16-stored
+ *     state (new symbols only, no existing layout changes: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -445,6 +447,24 @@ int psgd_splu_update_stage3_f32(const float *L12, const float *l3, const float *
 int psgd_splu_update_stage4_f32(const float *L12, const float *l3, const float *U12, const float *u3, const float *dx,
                                 const float *dg, float *L12_new, float *l3_new, float *U12_new, float *u3_new, int64_t N,
                                 int r, float step, float tiny, int has_tail, void *ws, int64_t ws_bytes, void *stream);
+
+/* ------------------------------------------------- sparse LU, bf16 state ---
+ * The same preconditioner with L12 ([N, r]), U12 ([r, N]), l3 and u3 ([N - r]) STORED as bf16 (psgd_splu_bf16.hip); dx, dg, g
+ * and out stay fp32.  Elements are widened when loaded and narrowed once when written; all arithmetic is fp64.
+ * 1 <= r <= PSGD_UVD_MAX_RANK (PSGD_ERR_RANK above), N >= r (N == r: no tail, l3 / u3 may be null).  The four state pointers
+ * (inputs and outputs) must be 16-byte aligned (PSGD_ERR_ALIGN).  The workspace (psgd_splu_bf16_workspace_bytes, 256-byte
+ * aligned, about 0.6 MiB whatever N) has a layout of its own.  Argument checks return before any HIP call.
+ * psgd_splu_update_bf16 is pure: the new factors go to the *_new buffers, which must not overlap the inputs or one another
+ * (PSGD_ERR_BAD_ARG).  The balance of psgd.py:411-417 rescales every element, so every element of the state is re-rounded
+ * by every update.  rounding: 0 = round to nearest even, 1 = stochastic, the stream keyed by (seed, tensor, flat element
+ * index) as in the bf16 UVd state, with tensor ids 8, 9, 10, 11 for L12, l3, U12, u3
+ * (psgd_uvd_bf16_rounding_key(seed, id) is the key of a stream).  NaN and Inf are stored as they are.                    */
+int64_t psgd_splu_bf16_workspace_bytes(int64_t N, int r);
+int psgd_splu_apply_bf16(const void *L12, const void *l3, const void *U12, const void *u3, const float *g, float *out,
+                         int64_t N, int r, void *ws, int64_t ws_bytes, void *stream);
+int psgd_splu_update_bf16(const void *L12, const void *l3, const void *U12, const void *u3, const float *dx,
+                          const float *dg, void *L12_new, void *l3_new, void *U12_new, void *u3_new, int64_t N, int r,
+                          float step, float tiny, int rounding, uint64_t seed, void *ws, int64_t ws_bytes, void *stream);
 
 /* ----------------------------------------------------------------- Kron ---
  * P = kron(Qr'Qr, Ql'Ql) with dense upper-triangular Ql [M,M], Qr [N,N]

@@ -133,6 +133,9 @@ SIGNATURES = {
     "psgd_splu_update_stage2_f32": (_int, [_c_f32p] * 6 + [_i64, _int, _c_ws, _i64, _strm]),
     "psgd_splu_update_stage3_f32": (_int, [_c_f32p] * 6 + [_i64, _int, _c_ws, _i64, _strm]),
     "psgd_splu_update_stage4_f32": (_int, [_c_f32p] * 10 + [_i64, _int, ctypes.c_float, ctypes.c_float, _int, _c_ws, _i64, _strm]),
+    "psgd_splu_bf16_workspace_bytes": (_i64, [_i64, _int]),
+    "psgd_splu_apply_bf16": (_int, [_c_f32p] * 6 + [_i64, _int, _c_ws, _i64, _strm]),
+    "psgd_splu_update_bf16": (_int, [_c_f32p] * 10 + [_i64, _int, _flt, _flt, _int, ctypes.c_uint64, _c_ws, _i64, _strm]),
     "psgd_kron_dd_workspace_bytes": (_i64, [_int, _int]),
     "psgd_kron_set_tuning": (_int, [_int, _int]),
     "psgd_kron_dd_workspace_bytes_batched": (_i64, [ctypes.POINTER(_int), ctypes.POINTER(_int), _int]),

@@ -9,7 +9,7 @@ hello_psgd.py:5) carry over with torch tensors in place of tf tensors:
     precond_grad_dense(Q, grads) -> list                               psgd.py:45
     update_precond_kron(Ql, Qr, dX, dG, step=0.01) -> (Ql, Qr)         psgd.py:72
     precond_grad_kron(Ql, Qr, Grad) -> Tensor                          psgd.py:116
-    update_precond_splu(L12, l3, U12, u3, dxs, dgs, step=0.01) -> 4    psgd.py:396
+    update_precond_splu(L12, l3, U12, u3, dxs, dgs, step=0.01) -> 4    psgd.py:396  (fp32 or bf16-stored factors)
     precond_grad_splu(L12, l3, U12, u3, grads) -> list                 psgd.py:483
     IpUVtmatvec(U, V, x)                                               psgd.py:540
     update_precond_UVd_math_(U, V, d, v, h, step, tiny) -> None        psgd.py:554  (in place)
@@ -382,13 +382,75 @@ def _splu_chunked(r):
     return r > _lib.SPLU_MAX_RANK or (r > _lib.UVD_MAX_RANK and os.environ.get("PSGD_SPLU_CHUNKS") == "1")
 
 
-def update_precond_splu(L12, l3, U12, u3, dxs, dgs, step=0.01):
-    """psgd.py:396-480: returns (L12_new, l3_new, U12_new, u3_new); inputs are not modified."""
+_SPLU_BF16_STATE = {"dtypes": (torch.bfloat16,) * 4,
+                    "dtype_msg": "with a bfloat16 state the vectors dx, dg, g stay float32"}
+
+
+def _splu_bf16_workspace(device, N, r):
+    """Cached workspace of the bf16-state sparse-LU kernels (psgd_splu_bf16_workspace_bytes: a layout of its own)."""
+    return _workspace(("splu_bf16",), device, "psgd_splu_bf16_workspace_bytes", N, r)
+
+
+def _splu_bf16_state(name, L12, l3, U12, u3):
+    """Classifies the sparse-LU state, as _bf16_state does for UVd: True for a bf16-stored one (psgd_splu_bf16.hip: all four
+    factors bfloat16, rank <= 32), False for anything the fp32 entry points judge; raises for a float16 or mixed state and for a
+    bfloat16 state of rank above 32 (the wider native kernels and the chunked route of splu_wide.py are fp32 only)."""
+    state = (L12, l3, U12, u3)
+    if not all(isinstance(t, torch.Tensor) for t in state):
+        return False
+    dts = {t.dtype for t in state}
+    if dts == {torch.float32} or not (dts & {torch.bfloat16, torch.float16}):
+        return False
+    if torch.float16 in dts:
+        raise TypeError("%s: a float16 state is not supported (the native narrow state is bfloat16 only)" % name)
+    if dts != {torch.bfloat16}:
+        raise TypeError("%s: mixed state dtypes %s; L12, l3, U12 and u3 must all be bfloat16 (or all float32)"
+                        % (name, sorted(str(x) for x in dts)))
+    if L12.dim() == 2 and L12.shape[1] > _lib.UVD_MAX_RANK:
+        raise ValueError("%s: a bfloat16 state supports ranks up to %d, got %d" % (name, _lib.UVD_MAX_RANK, L12.shape[1]))
+    return True
+
+
+def _unflatten(out, grads):
+    """psgd.py:518-522: the flat result as a list shaped like grads."""
+    pre_grads, idx = [], 0
+    for x in grads:
+        n = x.numel()
+        pre_grads.append(torch.reshape(out[idx:idx + n], x.shape))
+        idx += n
+    return pre_grads
+
+
+def update_precond_splu(L12, l3, U12, u3, dxs, dgs, step=0.01, *, rounding="nearest", rounding_seed=None):
+    """psgd.py:396-480: returns (L12_new, l3_new, U12_new, u3_new); inputs are not modified.
+
+    A bfloat16 L12, l3, U12, u3 (all four; fp32 dxs, dgs; r <= 32) is updated by the bf16-state kernels (psgd_splu_bf16.hip) and
+    four bfloat16 tensors come back: fp64 arithmetic on the widened codes, each written element narrowed once --
+    rounding="nearest" or "stochastic" (seeded by rounding_seed; None draws one from the module's branch generator).  The
+    balance of :411-417 rescales every element, so every element of the state is re-rounded by every call.  An fp32 state is
+    not rounded: any rounding other than the default, or a rounding_seed, raises ValueError there."""
+    name = "update_precond_splu"
     L12, l3, U12, u3 = _c(L12), _c(l3), _c(U12), _c(u3)
-    dev = _require_hip("update_precond_splu", L12, l3, U12, u3)
-    N, r = _splu_shapes("update_precond_splu", L12, l3, U12, u3)
-    dx, dg = _tall("update_precond_splu", dxs, N), _tall("update_precond_splu", dgs, N)
-    _require_hip("update_precond_splu", dx, dg, L12)
+    bf16 = _splu_bf16_state(name, L12, l3, U12, u3)
+    mode = _rounding_mode(name, bf16, rounding, rounding_seed)
+    dev = _require_hip(name, L12, l3, U12, u3, **(_SPLU_BF16_STATE if bf16 else _FP32_STATE))
+    N, r = _splu_shapes(name, L12, l3, U12, u3)
+    dx, dg = _tall(name, dxs, N), _tall(name, dgs, N)
+    _require_hip(name, dx, dg)
+    if dx.device != dev or dg.device != dev:
+        raise ValueError("%s: all tensors must be on one device" % name)
+    if bf16:
+        seed = 0 if rounding_seed is None else int(rounding_seed) & (2 ** 64 - 1)
+        if mode and rounding_seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (), generator=_branch_rng).item())
+        out = [torch.empty_like(t) for t in (L12, l3, U12, u3)]
+        ws = _splu_bf16_workspace(dev, N, r)
+        rc = _lib.load().psgd_splu_update_bf16(L12.data_ptr(), l3.data_ptr(), U12.data_ptr(), u3.data_ptr(), dx.data_ptr(),
+                                               dg.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                               out[3].data_ptr(), N, r, float(step), float(_tiny), mode, seed, ws.data_ptr(),
+                                               ws.numel(), _stream_ptr(dev))
+        _lib.check(rc, "psgd_splu_update_bf16")
+        return tuple(out)
     if _splu_chunked(r):                           # wide rank: column chunks of L2 and U2' (splu_wide.py)
         return _splu_wide.update(L12, l3, U12, u3, dx, dg, float(step), float(_tiny), uvd_workspace)
     out = [torch.empty_like(t) for t in (L12, l3, U12, u3)]
@@ -402,31 +464,26 @@ def update_precond_splu(L12, l3, U12, u3, dxs, dgs, step=0.01):
 
 
 def precond_grad_splu(L12, l3, U12, u3, grads):
-    """psgd.py:483-524: list of gradients in, list of preconditioned gradients (same shapes) out."""
+    """psgd.py:483-524: list of gradients in, list of preconditioned gradients (same shapes) out.
+    A bfloat16 L12, l3, U12, u3 (all four, r <= 32; psgd_splu_bf16.hip): fp32 gradients in, fp32 preconditioned gradients out."""
+    name = "precond_grad_splu"
     L12, l3, U12, u3 = _c(L12), _c(l3), _c(U12), _c(u3)
-    dev = _require_hip("precond_grad_splu", L12, l3, U12, u3)
-    N, r = _splu_shapes("precond_grad_splu", L12, l3, U12, u3)
-    g = _tall("precond_grad_splu", grads, N)
-    _require_hip("precond_grad_splu", g, L12)
-    if _splu_chunked(r):
-        out = _splu_wide.precond_grad(L12, l3, U12, u3, g, uvd_workspace)
-        pre_grads, idx = [], 0
-        for x in grads:
-            n = x.numel()
-            pre_grads.append(torch.reshape(out[idx:idx + n], x.shape))
-            idx += n
-        return pre_grads
+    bf16 = _splu_bf16_state(name, L12, l3, U12, u3)
+    dev = _require_hip(name, L12, l3, U12, u3, **(_SPLU_BF16_STATE if bf16 else _FP32_STATE))
+    N, r = _splu_shapes(name, L12, l3, U12, u3)
+    g = _tall(name, grads, N)
+    _require_hip(name, g)
+    if g.device != dev:
+        raise ValueError("%s: all tensors must be on one device" % name)
+    if not bf16 and _splu_chunked(r):
+        return _unflatten(_splu_wide.precond_grad(L12, l3, U12, u3, g, uvd_workspace), grads)
     out = torch.empty_like(g)
-    ws = _splu_workspace(dev, N, r)
-    rc = _lib.load().psgd_splu_apply_f32(L12.data_ptr(), l3.data_ptr(), U12.data_ptr(), u3.data_ptr(), g.data_ptr(),
-                                         out.data_ptr(), N, r, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "psgd_splu_apply_f32")
-    pre_grads, idx = [], 0                                                       # :518-522
-    for x in grads:
-        n = x.numel()
-        pre_grads.append(torch.reshape(out[idx:idx + n], x.shape))
-        idx += n
-    return pre_grads
+    ws = (_splu_bf16_workspace if bf16 else _splu_workspace)(dev, N, r)
+    fn = "psgd_splu_apply_bf16" if bf16 else "psgd_splu_apply_f32"
+    rc = getattr(_lib.load(), fn)(L12.data_ptr(), l3.data_ptr(), U12.data_ptr(), u3.data_ptr(), g.data_ptr(), out.data_ptr(),
+                                  N, r, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    _lib.check(rc, fn)
+    return _unflatten(out, grads)
 
 
 # --------------------------------------------------------------------------- UVd math

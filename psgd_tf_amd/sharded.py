@@ -744,6 +744,14 @@ def _splu_backend_for(L12):
     return _splu_backends[key]
 
 
+def _refuse_bf16_splu(name, L12, l3, U12, u3):
+    """Row sharding of a bf16-stored sparse-LU state does not exist: the state is classified as the single-GPU calls classify it
+    (a float16 or mixed state raises TypeError there) and a bfloat16 one is refused before anything is launched."""
+    if _psgd._splu_bf16_state(name, L12, l3, U12, u3):
+        raise ValueError("%s: a bfloat16 sparse-LU state is not row-sharded (single-GPU update_precond_splu / precond_grad_splu "
+                         "only); shard an fp32 state" % name)
+
+
 def _splu_is_wide(L12, backend):
     return backend is None and L12.dim() == 2 and L12.shape[1] > _lib.SPLU_MAX_RANK
 
@@ -752,6 +760,7 @@ def precond_grad_splu(L12, l3, U12, u3, grad, group=None, backend=None):
     """Sharded psgd.py:483-524.  `grad` is this rank's flat vector [r corner entries; local tail slice]; returns the
     same layout (corner entries identical on every rank).  2 exchanges (r sums; 2r sums of which r are used).  Ranks above 32
     (the reference has no limit, psgd.py:420) run on column chunks (splu_wide.py) with an all-reduce per exchange."""
+    _refuse_bf16_splu("sharded precond_grad_splu", L12, l3, U12, u3)
     if _splu_is_wide(L12, backend):
         _psgd._require_hip("sharded precond_grad_splu", L12, l3, U12, u3, grad)
         return _splu_wide.precond_grad(L12, l3, U12, u3, grad.reshape(-1), _psgd.uvd_workspace,
@@ -768,6 +777,7 @@ def update_precond_splu(L12, l3, U12, u3, dx, dg, step=0.01, tiny=None, has_tail
     """Sharded psgd.py:396-480 on this rank's rows; returns this rank's (L12, l3, U12, u3) (corner blocks identical on
     every rank).  3 exchanges: r sums, 2r sums, [r sums | 4 maxima].  has_tail: the global problem has tail rows."""
     tiny = _psgd._tiny if tiny is None else tiny
+    _refuse_bf16_splu("sharded update_precond_splu", L12, l3, U12, u3)
     if _splu_is_wide(L12, backend):
         _psgd._require_hip("sharded update_precond_splu", L12, l3, U12, u3, dx, dg)
         return _splu_wide.update(L12, l3, U12, u3, dx.reshape(-1), dg.reshape(-1), float(step), float(tiny), _psgd.uvd_workspace,
