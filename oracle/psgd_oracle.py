@@ -7,15 +7,19 @@ never imported by the product package (``psgd_tf_amd``).  Only ``tests/``,
 ``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of ``bench.py`` may
 import it.
 
-PARITY UNPINNED: the reference is Python-on-TensorFlow, TensorFlow is not
-installable in the build container, and the reference ships no tests, golden
-vectors or fixtures.  What pins this restatement instead:
+PARITY: the reference is Python-on-TensorFlow, TensorFlow is not installable
+where this is built, and the reference ships no tests, golden vectors or
+fixtures.  What pins this restatement:
+  * the reference's own program text, run unmodified on oracle/tf_standin (a
+    stand-in for the tf.* names it touches) in fp32 and fp64; its outputs are
+    the fixtures of tests/golden/tf/, which tests/test_golden.py holds the fp64
+    run of this file to (1e-12 or better);
   * analytic known-answer tests derived from the source alone
     (tests/test_oracle_kat.py: identity, fixed point, Woodbury inverse,
     Rosenbrock first step, dispatcher table, triangularity ...);
   * cross-checks against independent dense linear algebra in fp64.
-These pin the *mathematical specification as read from source*, not
-TensorFlow's rounding.
+These pin the reference's formulas, op order and branch logic, not the
+rounding of TensorFlow's kernels (which have not been run).
 
 Conventions
   * Every function works in the dtype of its inputs (fp32 or fp64) and keeps
