@@ -55,6 +55,8 @@ extern "C" {
  *     psgd_uvd_bf16_narrow_f32, the fp32 -> stored bf16 narrowing of a checkpoint load (new symbol only: still 7).
  *     psgd_splu_bf16_workspace_bytes, psgd_splu_apply_bf16 and psgd_splu_update_bf16, the sparse-LU preconditioner on a bf16-stored
  *     state (new symbols only, no existing layout changes: still 7).
+ *     psgd_uvd_pack_blend_f32 and psgd_uvd_param_update_multi_wd, momentum and decoupled weight decay in the tail of UVd.step
+ *     (new symbols only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -366,6 +368,14 @@ int psgd_uvd_apply_sweep3_bf16(const void *V, const void *d, float *out, int64_t
 int psgd_uvd_pack_f32(const void *segs, int k, const void *chunks, int64_t nchunks, int dtype, float scale, float *out,
                       void *stream);
 
+/* The same pack BLENDED into out (the momentum buffer of class UVd): x = fl32(float(tensor[i]) * scale), then
+ *     out[start + i] = fl32(fl32(beta * out[start + i]) + fl32(omb * x)),
+ * every operation rounded on its own.  beta and omb are separate arguments: the caller passes omb = float(1) - beta, rounded once
+ * on the host.  beta == 0 does NOT read out: out[start + i] = fl32(omb * x), whatever out held (with omb == 1 the bits of
+ * psgd_uvd_pack_f32).  Same tables, dtypes and argument checks as psgd_uvd_pack_f32.                                             */
+int psgd_uvd_pack_blend_f32(const void *segs, int k, const void *chunks, int64_t nchunks, int dtype, float scale, float beta,
+                            float omb, float *out, void *stream);
+
 /* out[0] = sum_i fl32(x[i] * x[i]), summed in fp64 in a fixed order (the square of the clip norm of psgd.py:753): two launches,
  * no floating-point atomics, the same bits on every call.  N >= 0; x 4-byte aligned.                                             */
 int psgd_uvd_sumsq_f32(const float *x, int64_t N, double *out, void *ws, int64_t ws_bytes, void *stream);
@@ -378,6 +388,15 @@ int psgd_uvd_sumsq_f32(const float *x, int64_t N, double *out, void *ws, int64_t
  * vs_segs: the segment table of the vs tensors (same sizes and dtype as the parameters), or NULL.                              */
 int psgd_uvd_param_update_multi(const void *param_segs, const void *vs_segs, int k, const void *chunks, int64_t nchunks, int dtype,
                                 const float *pre_grad, float lr, const double *sumsq, float max_norm, float tiny, void *stream);
+
+/* psgd_uvd_param_update_multi with decoupled weight decay, in the parameters' type: with c = fl32(lr_eff * wd),
+ *     delta = T(fl32(lr_eff * pre_grad[start + i]));   vs_segs given: delta = T(delta + v[i]);
+ *     wd != 0: delta = T(delta + T(fl32(c * float(p[i]))));   p[i] = T(p[i] - delta).
+ * wd == 0 takes no extra rounding step: the bits of psgd_uvd_param_update_multi (which forwards here).  pre_grad == NULL with
+ * wd != 0 is PSGD_ERR_BAD_ARG.                                                                                                  */
+int psgd_uvd_param_update_multi_wd(const void *param_segs, const void *vs_segs, int k, const void *chunks, int64_t nchunks, int dtype,
+                                   const float *pre_grad, float lr, const double *sumsq, float max_norm, float tiny, float wd,
+                                   void *stream);
 
 /* Tuning knobs for experiments (not part of the stable ABI).
  * key 0: streaming policy (0 = automatic: non-temporal when U,V exceed the Infinity Cache,

@@ -121,8 +121,11 @@ SIGNATURES = {
     "psgd_uvd_apply_sweep2_bf16": (_int, [_c_f32p] * 4 + [_i64, _int, _c_ws, _i64, _strm]),
     "psgd_uvd_apply_sweep3_bf16": (_int, [_c_f32p] * 3 + [_i64, _int, _c_ws, _i64, _strm]),
     "psgd_uvd_pack_f32": (_int, [_c_f32p, _int, _c_f32p, _i64, _int, _flt, _c_f32p, _strm]),
+    "psgd_uvd_pack_blend_f32": (_int, [_c_f32p, _int, _c_f32p, _i64, _int, _flt, _flt, _flt, _c_f32p, _strm]),
     "psgd_uvd_sumsq_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_ws, _i64, _strm]),
     "psgd_uvd_param_update_multi": (_int, [_c_f32p, _c_f32p, _int, _c_f32p, _i64, _int, _c_f32p, _flt, _c_f32p, _flt, _flt, _strm]),
+    "psgd_uvd_param_update_multi_wd": (_int, [_c_f32p, _c_f32p, _int, _c_f32p, _i64, _int, _c_f32p, _flt, _c_f32p, _flt, _flt, _flt,
+                                       _strm]),
     "psgd_splu_workspace_bytes": (_i64, [_i64, _int]),
     "psgd_splu_apply_f32": (_int, [_c_f32p] * 6 + [_i64, _int, _c_ws, _i64, _strm]),
     "psgd_splu_update_f32": (_int, [_c_f32p] * 10 + [_i64, _int, ctypes.c_float, ctypes.c_float, _c_ws, _i64, _strm]),

@@ -1,8 +1,10 @@
 // psgd_uvd_tail.hip -- the tail of UVd.step (psgd.py:729-730, :747, :750-762) on gfx950, whatever the number of parameter tensors.
 //
 //   psgd_uvd_pack_f32            k tensors of one dtype (fp32 / bf16 / fp16) -> one flat fp32 vector, times a scale      (:729-736, :747)
+//   psgd_uvd_pack_blend_f32      the same pack blended into the flat vector: out <- fl32(fl32(beta out) + fl32(omb x))  (momentum of class UVd)
 //   psgd_uvd_sumsq_f32           sum x^2 of a flat fp32 vector -> one device double (the clip norm's square)              (:753)
 //   psgd_uvd_param_update_multi  p <- T(p - [T(T(fl32(lr_eff pre_grad)) + v)])  for every element of every parameter      (:757-762)
+//   psgd_uvd_param_update_multi_wd  ... with decoupled weight decay: delta <- T(delta + T(fl32(fl32(lr_eff wd) p)))
 //
 // The work of pack and update is described by two device tables.  A SEGMENT is one tensor: {pointer, start offset in the flat vector,
 // element count}.  A CHUNK is one piece of at most kChunk consecutive elements of one segment: {segment index, offset inside it}; the
@@ -129,9 +131,22 @@ __device__ __forceinline__ int head_of(const void* p, int bytes, int n) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------- pack
-template <class T>
+// kBlend (psgd_uvd_pack_blend_f32): x = fl32(widen(t) * scale) as in the plain pack, then out = fl32(fl32(beta * out) + fl32(omb * x)),
+// every operation rounded on its own.  kBlend && !kRead (beta == 0): out = fl32(omb * x), the flat vector is NOT read -- whatever
+// it held (NaN of a fresh allocation included) is gone after the first step.
+template <bool kBlend, bool kRead>
+__device__ __forceinline__ float pack_one(float x, float old, float scale, float beta, float omb) {
+  x = x * scale;
+  if constexpr (!kBlend) return x;
+  const float nx = omb * x;
+  if constexpr (!kRead) return nx;
+  const float bo = beta * old;
+  return bo + nx;
+}
+
+template <class T, bool kBlend = false, bool kRead = false>
 __global__ __launch_bounds__(kT) void k_uvd_pack(const Seg* __restrict__ segs, const Chunk* __restrict__ chunks, int64_t nchunks,
-                                                 int k, float scale, float* __restrict__ out) {
+                                                 int k, float scale, float beta, float omb, float* __restrict__ out) {
   using raw = typename T::raw;
   constexpr int E = T::E;
   const int t = threadIdx.x;
@@ -146,14 +161,22 @@ __global__ __launch_bounds__(kT) void k_uvd_pack(const Seg* __restrict__ segs, c
     float* dst = out + s.start + ch.off;
     const int head = head_of(dst, 4, n);
     const int nvec = (n - head) / E;
-    if (t < head) dst[t] = T::widen(src[t]) * scale;
+    if (t < head) dst[t] = pack_one<kBlend, kRead>(T::widen(src[t]), kRead ? dst[t] : 0.f, scale, beta, omb);
 #pragma unroll 2
     for (int g = t; g < nvec; g += kT) {
       const int i = head + g * E;
-      float x[E];
+      float x[E], o[E];
       load_any<T>(src + i, x);
+      if constexpr (kRead) {
 #pragma unroll
-      for (int e = 0; e < E; ++e) x[e] = x[e] * scale;
+        for (int q = 0; q < E / 4; ++q) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(dst + i + 4 * q);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[4 * q + e] = v[e];
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < E; ++e) x[e] = pack_one<kBlend, kRead>(x[e], kRead ? o[e] : 0.f, scale, beta, omb);
 #pragma unroll
       for (int q = 0; q < E / 4; ++q) {
         f32x4 v = {x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]};
@@ -161,7 +184,7 @@ __global__ __launch_bounds__(kT) void k_uvd_pack(const Seg* __restrict__ segs, c
       }
     }
     const int i = head + nvec * E + t;
-    if (i < n) dst[i] = T::widen(src[i]) * scale;
+    if (i < n) dst[i] = pack_one<kBlend, kRead>(T::widen(src[i]), kRead ? dst[i] : 0.f, scale, beta, omb);
   }
 }
 
@@ -209,8 +232,11 @@ __global__ __launch_bounds__(kT) void k_uvd_sumsq_fold(const double* __restrict_
 // kOpaque (the scalar head and tail of a chunk): the product reaches the narrowing as a rounded fp32 value in a register.  Left to
 // itself hipcc selects v_fma_mixlo_f16 lr_eff, g, 0 for the float16 narrow(lr_eff * g) there, and the +0 addend turns a -0 product
 // into +0: a parameter -0 then stays -0 where the torch tail gives -0 - (-0) = +0.  (The 16-byte body converts with v_cvt_pk_f16_f32.)
-template <class T, bool kPre, bool kVs, bool kOpaque = false>
-__device__ __forceinline__ float update_one(float p, float g, float v, float lr_eff) {
+// kWd (decoupled weight decay, psgd_uvd_param_update_multi_wd with wd != 0): after v, delta = T(delta + T(fl32(c * p))) with
+// c = fl32(lr_eff * wd).  Its product is opaque where the first one is, for the same reason (the sign of a -0 term); in the 16-byte
+// body an asm statement would also keep the loop from being unrolled (checked in the ISA: no v_fma_mix* in any instantiation).
+template <class T, bool kPre, bool kVs, bool kWd, bool kOpaque = false>
+__device__ __forceinline__ float update_one(float p, float g, float v, float lr_eff, float c) {
   if constexpr (!kPre) {
     return p + v;                                     // p.add_(v) of the finite-difference branch (:723)
   } else {
@@ -218,15 +244,20 @@ __device__ __forceinline__ float update_one(float p, float g, float v, float lr_
     if constexpr (kOpaque) asm("" : "+v"(prod));
     float delta = T::widen(T::narrow(prod));
     if constexpr (kVs) delta = T::widen(T::narrow(delta + v));
+    if constexpr (kWd) {
+      float dec = c * p;
+      if constexpr (kOpaque) asm("" : "+v"(dec));
+      delta = T::widen(T::narrow(delta + T::widen(T::narrow(dec))));
+    }
     return p - delta;
   }
 }
 
-template <class T, bool kPre, bool kVs>
+template <class T, bool kPre, bool kVs, bool kWd = false>
 __global__ __launch_bounds__(kT) void k_uvd_param_update(const Seg* __restrict__ psegs, const Seg* __restrict__ vsegs,
                                                          const Chunk* __restrict__ chunks, int64_t nchunks, int k,
                                                          const float* __restrict__ pre_grad, float lr, const double* __restrict__ sumsq,
-                                                         float max_norm, float tiny) {
+                                                         float max_norm, float tiny, float wd) {
   using raw = typename T::raw;
   constexpr int E = T::E;
   const int t = threadIdx.x;
@@ -237,6 +268,7 @@ __global__ __launch_bounds__(kT) void k_uvd_param_update(const Seg* __restrict__
     const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
     lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
   }
+  const float dc = kWd ? lr_eff * wd : 0.f;      // fl32(lr_eff * wd): one rounding, the same whether lr_eff was clipped or not
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const Chunk ch = chunks[c];
     if ((uint64_t)ch.seg >= (uint64_t)k) continue;
@@ -250,7 +282,7 @@ __global__ __launch_bounds__(kT) void k_uvd_param_update(const Seg* __restrict__
     const int head = head_of(p, (int)sizeof(raw), n);
     const int nvec = (n - head) / E;
     if (t < head)
-      p[t] = T::narrow(update_one<T, kPre, kVs, true>(T::widen(p[t]), kPre ? g[t] : 0.f, kVs ? T::widen(v[t]) : 0.f, lr_eff));
+      p[t] = T::narrow(update_one<T, kPre, kVs, kWd, true>(T::widen(p[t]), kPre ? g[t] : 0.f, kVs ? T::widen(v[t]) : 0.f, lr_eff, dc));
 #pragma unroll 2
     for (int q = t; q < nvec; q += kT) {
       const int i = head + q * E;
@@ -266,12 +298,12 @@ __global__ __launch_bounds__(kT) void k_uvd_param_update(const Seg* __restrict__
       }
       if constexpr (kVs) load_any<T>(v + i, vv);
 #pragma unroll
-      for (int e = 0; e < E; ++e) x[e] = update_one<T, kPre, kVs>(x[e], kPre ? gg[e] : 0.f, kVs ? vv[e] : 0.f, lr_eff);
+      for (int e = 0; e < E; ++e) x[e] = update_one<T, kPre, kVs, kWd>(x[e], kPre ? gg[e] : 0.f, kVs ? vv[e] : 0.f, lr_eff, dc);
       store_16<T>(p + i, x);
     }
     const int i = head + nvec * E + t;
     if (i < n)
-      p[i] = T::narrow(update_one<T, kPre, kVs, true>(T::widen(p[i]), kPre ? g[i] : 0.f, kVs ? T::widen(v[i]) : 0.f, lr_eff));
+      p[i] = T::narrow(update_one<T, kPre, kVs, kWd, true>(T::widen(p[i]), kPre ? g[i] : 0.f, kVs ? T::widen(v[i]) : 0.f, lr_eff, dc));
   }
 }
 
@@ -279,18 +311,54 @@ static int grid_for(int64_t nchunks) { return (int)(nchunks < kMaxGrid ? nchunks
 static bool bad_dtype(int dtype) { return dtype < PSGD_DTYPE_F32 || dtype > PSGD_DTYPE_F16; }
 static int launched() { return hipGetLastError() == hipSuccess ? PSGD_OK : PSGD_ERR_LAUNCH; }
 
+template <class T, bool kPre, bool kVs, bool kWd, class... A>
+static void launch_update_as(int grid, hipStream_t st, A... a) {
+  hipLaunchKernelGGL((k_uvd_param_update<T, kPre, kVs, kWd>), dim3(grid), dim3(kT), 0, st, a...);
+}
+
 template <class T>
 static void launch_update(bool pre, bool vs, int grid, hipStream_t st, const Seg* ps, const Seg* vsg, const Chunk* ch, int64_t nchunks,
-                          int k, const float* pre_grad, float lr, const double* sumsq, float max_norm, float tiny) {
+                          int k, const float* pre_grad, float lr, const double* sumsq, float max_norm, float tiny, float wd) {
+  const bool dec = wd != 0.f;                         // wd == 0 runs the kernels without the decay term: no extra rounding step
   if (!pre)
-    hipLaunchKernelGGL((k_uvd_param_update<T, false, true>), dim3(grid), dim3(kT), 0, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq,
-                       max_norm, tiny);
+    launch_update_as<T, false, true, false>(grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny, wd);
+  else if (vs && dec)
+    launch_update_as<T, true, true, true>(grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny, wd);
   else if (vs)
-    hipLaunchKernelGGL((k_uvd_param_update<T, true, true>), dim3(grid), dim3(kT), 0, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq,
-                       max_norm, tiny);
+    launch_update_as<T, true, true, false>(grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny, wd);
+  else if (dec)
+    launch_update_as<T, true, false, true>(grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny, wd);
   else
-    hipLaunchKernelGGL((k_uvd_param_update<T, true, false>), dim3(grid), dim3(kT), 0, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq,
-                       max_norm, tiny);
+    launch_update_as<T, true, false, false>(grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny, wd);
+}
+
+template <class T>
+static void launch_pack(int mode, int grid, hipStream_t st, const Seg* sg, const Chunk* ch, int64_t nchunks, int k, float scale,
+                        float beta, float omb, float* out) {
+  if (mode == 0)
+    hipLaunchKernelGGL((k_uvd_pack<T, false, false>), dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, beta, omb, out);
+  else if (mode == 1)
+    hipLaunchKernelGGL((k_uvd_pack<T, true, false>), dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, beta, omb, out);
+  else
+    hipLaunchKernelGGL((k_uvd_pack<T, true, true>), dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, beta, omb, out);
+}
+
+// mode 0: the plain pack; 1: blend with beta == 0 (out is not read); 2: blend
+static int pack_entry(int mode, const void* segs, int k, const void* chunks, int64_t nchunks, int dtype, float scale, float beta,
+                      float omb, float* out, void* stream) {
+  if (!segs || !chunks || !out || k < 0 || nchunks < 0 || bad_dtype(dtype)) return PSGD_ERR_BAD_ARG;
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const Seg* sg = (const Seg*)segs;
+  const Chunk* ch = (const Chunk*)chunks;
+  const int grid = grid_for(nchunks);
+  if (dtype == PSGD_DTYPE_F32)
+    launch_pack<F32>(mode, grid, st, sg, ch, nchunks, k, scale, beta, omb, out);
+  else if (dtype == PSGD_DTYPE_BF16)
+    launch_pack<BF16>(mode, grid, st, sg, ch, nchunks, k, scale, beta, omb, out);
+  else
+    launch_pack<F16>(mode, grid, st, sg, ch, nchunks, k, scale, beta, omb, out);
+  return launched();
 }
 
 }  // namespace psgdt
@@ -301,19 +369,12 @@ extern "C" {
 
 int psgd_uvd_pack_f32(const void* segs, int k, const void* chunks, int64_t nchunks, int dtype, float scale, float* out,
                       void* stream) {
-  if (!segs || !chunks || !out || k < 0 || nchunks < 0 || bad_dtype(dtype)) return PSGD_ERR_BAD_ARG;
-  if (nchunks == 0) return PSGD_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const Seg* sg = (const Seg*)segs;
-  const Chunk* ch = (const Chunk*)chunks;
-  const int grid = grid_for(nchunks);
-  if (dtype == PSGD_DTYPE_F32)
-    hipLaunchKernelGGL(k_uvd_pack<F32>, dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, out);
-  else if (dtype == PSGD_DTYPE_BF16)
-    hipLaunchKernelGGL(k_uvd_pack<BF16>, dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, out);
-  else
-    hipLaunchKernelGGL(k_uvd_pack<F16>, dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, out);
-  return launched();
+  return pack_entry(0, segs, k, chunks, nchunks, dtype, scale, 0.f, 1.f, out, stream);
+}
+
+int psgd_uvd_pack_blend_f32(const void* segs, int k, const void* chunks, int64_t nchunks, int dtype, float scale, float beta,
+                            float omb, float* out, void* stream) {
+  return pack_entry(beta == 0.f ? 1 : 2, segs, k, chunks, nchunks, dtype, scale, beta, omb, out, stream);
 }
 
 int psgd_uvd_sumsq_f32(const float* x, int64_t N, double* out, void* ws, int64_t ws_bytes, void* stream) {
@@ -327,10 +388,12 @@ int psgd_uvd_sumsq_f32(const float* x, int64_t N, double* out, void* ws, int64_t
   return launched();
 }
 
-int psgd_uvd_param_update_multi(const void* param_segs, const void* vs_segs, int k, const void* chunks, int64_t nchunks, int dtype,
-                                const float* pre_grad, float lr, const double* sumsq, float max_norm, float tiny, void* stream) {
+int psgd_uvd_param_update_multi_wd(const void* param_segs, const void* vs_segs, int k, const void* chunks, int64_t nchunks, int dtype,
+                                   const float* pre_grad, float lr, const double* sumsq, float max_norm, float tiny, float wd,
+                                   void* stream) {
   if (!param_segs || !chunks || k < 0 || nchunks < 0 || bad_dtype(dtype)) return PSGD_ERR_BAD_ARG;
   if (!pre_grad && (!vs_segs || sumsq)) return PSGD_ERR_BAD_ARG;            // nothing to do, or a clip norm without a gradient
+  if (!pre_grad && wd != 0.f) return PSGD_ERR_BAD_ARG;                      // the perturbation of :723 decays nothing
   if (nchunks == 0) return PSGD_OK;
   hipStream_t st = (hipStream_t)stream;
   const Seg* ps = (const Seg*)param_segs;
@@ -339,12 +402,18 @@ int psgd_uvd_param_update_multi(const void* param_segs, const void* vs_segs, int
   const int grid = grid_for(nchunks);
   const bool pre = pre_grad != nullptr, vs = vs_segs != nullptr;
   if (dtype == PSGD_DTYPE_F32)
-    launch_update<F32>(pre, vs, grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny);
+    launch_update<F32>(pre, vs, grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny, wd);
   else if (dtype == PSGD_DTYPE_BF16)
-    launch_update<BF16>(pre, vs, grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny);
+    launch_update<BF16>(pre, vs, grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny, wd);
   else
-    launch_update<F16>(pre, vs, grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny);
+    launch_update<F16>(pre, vs, grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny, wd);
   return launched();
+}
+
+int psgd_uvd_param_update_multi(const void* param_segs, const void* vs_segs, int k, const void* chunks, int64_t nchunks, int dtype,
+                                const float* pre_grad, float lr, const double* sumsq, float max_norm, float tiny, void* stream) {
+  return psgd_uvd_param_update_multi_wd(param_segs, vs_segs, k, chunks, nchunks, dtype, pre_grad, lr, sumsq, max_norm, tiny, 0.f,
+                                        stream);
 }
 
 }  // extern "C"

@@ -776,6 +776,38 @@ def uvd_pack(tensors, out, scale=1.0, *, plan=None, role="pack"):
     return out.view(-1)[:plan.total]
 
 
+def uvd_momentum_coefficients(k, momentum):
+    """(beta_k, 1 - beta_k) of step k (counted from 0) as Python floats that hold float32 values: beta_k = float32(min(k / (k + 1),
+    momentum)), the warm-up of the PyTorch PSGD optimizers (the first step has beta = 0), and float32(1) - beta_k rounded once --
+    the pair every tail of class UVd and the kernel receive, so that host and device cannot disagree"""
+    import numpy as np
+    beta = np.float32(min(k / (k + 1.0), float(momentum)))
+    return float(beta), float(np.float32(1.0) - beta)
+
+
+def uvd_pack_blend(tensors, out, beta, scale=1.0, *, plan=None, role="pack"):
+    """uvd_pack BLENDED into out, the momentum buffer, in ONE launch: with x = torch.cat([...]).float() * scale,
+        out[:n] = beta * out[:n] + (float32(1) - float32(beta)) * x
+    every product and the sum rounded to float32 on its own (out.mul_(beta); out.add_(x.mul(1 - beta)) in torch).  beta == 0 does
+    not read out: whatever it held, NaN included, is replaced by x.  Arguments as uvd_pack; 0 <= beta < 1."""
+    import numpy as np
+    tensors = list(tensors)
+    beta = float(np.float32(beta))
+    if not 0.0 <= beta < 1.0:
+        raise ValueError("uvd_pack_blend: beta must be in [0, 1), got %r" % (beta,))
+    omb = float(np.float32(1.0) - np.float32(beta))
+    plan = plan if plan is not None else _tail_plan(tensors, "uvd_pack_blend")
+    dev = _require_hip("uvd_pack_blend", out)
+    if out.numel() < plan.total:
+        raise ValueError("uvd_pack_blend: out has %d elements, the tensors have %d" % (out.numel(), plan.total))
+    segs = plan.table(role, tensors, "uvd_pack_blend")
+    if plan.nchunks:
+        rc = _lib.load().psgd_uvd_pack_blend_f32(segs, len(tensors), plan.chunks.data_ptr(), plan.nchunks, plan.code, float(scale),
+                                                 beta, omb, out.data_ptr(), _stream_ptr(dev))
+        _lib.check(rc, "psgd_uvd_pack_blend_f32")
+    return out.view(-1)[:plan.total]
+
+
 def uvd_sumsq(x, *, plan):
     """plan.sumsq[0] = sum of fl32(x * x) in fp64, fixed order (the square of the clip norm of psgd.py:753); returns that tensor"""
     dev = _require_hip("uvd_sumsq", x)
@@ -785,7 +817,7 @@ def uvd_sumsq(x, *, plan):
     return plan.sumsq
 
 
-def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group=None, *, plan=None):
+def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group=None, *, plan=None, weight_decay=0.0):
     """psgd.py:750-762 on all parameters in place, in launches that do not depend on len(params):
         lr_eff = lr                                                         (max_norm None or inf, :750-751)
                  lr * min(max_norm / (||pre_grad|| + tiny), 1)              (:753-754; the norm never reaches the host)
@@ -794,6 +826,8 @@ def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group
     of one dtype; pre_grad: the flat fp32 preconditioned gradient of their concatenation.  tiny defaults to the dtype's smallest
     normal (:682).  group: pre_grad holds this rank's rows of a row-sharded vector -- the sum of squares is all-reduced (one fp64
     scalar, the collective sharded.global_norm uses).  pre_grad None (vs required): p <- T(p + v), the perturbation of :723.
+    weight_decay (extension, decoupled): with c = fl32(lr_eff * weight_decay), delta = T(delta + T(fl32(c * p))) after the vs term;
+    0 (default) adds no rounding step.
     The parameters are written through their pointers: autograd's version counters do not move."""
     params = list(params)
     plan = plan if plan is not None else _tail_plan(params, "uvd_step_tail")
@@ -802,9 +836,13 @@ def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group
     vsegs = plan.table("vs", list(vs), "uvd_step_tail (vs)") if vs is not None else None
     clip = max_norm is not None and not math.isinf(float(max_norm))
     sumsq = None
+    wd = float(weight_decay)
+    if not wd >= 0.0:
+        raise ValueError("uvd_step_tail: weight_decay must be >= 0, got %r" % (weight_decay,))
     if pre_grad is None:
-        if vsegs is None or clip:
-            raise ValueError("uvd_step_tail: pre_grad=None adds vs to the parameters; it needs vs and takes no max_norm")
+        if vsegs is None or clip or wd != 0.0:
+            raise ValueError("uvd_step_tail: pre_grad=None adds vs to the parameters; it needs vs and takes no max_norm and no "
+                             "weight_decay")
     else:
         _require_hip("uvd_step_tail", pre_grad)
         if pre_grad.device != dev or pre_grad.numel() != plan.total:
@@ -816,11 +854,15 @@ def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group
                 _sharded.all_reduce_sum_f64_(sumsq, group)
     if plan.nchunks:
         tiny = torch.finfo(plan.dtype).tiny if tiny is None else tiny
-        rc = _lib.load().psgd_uvd_param_update_multi(
-            psegs, vsegs, len(params), plan.chunks.data_ptr(), plan.nchunks, plan.code,
-            None if pre_grad is None else pre_grad.data_ptr(), float(lr), None if sumsq is None else sumsq.data_ptr(),
-            float(max_norm) if clip else 0.0, float(tiny), _stream_ptr(dev))
-        _lib.check(rc, "psgd_uvd_param_update_multi")
+        args = (psegs, vsegs, len(params), plan.chunks.data_ptr(), plan.nchunks, plan.code,
+                None if pre_grad is None else pre_grad.data_ptr(), float(lr), None if sumsq is None else sumsq.data_ptr(),
+                float(max_norm) if clip else 0.0, float(tiny))
+        if wd == 0.0:
+            rc = _lib.load().psgd_uvd_param_update_multi(*args, _stream_ptr(dev))
+            _lib.check(rc, "psgd_uvd_param_update_multi")
+        else:
+            rc = _lib.load().psgd_uvd_param_update_multi_wd(*args, wd, _stream_ptr(dev))
+            _lib.check(rc, "psgd_uvd_param_update_multi_wd")
 
 
 # --------------------------------------------------------------------------- UVd optimizer wrapper
@@ -888,7 +930,8 @@ class UVd:
                  lr_params=0.01, lr_preconditioner=0.01,
                  grad_clip_max_norm=None, preconditioner_update_probability=1.0,
                  exact_hessian_vector_product: bool = True, generator=None, state_dtype=None, group=None,
-                 stage_backend=None, placement="auto", state_route="widen", state_rounding=None, step_tail="torch"):
+                 stage_backend=None, placement="auto", state_route="widen", state_rounding=None, step_tail="torch",
+                 momentum=0.0, weight_decay=0.0):
         # group (extension): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
         # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the
         # concatenation of the ranks' vectors in rank order, and U, V, d hold this rank's rows only.  A step then costs three
@@ -963,6 +1006,21 @@ class UVd:
         self.grad_clip_max_norm = _Hyper(math.inf if grad_clip_max_norm is None else grad_clip_max_norm)  # :675-678
         self.preconditioner_update_probability = _Hyper(preconditioner_update_probability)  # :679
         self.exact_hessian_vector_product = _Hyper(bool(exact_hessian_vector_product))       # :680
+        # momentum, weight_decay (extensions, off by default; _Hyper objects like the others).  momentum: the flat gradient of :747
+        # is blended into a buffer m that this object keeps, m <- beta_k m + (1 - beta_k) g with beta_k = min(k / (k + 1), momentum)
+        # (the warm-up of the PyTorch PSGD optimizers; k counts the steps blended so far, and a step taken with momentum == 0 sets
+        # it back to 0), and m takes the place of g in :748 -- v, h, the finite-difference undo and the clip norm (now of P m) are
+        # as before.  m is this rank's flat fp32 vector: the arena's g region when the state is placed, one tensor otherwise; with
+        # the fused tail the blend rides on the pack of g (uvd_pack_blend: no flat g exists).  weight_decay (decoupled): the update
+        # of :757-762 gains delta <- T(delta + T(fl32(fl32(lr_eff wd) p))).  Both tails round alike (every operation on its own);
+        # with either one on, the torch tail forms the clipped lr as the kernel does (fp64 from the fp32 squares, one rounding).
+        if not 0.0 <= float(momentum) < 1.0:
+            raise ValueError("UVd: momentum must be in [0, 1), got %r" % (momentum,))
+        if not float(weight_decay) >= 0.0:
+            raise ValueError("UVd: weight_decay must be >= 0, got %r" % (weight_decay,))
+        self.momentum = _Hyper(momentum)
+        self.weight_decay = _Hyper(weight_decay)
+        self._m, self._m_step = None, 0
         self._tiny = torch.finfo(self._dtype).tiny                                           # :682
         self._delta_param_scale = torch.finfo(self._dtype).eps ** 0.5                        # :683
         self._param_sizes, self._param_cumsizes = uvd_param_index(self._params_with_grad)    # :684-685
@@ -1051,6 +1109,42 @@ class UVd:
             return torch.cat(parts, 0, out=getattr(self._arena, name).view(-1))
         return torch.cat(parts, 0).to(self._state_dtype)
 
+    def _momentum_buffer(self):
+        """this rank's flat fp32 momentum vector: the arena's g region when the state is placed, else one zero-initialised tensor
+        created on first use"""
+        if self._arena is not None:
+            return self._arena.g.view(-1)
+        if self._m is None:
+            self._m = torch.zeros(self._param_cumsizes[-1], dtype=torch.float32, device=self._device)
+        return self._m
+
+    def _hyper_momentum(self):
+        mom, wd = float(self.momentum), float(self.weight_decay)
+        if not 0.0 <= mom < 1.0:
+            raise ValueError("UVd: momentum must be in [0, 1), got %r" % (mom,))
+        if not wd >= 0.0:
+            raise ValueError("UVd: weight_decay must be >= 0, got %r" % (wd,))
+        return mom, wd
+
+    def _grad_flat(self, grads, mom):
+        """psgd.py:747; with momentum the gradients blended into the momentum buffer, which is returned in their place"""
+        if mom == 0.0:
+            self._m_step = 0                                  # the buffer is not kept up: a later momentum warms up again
+            return self._flat(grads, "g")
+        beta, omb = uvd_momentum_coefficients(self._m_step, mom)
+        self._m_step += 1
+        m = self._momentum_buffer()
+        if self._tail is not None:
+            return uvd_pack_blend([_c(x) for x in grads], m, beta, plan=self._tail, role="g")
+        g = torch.cat([torch.reshape(x, [-1]) for x in grads], 0).to(torch.float32)
+        with torch.no_grad():
+            if beta == 0.0:
+                m.copy_(g.mul(omb))                           # the buffer is not read (as in the kernel): NaN in it does not leak
+            else:
+                m.mul_(beta)
+                m.add_(g.mul(omb))
+        return m
+
     def _loss_of(self, closure_returns):
         return closure_returns if isinstance(closure_returns, torch.Tensor) else closure_returns[0]
 
@@ -1083,6 +1177,9 @@ class UVd:
             round_seed0, round_step  native route only: together they fix every stored code of every later step
             hyper                    lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability (floats),
                                      exact_hessian_vector_product (bool)
+                                     and, optional when loading, momentum and weight_decay (floats)
+            momentum_buffer, momentum_step    only when momentum > 0: this rank's rows of the momentum buffer (fp32) and the number of
+                                     steps blended into it
             branch_rng               get_state() of the generator behind the coin flips: the generator= argument, else the
                                      module's branch generator; row-sharded, the synchronised generator all ranks draw from
 
@@ -1101,6 +1198,9 @@ class UVd:
               "state_rounding": self._state_rounding if self._state_rounding is not None else "none",
               "hyper": {k: (bool if k == "exact_hessian_vector_product" else float)(getattr(self, k)) for k in self._HYPER_KEYS},
               "branch_rng": self._coin_generator().get_state().clone()}
+        sd["hyper"]["momentum"], sd["hyper"]["weight_decay"] = float(self.momentum), float(self.weight_decay)
+        if float(self.momentum) > 0.0:
+            sd["momentum_buffer"], sd["momentum_step"] = host(self._momentum_buffer()), int(self._m_step)
         if self._native:
             sd["round_seed0"], sd["round_step"] = int(self._round_seed0), int(self._round_step)
         return sd
@@ -1108,7 +1208,9 @@ class UVd:
     def load_state_dict(self, sd, *, strict=True, narrow_rounding=None, narrow_seed=None):
         """Restore what state_dict() saved, IN PLACE: U, V, d are written into the tensors this object already holds (a placed
         state stays in its arena; every pointer the tail plan and the workspaces cache stays valid), the hyper-parameters are
-        assigned, the generator behind the coins gets the saved state (row-sharded: every rank loads the same bytes into the
+        assigned (momentum and weight_decay when the dict has them; momentum_buffer / momentum_step are restored, and a dict
+        without them zeroes the buffer of a momentum optimizer and restarts its warm-up), the generator behind the coins gets the
+        saved state (row-sharded: every rank loads the same bytes into the
         synchronised generator; nothing is broadcast again) and, on the native route, so do round_seed0 / round_step.
 
         Checked against this object (ValueError naming the key): format, rank, num_params, param_sizes (skipped when the dict
@@ -1169,6 +1271,11 @@ class UVd:
         for k in self._HYPER_KEYS:
             if k not in hyper:
                 raise ValueError("%s: 'hyper' has no %r" % (name, k))
+        mbuf = sd.get("momentum_buffer")
+        if mbuf is not None and (not isinstance(mbuf, torch.Tensor) or mbuf.dtype != torch.float32 or mbuf.numel() != n):
+            raise ValueError("%s: 'momentum_buffer' must be a float32 tensor of %d elements" % (name, n))
+        if mbuf is not None:
+            need("momentum_step")
         rng_state = need("branch_rng")
         try:
             self._coin_generator().set_state(rng_state)
@@ -1176,6 +1283,17 @@ class UVd:
             raise ValueError("%s: 'branch_rng' does not fit this optimizer's generator: %s" % (name, e))
         for k in self._HYPER_KEYS:
             getattr(self, k).assign(hyper[k])
+        for k in ("momentum", "weight_decay"):               # optional: a checkpoint from before them leaves this object's values
+            if k in hyper:
+                getattr(self, k).assign(hyper[k])
+        with torch.no_grad():
+            if mbuf is not None:
+                self._momentum_buffer().copy_(mbuf.reshape(-1))
+                self._m_step = int(sd["momentum_step"])
+            else:                                            # no buffer saved: a momentum optimizer starts its warm-up again
+                self._m_step = 0
+                if float(self.momentum) > 0.0:
+                    self._momentum_buffer().zero_()
         if self._native and "round_seed0" in sd:
             self._round_seed0, self._round_step = int(sd["round_seed0"]), int(need("round_step"))
         with torch.no_grad():
@@ -1235,6 +1353,7 @@ class UVd:
         else:
             update_Q = self._coins.draw(float(self.preconditioner_update_probability))       # the same coin on every rank
         exact = bool(self.exact_hessian_vector_product)
+        mom, wd = self._hyper_momentum()
         vs = None
         if update_Q:
             if exact:                                                                         # :706-714
@@ -1264,19 +1383,31 @@ class UVd:
             if not exact and self._tail is None:                                              # :734-736
                 v = v / self._delta_param_scale
                 h = h / self._delta_param_scale
-            grad = self._flat(grads, "g")                                                     # :747
+            grad = self._grad_flat(grads, mom)                                                # :747
             pre_grad = self._precondition(v, h, grad)                                         # :732-733, :748
         else:                                                                                 # :737-744
             with torch.enable_grad():
                 closure_returns = closure()
                 grads = torch.autograd.grad(self._loss_of(closure_returns), params)
-            pre_grad = self._precondition(None, None, self._flat(grads, "g"))                 # :747-748
+            pre_grad = self._precondition(None, None, self._grad_flat(grads, mom))            # :747-748
         max_norm = float(self.grad_clip_max_norm)
         if self._tail is not None:                                                            # :750-762 in the step-tail kernels
             uvd_step_tail(params, pre_grad, float(self.lr_params), max_norm, self._tiny, vs if (not exact) and update_Q else None,
-                          self._group, plan=self._tail)
+                          self._group, plan=self._tail, weight_decay=wd)
             return closure_returns
-        if math.isinf(max_norm):                                                              # :750-751
+        decay = None
+        if mom != 0.0 or wd != 0.0:      # the torch tail of the extensions: lr_eff as the step-tail kernel forms it, one op per rounding
+            lr = torch.tensor(float(self.lr_params), dtype=torch.float32, device=pre_grad.device)
+            if not math.isinf(max_norm):
+                sq = torch.sum((pre_grad * pre_grad).double()).reshape(1)
+                if self._group is not None:
+                    self._sharded.all_reduce_sum_f64_(sq, self._group)
+                f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))          # the kernel takes max_norm and tiny as floats
+                ratio = f32(max_norm) / (torch.sqrt(sq[0]) + f32(self._tiny))
+                lr = (lr.double() * torch.clamp(ratio, max=1.0)).float()
+            if wd != 0.0:
+                decay = lr * torch.tensor(wd, dtype=torch.float32, device=pre_grad.device)
+        elif math.isinf(max_norm):                                                            # :750-751
             lr = float(self.lr_params)
         else:                                                                                 # :753-754
             if self._group is None:
@@ -1290,5 +1421,7 @@ class UVd:
                 delta = (lr * torch.reshape(pre_grad[j - i:j], p.shape)).to(p.dtype)
                 if undo:
                     delta = delta + vs[k]
+                if decay is not None:
+                    delta = delta + (decay * p.float()).to(p.dtype)
                 p.sub_(delta)
         return closure_returns                                                                # :764

@@ -249,8 +249,8 @@ def shard_rows(n_global, rank, world):
 def reshard_uvd_state(state_dicts, new_row_counts):
     """The W state dicts of ONE row-sharded checkpoint (UVd.state_dict() of every rank, in any order) as W' dicts whose row
     counts are new_row_counts: offline, on the CPU, no process group.  The inputs must tile [0, num_params_global) without gap
-    or overlap and agree on format, rank, dtypes, route, rounding, hyper, round_seed0 / round_step and branch_rng (ValueError
-    naming what does not).  new_row_counts must sum to num_params_global, and every entry but the last must be a multiple of 64
+    or overlap and agree on format, rank, dtypes, route, rounding, hyper, round_seed0 / round_step, momentum_step and branch_rng
+    (ValueError naming what does not).  momentum_buffer is split by rows as d is when every input dict has one (dropped otherwise).  new_row_counts must sum to num_params_global, and every entry but the last must be a multiple of 64
     (shards start at multiples of 64 rows, see shard_rows).  Output k holds rows [row0', row0' + n') with its own num_params
     and row0; its param_sizes is None (the new ranks' parameter lists are not known here), which UVd.load_state_dict skips.
 
@@ -264,7 +264,7 @@ def reshard_uvd_state(state_dicts, new_row_counts):
     if first.get("format") != 1:
         raise ValueError("%s: 'format' is %r; this version reads format 1" % (name, first.get("format")))
     for key in ("format", "rank", "num_params_global", "state_dtype", "state_route", "state_rounding", "hyper", "round_seed0",
-                "round_step"):
+                "round_step", "momentum_step"):
         for s in sds[1:]:
             if s.get(key) != first.get(key):
                 raise ValueError("%s: the state dicts disagree on %r (%r and %r)" % (name, key, first.get(key), s.get(key)))
@@ -290,13 +290,21 @@ def reshard_uvd_state(state_dicts, new_row_counts):
     if any(c % 64 for c in counts[:-1]):
         raise ValueError("%s: every entry of new_row_counts but the last must be a multiple of 64, got %r" % (name, counts))
     whole = {k: torch.cat([s[k] for s in sds], 0) for k in ("U", "V", "d")}
+    if all(s.get("momentum_buffer") is not None for s in sds):      # the momentum buffer of class UVd: split by rows, as d is
+        for s in sds:
+            if s["momentum_buffer"].numel() != int(s["num_params"]):
+                raise ValueError("%s: 'momentum_buffer' has %d elements where 'num_params' says %d"
+                                 % (name, s["momentum_buffer"].numel(), int(s["num_params"])))
+        whole["momentum_buffer"] = torch.cat([s["momentum_buffer"].reshape(-1) for s in sds], 0)
     out, lo = [], 0
     for c in counts:
-        new = {k: v for k, v in first.items() if k not in ("U", "V", "d")}
+        new = {k: v for k, v in first.items() if k not in ("U", "V", "d", "momentum_buffer")}
         new["hyper"] = dict(first["hyper"])
         new["branch_rng"] = first["branch_rng"].clone()
-        for k in ("U", "V", "d"):
+        for k in whole:
             new[k] = whole[k][lo:lo + c].clone()
+        if "momentum_buffer" not in whole:
+            new.pop("momentum_step", None)
         new["num_params"], new["row0"], new["param_sizes"] = c, lo, None
         out.append(new)
         lo += c

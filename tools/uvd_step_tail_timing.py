@@ -14,6 +14,10 @@ Peak memory: torch.cuda.max_memory_allocated over three further steps minus what
     python tools/uvd_step_tail_timing.py --tail torch         # one route only (also runs on a checkout that has no step_tail)
     python tools/uvd_step_tail_timing.py --trace N K TAIL     # 20 steps of one configuration and nothing else, for
                                                               # rocprofv3 --kernel-trace --stats -- python tools/... --trace 1000000 256 fused
+    python tools/uvd_step_tail_timing.py --momentum           # the fused step at N = 4M and N = 100M, r = 20, 256 tensors: plain,
+                                                              # momentum=0.9, and momentum=0.9 with weight_decay=0.01
+    python tools/uvd_step_tail_timing.py --momentum --legs plain --root OTHER   # the plain leg of another checkout (one that has
+                                                              # no momentum argument): the baseline of the comparison
 """
 import argparse
 import os
@@ -23,7 +27,10 @@ import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+_root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--root" in sys.argv[1:-1]:                                # the checkout to import from (default: the one this file is in)
+    _root = os.path.abspath(sys.argv[sys.argv.index("--root") + 1])
+sys.path.insert(0, _root)
 import preconditioned_stochastic_gradient_descent as psgd  # noqa: E402
 
 
@@ -36,12 +43,12 @@ def split(N, k):
     return sizes
 
 
-def build(N, r, k, dtype, clip, tail, seed=0):
+def build(N, r, k, dtype, clip, tail, seed=0, **extra):
     dev = torch.device("cuda:0")
     torch.manual_seed(seed)
     psgd.manual_seed(seed)
     params = [(torch.randn(n, device=dev) * 0.1).to(dtype).requires_grad_(True) for n in split(N, k)]
-    kw = {} if tail == "torch" else {"step_tail": tail}
+    kw = dict(extra) if tail == "torch" else dict(extra, step_tail=tail)
     opt = psgd.UVd(params, rank_of_modification=r, lr_params=1e-3, lr_preconditioner=0.01,
                    grad_clip_max_norm=1.0 if clip else None, **kw)
 
@@ -89,6 +96,28 @@ def peak_delta(fn):
     return torch.cuda.max_memory_allocated() - before
 
 
+MOMENTUM_LEGS = {"plain": {}, "momentum": {"momentum": 0.9}, "momentum+decay": {"momentum": 0.9, "weight_decay": 0.01}}
+
+
+def momentum_table(a):
+    """the fused step with and without the momentum buffer and the decay term; N floats more to read per step is the expected cost
+    of momentum, nothing that of decay"""
+    legs = a.legs.split(",")
+    print("# fused tail, fp32, r = 20, 256 tensors | leg: median step [min .. max] us, peak bytes over 3 steps   (root: %s)" % _root)
+    for N in ([4_000_000] if a.quick else [4_000_000, 100_000_000]):
+        steps = a.steps if N <= 4_000_000 else max(5, a.steps // 4)
+        for clip in (False, True):
+            row = "N=%d r=20 k=256 float32 clip=%s |" % (N, "on" if clip else "off")
+            for leg in legs:
+                params, opt, closure = build(N, 20, 256, torch.float32, clip, "fused", **MOMENTUM_LEGS[leg])
+                med, lo, hi = timed(lambda: opt.step(closure), steps, a.chunks, a.warm_seconds)
+                peak = peak_delta(lambda: opt.step(closure))
+                row += " %s: %.1f [%.1f .. %.1f] us, peak +%d B |" % (leg, med * 1e6, lo * 1e6, hi * 1e6, peak)
+                del params, opt, closure
+                torch.cuda.empty_cache()
+            print(row, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tail", choices=["torch", "fused", "both"], default="both")
@@ -97,8 +126,14 @@ def main():
     ap.add_argument("--chunks", type=int, default=7)
     ap.add_argument("--warm-seconds", type=float, default=0.3)
     ap.add_argument("--trace", nargs=3, metavar=("N", "K", "TAIL"))
+    ap.add_argument("--momentum", action="store_true", help="the momentum / weight-decay table instead of the tail table")
+    ap.add_argument("--legs", default="plain,momentum,momentum+decay", help="with --momentum: which legs (comma-separated)")
+    ap.add_argument("--root", default=None, help="import the package from this checkout instead of the tool's own")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "this tool measures on the GPU"
+    if a.momentum:
+        assert a.chunks >= 7 and all(leg in MOMENTUM_LEGS for leg in a.legs.split(","))
+        return momentum_table(a)
     if a.trace:
         N, k, tail = int(a.trace[0]), int(a.trace[1]), a.trace[2]
         params, opt, closure = build(N, 10 if N <= 1_000_000 else 20, k, torch.float32, True, tail)
