@@ -33,6 +33,16 @@ def _num(words, key):
     return int(next(w for w in words if w.startswith(key))[len(key):])
 
 
+def _gram_cases(names):
+    """every fifth case (it % 5 == 2; names are in the order of it) of rank 2 and above is a problem of make_uvd_problem_with_gram, and
+    no other: at least three, each kind of the rotation met"""
+    from tests import fuzz_gpu
+    kinds = {it: x[len("gram-"):] for it, w in enumerate(names) for x in w if x.startswith("gram-")}
+    assert sorted(kinds) == [it for it, w in enumerate(names) if it % 5 == 2 and _num(w, "r=") > 1], sorted(kinds)
+    assert len(kinds) >= max(3, len(names) // 5 - 2), kinds
+    assert set(kinds.values()) == set(fuzz_gpu.GRAM_KINDS), kinds
+
+
 def test_dense(hip_lib, capsys):
     """36 cases: it % 2 (upper / full), it % 3 with (it // 3) % 4 (the four edge classes, three cases each), it % 4 (unaligned Q),
     one scaled case in every three."""
@@ -54,8 +64,10 @@ def test_dense(hip_lib, capsys):
 
 def test_uvd_bf16(hip_lib, capsys):
     """64 cases: it % 2 (U / V), (it // 2) % 2 (rounding), (it // 4) % 2 (fused / two calls), it % 5 (balance), it % 3 with
-    (it // 3) % 3 (three tile multiples), it % 4 (N to 400 000).  The rank is a uniform draw: this seed meets 24 of the 32 ranks (the
-    others: 2, 3, 6, 10, 17, 21, 25, 29; profiles/fuzz_families.txt), and a change of seed or generator may not meet fewer."""
+    (it // 3) % 3 (three tile multiples), it % 4 (N to 400 000), it % 5 == 2 (13 slots for problems with a chosen Gram,
+    tests/uvd_cases.py, at every rank but 1; hard bars like the rest).  The rank is a uniform draw: this seed meets 24 of the 32
+    ranks (the others: 2, 3, 6, 10, 17, 21, 25, 29; profiles/fuzz_families.txt), and a change of seed or generator may not meet
+    fewer."""
     names = _run("uvd-bf16", 64, capsys)
     for word in ("U", "V", "bal", "nearest", "stochastic", "fused", "two-call", "edge64", "edge256"):
         assert sum(word in w for w in names) >= 2, word
@@ -65,6 +77,7 @@ def test_uvd_bf16(hip_lib, capsys):
     with capsys.disabled():
         print("  ranks met: %d of 32, missing %s" % (len(ranks), sorted(set(range(1, 33)) - ranks)))
     assert min(ranks) >= 1 and max(ranks) <= 32 and len(ranks) >= 24, sorted(ranks)
+    _gram_cases(names)
 
 
 def test_splu(hip_lib, capsys):
@@ -75,6 +88,9 @@ def test_splu(hip_lib, capsys):
 
 
 def test_uvd(hip_lib, capsys):
-    """30 cases: it % 15 (ranks above 32), it % 2 (U / V, and the matrix g on the even ones), it % 3, it % 4, it % 5."""
+    """30 cases: it % 15 (ranks above 32), it % 2 (U / V, and the matrix g on the even ones), it % 3, it % 4, it % 5 (== 0: balance;
+    == 2: six slots for problems with a chosen Gram, tests/uvd_cases.py, at every rank but 1, never with the sensitivity
+    relaxation)."""
     names = _run("uvd", 30, capsys)
     assert sum(_num(w, "r=") > 32 for w in names) >= 2 and sum(_num(w, "r=") <= 32 for w in names) >= 15
+    _gram_cases(names)
