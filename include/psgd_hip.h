@@ -57,6 +57,7 @@ extern "C" {
  *     state (new symbols only, no existing layout changes: still 7).
  *     psgd_uvd_pack_blend_f32 and psgd_uvd_param_update_multi_wd, momentum and decoupled weight decay in the tail of UVd.step
  *     (new symbols only: still 7).
+ *     psgd_uvd_pack_check_f32 and psgd_uvd_check_multi, the non-finite guard of UVd.step (new symbols only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -375,6 +376,19 @@ int psgd_uvd_pack_f32(const void *segs, int k, const void *chunks, int64_t nchun
  * psgd_uvd_pack_f32).  Same tables, dtypes and argument checks as psgd_uvd_pack_f32.                                             */
 int psgd_uvd_pack_blend_f32(const void *segs, int k, const void *chunks, int64_t nchunks, int dtype, float scale, float beta,
                             float omb, float *out, void *stream);
+
+/* The guarded step of class UVd (nonfinite="skip").  psgd_uvd_pack_check_f32 writes exactly the bits of psgd_uvd_pack_f32 and, when
+ * any value it WRITES, fl32(float(tensor[i]) * scale), is not finite (+-Inf or NaN: a finite input that overflows under scale
+ * counts), stores stamp to *flag.  psgd_uvd_check_multi applies the same predicate to the same tables, reading every element once
+ * in its own type, and writes nothing but the flag (for the gradients of a momentum step: psgd_uvd_pack_blend_f32 overwrites the
+ * buffer it blends into, so they are judged before the blend).
+ * flag: one 4-byte aligned device word.  Every writer stores the same value with an ordinary store: no atomics, no reduction.  The
+ * word is never zeroed: the caller passes a stamp it has not used on this word before (1, 2, ... 2^31 - 1, then 1 again) and reads
+ * "bad" as *flag == stamp after the launch has completed.  flag == NULL or stamp <= 0: PSGD_ERR_BAD_ARG before any HIP call. */
+int psgd_uvd_pack_check_f32(const void *segs, int k, const void *chunks, int64_t nchunks, int dtype, float scale, float *out,
+                            int32_t *flag, int32_t stamp, void *stream);
+int psgd_uvd_check_multi(const void *segs, int k, const void *chunks, int64_t nchunks, int dtype, float scale, int32_t *flag,
+                         int32_t stamp, void *stream);
 
 /* out[0] = sum_i fl32(x[i] * x[i]), summed in fp64 in a fixed order (the square of the clip norm of psgd.py:753): two launches,
  * no floating-point atomics, the same bits on every call.  N >= 0; x 4-byte aligned.                                             */

@@ -122,6 +122,8 @@ SIGNATURES = {
     "psgd_uvd_apply_sweep3_bf16": (_int, [_c_f32p] * 3 + [_i64, _int, _c_ws, _i64, _strm]),
     "psgd_uvd_pack_f32": (_int, [_c_f32p, _int, _c_f32p, _i64, _int, _flt, _c_f32p, _strm]),
     "psgd_uvd_pack_blend_f32": (_int, [_c_f32p, _int, _c_f32p, _i64, _int, _flt, _flt, _flt, _c_f32p, _strm]),
+    "psgd_uvd_pack_check_f32": (_int, [_c_f32p, _int, _c_f32p, _i64, _int, _flt, _c_f32p, _c_f32p, ctypes.c_int32, _strm]),
+    "psgd_uvd_check_multi": (_int, [_c_f32p, _int, _c_f32p, _i64, _int, _flt, _c_f32p, ctypes.c_int32, _strm]),
     "psgd_uvd_sumsq_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_ws, _i64, _strm]),
     "psgd_uvd_param_update_multi": (_int, [_c_f32p, _c_f32p, _int, _c_f32p, _i64, _int, _c_f32p, _flt, _c_f32p, _flt, _flt, _strm]),
     "psgd_uvd_param_update_multi_wd": (_int, [_c_f32p, _c_f32p, _int, _c_f32p, _i64, _int, _c_f32p, _flt, _c_f32p, _flt, _flt, _flt,

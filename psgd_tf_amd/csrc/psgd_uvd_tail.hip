@@ -2,6 +2,8 @@
 //
 //   psgd_uvd_pack_f32            k tensors of one dtype (fp32 / bf16 / fp16) -> one flat fp32 vector, times a scale      (:729-736, :747)
 //   psgd_uvd_pack_blend_f32      the same pack blended into the flat vector: out <- fl32(fl32(beta out) + fl32(omb x))  (momentum of class UVd)
+//   psgd_uvd_pack_check_f32      the plain pack, and a stamp stored to a flag word when a written value is not finite     (guarded step)
+//   psgd_uvd_check_multi         the same predicate on the same tables; writes the flag alone (the gradients before a blend)
 //   psgd_uvd_sumsq_f32           sum x^2 of a flat fp32 vector -> one device double (the clip norm's square)              (:753)
 //   psgd_uvd_param_update_multi  p <- T(p - [T(T(fl32(lr_eff pre_grad)) + v)])  for every element of every parameter      (:757-762)
 //   psgd_uvd_param_update_multi_wd  ... with decoupled weight decay: delta <- T(delta + T(fl32(fl32(lr_eff wd) p)))
@@ -144,12 +146,20 @@ __device__ __forceinline__ float pack_one(float x, float old, float scale, float
   return bo + nx;
 }
 
-template <class T, bool kBlend = false, bool kRead = false>
+// The non-finite predicate of the guarded step, on a value as it is WRITTEN: exponent all ones (+-Inf, NaN).
+__device__ __forceinline__ bool not_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) == 0x7F800000u; }
+
+// kCheck (psgd_uvd_pack_check_f32): the plain pack, and a lane that wrote a non-finite value stores `stamp` to *flag when it is
+// done -- an ordinary store of one value by every writer: no atomic, no reduction, and nobody zeroes the word (the host passes a
+// stamp it has not used before and reads "bad" as *flag == stamp once the launch has completed).
+template <class T, bool kBlend = false, bool kRead = false, bool kCheck = false>
 __global__ __launch_bounds__(kT) void k_uvd_pack(const Seg* __restrict__ segs, const Chunk* __restrict__ chunks, int64_t nchunks,
-                                                 int k, float scale, float beta, float omb, float* __restrict__ out) {
+                                                 int k, float scale, float beta, float omb, float* __restrict__ out,
+                                                 int32_t* __restrict__ flag, int32_t stamp) {
   using raw = typename T::raw;
   constexpr int E = T::E;
   const int t = threadIdx.x;
+  bool bad = false;
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const Chunk ch = chunks[c];
     if ((uint64_t)ch.seg >= (uint64_t)k) continue;              // a table that does not belong to these segments moves nothing
@@ -161,7 +171,11 @@ __global__ __launch_bounds__(kT) void k_uvd_pack(const Seg* __restrict__ segs, c
     float* dst = out + s.start + ch.off;
     const int head = head_of(dst, 4, n);
     const int nvec = (n - head) / E;
-    if (t < head) dst[t] = pack_one<kBlend, kRead>(T::widen(src[t]), kRead ? dst[t] : 0.f, scale, beta, omb);
+    if (t < head) {
+      const float y = pack_one<kBlend, kRead>(T::widen(src[t]), kRead ? dst[t] : 0.f, scale, beta, omb);
+      if constexpr (kCheck) bad |= not_finite(y);
+      dst[t] = y;
+    }
 #pragma unroll 2
     for (int g = t; g < nvec; g += kT) {
       const int i = head + g * E;
@@ -177,6 +191,10 @@ __global__ __launch_bounds__(kT) void k_uvd_pack(const Seg* __restrict__ segs, c
       }
 #pragma unroll
       for (int e = 0; e < E; ++e) x[e] = pack_one<kBlend, kRead>(x[e], kRead ? o[e] : 0.f, scale, beta, omb);
+      if constexpr (kCheck) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) bad |= not_finite(x[e]);
+      }
 #pragma unroll
       for (int q = 0; q < E / 4; ++q) {
         f32x4 v = {x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]};
@@ -184,8 +202,48 @@ __global__ __launch_bounds__(kT) void k_uvd_pack(const Seg* __restrict__ segs, c
       }
     }
     const int i = head + nvec * E + t;
-    if (i < n) dst[i] = pack_one<kBlend, kRead>(T::widen(src[i]), kRead ? dst[i] : 0.f, scale, beta, omb);
+    if (i < n) {
+      const float y = pack_one<kBlend, kRead>(T::widen(src[i]), kRead ? dst[i] : 0.f, scale, beta, omb);
+      if constexpr (kCheck) bad |= not_finite(y);
+      dst[i] = y;
+    }
   }
+  if constexpr (kCheck) {
+    if (bad) *flag = stamp;
+  }
+}
+
+// psgd_uvd_check_multi: the predicate of the checked pack on the same tables, and nothing written but the flag.  Every element is
+// read once in its own type; the 16-byte body is aligned on the SOURCE (there is no stored side), head and tail are scalar.
+template <class T>
+__global__ __launch_bounds__(kT) void k_uvd_check(const Seg* __restrict__ segs, const Chunk* __restrict__ chunks, int64_t nchunks, int k,
+                                                  float scale, int32_t* __restrict__ flag, int32_t stamp) {
+  using raw = typename T::raw;
+  constexpr int E = T::E;
+  const int t = threadIdx.x;
+  bool bad = false;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Chunk ch = chunks[c];
+    if ((uint64_t)ch.seg >= (uint64_t)k) continue;
+    const Seg s = segs[ch.seg];
+    const int64_t left = s.count - ch.off;
+    if (ch.off < 0 || left <= 0) continue;
+    const int n = (int)(left < kChunk ? left : kChunk);
+    const raw* src = reinterpret_cast<const raw*>(s.ptr) + ch.off;
+    const int head = head_of(src, (int)sizeof(raw), n);
+    const int nvec = (n - head) / E;
+    if (t < head) bad |= not_finite(T::widen(src[t]) * scale);
+#pragma unroll 2
+    for (int g = t; g < nvec; g += kT) {
+      float x[E];
+      load_16<T>(src + head + g * E, x);
+#pragma unroll
+      for (int e = 0; e < E; ++e) bad |= not_finite(x[e] * scale);
+    }
+    const int i = head + nvec * E + t;
+    if (i < n) bad |= not_finite(T::widen(src[i]) * scale);
+  }
+  if (bad) *flag = stamp;
 }
 
 // ------------------------------------------------------------------------------------------------------------- sum of squares
@@ -334,30 +392,37 @@ static void launch_update(bool pre, bool vs, int grid, hipStream_t st, const Seg
 
 template <class T>
 static void launch_pack(int mode, int grid, hipStream_t st, const Seg* sg, const Chunk* ch, int64_t nchunks, int k, float scale,
-                        float beta, float omb, float* out) {
+                        float beta, float omb, float* out, int32_t* flag, int32_t stamp) {
   if (mode == 0)
-    hipLaunchKernelGGL((k_uvd_pack<T, false, false>), dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, beta, omb, out);
+    hipLaunchKernelGGL((k_uvd_pack<T, false, false>), dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, beta, omb, out, flag,
+                       stamp);
   else if (mode == 1)
-    hipLaunchKernelGGL((k_uvd_pack<T, true, false>), dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, beta, omb, out);
+    hipLaunchKernelGGL((k_uvd_pack<T, true, false>), dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, beta, omb, out, flag,
+                       stamp);
+  else if (mode == 2)
+    hipLaunchKernelGGL((k_uvd_pack<T, true, true>), dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, beta, omb, out, flag,
+                       stamp);
   else
-    hipLaunchKernelGGL((k_uvd_pack<T, true, true>), dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, beta, omb, out);
+    hipLaunchKernelGGL((k_uvd_pack<T, false, false, true>), dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, beta, omb, out,
+                       flag, stamp);
 }
 
-// mode 0: the plain pack; 1: blend with beta == 0 (out is not read); 2: blend
+// mode 0: the plain pack; 1: blend with beta == 0 (out is not read); 2: blend; 3: the plain pack with the non-finite check
 static int pack_entry(int mode, const void* segs, int k, const void* chunks, int64_t nchunks, int dtype, float scale, float beta,
-                      float omb, float* out, void* stream) {
+                      float omb, float* out, void* stream, int32_t* flag = nullptr, int32_t stamp = 0) {
   if (!segs || !chunks || !out || k < 0 || nchunks < 0 || bad_dtype(dtype)) return PSGD_ERR_BAD_ARG;
+  if (mode == 3 && (!flag || stamp <= 0)) return PSGD_ERR_BAD_ARG;
   if (nchunks == 0) return PSGD_OK;
   hipStream_t st = (hipStream_t)stream;
   const Seg* sg = (const Seg*)segs;
   const Chunk* ch = (const Chunk*)chunks;
   const int grid = grid_for(nchunks);
   if (dtype == PSGD_DTYPE_F32)
-    launch_pack<F32>(mode, grid, st, sg, ch, nchunks, k, scale, beta, omb, out);
+    launch_pack<F32>(mode, grid, st, sg, ch, nchunks, k, scale, beta, omb, out, flag, stamp);
   else if (dtype == PSGD_DTYPE_BF16)
-    launch_pack<BF16>(mode, grid, st, sg, ch, nchunks, k, scale, beta, omb, out);
+    launch_pack<BF16>(mode, grid, st, sg, ch, nchunks, k, scale, beta, omb, out, flag, stamp);
   else
-    launch_pack<F16>(mode, grid, st, sg, ch, nchunks, k, scale, beta, omb, out);
+    launch_pack<F16>(mode, grid, st, sg, ch, nchunks, k, scale, beta, omb, out, flag, stamp);
   return launched();
 }
 
@@ -375,6 +440,28 @@ int psgd_uvd_pack_f32(const void* segs, int k, const void* chunks, int64_t nchun
 int psgd_uvd_pack_blend_f32(const void* segs, int k, const void* chunks, int64_t nchunks, int dtype, float scale, float beta,
                             float omb, float* out, void* stream) {
   return pack_entry(beta == 0.f ? 1 : 2, segs, k, chunks, nchunks, dtype, scale, beta, omb, out, stream);
+}
+
+int psgd_uvd_pack_check_f32(const void* segs, int k, const void* chunks, int64_t nchunks, int dtype, float scale, float* out,
+                            int32_t* flag, int32_t stamp, void* stream) {
+  return pack_entry(3, segs, k, chunks, nchunks, dtype, scale, 0.f, 1.f, out, stream, flag, stamp);
+}
+
+int psgd_uvd_check_multi(const void* segs, int k, const void* chunks, int64_t nchunks, int dtype, float scale, int32_t* flag,
+                         int32_t stamp, void* stream) {
+  if (!segs || !chunks || !flag || stamp <= 0 || k < 0 || nchunks < 0 || bad_dtype(dtype)) return PSGD_ERR_BAD_ARG;
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const Seg* sg = (const Seg*)segs;
+  const Chunk* ch = (const Chunk*)chunks;
+  const int grid = grid_for(nchunks);
+  if (dtype == PSGD_DTYPE_F32)
+    hipLaunchKernelGGL(k_uvd_check<F32>, dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, flag, stamp);
+  else if (dtype == PSGD_DTYPE_BF16)
+    hipLaunchKernelGGL(k_uvd_check<BF16>, dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, flag, stamp);
+  else
+    hipLaunchKernelGGL(k_uvd_check<F16>, dim3(grid), dim3(kT), 0, st, sg, ch, nchunks, k, scale, flag, stamp);
+  return launched();
 }
 
 int psgd_uvd_sumsq_f32(const float* x, int64_t N, double* out, void* ws, int64_t ws_bytes, void* stream) {

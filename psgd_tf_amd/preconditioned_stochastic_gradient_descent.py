@@ -724,6 +724,9 @@ class UVdTailPlan:
         self.chunks = torch.from_numpy(chunks).to(self.device) if self.nchunks else None
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=self.device)
         self.ws = torch.empty(_lib.UVD_SUMSQ_WS_BYTES, dtype=torch.uint8, device=self.device)
+        # the flag words of the guarded step (uvd_pack(flag=, stamp=), uvd_check): slots v, h, g and one spare.  Zero ONCE, here:
+        # the kernels store a stamp the caller has not used before, so nothing ever clears them again
+        self.flags = torch.zeros(4, dtype=torch.int32, device=self.device)
         self._tables = {}
 
     def table(self, role, tensors, what):
@@ -759,21 +762,70 @@ def _tail_plan(tensors, what):
     return plan
 
 
-def uvd_pack(tensors, out, scale=1.0, *, plan=None, role="pack"):
+def _flag_word(what, flag, stamp, dev):
+    """the device pointer of a guard flag (one int32 word on dev) after the checks the host can make"""
+    if not isinstance(flag, torch.Tensor) or flag.dtype != torch.int32 or flag.device != dev or flag.numel() < 1:
+        raise ValueError("%s: flag must be an int32 tensor of at least one element on %s" % (what, dev))
+    if int(stamp) != stamp:
+        raise ValueError("%s: stamp must be an integer, got %r" % (what, stamp))
+    return flag.data_ptr()
+
+
+def uvd_pack(tensors, out, scale=1.0, *, plan=None, role="pack", flag=None, stamp=None):
     """out[:n] = torch.cat([t.reshape(-1) for t in tensors]).float() * scale in ONE launch whatever len(tensors) (psgd.py:729-730, :747;
     scale: the 1 / delta_param_scale of :734-736).  tensors: contiguous device tensors of one dtype (float32, bfloat16 or float16),
-    empty ones allowed; out: a contiguous fp32 device tensor of at least n elements.  Returns out's first n elements, flat."""
+    empty ones allowed; out: a contiguous fp32 device tensor of at least n elements.  Returns out's first n elements, flat.
+    flag and stamp (both or neither): the same bits from psgd_uvd_pack_check_f32, which also stores stamp (1 .. 2^31 - 1, one the
+    caller has not used on this word before) to flag[0], an int32 device word, when a value it writes is not finite; the caller
+    reads flag[0] == stamp after the launch.  Nothing zeroes the word."""
     tensors = list(tensors)
+    if (flag is None) != (stamp is None):
+        raise ValueError("uvd_pack: flag and stamp go together (got flag=%s, stamp=%r)" % ("None" if flag is None else "given", stamp))
     plan = plan if plan is not None else _tail_plan(tensors, "uvd_pack")
     dev = _require_hip("uvd_pack", out)
     if out.numel() < plan.total:
         raise ValueError("uvd_pack: out has %d elements, the tensors have %d" % (out.numel(), plan.total))
     segs = plan.table(role, tensors, "uvd_pack")
-    if plan.nchunks:
+    word = None if flag is None else _flag_word("uvd_pack", flag, stamp, plan.device)
+    if plan.nchunks and flag is not None:
+        rc = _lib.load().psgd_uvd_pack_check_f32(segs, len(tensors), plan.chunks.data_ptr(), plan.nchunks, plan.code, float(scale),
+                                                 out.data_ptr(), word, int(stamp), _stream_ptr(dev))
+        _lib.check(rc, "psgd_uvd_pack_check_f32")
+    elif plan.nchunks:
         rc = _lib.load().psgd_uvd_pack_f32(segs, len(tensors), plan.chunks.data_ptr(), plan.nchunks, plan.code, float(scale),
                                            out.data_ptr(), _stream_ptr(dev))
         _lib.check(rc, "psgd_uvd_pack_f32")
     return out.view(-1)[:plan.total]
+
+
+def uvd_check(tensors, scale=1.0, *, plan=None, role="check", flag, stamp):
+    """The predicate of uvd_pack(..., flag=, stamp=) without the pack (psgd_uvd_check_multi): stamp is stored to flag[0] when
+    float32(t) * scale is not finite for an element t of any tensor.  Every element is read once in its own dtype and nothing else is
+    written.  For the gradients of a momentum step, which must be judged BEFORE uvd_pack_blend overwrites the buffer."""
+    tensors = list(tensors)
+    plan = plan if plan is not None else _tail_plan(tensors, "uvd_check")
+    dev = plan.device
+    if dev.type != "cuda":
+        raise _lib.PsgdHipError("uvd_check runs on the HIP device only; no CPU fallback")
+    segs = plan.table(role, tensors, "uvd_check")
+    word = _flag_word("uvd_check", flag, stamp, dev)
+    if plan.nchunks:
+        rc = _lib.load().psgd_uvd_check_multi(segs, len(tensors), plan.chunks.data_ptr(), plan.nchunks, plan.code, float(scale), word,
+                                              int(stamp), _stream_ptr(dev))
+        _lib.check(rc, "psgd_uvd_check_multi")
+
+
+def uvd_loss_scale_next(scale, good_steps, skipped, *, growth_interval, growth=2.0, backoff=0.5, min_scale=1.0, max_scale=2.0 ** 24):
+    """The dynamic loss-scale schedule of class UVd as a pure function: (scale, good_steps) after one more step.  A skipped step
+    multiplies the scale by backoff and sets the counter to 0; growth_interval good steps in a row multiply it by growth and set the
+    counter to 0; the scale stays in [min_scale, max_scale].  With the defaults every scale is a power of two."""
+    scale, good_steps = float(scale), int(good_steps)
+    if skipped:
+        return max(scale * backoff, float(min_scale)), 0
+    good_steps += 1
+    if good_steps >= int(growth_interval):
+        return min(scale * growth, float(max_scale)), 0
+    return scale, good_steps
 
 
 def uvd_momentum_coefficients(k, momentum):
@@ -931,7 +983,7 @@ class UVd:
                  grad_clip_max_norm=None, preconditioner_update_probability=1.0,
                  exact_hessian_vector_product: bool = True, generator=None, state_dtype=None, group=None,
                  stage_backend=None, placement="auto", state_route="widen", state_rounding=None, step_tail="torch",
-                 momentum=0.0, weight_decay=0.0):
+                 momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000):
         # group (extension): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
         # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the
         # concatenation of the ranks' vectors in rank order, and U, V, d hold this rank's rows only.  A step then costs three
@@ -1021,6 +1073,24 @@ class UVd:
         self.momentum = _Hyper(momentum)
         self.weight_decay = _Hyper(weight_decay)
         self._m, self._m_step = None, 0
+        # nonfinite, loss_scale, loss_scale_growth_interval (extensions, off by default; see step()).  nonfinite="propagate" is the
+        # code path from before them.  "skip": a step whose v, h or g holds a non-finite value changes nothing.  loss_scale: None, a
+        # power of two, or "dynamic" (starts at 2^16, uvd_loss_scale_next); a _Hyper that holds the CURRENT scale.
+        if nonfinite not in ("propagate", "skip"):
+            raise ValueError("UVd: nonfinite must be 'propagate' or 'skip', got %r" % (nonfinite,))
+        self._guard = nonfinite == "skip"
+        if loss_scale is not None and not self._guard:
+            raise ValueError("UVd: loss_scale needs nonfinite='skip' (a scaled gradient that overflows must not reach the state)")
+        self._dynamic_scale = isinstance(loss_scale, str)
+        if self._dynamic_scale and loss_scale != "dynamic":
+            raise ValueError("UVd: loss_scale must be None, a power of two or 'dynamic', got %r" % (loss_scale,))
+        self.loss_scale = _Hyper(2.0 ** 16 if self._dynamic_scale else loss_scale)
+        self._loss_scale_value()
+        self.loss_scale_growth_interval = int(loss_scale_growth_interval)
+        if self.loss_scale_growth_interval < 1:
+            raise ValueError("UVd: loss_scale_growth_interval must be >= 1, got %r" % (loss_scale_growth_interval,))
+        self._good_steps, self._stamp = 0, 0
+        self.skipped_steps, self.last_step_skipped = 0, False
         self._tiny = torch.finfo(self._dtype).tiny                                           # :682
         self._delta_param_scale = torch.finfo(self._dtype).eps ** 0.5                        # :683
         self._param_sizes, self._param_cumsizes = uvd_param_index(self._params_with_grad)    # :684-685
@@ -1095,19 +1165,44 @@ class UVd:
             self._V.copy_(V)
             self._d.copy_(d)
 
-    def _flat(self, tensors, name, fd_scaled=False):
+    def _loss_scale_value(self):
+        """the current loss scale S as a float (1.0 without loss scaling), checked: a power of two"""
+        S = self.loss_scale.value
+        if S is None:
+            return 1.0
+        S = float(S)
+        if not (S > 0.0 and math.isfinite(S) and math.frexp(S)[0] == 0.5):
+            raise ValueError("UVd: loss_scale must be a power of two (1 / loss_scale must be exact), got %r" % (self.loss_scale.value,))
+        return S
+
+    def _pack_scale(self, fd_scaled, inv):
+        """the scale of a pack: 1 / delta_param_scale (:734-736) where fd_scaled, times inv = 1 / loss_scale, rounded once to fp32"""
+        base = self._fd_inv_scale if fd_scaled else 1.0
+        if inv == 1.0:
+            return base
+        import numpy as np
+        return float(np.float32(base) * np.float32(inv))
+
+    def _flat(self, tensors, name, fd_scaled=False, inv=1.0, slot=None):
         """psgd.py:729-730, :747: the per-parameter tensors as one flat vector in the state's type -- concatenated straight into
         the arena's region for it when the state is placed (no second copy, and the vector sits where the sweeps read it).
-        fd_scaled (fused tail only): the division of :734-736 rides on the pack."""
+        fd_scaled (fused tail only): the division of :734-736 rides on the pack.  inv: 1 / loss_scale, a power of two, folded into
+        the pack (torch tail: one exact multiplication).  slot (guarded step, fused tail): the pack checks what it writes and
+        stamps that word of the plan's flags."""
         if self._tail is not None:
             out = getattr(self._arena, name).view(-1) if self._arena is not None else self._flat_bufs.get(name)
             if out is None:
                 out = self._flat_bufs[name] = torch.empty(self._tail.total, dtype=torch.float32, device=self._device)
-            return uvd_pack([_c(x) for x in tensors], out, self._fd_inv_scale if fd_scaled else 1.0, plan=self._tail, role=name)
+            if slot is not None:
+                return uvd_pack([_c(x) for x in tensors], out, self._pack_scale(fd_scaled, inv), plan=self._tail, role=name,
+                                flag=self._tail.flags[slot:slot + 1], stamp=self._stamp)
+            return uvd_pack([_c(x) for x in tensors], out, self._pack_scale(fd_scaled, inv), plan=self._tail, role=name)
         parts = [torch.reshape(x, [-1]) for x in tensors]
         if self._arena is not None and all(x.dtype == self._state_dtype for x in parts):
-            return torch.cat(parts, 0, out=getattr(self._arena, name).view(-1))
-        return torch.cat(parts, 0).to(self._state_dtype)
+            flat = torch.cat(parts, 0, out=getattr(self._arena, name).view(-1))
+        else:
+            flat = torch.cat(parts, 0).to(self._state_dtype)
+        return flat if inv == 1.0 else flat.mul_(inv)
 
     def _momentum_buffer(self):
         """this rank's flat fp32 momentum vector: the arena's g region when the state is placed, else one zero-initialised tensor
@@ -1126,17 +1221,18 @@ class UVd:
             raise ValueError("UVd: weight_decay must be >= 0, got %r" % (wd,))
         return mom, wd
 
-    def _grad_flat(self, grads, mom):
-        """psgd.py:747; with momentum the gradients blended into the momentum buffer, which is returned in their place"""
+    def _grad_flat(self, grads, mom, inv=1.0, flat=None):
+        """psgd.py:747; with momentum the gradients blended into the momentum buffer, which is returned in their place.  inv:
+        1 / loss_scale, folded into the pack; flat: the flat fp32 gradient where the guarded step has formed it already"""
         if mom == 0.0:
             self._m_step = 0                                  # the buffer is not kept up: a later momentum warms up again
-            return self._flat(grads, "g")
+            return flat if flat is not None else self._flat(grads, "g", inv=inv)
         beta, omb = uvd_momentum_coefficients(self._m_step, mom)
         self._m_step += 1
         m = self._momentum_buffer()
         if self._tail is not None:
-            return uvd_pack_blend([_c(x) for x in grads], m, beta, plan=self._tail, role="g")
-        g = torch.cat([torch.reshape(x, [-1]) for x in grads], 0).to(torch.float32)
+            return uvd_pack_blend([_c(x) for x in grads], m, beta, self._pack_scale(False, inv), plan=self._tail, role="g")
+        g = flat if flat is not None else self._grad_cat(grads, inv)
         with torch.no_grad():
             if beta == 0.0:
                 m.copy_(g.mul(omb))                           # the buffer is not read (as in the kernel): NaN in it does not leak
@@ -1144,6 +1240,56 @@ class UVd:
                 m.mul_(beta)
                 m.add_(g.mul(omb))
         return m
+
+    def _grad_cat(self, grads, inv):
+        g = torch.cat([torch.reshape(x, [-1]) for x in grads], 0).to(torch.float32)
+        return g if inv == 1.0 else g * inv
+
+    def _guarded_grad(self, grads, mom, inv, others):
+        """The decision of a guarded step, then _grad_flat: the flat gradient (the momentum buffer with momentum), or None when v,
+        h (others: checked already by their packs on the fused tail) or the gradient holds a non-finite value -- in which case
+        nothing has been written but flat scratch vectors: the momentum blend runs only after the decision.  Row-sharded: every
+        rank's verdict crosses the ranks in ONE collective (sharded.all_reduce_max_i32_), issued here on every rank whatever it
+        saw, so that all ranks skip or none does.  The single host read of the step is here."""
+        flat = None
+        if self._tail is not None:
+            flags = self._tail.flags
+            if mom == 0.0:
+                flat = self._flat(grads, "g", inv=inv, slot=2)
+            else:               # the blend overwrites the buffer: judge the gradients where they are, blend on a good step only
+                uvd_check([_c(x) for x in grads], self._pack_scale(False, inv), plan=self._tail, role="g", flag=flags[2:3],
+                          stamp=self._stamp)
+            if self._group is None:
+                bad = self._stamp in flags.tolist()                                          # the 16 flag bytes: the host read
+            else:
+                bad = (flags == self._stamp).any()
+        else:
+            flat = self._flat(grads, "g", inv=inv) if mom == 0.0 else self._grad_cat(grads, inv)
+            ok = torch.isfinite(flat).all()
+            for x in others:
+                ok = ok & torch.isfinite(x).all()
+            bad = ~ok
+        if self._group is not None:
+            bad = self._sharded.all_reduce_max_i32_(bad.to(torch.int32).reshape(1), self._group)
+        if not isinstance(bad, bool):
+            bad = bool(bad.item())                                                           # ... or this one
+        if bad:
+            return None
+        return self._grad_flat(grads, mom, inv, flat)
+
+    def _guard_outcome(self, skipped, undo_vs=None):
+        """book-keeping of a guarded step once its decision is known; a skipped finite-difference step takes the perturbation of
+        :723 back, p <- T(p - v): the reference's own undo, within one rounding of T of the parameters before the step"""
+        if undo_vs is not None:
+            with torch.no_grad():
+                for p, v in zip(self._params_with_grad, undo_vs):
+                    p.sub_(v)
+        self.last_step_skipped = bool(skipped)
+        self.skipped_steps += int(bool(skipped))
+        if self._dynamic_scale:
+            S, self._good_steps = uvd_loss_scale_next(self._loss_scale_value(), self._good_steps, skipped,
+                                                      growth_interval=self.loss_scale_growth_interval)
+            self.loss_scale.assign(S)
 
     def _loss_of(self, closure_returns):
         return closure_returns if isinstance(closure_returns, torch.Tensor) else closure_returns[0]
@@ -1180,6 +1326,9 @@ class UVd:
                                      and, optional when loading, momentum and weight_decay (floats)
             momentum_buffer, momentum_step    only when momentum > 0: this rank's rows of the momentum buffer (fp32) and the number of
                                      steps blended into it
+            nonfinite, skipped_steps, loss_scale, loss_scale_good_steps    only when nonfinite="skip": "skip", the number of
+                                     skipped steps, the current loss scale (None without loss scaling) and the good steps
+                                     counted towards the next growth of a dynamic scale
             branch_rng               get_state() of the generator behind the coin flips: the generator= argument, else the
                                      module's branch generator; row-sharded, the synchronised generator all ranks draw from
 
@@ -1203,6 +1352,10 @@ class UVd:
             sd["momentum_buffer"], sd["momentum_step"] = host(self._momentum_buffer()), int(self._m_step)
         if self._native:
             sd["round_seed0"], sd["round_step"] = int(self._round_seed0), int(self._round_step)
+        if self._guard:
+            sd["nonfinite"], sd["skipped_steps"] = "skip", int(self.skipped_steps)
+            sd["loss_scale"] = None if self.loss_scale.value is None else float(self.loss_scale)
+            sd["loss_scale_good_steps"] = int(self._good_steps)
         return sd
 
     def load_state_dict(self, sd, *, strict=True, narrow_rounding=None, narrow_seed=None):
@@ -1211,7 +1364,10 @@ class UVd:
         assigned (momentum and weight_decay when the dict has them; momentum_buffer / momentum_step are restored, and a dict
         without them zeroes the buffer of a momentum optimizer and restarts its warm-up), the generator behind the coins gets the
         saved state (row-sharded: every rank loads the same bytes into the
-        synchronised generator; nothing is broadcast again) and, on the native route, so do round_seed0 / round_step.
+        synchronised generator; nothing is broadcast again) and, on the native route, so do round_seed0 / round_step.  A guarded
+        optimizer (nonfinite="skip") restores skipped_steps, loss_scale_good_steps and, when both sides scale the loss, loss_scale
+        where the dict has them and starts them fresh where it has not (a dict of an unguarded optimizer); an unguarded one
+        ignores them.
 
         Checked against this object (ValueError naming the key): format, rank, num_params, param_sizes (skipped when the dict
         holds None, as a resharded one does); with strict=True also num_params_global and row0.  strict=False is for loading a
@@ -1296,6 +1452,12 @@ class UVd:
                     self._momentum_buffer().zero_()
         if self._native and "round_seed0" in sd:
             self._round_seed0, self._round_step = int(sd["round_seed0"]), int(need("round_step"))
+        if self._guard:                  # a dict from an unguarded optimizer has none of these: the guard starts fresh
+            self.skipped_steps, self.last_step_skipped = int(sd.get("skipped_steps", 0)), False
+            self._good_steps = int(sd.get("loss_scale_good_steps", 0))
+            if sd.get("loss_scale") is not None and self.loss_scale.value is not None:
+                self.loss_scale.assign(float(sd["loss_scale"]))
+                self._loss_scale_value()
         with torch.no_grad():
             if how == "copy":
                 for k, mine in (("U", self._U), ("V", self._V), ("d", self._d)):
@@ -1346,7 +1508,31 @@ class UVd:
         return pre_grad
 
     def step(self, closure):
-        """psgd.py:692-764."""
+        """psgd.py:692-764.
+
+        Guarded (nonfinite="skip"; with the default "propagate" none of this runs: the same launches, the same bits, no host read):
+        a step whose flat v, h or g -- as written, scales included -- holds +-Inf or NaN is SKIPPED.  It never reaches the
+        preconditioner, the momentum blend or the parameter update: the bits of U, V, d, the parameters and the momentum buffer
+        and the counters behind momentum warm-up and stochastic rounding stay as they were; it has consumed the coin of :703 and
+        the probe vectors and nothing else.  skipped_steps counts such steps, last_step_skipped tells about the latest, and the
+        closure's return value is passed through as always.  On the finite-difference route the perturbation of :723 is taken
+        back by p <- T(p - v), the reference's own undo: the parameters are then within one rounding of T of their old values, not
+        bit-equal.  A step that leaves the preconditioner alone checks g only.
+        With the fused tail the check rides on the packs of h and g (and of v on the finite-difference route:
+        psgd_uvd_pack_check_f32 moves the bytes of the plain pack); with momentum the gradients are judged where they are
+        (uvd_check) and blended only on a good step.  The decision costs ONE device-to-host read, of the plan's 16 flag bytes: the
+        only host read a guarded step adds.  The torch tail decides by torch.isfinite(...).all() on the flat vectors (one read of
+        one bool).  Row-sharded, the ranks' verdicts cross in one extra collective per guarded step (a MAX over one int), issued at
+        the same point on every rank: all ranks skip or none does.
+
+        loss_scale=S: every gradient this step takes is that of loss * S (the closure is unchanged and returns the unscaled
+        loss), so the gradients, the Hessian-vector products and the perturbed gradients are S times larger where they are
+        formed, in the parameters' type; 1 / S, exact because S is a power of two, is folded into the pack scale of h and g (on
+        the finite-difference route into the product with 1 / delta_param_scale, rounded once on the host), v is not scaled.
+        "dynamic": S starts at 2^16, halves on a skipped step and doubles after loss_scale_growth_interval good steps in a row
+        (uvd_loss_scale_next).
+        Out of scope: a non-finite value that the state itself produces from finite inputs propagates as before, and the
+        functional preconditioner calls (update_precond_UVd_math_ and the others) are unchanged."""
         params = self._params_with_grad
         if self._group is None:
             update_Q = _draw_branch(float(self.preconditioner_update_probability), self._generator)   # :703
@@ -1354,12 +1540,18 @@ class UVd:
             update_Q = self._coins.draw(float(self.preconditioner_update_probability))       # the same coin on every rank
         exact = bool(self.exact_hessian_vector_product)
         mom, wd = self._hyper_momentum()
+        guard, fused = self._guard, self._tail is not None
+        S = self._loss_scale_value() if guard else 1.0
+        inv = 1.0 / S                                           # exact: S is a power of two
+        scaled = (lambda loss: loss) if S == 1.0 else (lambda loss: loss * S)
+        if guard:
+            self._stamp = self._stamp % (2 ** 31 - 1) + 1       # 1 .. 2^31 - 1, then 1 again: the flags are never zeroed
         vs = None
         if update_Q:
             if exact:                                                                         # :706-714
                 with torch.enable_grad():
                     closure_returns = closure()
-                    loss = self._loss_of(closure_returns)
+                    loss = scaled(self._loss_of(closure_returns))
                     grads = torch.autograd.grad(loss, params, create_graph=True)
                     vs = [_randn_like(p) for p in params]
                     Hvs = torch.autograd.grad(grads, params, vs)
@@ -1367,7 +1559,7 @@ class UVd:
             else:                                                                             # :715-727
                 with torch.enable_grad():
                     closure_returns = closure()
-                    grads = torch.autograd.grad(self._loss_of(closure_returns), params)
+                    grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
                 vs = [_randn_like(p) * self._delta_param_scale for p in params]
                 with torch.no_grad():
                     if self._tail is not None:
@@ -1376,22 +1568,35 @@ class UVd:
                         for p, v in zip(params, vs):
                             p.add_(v)
                 with torch.enable_grad():
-                    perturbed_grads = torch.autograd.grad(self._loss_of(closure()), params)
+                    perturbed_grads = torch.autograd.grad(scaled(self._loss_of(closure())), params)
                 Hvs = [pg - g for pg, g in zip(perturbed_grads, grads)]
-            v = self._flat(vs, "v", not exact)                                                # :729
-            h = self._flat(Hvs, "h", not exact)                                               # :730
-            if not exact and self._tail is None:                                              # :734-736
+            v = self._flat(vs, "v", not exact, slot=0 if guard and fused and not exact else None)        # :729
+            h = self._flat(Hvs, "h", not exact, inv, slot=1 if guard and fused else None)                 # :730
+            if not exact and not fused:                                                       # :734-736
                 v = v / self._delta_param_scale
                 h = h / self._delta_param_scale
-            grad = self._grad_flat(grads, mom)                                                # :747
+            if guard:
+                grad = self._guarded_grad(grads, mom, inv, (v, h))
+                self._guard_outcome(grad is None, vs if grad is None and not exact else None)
+                if grad is None:
+                    return closure_returns
+            else:
+                grad = self._grad_flat(grads, mom)                                            # :747
             pre_grad = self._precondition(v, h, grad)                                         # :732-733, :748
         else:                                                                                 # :737-744
             with torch.enable_grad():
                 closure_returns = closure()
-                grads = torch.autograd.grad(self._loss_of(closure_returns), params)
-            pre_grad = self._precondition(None, None, self._grad_flat(grads, mom))            # :747-748
+                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
+            if guard:
+                grad = self._guarded_grad(grads, mom, inv, ())
+                self._guard_outcome(grad is None)
+                if grad is None:
+                    return closure_returns
+            else:
+                grad = self._grad_flat(grads, mom)
+            pre_grad = self._precondition(None, None, grad)                                   # :747-748
         max_norm = float(self.grad_clip_max_norm)
-        if self._tail is not None:                                                            # :750-762 in the step-tail kernels
+        if fused:                                                                             # :750-762 in the step-tail kernels
             uvd_step_tail(params, pre_grad, float(self.lr_params), max_norm, self._tiny, vs if (not exact) and update_Q else None,
                           self._group, plan=self._tail, weight_decay=wd)
             return closure_returns

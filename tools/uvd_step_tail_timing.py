@@ -18,6 +18,10 @@ Peak memory: torch.cuda.max_memory_allocated over three further steps minus what
                                                               # momentum=0.9, and momentum=0.9 with weight_decay=0.01
     python tools/uvd_step_tail_timing.py --momentum --legs plain --root OTHER   # the plain leg of another checkout (one that has
                                                               # no momentum argument): the baseline of the comparison
+    python tools/uvd_step_tail_timing.py --guard              # the same shapes: plain against nonfinite="skip" (the checked packs and
+                                                              # the 16-byte host read), with a loss scale, and both with momentum=0.9
+                                                              # (one more read of the gradients); the legs alternate, --rounds times
+    python tools/uvd_step_tail_timing.py --guard --legs plain --root OTHER      # the plain leg of a checkout without the arguments
 """
 import argparse
 import os
@@ -118,6 +122,30 @@ def momentum_table(a):
             print(row, flush=True)
 
 
+GUARD_LEGS = {"plain": {}, "guard": {"nonfinite": "skip"}, "guard+scale": {"nonfinite": "skip", "loss_scale": 2.0 ** 10},
+              "momentum": {"momentum": 0.9}, "guard+momentum": {"nonfinite": "skip", "momentum": 0.9}}
+
+
+def guard_table(a):
+    """the fused step unguarded and guarded, in the same job and alternating (--rounds passes over the legs): a guarded step packs
+    with the check (the bytes of the plain pack), reads 16 bytes back on the host -- which also ends the host's run-ahead of the
+    device -- and with momentum reads the gradients once more"""
+    legs = a.legs.split(",")
+    print("# fused tail, fp32, r = 20, 256 tensors, clip on | leg: median step [min .. max] us   (root: %s)" % _root)
+    for N in ([4_000_000] if a.quick else [4_000_000, 100_000_000]):
+        steps = a.steps if N <= 4_000_000 else max(5, a.steps // 4)
+        for rnd in range(a.rounds):
+            row = "N=%d r=20 k=256 float32 round %d |" % (N, rnd)
+            for leg in legs:
+                params, opt, closure = build(N, 20, 256, torch.float32, True, "fused", **GUARD_LEGS[leg])
+                med, lo, hi = timed(lambda: opt.step(closure), steps, a.chunks, a.warm_seconds)
+                assert getattr(opt, "skipped_steps", 0) == 0
+                row += " %s: %.1f [%.1f .. %.1f] us |" % (leg, med * 1e6, lo * 1e6, hi * 1e6)
+                del params, opt, closure
+                torch.cuda.empty_cache()
+            print(row, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tail", choices=["torch", "fused", "both"], default="both")
@@ -127,10 +155,17 @@ def main():
     ap.add_argument("--warm-seconds", type=float, default=0.3)
     ap.add_argument("--trace", nargs=3, metavar=("N", "K", "TAIL"))
     ap.add_argument("--momentum", action="store_true", help="the momentum / weight-decay table instead of the tail table")
-    ap.add_argument("--legs", default="plain,momentum,momentum+decay", help="with --momentum: which legs (comma-separated)")
+    ap.add_argument("--guard", action="store_true", help="the guarded-step table instead of the tail table")
+    ap.add_argument("--rounds", type=int, default=2, help="with --guard: passes over the legs")
+    ap.add_argument("--legs", default=None, help="with --momentum / --guard: which legs (comma-separated; default: all)")
     ap.add_argument("--root", default=None, help="import the package from this checkout instead of the tool's own")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "this tool measures on the GPU"
+    if a.legs is None:
+        a.legs = ",".join(GUARD_LEGS if a.guard else MOMENTUM_LEGS)
+    if a.guard:
+        assert a.chunks >= 7 and all(leg in GUARD_LEGS for leg in a.legs.split(","))
+        return guard_table(a)
     if a.momentum:
         assert a.chunks >= 7 and all(leg in MOMENTUM_LEGS for leg in a.legs.split(","))
         return momentum_table(a)
