@@ -360,13 +360,13 @@ __global__ __launch_bounds__(kThreads) void k_update_d(float* d, const float* __
   for (long i = tid; i < n4; i += nth) {
     float4 a = d4[i];
     const float4 b = n4p[i];
-    a.x = a.x - (mu * a.x) * b.x;
-    a.y = a.y - (mu * a.y) * b.y;
-    a.z = a.z - (mu * a.z) * b.z;
-    a.w = a.w - (mu * a.w) * b.w;
+    a.x = uvd_d_step(a.x, mu, b.x);
+    a.y = uvd_d_step(a.y, mu, b.y);
+    a.z = uvd_d_step(a.z, mu, b.z);
+    a.w = uvd_d_step(a.w, mu, b.w);
     d4[i] = a;
   }
-  for (long i = n4 * 4 + tid; i < N; i += nth) d[i] = d[i] - (mu * d[i]) * nabla[i];
+  for (long i = n4 * 4 + tid; i < N; i += nth) d[i] = uvd_d_step(d[i], mu, nabla[i]);
 }
 
 // max|U|, max|V| over the flat [N*r] arrays                       psgd.py:563-564

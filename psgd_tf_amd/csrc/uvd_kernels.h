@@ -956,6 +956,32 @@ __global__ __launch_bounds__(kThreads) void k_apply4_s3(const float* V, const fl
                               });
 }
 
+// The row-local expressions that decide the stored state (nablaD, the rank-2 update of a factor row, the d step), written with
+// the fused multiply-adds spelled out and contraction off for the rest: k_update_s2 is instantiated with and without FUSE, and the d
+// step runs in k_update_d (psgd_uvd.hip) and in k_uvd_final.  Left to the compiler, each instantiation picks which product of
+// x y - z w joins the subtraction on its own, and the fused call and update + apply part ways in the last place -- after 200
+// steps by a few ulp (tests/test_trajectory_gpu.py).  Spelled out, every route rounds alike.
+__device__ __forceinline__ float uvd_qh(float dd, float hh, float us1) {           // d h + U s1, d h rounded as psgd.py:569 does
+#pragma clang fp contract(off)
+  const float t = dd * hh;
+  return t + us1;
+}
+__device__ __forceinline__ float uvd_nabla(float Ph, float hh, float vv, float invPv) {     // Ph h - v invPv
+#pragma clang fp contract(off)
+  const float z = vv * invPv;
+  return fmaf(Ph, hh, -z);
+}
+__device__ __forceinline__ float uvd_rank2(float x, float mu, float a, float c1, float b, float c2) {   // x - mu (a c1 - b c2)
+#pragma clang fp contract(off)
+  const float z = b * c2;
+  return fmaf(-mu, fmaf(a, c1, -z), x);
+}
+__device__ __forceinline__ float uvd_d_step(float d, float mu, float nab) {        // d - (mu d) nablaD
+#pragma clang fp contract(off)
+  const float md = mu * d;
+  return fmaf(-md, nab, d);
+}
+
 // update sweep 2 (row-local; psgd.py:569-601 / :603-615 given the r-vectors):
 //   a = t + U s1 (Qh)            b = w - V x1 (invQtv)
 //   Ph = d (a + V s2)            invPv = (b - U x2) / d
@@ -989,25 +1015,24 @@ __global__ __launch_bounds__(kThreads) void k_update_s2(float* U, float* V, cons
   const float* const (&vecs)[NV] = reinterpret_cast<const float* const (&)[NV]>(vecs_);
   auto body = [&](long row, bool valid, float (&x)[2][R], float (&s)[NV]) {
     const float dd = s[0], vv = s[1], hh = s[2];
-    const float t = dd * hh;
     const float ww = valid ? vv / dd : 0.0f;
-    const float a = t + dot_row<R>(x[0], coef + K::kS1);
+    const float a = uvd_qh(dd, hh, dot_row<R>(x[0], coef + K::kS1));
     const float b = ww - dot_row<R>(x[1], coef + K::kX1);
     const float Ph = dd * (a + dot_row<R>(x[1], coef + K::kS2));
     const float invPv = valid ? (b - dot_row<R>(x[0], coef + K::kX2)) / dd : 0.0f;
-    const float nd = Ph * hh - vv * invPv;
+    const float nd = uvd_nabla(Ph, hh, vv, invPv);
     if (valid) {
       stream_store<NT>(nabla + row, nd);
       vmax = amaxf(vmax, fabsf(nd));
     }
     if constexpr (UPDATE_U) {
 #pragma unroll
-      for (int c = 0; c < R; ++c) x[0][c] = x[0][c] - mu * (a * coef[K::kC1 + c] - b * coef[K::kC2 + c]);
+      for (int c = 0; c < R; ++c) x[0][c] = uvd_rank2(x[0][c], mu, a, coef[K::kC1 + c], b, coef[K::kC2 + c]);
     } else {
       const float al = a + dot_row<R>(x[1], coef + K::kC1);
       const float be = b + dot_row<R>(x[1], coef + K::kC2);
 #pragma unroll
-      for (int c = 0; c < R; ++c) x[1][c] = x[1][c] - mu * (al * coef[K::kC1 + c] - be * coef[K::kC2 + c]);
+      for (int c = 0; c < R; ++c) x[1][c] = uvd_rank2(x[1][c], mu, al, coef[K::kC1 + c], be, coef[K::kC2 + c]);
     }
     if constexpr (FUSE) {
       const float tg = dd * s[NV - 1];          // d .* g        (rows past N: zero-filled)
@@ -1040,7 +1065,7 @@ __global__ __launch_bounds__(kThreads) void k_uvd_final(const float* U, const fl
   const float* const vecs[3] = {d, nabla, g};
   sweep_rows<R, 2, 3, -1, NT>(mats, vecs, nullptr, N, lds[wave_in_block()],
                               [&](long row, bool valid, float (&x)[2][R], float (&s)[3]) {
-                                const float dn = s[0] - (mu * s[0]) * s[1];
+                                const float dn = uvd_d_step(s[0], mu, s[1]);
                                 const float g1 = dn * s[2] + dot_row<R>(x[0], coef);
                                 const float o = dn * (g1 + dot_row<R>(x[1], coef + R));
                                 if (valid) {
