@@ -58,6 +58,8 @@ extern "C" {
  *     psgd_uvd_pack_blend_f32 and psgd_uvd_param_update_multi_wd, momentum and decoupled weight decay in the tail of UVd.step
  *     (new symbols only: still 7).
  *     psgd_uvd_pack_check_f32 and psgd_uvd_check_multi, the non-finite guard of UVd.step (new symbols only: still 7).
+ *     psgd_multi_sumsq_f32, psgd_multi_param_update_f32 and psgd_multi_diff_scale_f32, the step tail on lists of tensors of
+ *     class Kron (new symbols only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -411,6 +413,34 @@ int psgd_uvd_param_update_multi(const void *param_segs, const void *vs_segs, int
 int psgd_uvd_param_update_multi_wd(const void *param_segs, const void *vs_segs, int k, const void *chunks, int64_t nchunks, int dtype,
                                    const float *pre_grad, float lr, const double *sumsq, float max_norm, float tiny, float wd,
                                    void *stream);
+
+/* ------------------------------------------------- step tail on lists of tensors ---
+ * What an optimizer does around per-layer preconditioner calls (class Kron: mnist_with_lenet5.py:54-56 and the finite-difference
+ * route of psgd.py:716-727, :734-736, :761) when NO operand is a flat vector: every operand is a list of k fp32 tensors with its own
+ * segment table (psgd_multi_tail.hip).  Tables as above; `start` is not read.  All tables of one call describe tensors of the same
+ * element counts and share one chunk table; a chunk never runs past the shortest of its segments.  fp32 only.
+ * Null tables, k < 0 and nchunks < 0 return PSGD_ERR_BAD_ARG before any HIP call; nchunks == 0 is a no-op (nothing is written).   */
+#define PSGD_MULTI_SUMSQ_WS_BYTES  8192   /* workspace of psgd_multi_sumsq_f32 (8-byte aligned, needs no initialisation) */
+
+/* out[0] = sum over every element of every tensor of fl32(x * x), summed in fp64: one partial per workgroup over a fixed set of
+ * chunks, lanes -> waves -> workgroup folded in a fixed order, then a one-workgroup fold of the partials: two launches, no atomics,
+ * the same bits on every call.  out: 8-byte aligned.  Only the first PSGD_MULTI_SUMSQ_WS_BYTES bytes of ws are touched; a missing,
+ * short or misaligned workspace is PSGD_ERR_WORKSPACE (ws == NULL: PSGD_ERR_BAD_ARG).                                            */
+int psgd_multi_sumsq_f32(const void *segs, int k, const void *chunks, int64_t nchunks, double *out, void *ws, int64_t ws_bytes,
+                         void *stream);
+
+/* For every element of every parameter, in ONE launch, every operation rounded to nearest even on its own:
+ *     delta = fl32(lr_eff * g[i]);   vs_segs given: delta = fl32(delta + v[i]);   p[i] = fl32(p[i] - delta)
+ * lr_eff = lr when sumsq is NULL; otherwise lr_eff = fl32(lr * min(max_norm / (sqrt(*sumsq) + tiny), 1)), evaluated in fp64 on the
+ * device from the double psgd_multi_sumsq_f32 left: no host read; a NaN *sumsq makes lr_eff NaN.
+ * grad_segs == NULL (vs_segs required, sumsq must be NULL): p[i] = fl32(p[i] + v[i]), the perturbation of psgd.py:723.          */
+int psgd_multi_param_update_f32(const void *param_segs, const void *grad_segs, const void *vs_segs, int k, const void *chunks,
+                                int64_t nchunks, float lr, const double *sumsq, float max_norm, float tiny, void *stream);
+
+/* h[i] = fl32(fl32(a[i] - b[i]) * s) and, when v_segs and x_segs are given (both or neither), x[i] = fl32(v[i] * s): the
+ * finite-difference dG = (g' - g) / delta and dX = v / delta of psgd.py:727, :734-736 with s = 1 / delta, in ONE launch.         */
+int psgd_multi_diff_scale_f32(const void *a_segs, const void *b_segs, const void *h_segs, const void *v_segs, const void *x_segs,
+                              int k, const void *chunks, int64_t nchunks, float s, void *stream);
 
 /* Tuning knobs for experiments (not part of the stable ABI).
  * key 0: streaming policy (0 = automatic: non-temporal when U,V exceed the Infinity Cache,

@@ -23,6 +23,7 @@ UVD_TAIL_CHUNK = 4096    # PSGD_UVD_TAIL_CHUNK: elements per entry of the chunk 
 UVD_SUMSQ_WS_BYTES = 8192
 UVD_TAIL_MAX_GRID = 2048                         # kMaxGrid of psgd_uvd_tail.hip: workgroups of pack / update; further chunks are grid-stride
 UVD_SUMSQ_PARTIALS = UVD_SUMSQ_WS_BYTES // 8     # kSumsqBlocks: workgroups (one fp64 partial each) of the sum of squares
+MULTI_SUMSQ_WS_BYTES = 8192                      # PSGD_MULTI_SUMSQ_WS_BYTES: workspace of psgd_multi_sumsq_f32 (psgd_multi_tail.hip)
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2     # PSGD_DTYPE_*
 SPLU_MAX_RANK = 64       # PSGD_SPLU_MAX_RANK: the native sparse-LU entry points (round 5)
 # psgd_kron_dd_route_flags bits (PSGD_KRON_ROUTE_* of include/psgd_hip.h)
@@ -128,6 +129,9 @@ SIGNATURES = {
     "psgd_uvd_param_update_multi": (_int, [_c_f32p, _c_f32p, _int, _c_f32p, _i64, _int, _c_f32p, _flt, _c_f32p, _flt, _flt, _strm]),
     "psgd_uvd_param_update_multi_wd": (_int, [_c_f32p, _c_f32p, _int, _c_f32p, _i64, _int, _c_f32p, _flt, _c_f32p, _flt, _flt, _flt,
                                        _strm]),
+    "psgd_multi_sumsq_f32": (_int, [_c_f32p, _int, _c_f32p, _i64, _c_f32p, _c_ws, _i64, _strm]),
+    "psgd_multi_param_update_f32": (_int, [_c_f32p, _c_f32p, _c_f32p, _int, _c_f32p, _i64, _flt, _c_f32p, _flt, _flt, _strm]),
+    "psgd_multi_diff_scale_f32": (_int, [_c_f32p] * 5 + [_int, _c_f32p, _i64, _flt, _strm]),
     "psgd_splu_workspace_bytes": (_i64, [_i64, _int]),
     "psgd_splu_apply_f32": (_int, [_c_f32p] * 6 + [_i64, _int, _c_ws, _i64, _strm]),
     "psgd_splu_update_f32": (_int, [_c_f32p] * 10 + [_i64, _int, ctypes.c_float, ctypes.c_float, _c_ws, _i64, _strm]),

@@ -1,0 +1,298 @@
+// psgd_multi_tail.hip -- the tail of a step on LISTS of fp32 tensors (class Kron: mnist_with_lenet5.py:54-56 and the finite-difference
+// route of psgd.py:716-727, :734-736, :761) on gfx950, whatever the number of tensors.
+//
+//   psgd_multi_sumsq_f32         sum of fl32(x x) over every element of every tensor -> one device double       (the clip norm's square)
+//   psgd_multi_param_update_f32  p <- p - fl32(lr_eff g),  with vs: p <- p - fl32(fl32(lr_eff g) + v);  without g: p <- p + v
+//   psgd_multi_diff_scale_f32    h <- fl32(fl32(a - b) s),  and x <- fl32(v s) when given
+//
+// The tables are those of psgd_uvd_tail.hip: a SEGMENT is one tensor {pointer, start, count}, a CHUNK one piece of at most
+// PSGD_UVD_TAIL_CHUNK consecutive elements of one segment {segment index, offset}.  Here EVERY operand is a list: each has its own
+// segment table, all tables of a call describe tensors of the same sizes, one chunk table serves them all, and `start` is not read.
+// A chunk never runs past the shortest of its segments, whatever the tables say.
+//
+// HBM-bound streaming as in k_uvd_pack: inside a chunk the first stored operand is brought to a 16-byte boundary by a scalar head,
+// the body moves 4 fp32 per lane and access, a scalar tail finishes; the other operands go through vector types whose declared
+// alignment is the element's, so tensors that start at any float still take wide accesses.
+//
+// The sum of squares rounds each product to fp32, accumulates in fp64 per lane, folds lanes -> waves -> workgroup in a fixed order
+// into one fp64 partial per workgroup; workgroup b takes chunks b, b + nb, b + 2 nb, ... with nb a function of nchunks alone, and a
+// second one-workgroup launch folds the partials in index order: no atomics, the same bits on every call.
+//
+// No entry point allocates or synchronises; argument checks return before any HIP call.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "psgd_hip.h"
+
+// The roundings are the contract (bit-equal to the torch expressions they replace): no product may be fused into a following sum.
+#pragma clang fp contract(off)
+
+namespace psgdm {
+
+constexpr int kT = 256;                    // threads per workgroup
+constexpr int kChunk = PSGD_UVD_TAIL_CHUNK;
+constexpr int kMaxGrid = 2048;             // 8 workgroups per CU; the rest is grid-stride
+constexpr int kSumsqBlocks = 1024;         // partials of the sum of squares: PSGD_MULTI_SUMSQ_WS_BYTES / 8
+static_assert(kSumsqBlocks * 8 == PSGD_MULTI_SUMSQ_WS_BYTES, "workspace constant of the header");
+
+struct Seg {
+  uint64_t ptr;
+  int64_t start, count;
+};
+struct Chunk {
+  int64_t seg, off;
+};
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));       // 16 bytes from any fp32 element
+
+// elements in front of the first 16-byte boundary at or after p, at most n
+__device__ __forceinline__ int head_of(const void* p, int n) {
+  const int h = (int)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) / 4;
+  return h < n ? h : n;
+}
+
+// One chunk of a call: its element count (0: nothing to do) and the element pointers of up to five operands.
+template <int kOps>
+struct Piece {
+  float* p[kOps];
+  int n;
+};
+
+// tabs[j] == nullptr: operand j is absent (its pointer stays null and its length does not count)
+template <int kOps>
+__device__ __forceinline__ Piece<kOps> piece_of(const Seg* const (&tabs)[kOps], const Chunk ch, int k) {
+  Piece<kOps> r;
+  r.n = 0;
+#pragma unroll
+  for (int j = 0; j < kOps; ++j) r.p[j] = nullptr;
+  if ((uint64_t)ch.seg >= (uint64_t)k || ch.off < 0) return r;      // a table that does not belong to these segments moves nothing
+  int64_t left = kChunk;
+#pragma unroll
+  for (int j = 0; j < kOps; ++j) {
+    if (!tabs[j]) continue;
+    const Seg s = tabs[j][ch.seg];
+    const int64_t l = s.count - ch.off;
+    left = l < left ? l : left;
+    r.p[j] = reinterpret_cast<float*>(s.ptr) + ch.off;
+  }
+  r.n = left > 0 ? (int)left : 0;
+  return r;
+}
+
+// ------------------------------------------------------------------------------------------------------------- sum of squares
+__device__ __forceinline__ double block_sum(double v, double* lds) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) lds[w] = v;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < kT / 64; ++k) s += lds[k];
+  return s;
+}
+
+__global__ __launch_bounds__(kT) void k_multi_sumsq_partial(const Seg* __restrict__ segs, const Chunk* __restrict__ chunks,
+                                                            int64_t nchunks, int k, double* __restrict__ partial) {
+  __shared__ double lds[kT / 64];
+  const int t = threadIdx.x;
+  double acc = 0.0;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Seg* const tabs[1] = {segs};
+    const Piece<1> pc = piece_of<1>(tabs, chunks[c], k);
+    const int n = pc.n;
+    if (n <= 0) continue;
+    const float* x = pc.p[0];
+    const int head = head_of(x, n);
+    const int nvec = (n - head) / 4;
+    if (t < head) acc += (double)(x[t] * x[t]);
+#pragma unroll 2
+    for (int g = t; g < nvec; g += kT) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(x + head + 4 * g);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc += (double)(v[e] * v[e]);
+    }
+    const int i = head + nvec * 4 + t;
+    if (i < n) acc += (double)(x[i] * x[i]);
+  }
+  const double s = block_sum(acc, lds);
+  if (t == 0) partial[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kT) void k_multi_sumsq_fold(const double* __restrict__ partial, int n, double* __restrict__ out) {
+  __shared__ double lds[kT / 64];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += kT) acc += partial[i];
+  const double s = block_sum(acc, lds);
+  if (threadIdx.x == 0) out[0] = s;
+}
+
+// ------------------------------------------------------------------------------------------------------------ parameter update
+// kPre: delta = fl32(lr_eff g); kVs: delta = fl32(delta + v); p = fl32(p - delta).  !kPre (kVs): p = fl32(p + v).  Every product,
+// sum and difference is rounded on its own.
+template <bool kPre, bool kVs>
+__device__ __forceinline__ float update_one(float p, float g, float v, float lr_eff) {
+  if constexpr (!kPre) {
+    return p + v;
+  } else {
+    float delta = lr_eff * g;
+    if constexpr (kVs) delta = delta + v;
+    return p - delta;
+  }
+}
+
+template <bool kPre, bool kVs>
+__global__ __launch_bounds__(kT) void k_multi_param_update(const Seg* __restrict__ psegs, const Seg* __restrict__ gsegs,
+                                                           const Seg* __restrict__ vsegs, const Chunk* __restrict__ chunks,
+                                                           int64_t nchunks, int k, float lr, const double* __restrict__ sumsq,
+                                                           float max_norm, float tiny) {
+  const int t = threadIdx.x;
+  float lr_eff = lr;
+  if (kPre && sumsq) {        // lr_eff = fl32(lr * min(max_norm / (sqrt(sumsq) + tiny), 1)) in fp64, one rounding
+    // the minimum propagates NaN as torch.minimum does: a NaN norm makes lr_eff, and with it every parameter, NaN
+    const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
+    lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
+  }
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Seg* const tabs[3] = {psegs, kPre ? gsegs : nullptr, kVs ? vsegs : nullptr};
+    const Piece<3> pc = piece_of<3>(tabs, chunks[c], k);
+    const int n = pc.n;
+    if (n <= 0) continue;
+    float* p = pc.p[0];
+    const float* g = pc.p[1];
+    const float* v = pc.p[2];
+    const int head = head_of(p, n);
+    const int nvec = (n - head) / 4;
+    if (t < head) p[t] = update_one<kPre, kVs>(p[t], kPre ? g[t] : 0.f, kVs ? v[t] : 0.f, lr_eff);
+#pragma unroll 2
+    for (int q = t; q < nvec; q += kT) {
+      const int i = head + q * 4;
+      f32x4 x = *reinterpret_cast<const f32x4*>(p + i);
+      f32x4 gg = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (kPre) gg = *reinterpret_cast<const f32x4_u*>(g + i);
+      if constexpr (kVs) vv = *reinterpret_cast<const f32x4_u*>(v + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) x[e] = update_one<kPre, kVs>(x[e], gg[e], vv[e], lr_eff);
+      *reinterpret_cast<f32x4*>(p + i) = x;
+    }
+    const int i = head + nvec * 4 + t;
+    if (i < n) p[i] = update_one<kPre, kVs>(p[i], kPre ? g[i] : 0.f, kVs ? v[i] : 0.f, lr_eff);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------- difference and scale
+// h = fl32(fl32(a - b) s); kX: x = fl32(v s).  The 16-byte body is aligned on h; x is stored through the element-aligned type.
+template <bool kX>
+__global__ __launch_bounds__(kT) void k_multi_diff_scale(const Seg* __restrict__ asegs, const Seg* __restrict__ bsegs,
+                                                         const Seg* __restrict__ hsegs, const Seg* __restrict__ vsegs,
+                                                         const Seg* __restrict__ xsegs, const Chunk* __restrict__ chunks,
+                                                         int64_t nchunks, int k, float s) {
+  const int t = threadIdx.x;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Seg* const tabs[5] = {asegs, bsegs, hsegs, kX ? vsegs : nullptr, kX ? xsegs : nullptr};
+    const Piece<5> pc = piece_of<5>(tabs, chunks[c], k);
+    const int n = pc.n;
+    if (n <= 0) continue;
+    const float* a = pc.p[0];
+    const float* b = pc.p[1];
+    float* h = pc.p[2];
+    const float* v = pc.p[3];
+    float* x = pc.p[4];
+    const int head = head_of(h, n);
+    const int nvec = (n - head) / 4;
+    if (t < head) {
+      const float d = a[t] - b[t];
+      h[t] = d * s;
+      if constexpr (kX) x[t] = v[t] * s;
+    }
+#pragma unroll 2
+    for (int q = t; q < nvec; q += kT) {
+      const int i = head + q * 4;
+      const f32x4_u aa = *reinterpret_cast<const f32x4_u*>(a + i);
+      const f32x4_u bb = *reinterpret_cast<const f32x4_u*>(b + i);
+      f32x4 hh;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float d = aa[e] - bb[e];
+        hh[e] = d * s;
+      }
+      *reinterpret_cast<f32x4*>(h + i) = hh;
+      if constexpr (kX) {
+        const f32x4_u vv = *reinterpret_cast<const f32x4_u*>(v + i);
+        f32x4_u xx;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xx[e] = vv[e] * s;
+        *reinterpret_cast<f32x4_u*>(x + i) = xx;
+      }
+    }
+    const int i = head + nvec * 4 + t;
+    if (i < n) {
+      const float d = a[i] - b[i];
+      h[i] = d * s;
+      if constexpr (kX) x[i] = v[i] * s;
+    }
+  }
+}
+
+static int grid_for(int64_t nchunks) { return (int)(nchunks < kMaxGrid ? nchunks : kMaxGrid); }
+static int launched() { return hipGetLastError() == hipSuccess ? PSGD_OK : PSGD_ERR_LAUNCH; }
+
+}  // namespace psgdm
+
+using namespace psgdm;
+
+extern "C" {
+
+int psgd_multi_sumsq_f32(const void* segs, int k, const void* chunks, int64_t nchunks, double* out, void* ws, int64_t ws_bytes,
+                         void* stream) {
+  if (!segs || !chunks || !out || ((uintptr_t)out & 7) || !ws || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
+  if (ws_bytes < PSGD_MULTI_SUMSQ_WS_BYTES || ((uintptr_t)ws & 7)) return PSGD_ERR_WORKSPACE;
+  if (nchunks == 0) return PSGD_OK;                                           // out is NOT written: the sum of nothing is the caller's
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = (int)(nchunks < kSumsqBlocks ? nchunks : kSumsqBlocks);      // a function of nchunks alone: the partition never changes
+  hipLaunchKernelGGL(k_multi_sumsq_partial, dim3(nb), dim3(kT), 0, st, (const Seg*)segs, (const Chunk*)chunks, nchunks, k,
+                     (double*)ws);
+  hipLaunchKernelGGL(k_multi_sumsq_fold, dim3(1), dim3(kT), 0, st, (const double*)ws, nb, out);
+  return launched();
+}
+
+int psgd_multi_param_update_f32(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
+                                int64_t nchunks, float lr, const double* sumsq, float max_norm, float tiny, void* stream) {
+  if (!param_segs || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
+  if (!grad_segs && (!vs_segs || sumsq)) return PSGD_ERR_BAD_ARG;            // nothing to do, or a clip norm without a gradient
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const Seg* ps = (const Seg*)param_segs;
+  const Seg* gs = (const Seg*)grad_segs;
+  const Seg* vsg = (const Seg*)vs_segs;
+  const Chunk* ch = (const Chunk*)chunks;
+  const int grid = grid_for(nchunks);
+  if (!gs)
+    hipLaunchKernelGGL((k_multi_param_update<false, true>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq,
+                       max_norm, tiny);
+  else if (vsg)
+    hipLaunchKernelGGL((k_multi_param_update<true, true>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq,
+                       max_norm, tiny);
+  else
+    hipLaunchKernelGGL((k_multi_param_update<true, false>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq,
+                       max_norm, tiny);
+  return launched();
+}
+
+int psgd_multi_diff_scale_f32(const void* a_segs, const void* b_segs, const void* h_segs, const void* v_segs, const void* x_segs,
+                              int k, const void* chunks, int64_t nchunks, float s, void* stream) {
+  if (!a_segs || !b_segs || !h_segs || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
+  if ((v_segs == nullptr) != (x_segs == nullptr)) return PSGD_ERR_BAD_ARG;   // v and x go together
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const Chunk* ch = (const Chunk*)chunks;
+  const int grid = grid_for(nchunks);
+  if (x_segs)
+    hipLaunchKernelGGL(k_multi_diff_scale<true>, dim3(grid), dim3(kT), 0, st, (const Seg*)a_segs, (const Seg*)b_segs,
+                       (const Seg*)h_segs, (const Seg*)v_segs, (const Seg*)x_segs, ch, nchunks, k, s);
+  else
+    hipLaunchKernelGGL(k_multi_diff_scale<false>, dim3(grid), dim3(kT), 0, st, (const Seg*)a_segs, (const Seg*)b_segs,
+                       (const Seg*)h_segs, (const Seg*)v_segs, (const Seg*)x_segs, ch, nchunks, k, s);
+  return launched();
+}
+
+}  // extern "C"

@@ -1,0 +1,473 @@
+"""class Kron: the per-layer Kronecker-product preconditioner as an optimizer, and the multi-tensor kernels of its step tail.
+
+The reference has no such class: its Kron demos hand-write the step (mnist_with_lenet5.py:43-57, repeated in
+lstm_with_xor_problem.py and the NMT demo).  The interface and the step(closure) contract are those of class UVd (psgd.py:630-764);
+the arithmetic is that of mnist_with_lenet5.py:43-57, with the finite-difference Hessian-vector product of psgd.py:716-727.
+
+    multi_sumsq, multi_param_update, multi_diff_scale     thin wrappers of the list kernels (csrc/psgd_multi_tail.hip)
+    kron_initial_factors                                  the initial factor pair of one layer
+    Kron(...).step(closure)                               the optimizer
+"""
+import contextlib
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import kron as _kron
+from . import preconditioned_stochastic_gradient_descent as _psgd
+
+_f32 = torch.float32
+_TINY = float(np.finfo(np.float32).tiny)
+_DELTA = float(np.float32(np.sqrt(np.float32(np.finfo(np.float32).eps))))      # psgd.py:683 for fp32 parameters
+_FD_INV = float(np.float32(1.0) / np.float32(_DELTA))                           # the s of dG = (g' - g) s, dX = v s
+
+
+# --------------------------------------------------------------------------- list kernels
+class MultiTailPlan(_psgd.UVdTailPlan):
+    """The chunk table, the segment tables (one per role), the device double of the clip norm and the workspace of its reduction for
+    lists of fp32 tensors of fixed sizes.  Calls that share a plan must run on one stream."""
+
+    def __init__(self, sizes, device):
+        super().__init__(sizes, torch.float32, device)
+        self.ws = torch.empty(_lib.MULTI_SUMSQ_WS_BYTES, dtype=torch.uint8, device=self.device)
+
+
+_multi_plans = {}
+
+
+def _check_list(what, name, tensors, sizes=None, device=None):
+    """one operand list of a list kernel: fp32 contiguous tensors on one HIP device, sizes[i] elements at position i"""
+    tensors = list(tensors)
+    if sizes is not None and len(tensors) != len(sizes):
+        raise ValueError("%s: %s has %d tensors, the first list has %d" % (what, name, len(tensors), len(sizes)))
+    for i, t in enumerate(tensors):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s[%d] is not a torch tensor (%r)" % (what, name, i, type(t)))
+        if t.dtype != _f32:
+            raise TypeError("%s: %s[%d] must be float32, got %s" % (what, name, i, t.dtype))
+        if not t.is_cuda:
+            raise _lib.PsgdHipError("%s runs on the HIP device only (%s[%d] is on %s); no CPU fallback" % (what, name, i, t.device))
+        if device is None:
+            device = t.device
+        if t.device != device:
+            raise ValueError("%s: all tensors must be on one device, %s[%d] is on %s, not %s" % (what, name, i, t.device, device))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s[%d] (shape %s) is not contiguous" % (what, name, i, tuple(t.shape)))
+        if sizes is not None and int(t.numel()) != sizes[i]:
+            raise ValueError("%s: %s[%d] has %d elements, position %d of the first list has %d"
+                             % (what, name, i, t.numel(), i, sizes[i]))
+    return tensors, device
+
+
+def _lists(what, first, *others, plan=None):
+    """checks every list against the first one; returns (lists, plan)"""
+    name0, t0 = first
+    t0, dev = _check_list(what, name0, t0)
+    if not t0:
+        raise ValueError("%s: empty tensor list" % what)
+    sizes = tuple(int(t.numel()) for t in t0)
+    out = [t0]
+    for name, ts in others:
+        out.append(None if ts is None else _check_list(what, name, ts, sizes, dev)[0])
+    if plan is None:
+        key = (dev, sizes)
+        plan = _multi_plans.get(key)
+        if plan is None:
+            while len(_multi_plans) >= 16:
+                _multi_plans.pop(next(iter(_multi_plans)))
+            plan = _multi_plans[key] = MultiTailPlan(sizes, dev)
+    elif plan.sizes != sizes or plan.device != dev:
+        raise ValueError("%s: the plan is for sizes %r on %s, the tensors have %r on %s" % (what, plan.sizes, plan.device, sizes, dev))
+    return out, plan
+
+
+def multi_sumsq(tensors, *, plan=None, out=None, ws=None):
+    """out[0] = sum of fl32(x * x) over every element of every tensor, in fp64 and in a fixed order (psgd_multi_sumsq_f32: two launches
+    whatever len(tensors), the same bits on every call).  tensors: contiguous fp32 tensors on one HIP device, empty ones allowed.
+    out: a float64 device tensor of one element (default: the plan's); ws: a uint8 device tensor of at least
+    _lib.MULTI_SUMSQ_WS_BYTES bytes (default: the plan's).  Returns out."""
+    (tensors,), plan = _lists("multi_sumsq", ("tensors", tensors), plan=plan)
+    out = plan.sumsq if out is None else out
+    ws = plan.ws if ws is None else ws
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != plan.device or out.numel() < 1:
+        raise ValueError("multi_sumsq: out must be a float64 tensor of at least one element on %s" % (plan.device,))
+    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != plan.device or not ws.is_contiguous():
+        raise ValueError("multi_sumsq: ws must be a contiguous uint8 tensor on %s" % (plan.device,))
+    if not plan.nchunks:
+        out[:1].zero_()                                              # the kernel launches nothing: the sum of nothing is 0
+        return out
+    rc = _lib.load().psgd_multi_sumsq_f32(plan.table("sumsq", tensors, "multi_sumsq"), len(tensors), plan.chunks.data_ptr(),
+                                          plan.nchunks, out.data_ptr(), ws.data_ptr(), ws.numel(), _psgd._stream_ptr(plan.device))
+    _lib.check(rc, "psgd_multi_sumsq_f32")
+    return out
+
+
+def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None, tiny=None, *, plan=None):
+    """For all parameters in ONE launch (psgd_multi_param_update_f32), every operation rounded to float32 on its own:
+        p <- p - lr_eff * g                     vs None
+        p <- p - (lr_eff * g + v)               vs given (the undo of the finite-difference perturbation, psgd.py:761)
+        p <- p + v                              grads None (the perturbation itself, psgd.py:723; lr, sumsq are not used)
+    lr_eff = float32(lr) when sumsq is None; with sumsq (a float64 device tensor of one element, what multi_sumsq left) and max_norm,
+    lr_eff = float32(lr * min(max_norm / (sqrt(sumsq) + tiny), 1)) formed on the device in fp64: no host read; a NaN sumsq makes
+    every parameter NaN, as torch.minimum does.  tiny defaults to the smallest normal float32.
+    The parameters are written through their pointers: autograd's version counters do not move."""
+    what = "multi_param_update"
+    (params, grads, vs), plan = _lists(what, ("params", params), ("grads", grads), ("vs", vs), plan=plan)
+    if grads is None and (vs is None or sumsq is not None):
+        raise ValueError("%s: grads=None adds vs to the parameters; it needs vs and takes no sumsq" % what)
+    if (sumsq is None) != (max_norm is None):
+        raise ValueError("%s: sumsq and max_norm go together" % what)
+    if sumsq is not None and (not isinstance(sumsq, torch.Tensor) or sumsq.dtype != torch.float64 or sumsq.device != plan.device
+                              or sumsq.numel() < 1):
+        raise ValueError("%s: sumsq must be a float64 tensor of at least one element on %s" % (what, plan.device))
+    if not plan.nchunks:
+        return
+    rc = _lib.load().psgd_multi_param_update_f32(
+        plan.table("params", params, what), None if grads is None else plan.table("grads", grads, what),
+        None if vs is None else plan.table("vs", vs, what), len(params), plan.chunks.data_ptr(), plan.nchunks, float(lr),
+        None if sumsq is None else sumsq.data_ptr(), 0.0 if max_norm is None else float(max_norm),
+        _TINY if tiny is None else float(tiny), _psgd._stream_ptr(plan.device))
+    _lib.check(rc, "psgd_multi_param_update_f32")
+
+
+def multi_diff_scale(a, b, h, v=None, x=None, s=1.0, *, plan=None):
+    """h <- (a - b) * s and, with v and x (both or neither), x <- v * s for all tensors of the lists in ONE launch
+    (psgd_multi_diff_scale_f32), the difference and each product rounded to float32 on its own: the finite-difference
+    dG = (g' - g) / delta, dX = v / delta of psgd.py:727, :734-736 with s = 1 / delta."""
+    what = "multi_diff_scale"
+    if (v is None) != (x is None):
+        raise ValueError("%s: v and x go together" % what)
+    (a, b, h, v, x), plan = _lists(what, ("a", a), ("b", b), ("h", h), ("v", v), ("x", x), plan=plan)
+    if not plan.nchunks:
+        return
+    rc = _lib.load().psgd_multi_diff_scale_f32(
+        plan.table("a", a, what), plan.table("b", b, what), plan.table("h", h, what),
+        None if v is None else plan.table("v", v, what), None if x is None else plan.table("x", x, what),
+        len(a), plan.chunks.data_ptr(), plan.nchunks, float(s), _psgd._stream_ptr(plan.device))
+    _lib.check(rc, "psgd_multi_diff_scale_f32")
+
+
+# --------------------------------------------------------------------------- formats and initial factors
+KRON_SIDES = ("dense", "norm", "scale")
+KRON_PAIRS = (("dense", "dense"), ("dense", "norm"), ("dense", "scale"), ("norm", "dense"), ("norm", "scale"), ("scale", "dense"),
+              ("scale", "norm"))                                   # the seven formats of the dispatcher (psgd.py:82-107)
+
+
+def _format_pair(pair, what):
+    if isinstance(pair, str):
+        pair = (pair, pair)
+    try:
+        pair = tuple(pair)
+    except TypeError:
+        raise ValueError("%s: a preconditioner format is a side name or a (left, right) pair, got %r" % (what, pair))
+    if len(pair) != 2 or any(s not in KRON_SIDES for s in pair):
+        raise ValueError("%s: a preconditioner format is a (left, right) pair of %r, got %r" % (what, KRON_SIDES, pair))
+    if pair not in KRON_PAIRS:
+        raise ValueError("%s: the format %r does not exist: update_precond_kron / precond_grad_kron dispatch on the seven pairs of "
+                         "psgd.py:82-107, where a normalization or scaling factor always faces a factor of another kind" % (what, pair))
+    return pair
+
+
+def kron_formats(preconditioner_formats, k):
+    """`preconditioner_formats` of class Kron as a list of k (left, right) pairs.  Accepted: one side name ("dense" means
+    ("dense", "dense")); one pair of two names, for every parameter (also when k == 2); or a sequence of k entries, each a pair or
+    a side name."""
+    f = preconditioner_formats
+    if isinstance(f, str) or (isinstance(f, (tuple, list)) and len(f) == 2 and all(isinstance(s, str) for s in f)):
+        return [_format_pair(f, "Kron")] * k
+    try:
+        f = list(f)
+    except TypeError:
+        raise ValueError("Kron: preconditioner_formats must be a side name, a (left, right) pair or one of either per parameter, got %r"
+                         % (f,))
+    if len(f) != k:
+        raise ValueError("Kron: preconditioner_formats lists %d formats for %d parameters" % (len(f), k))
+    return [_format_pair(p, "Kron (parameter %d)" % i) for i, p in enumerate(f)]
+
+
+def _initial_factor(side, n, scale, device):
+    """demo_usage_of_all_preconditioners.py:68-78"""
+    if side == "dense":
+        q = torch.eye(n, dtype=_f32, device=device)
+    elif side == "scale":
+        q = torch.ones(1, n, dtype=_f32, device=device)
+    else:
+        q = torch.stack([torch.ones(n, dtype=_f32, device=device), torch.zeros(n, dtype=_f32, device=device)])
+    return q if scale == 1.0 else q * scale
+
+
+def kron_initial_factors(shape, pair, init_scale=1.0, device=None, name="parameter"):
+    """[Ql, Qr] of an (M, N) layer in the format `pair` (demo_usage_of_all_preconditioners.py:68-78): dense eye(n), scale ones(1, n),
+    norm stack([ones(n), zeros(n)]); the LEFT factor is multiplied by init_scale.  Refuses a scaling side of length 1 and a
+    normalization side of length 2: their factors are square, and the dispatcher, which knows a format by the factor shapes alone
+    and tests for square first, would run them as dense factors."""
+    pair = _format_pair(pair, "kron_initial_factors")
+    M, N = (int(s) for s in shape)
+    for side, n, where in ((pair[0], M, "left"), (pair[1], N, "right")):
+        if n < 1:
+            raise ValueError("Kron: %s of shape %s has an empty side" % (name, (M, N)))
+        if (side == "scale" and n == 1) or (side == "norm" and n == 2):
+            raise ValueError("Kron: %s of shape %s cannot take a %r factor on its %s side of length %d: that factor has shape (%d, %d), "
+                             "square like a dense one, and update_precond_kron / precond_grad_kron, which tell the formats apart by "
+                             "the factor shapes and test for square first, would treat it as dense -- use 'dense' for this side"
+                             % (name, (M, N), side, where, n, n, n))
+    return [_initial_factor(pair[0], M, float(init_scale), device), _initial_factor(pair[1], N, 1.0, device)]
+
+
+def _factor_shape(side, n):
+    return (n, n) if side == "dense" else (1, n) if side == "scale" else (2, n)
+
+
+# --------------------------------------------------------------------------- checkpoint, host part
+_HYPER_KEYS = ("lr_params", "lr_preconditioner", "grad_clip_max_norm", "preconditioner_update_probability",
+               "exact_hessian_vector_product")
+
+
+def _encode_state(factors, formats, shapes, hyper, rng_state):
+    """state_dict() of class Kron from its parts (CPU clones of the factors; plain Python values otherwise)"""
+    return {"format": 1, "kind": "kron",
+            "factors": [[q.detach().to("cpu", copy=True).contiguous() for q in pair] for pair in factors],
+            "preconditioner_formats": [list(p) for p in formats], "param_shapes": [list(map(int, s)) for s in shapes],
+            "hyper": {k: (bool if k == "exact_hessian_vector_product" else float)(hyper[k]) for k in _HYPER_KEYS},
+            "rng": rng_state.clone()}
+
+
+def _decode_state(sd, formats, shapes):
+    """the checks of load_state_dict(): returns (factors, hyper, rng_state) of a dict that fits an optimizer with these formats and
+    parameter shapes; ValueError naming the key otherwise"""
+    name = "Kron.load_state_dict"
+
+    def need(key):
+        if key not in sd:
+            raise ValueError("%s: the state dict has no %r" % (name, key))
+        return sd[key]
+    if need("format") != 1 or need("kind") != "kron":
+        raise ValueError("%s: 'format' / 'kind' are %r / %r; this version reads format 1 of kind 'kron'"
+                         % (name, sd.get("format"), sd.get("kind")))
+    if [list(p) for p in need("preconditioner_formats")] != [list(p) for p in formats]:
+        raise ValueError("%s: 'preconditioner_formats' is %r in the state dict, %r in this optimizer"
+                         % (name, sd["preconditioner_formats"], [list(p) for p in formats]))
+    if [list(map(int, s)) for s in need("param_shapes")] != [list(map(int, s)) for s in shapes]:
+        raise ValueError("%s: 'param_shapes' is %r in the state dict, %r in this optimizer"
+                         % (name, sd["param_shapes"], [list(map(int, s)) for s in shapes]))
+    factors = need("factors")
+    if len(factors) != len(shapes):
+        raise ValueError("%s: 'factors' holds %d pairs for %d parameters" % (name, len(factors), len(shapes)))
+    for i, (pair, fmt, (M, N)) in enumerate(zip(factors, formats, shapes)):
+        want = (_factor_shape(fmt[0], M), _factor_shape(fmt[1], N))
+        if len(pair) != 2 or any(not isinstance(q, torch.Tensor) or q.dtype != _f32 or tuple(q.shape) != w
+                                 for q, w in zip(pair, want)):
+            raise ValueError("%s: 'factors'[%d] must be two float32 tensors of shapes %s and %s" % (name, i, want[0], want[1]))
+    hyper = need("hyper")
+    for k in _HYPER_KEYS:
+        if k not in hyper:
+            raise ValueError("%s: 'hyper' has no %r" % (name, k))
+    return factors, hyper, need("rng")
+
+
+# --------------------------------------------------------------------------- the optimizer
+def _flatten(params_with_grad):
+    """the flattening order of class UVd (lists / tuples depth first, dict keys sorted); anything else is a leaf for the checks"""
+    if isinstance(params_with_grad, dict):
+        return [q for k in sorted(params_with_grad) for q in _flatten(params_with_grad[k])]
+    if isinstance(params_with_grad, (list, tuple)):
+        return [q for p in params_with_grad for q in _flatten(p)]
+    return [params_with_grad]
+
+
+class Kron:
+    """Kronecker-product preconditioned SGD, one factor pair per rank-2 parameter: the train_step of mnist_with_lenet5.py:43-57 behind
+    the interface of class UVd.
+
+    params_with_grad: contiguous float32 rank-2 tensors with requires_grad=True on one HIP device (nested lists / dicts are flattened
+    as class UVd does).  preconditioner_formats: "dense", a (left, right) pair of "dense" / "norm" / "scale", or one of either per
+    parameter.  The five hyper-parameters are _Hyper objects (.assign()).  grad_clip_max_norm=None: no clipping.
+    layer_batch: the per-layer calls of a step run inside kron.layer_batch() blocks (one for the updates, one for the applies).
+    step_tail: "torch" = per-tensor torch expressions around the preconditioner calls; "fused" = the list kernels (at most five
+    launches whatever the number of layers).  Both round alike.
+    generator: draws the update coin, then the perturbations in parameter order, each step; a CPU or a device generator.  None: the
+    coin comes from the module's branch generator (psgd.manual_seed), the perturbations from the global device generator, as in
+    class UVd.
+
+    Out of scope: half-precision parameters, parameters of rank 1 or 3, momentum, weight decay."""
+
+    def __init__(self, params_with_grad, preconditioner_formats="dense", preconditioner_init_scale=1.0, lr_params=0.01,
+                 lr_preconditioner=0.01, grad_clip_max_norm=None, preconditioner_update_probability=1.0,
+                 exact_hessian_vector_product=True, *, layer_batch=True, step_tail="torch", generator=None):
+        if step_tail not in ("torch", "fused"):
+            raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
+        params = _flatten(params_with_grad)
+        if not params:
+            raise ValueError("Kron: no parameters")
+        for i, p in enumerate(params):
+            if not isinstance(p, torch.Tensor):
+                raise TypeError("Kron: parameter %d is not a torch tensor (%r)" % (i, type(p)))
+            tag = "parameter %d (shape %s, %s)" % (i, tuple(p.shape), p.dtype)
+            if p.dtype != _f32:
+                raise TypeError("Kron: %s must be float32; half-precision parameters are out of scope" % tag)
+            if p.dim() != 2:
+                raise ValueError("Kron: %s must have rank 2; reshape it (the reference's demos fold a bias into its matrix)" % tag)
+            if not p.requires_grad:
+                raise ValueError("Kron: %s does not require grad" % tag)
+            if not p.is_contiguous():
+                raise ValueError("Kron: %s is not contiguous" % tag)
+        self._formats = kron_formats(preconditioner_formats, len(params))
+        self._shapes = [tuple(int(s) for s in p.shape) for p in params]
+        dev = params[0].device
+        for i, p in enumerate(params):
+            if not p.is_cuda or p.device != dev:
+                raise ValueError("Kron: parameter %d (shape %s) is on %s; all parameters must be on one HIP device (parameter 0 is on %s)"
+                                 % (i, tuple(p.shape), p.device, dev))
+        self._params, self._device = params, dev
+        self._Qs = [kron_initial_factors(s, f, preconditioner_init_scale, dev, "parameter %d" % i)
+                    for i, (s, f) in enumerate(zip(self._shapes, self._formats))]
+        self.lr_params = _psgd._Hyper(lr_params)
+        self.lr_preconditioner = _psgd._Hyper(lr_preconditioner)
+        self.grad_clip_max_norm = _psgd._Hyper(math.inf if grad_clip_max_norm is None else grad_clip_max_norm)
+        self.preconditioner_update_probability = _psgd._Hyper(preconditioner_update_probability)
+        self.exact_hessian_vector_product = _psgd._Hyper(bool(exact_hessian_vector_product))
+        self._layer_batch = bool(layer_batch)
+        self._generator = generator
+        self._tail = None
+        if step_tail == "fused":
+            self._tail = MultiTailPlan([int(p.numel()) for p in params], dev)
+            # dG and dX of the finite-difference route: written whole by multi_diff_scale before anything reads them
+            self._fd_h = [torch.empty_like(p, requires_grad=False) for p in params]
+            self._fd_x = [torch.empty_like(p, requires_grad=False) for p in params]
+
+    # ------------------------------------------------------------------------------------------------- state
+    @property
+    def factors(self):
+        """[[Ql, Qr], ...] in parameter order: the tensors the last update returned (never copies)"""
+        return self._Qs
+
+    def _coin_generator(self):
+        return self._generator if self._generator is not None else _psgd._branch_rng
+
+    def state_dict(self):
+        """Everything a bit-faithful resume needs except the parameters (the caller's): the factors (CPU clones), the formats and
+        parameter shapes, the five hyper-parameters, and get_state() of the generator behind the coin and the perturbations
+        (generator=None: of the module's branch generator; the global device generator that then draws the perturbations is the
+        caller's, as in class UVd)."""
+        return _encode_state(self._Qs, self._formats, self._shapes, {k: getattr(self, k) for k in _HYPER_KEYS},
+                             self._coin_generator().get_state())
+
+    def load_state_dict(self, sd):
+        """Restore what state_dict() saved.  The factors become NEW device tensors (as after an update), the hyper-parameters are
+        assigned, the generator gets the saved state.  Formats and parameter shapes must be this optimizer's."""
+        factors, hyper, rng = _decode_state(sd, self._formats, self._shapes)
+        try:
+            self._coin_generator().set_state(rng)
+        except (RuntimeError, TypeError) as e:
+            raise ValueError("Kron.load_state_dict: 'rng' does not fit this optimizer's generator: %s" % e)
+        for k in _HYPER_KEYS:
+            getattr(self, k).assign(hyper[k])
+        self._Qs = [[q.to(self._device, copy=True) for q in pair] for pair in factors]
+
+    # ------------------------------------------------------------------------------------------------- step
+    def _randn(self, p):
+        gen = self._generator
+        if gen is None:
+            return torch.randn_like(p, requires_grad=False)
+        v = torch.randn(p.shape, dtype=_f32, device=gen.device, generator=gen)
+        return v if v.device == p.device else v.to(p.device)
+
+    def _coin(self):
+        """psgd.py:703, drawn as class UVd draws it (always, whatever the probability); a device generator gives a device draw"""
+        gen = self._generator
+        if gen is None or gen.device.type == "cpu":
+            return _psgd._draw_branch(float(self.preconditioner_update_probability), gen)
+        return bool(torch.rand((), generator=gen, device=gen.device).item() < float(self.preconditioner_update_probability))
+
+    def _block(self):
+        return _kron.layer_batch() if self._layer_batch else contextlib.nullcontext()
+
+    @staticmethod
+    def _loss_of(closure_returns):
+        return closure_returns if isinstance(closure_returns, torch.Tensor) else closure_returns[0]
+
+    def step(self, closure):
+        """One step; returns what closure() returns (the loss is its first element when it is an iterable).
+
+        1. the coin of psgd.py:703: update the factors this step?
+        2. exact product: vs = randn per parameter, gradients with create_graph, Hvs from a second autograd.grad; dX = v, dG = Hv.
+        3. finite differences (psgd.py:716-727, :734-736): vs = randn * delta, delta = sqrt(eps_fp32); p += v; the closure runs a
+           second time; dG = (g' - g) * s, dX = v * s with s = float32(1) / float32(delta); the perturbation is undone in step 7.
+        4. one update_precond_kron per layer (inside one kron.layer_batch() block); the factor references are rebound to the returned
+           tensors, nothing is copied.
+        5. one precond_grad_kron per layer (a second block).
+        6. with clipping, lr_eff = float32(lr_params * min(max_norm / (sqrt(S) + tiny), 1)) evaluated in fp64, S = the fp64 sum of
+           the float32 squares of all preconditioned gradients.  tiny = finfo(float32).tiny follows psgd.py:753 (class UVd), not
+           mnist_with_lenet5.py:54-55, which divides by the bare norm: a zero gradient gives a zero step, not NaN.
+        7. p <- p - float32(lr_eff * pg); after step 3, p <- p - float32(float32(lr_eff * pg) + v) (psgd.py:761)."""
+        params = self._params
+        update_Q = self._coin()
+        exact = bool(self.exact_hessian_vector_product)
+        fused = self._tail is not None
+        undo = None
+        if update_Q and exact:
+            with torch.enable_grad():
+                closure_returns = closure()
+                grads = torch.autograd.grad(self._loss_of(closure_returns), params, create_graph=True)
+                vs = [self._randn(p) for p in params]
+                Hvs = torch.autograd.grad(grads, params, vs)
+            grads = [g.detach() for g in grads]
+            dXs, dGs = vs, [h.detach() for h in Hvs]
+        elif update_Q:
+            with torch.enable_grad():
+                closure_returns = closure()
+                grads = torch.autograd.grad(self._loss_of(closure_returns), params)
+            undo = vs = [self._randn(p) * _DELTA for p in params]
+            with torch.no_grad():
+                if fused:
+                    multi_param_update(params, None, vs, plan=self._tail)
+                else:
+                    for p, v in zip(params, vs):
+                        p.add_(v)
+            with torch.enable_grad():
+                perturbed = torch.autograd.grad(self._loss_of(closure()), params)
+            with torch.no_grad():
+                if fused:
+                    dXs, dGs = self._fd_x, self._fd_h
+                    multi_diff_scale([g.contiguous() for g in perturbed], [g.contiguous() for g in grads], dGs, vs, dXs, _FD_INV,
+                                     plan=self._tail)
+                else:
+                    dGs = [(pg - g) * _FD_INV for pg, g in zip(perturbed, grads)]
+                    dXs = [v * _FD_INV for v in vs]
+        else:
+            with torch.enable_grad():
+                closure_returns = closure()
+                grads = torch.autograd.grad(self._loss_of(closure_returns), params)
+        with torch.no_grad():
+            if update_Q:
+                lr_q = float(self.lr_preconditioner)
+                with self._block():
+                    new = [_psgd.update_precond_kron(q[0], q[1], dX, dG, lr_q) for q, dX, dG in zip(self._Qs, dXs, dGs)]
+                self._Qs = [[a, b] for a, b in new]
+            with self._block():
+                pre_grads = [_psgd.precond_grad_kron(q[0], q[1], g) for q, g in zip(self._Qs, grads)]
+            lr, max_norm = float(self.lr_params), float(self.grad_clip_max_norm)
+            clip = not math.isinf(max_norm)
+            if fused:
+                pre_grads = [g.contiguous() for g in pre_grads]          # (the mirrored formats return transposed views)
+                sumsq = multi_sumsq(pre_grads, plan=self._tail) if clip else None
+                multi_param_update(params, pre_grads, undo, lr, sumsq, max_norm if clip else None, _TINY, plan=self._tail)
+                return closure_returns
+            if clip:
+                S = None
+                for g in pre_grads:
+                    s = torch.sum((g * g).double())
+                    S = s if S is None else S + s
+                f64 = lambda x: torch.tensor(float(np.float32(x)), dtype=torch.float64, device=self._device)
+                ratio = torch.minimum(f64(max_norm) / (torch.sqrt(S) + f64(_TINY)), f64(1.0))
+                lr = (f64(lr) * ratio).float()
+            else:
+                lr = float(np.float32(lr))
+            for k, (p, g) in enumerate(zip(params, pre_grads)):
+                delta = g * lr
+                if undo is not None:
+                    delta = delta + undo[k]
+                p.sub_(delta)
+        return closure_returns

@@ -15,6 +15,7 @@ hello_psgd.py:5) carry over with torch tensors in place of tf tensors:
     update_precond_UVd_math_(U, V, d, v, h, step, tiny) -> None        psgd.py:554  (in place)
     precond_grad_UVd_math(U, V, d, g) -> Tensor                        psgd.py:619
     class UVd(...).step(closure)                                       psgd.py:630
+    class Kron(...).step(closure)                                      (extension: the train_step of mnist_with_lenet5.py:43-57)
 
 The UVd, sparse-LU and Kron arithmetic runs in hand-written HIP kernels behind the
 C ABI of include/psgd_hip.h (bound in _lib.py).  Tensors must be fp32 and resident on a ROCm
@@ -1630,3 +1631,8 @@ class UVd:
                     delta = delta + (decay * p.float()).to(p.dtype)
                 p.sub_(delta)
         return closure_returns                                                                # :764
+
+
+# --------------------------------------------------------------------------- Kron optimizer (kron_optimizer.py)
+# (imported last: that module builds on the step-tail plan, _Hyper and the Kron entry points above)
+from .kron_optimizer import Kron, multi_sumsq, multi_param_update, multi_diff_scale, kron_initial_factors  # noqa: E402,F401
