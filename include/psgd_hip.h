@@ -60,6 +60,8 @@ extern "C" {
  *     psgd_uvd_pack_check_f32 and psgd_uvd_check_multi, the non-finite guard of UVd.step (new symbols only: still 7).
  *     psgd_multi_sumsq_f32, psgd_multi_param_update_f32 and psgd_multi_diff_scale_f32, the step tail on lists of tensors of
  *     class Kron (new symbols only: still 7).
+ *     psgd_multi_blend_f32, psgd_multi_scale_check_f32 and psgd_multi_param_update_wd_f32: momentum, the non-finite guard with the
+ *     loss scale, and decoupled weight decay of class Kron (additive, new symbols only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -441,6 +443,31 @@ int psgd_multi_param_update_f32(const void *param_segs, const void *grad_segs, c
  * finite-difference dG = (g' - g) / delta and dX = v / delta of psgd.py:727, :734-736 with s = 1 / delta, in ONE launch.         */
 int psgd_multi_diff_scale_f32(const void *a_segs, const void *b_segs, const void *h_segs, const void *v_segs, const void *x_segs,
                               int k, const void *chunks, int64_t nchunks, float s, void *stream);
+
+/* Momentum of class Kron: m[i] = fl32(fl32(beta * m[i]) + fl32(omb * g[i])) for every element of every tensor, in ONE launch, every
+ * operation rounded on its own.  beta and omb are separate arguments: the caller passes omb = float(1) - beta, rounded once on the
+ * host (the convention of psgd_uvd_pack_blend_f32).  beta == 0 does NOT read m: m[i] = fl32(omb * g[i]), whatever m held.          */
+int psgd_multi_blend_f32(const void *m_segs, const void *g_segs, int k, const void *chunks, int64_t nchunks, float beta, float omb,
+                         void *stream);
+
+/* The guarded step of class Kron: one to three lists (segs1 and segs2 may be NULL; their scales are then not read) in ONE launch.
+ * For every element of list j, y = fl32(x * scale_j); where scale_j != 1, y is stored back in place (a list with scale_j == 1 is
+ * only read).  flag != NULL: when any y is +-Inf or NaN (a finite input that overflows under its scale counts), stamp is stored to
+ * *flag -- the flag contract of psgd_uvd_pack_check_f32: one 4-byte aligned device word that is never zeroed, every writer stores
+ * the same value with an ordinary store, no atomics, "bad" is *flag == stamp after the launch has completed.  flag != NULL with
+ * stamp <= 0 is PSGD_ERR_BAD_ARG.  flag == NULL is a pure rescale (stamp is ignored); all scales of the given lists equal to 1 is
+ * then PSGD_ERR_BAD_ARG: there is nothing to do.                                                                                  */
+int psgd_multi_scale_check_f32(const void *segs0, const void *segs1, const void *segs2, float scale0, float scale1, float scale2,
+                               int k, const void *chunks, int64_t nchunks, int32_t *flag, int32_t stamp, void *stream);
+
+/* psgd_multi_param_update_f32 with decoupled weight decay: with c = fl32(lr_eff * wd),
+ *     delta = fl32(lr_eff * g[i]);   vs_segs given: delta = fl32(delta + v[i]);
+ *     wd != 0: delta = fl32(delta + fl32(c * p[i]));   p[i] = fl32(p[i] - delta).
+ * wd == 0 takes no extra rounding step: the bits of psgd_multi_param_update_f32 (which forwards here).  grad_segs == NULL with
+ * wd != 0 is PSGD_ERR_BAD_ARG.                                                                                                  */
+int psgd_multi_param_update_wd_f32(const void *param_segs, const void *grad_segs, const void *vs_segs, int k, const void *chunks,
+                                   int64_t nchunks, float lr, const double *sumsq, float max_norm, float tiny, float wd,
+                                   void *stream);
 
 /* Tuning knobs for experiments (not part of the stable ABI).
  * key 0: streaming policy (0 = automatic: non-temporal when U,V exceed the Infinity Cache,

@@ -4,6 +4,10 @@
 //   psgd_multi_sumsq_f32         sum of fl32(x x) over every element of every tensor -> one device double       (the clip norm's square)
 //   psgd_multi_param_update_f32  p <- p - fl32(lr_eff g),  with vs: p <- p - fl32(fl32(lr_eff g) + v);  without g: p <- p + v
 //   psgd_multi_diff_scale_f32    h <- fl32(fl32(a - b) s),  and x <- fl32(v s) when given
+//   psgd_multi_blend_f32         m <- fl32(fl32(beta m) + fl32(omb g));  beta == 0 does not read m                (momentum of class Kron)
+//   psgd_multi_scale_check_f32   one to three lists: x <- fl32(x s_j) where s_j != 1, and a stamp stored to a flag word when a
+//                                product is not finite                                                              (guarded step)
+//   psgd_multi_param_update_wd_f32  the update with decoupled weight decay: delta <- fl32(delta + fl32(fl32(lr_eff wd) p))
 //
 // The tables are those of psgd_uvd_tail.hip: a SEGMENT is one tensor {pointer, start, count}, a CHUNK one piece of at most
 // PSGD_UVD_TAIL_CHUNK consecutive elements of one segment {segment index, offset}.  Here EVERY operand is a list: each has its own
@@ -127,24 +131,28 @@ __global__ __launch_bounds__(kT) void k_multi_sumsq_fold(const double* __restric
 }
 
 // ------------------------------------------------------------------------------------------------------------ parameter update
-// kPre: delta = fl32(lr_eff g); kVs: delta = fl32(delta + v); p = fl32(p - delta).  !kPre (kVs): p = fl32(p + v).  Every product,
-// sum and difference is rounded on its own.
-template <bool kPre, bool kVs>
-__device__ __forceinline__ float update_one(float p, float g, float v, float lr_eff) {
+// kPre: delta = fl32(lr_eff g); kVs: delta = fl32(delta + v); kWd: delta = fl32(delta + fl32(c p)), c = fl32(lr_eff wd);
+// p = fl32(p - delta).  !kPre (kVs): p = fl32(p + v).  Every product, sum and difference is rounded on its own.
+template <bool kPre, bool kVs, bool kWd>
+__device__ __forceinline__ float update_one(float p, float g, float v, float lr_eff, float c) {
   if constexpr (!kPre) {
     return p + v;
   } else {
     float delta = lr_eff * g;
     if constexpr (kVs) delta = delta + v;
+    if constexpr (kWd) {
+      const float decay = c * p;
+      delta = delta + decay;
+    }
     return p - delta;
   }
 }
 
-template <bool kPre, bool kVs>
+template <bool kPre, bool kVs, bool kWd = false>
 __global__ __launch_bounds__(kT) void k_multi_param_update(const Seg* __restrict__ psegs, const Seg* __restrict__ gsegs,
                                                            const Seg* __restrict__ vsegs, const Chunk* __restrict__ chunks,
                                                            int64_t nchunks, int k, float lr, const double* __restrict__ sumsq,
-                                                           float max_norm, float tiny) {
+                                                           float max_norm, float tiny, float wd) {
   const int t = threadIdx.x;
   float lr_eff = lr;
   if (kPre && sumsq) {        // lr_eff = fl32(lr * min(max_norm / (sqrt(sumsq) + tiny), 1)) in fp64, one rounding
@@ -152,6 +160,7 @@ __global__ __launch_bounds__(kT) void k_multi_param_update(const Seg* __restrict
     const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
     lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
   }
+  const float decay_c = kWd ? lr_eff * wd : 0.f;         // c = fl32(lr_eff wd)
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const Seg* const tabs[3] = {psegs, kPre ? gsegs : nullptr, kVs ? vsegs : nullptr};
     const Piece<3> pc = piece_of<3>(tabs, chunks[c], k);
@@ -162,7 +171,7 @@ __global__ __launch_bounds__(kT) void k_multi_param_update(const Seg* __restrict
     const float* v = pc.p[2];
     const int head = head_of(p, n);
     const int nvec = (n - head) / 4;
-    if (t < head) p[t] = update_one<kPre, kVs>(p[t], kPre ? g[t] : 0.f, kVs ? v[t] : 0.f, lr_eff);
+    if (t < head) p[t] = update_one<kPre, kVs, kWd>(p[t], kPre ? g[t] : 0.f, kVs ? v[t] : 0.f, lr_eff, decay_c);
 #pragma unroll 2
     for (int q = t; q < nvec; q += kT) {
       const int i = head + q * 4;
@@ -171,11 +180,11 @@ __global__ __launch_bounds__(kT) void k_multi_param_update(const Seg* __restrict
       if constexpr (kPre) gg = *reinterpret_cast<const f32x4_u*>(g + i);
       if constexpr (kVs) vv = *reinterpret_cast<const f32x4_u*>(v + i);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) x[e] = update_one<kPre, kVs>(x[e], gg[e], vv[e], lr_eff);
+      for (int e = 0; e < 4; ++e) x[e] = update_one<kPre, kVs, kWd>(x[e], gg[e], vv[e], lr_eff, decay_c);
       *reinterpret_cast<f32x4*>(p + i) = x;
     }
     const int i = head + nvec * 4 + t;
-    if (i < n) p[i] = update_one<kPre, kVs>(p[i], kPre ? g[i] : 0.f, kVs ? v[i] : 0.f, lr_eff);
+    if (i < n) p[i] = update_one<kPre, kVs, kWd>(p[i], kPre ? g[i] : 0.f, kVs ? v[i] : 0.f, lr_eff, decay_c);
   }
 }
 
@@ -233,6 +242,105 @@ __global__ __launch_bounds__(kT) void k_multi_diff_scale(const Seg* __restrict__
   }
 }
 
+// ----------------------------------------------------------------------------------------------------------------------- blend
+// m = fl32(fl32(beta m) + fl32(omb g)); !kRead (beta == 0): m = fl32(omb g), m is not read.  The 16-byte body is aligned on m.
+template <bool kRead>
+__device__ __forceinline__ float blend_one(float m, float g, float beta, float omb) {
+  const float b = omb * g;
+  if constexpr (!kRead) {
+    return b;
+  } else {
+    const float a = beta * m;
+    return a + b;
+  }
+}
+
+template <bool kRead>
+__global__ __launch_bounds__(kT) void k_multi_blend(const Seg* __restrict__ msegs, const Seg* __restrict__ gsegs,
+                                                    const Chunk* __restrict__ chunks, int64_t nchunks, int k, float beta, float omb) {
+  const int t = threadIdx.x;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Seg* const tabs[2] = {msegs, gsegs};
+    const Piece<2> pc = piece_of<2>(tabs, chunks[c], k);
+    const int n = pc.n;
+    if (n <= 0) continue;
+    float* m = pc.p[0];
+    const float* g = pc.p[1];
+    const int head = head_of(m, n);
+    const int nvec = (n - head) / 4;
+    if (t < head) m[t] = blend_one<kRead>(kRead ? m[t] : 0.f, g[t], beta, omb);
+#pragma unroll 2
+    for (int q = t; q < nvec; q += kT) {
+      const int i = head + q * 4;
+      f32x4 mm = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (kRead) mm = *reinterpret_cast<const f32x4*>(m + i);
+      const f32x4_u gg = *reinterpret_cast<const f32x4_u*>(g + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) mm[e] = blend_one<kRead>(mm[e], gg[e], beta, omb);
+      *reinterpret_cast<f32x4*>(m + i) = mm;
+    }
+    const int i = head + nvec * 4 + t;
+    if (i < n) m[i] = blend_one<kRead>(kRead ? m[i] : 0.f, g[i], beta, omb);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- scale and check
+// The non-finite predicate of the guarded step, on a value as it is formed: exponent all ones (+-Inf, NaN).
+__device__ __forceinline__ bool not_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) == 0x7F800000u; }
+
+// one list inside one chunk: y = fl32(x s), stored in place where s != 1 (a list with s == 1 is only read); returns whether a y of
+// this lane is not finite.  Every list is its own stored operand: head, body and tail are laid on its own 16-byte boundaries.
+__device__ __forceinline__ bool scale_check_list(float* x, int n, float s, int t) {
+  const bool store = s != 1.f;
+  bool bad = false;
+  const int head = head_of(x, n);
+  const int nvec = (n - head) / 4;
+  if (t < head) {
+    const float y = x[t] * s;
+    bad |= not_finite(y);
+    if (store) x[t] = y;
+  }
+#pragma unroll 2
+  for (int q = t; q < nvec; q += kT) {
+    const int i = head + q * 4;
+    f32x4 v = *reinterpret_cast<const f32x4*>(x + i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = v[e] * s;
+      bad |= not_finite(v[e]);
+    }
+    if (store) *reinterpret_cast<f32x4*>(x + i) = v;
+  }
+  const int i = head + nvec * 4 + t;
+  if (i < n) {
+    const float y = x[i] * s;
+    bad |= not_finite(y);
+    if (store) x[i] = y;
+  }
+  return bad;
+}
+
+// A lane that formed a non-finite product stores `stamp` to *flag when it is done -- an ordinary store of one value by every
+// writer, from a vector lane under a per-lane predicate: no atomic, no reduction, and nobody zeroes the word (the contract of
+// psgd_uvd_pack_check_f32).  flag == nullptr: a pure rescale.
+__global__ __launch_bounds__(kT) void k_multi_scale_check(const Seg* __restrict__ segs0, const Seg* __restrict__ segs1,
+                                                          const Seg* __restrict__ segs2, float s0, float s1, float s2,
+                                                          const Chunk* __restrict__ chunks, int64_t nchunks, int k,
+                                                          int32_t* flag, int32_t stamp) {
+  const int t = threadIdx.x;
+  bool bad = false;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Seg* const tabs[3] = {segs0, segs1, segs2};
+    const Piece<3> pc = piece_of<3>(tabs, chunks[c], k);
+    const int n = pc.n;
+    if (n <= 0) continue;
+    bad |= scale_check_list(pc.p[0], n, s0, t);
+    if (segs1) bad |= scale_check_list(pc.p[1], n, s1, t);
+    if (segs2) bad |= scale_check_list(pc.p[2], n, s2, t);
+  }
+  if (flag != nullptr && bad) *reinterpret_cast<volatile int32_t*>(flag) = stamp;
+}
+
 static int grid_for(int64_t nchunks) { return (int)(nchunks < kMaxGrid ? nchunks : kMaxGrid); }
 static int launched() { return hipGetLastError() == hipSuccess ? PSGD_OK : PSGD_ERR_LAUNCH; }
 
@@ -255,10 +363,12 @@ int psgd_multi_sumsq_f32(const void* segs, int k, const void* chunks, int64_t nc
   return launched();
 }
 
-int psgd_multi_param_update_f32(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
-                                int64_t nchunks, float lr, const double* sumsq, float max_norm, float tiny, void* stream) {
+int psgd_multi_param_update_wd_f32(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
+                                   int64_t nchunks, float lr, const double* sumsq, float max_norm, float tiny, float wd,
+                                   void* stream) {
   if (!param_segs || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
   if (!grad_segs && (!vs_segs || sumsq)) return PSGD_ERR_BAD_ARG;            // nothing to do, or a clip norm without a gradient
+  if (!grad_segs && wd != 0.f) return PSGD_ERR_BAD_ARG;                      // the perturbation p + v takes no decay
   if (nchunks == 0) return PSGD_OK;
   hipStream_t st = (hipStream_t)stream;
   const Seg* ps = (const Seg*)param_segs;
@@ -266,15 +376,56 @@ int psgd_multi_param_update_f32(const void* param_segs, const void* grad_segs, c
   const Seg* vsg = (const Seg*)vs_segs;
   const Chunk* ch = (const Chunk*)chunks;
   const int grid = grid_for(nchunks);
+#define PSGD_MULTI_UPDATE(PRE, VS, WD)                                                                                          \
+  hipLaunchKernelGGL((k_multi_param_update<PRE, VS, WD>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq, \
+                     max_norm, tiny, wd)
   if (!gs)
-    hipLaunchKernelGGL((k_multi_param_update<false, true>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq,
-                       max_norm, tiny);
-  else if (vsg)
-    hipLaunchKernelGGL((k_multi_param_update<true, true>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq,
-                       max_norm, tiny);
+    PSGD_MULTI_UPDATE(false, true, false);
+  else if (wd != 0.f) {                      // (a NaN wd decays too: it propagates)
+    if (vsg)
+      PSGD_MULTI_UPDATE(true, true, true);
+    else
+      PSGD_MULTI_UPDATE(true, false, true);
+  } else if (vsg)
+    PSGD_MULTI_UPDATE(true, true, false);
   else
-    hipLaunchKernelGGL((k_multi_param_update<true, false>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq,
-                       max_norm, tiny);
+    PSGD_MULTI_UPDATE(true, false, false);
+#undef PSGD_MULTI_UPDATE
+  return launched();
+}
+
+int psgd_multi_param_update_f32(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
+                                int64_t nchunks, float lr, const double* sumsq, float max_norm, float tiny, void* stream) {
+  return psgd_multi_param_update_wd_f32(param_segs, grad_segs, vs_segs, k, chunks, nchunks, lr, sumsq, max_norm, tiny, 0.f, stream);
+}
+
+int psgd_multi_blend_f32(const void* m_segs, const void* g_segs, int k, const void* chunks, int64_t nchunks, float beta, float omb,
+                         void* stream) {
+  if (!m_segs || !g_segs || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const Chunk* ch = (const Chunk*)chunks;
+  const int grid = grid_for(nchunks);
+  if (beta == 0.f)
+    hipLaunchKernelGGL(k_multi_blend<false>, dim3(grid), dim3(kT), 0, st, (const Seg*)m_segs, (const Seg*)g_segs, ch, nchunks, k,
+                       beta, omb);
+  else
+    hipLaunchKernelGGL(k_multi_blend<true>, dim3(grid), dim3(kT), 0, st, (const Seg*)m_segs, (const Seg*)g_segs, ch, nchunks, k,
+                       beta, omb);
+  return launched();
+}
+
+int psgd_multi_scale_check_f32(const void* segs0, const void* segs1, const void* segs2, float scale0, float scale1, float scale2,
+                               int k, const void* chunks, int64_t nchunks, int32_t* flag, int32_t stamp, void* stream) {
+  if (!segs0 || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
+  if (flag) {
+    if (stamp <= 0 || ((uintptr_t)flag & 3)) return PSGD_ERR_BAD_ARG;
+  } else if (scale0 == 1.f && (!segs1 || scale1 == 1.f) && (!segs2 || scale2 == 1.f)) {
+    return PSGD_ERR_BAD_ARG;                                                 // nothing to check and nothing to scale
+  }
+  if (nchunks == 0) return PSGD_OK;
+  hipLaunchKernelGGL(k_multi_scale_check, dim3(grid_for(nchunks)), dim3(kT), 0, (hipStream_t)stream, (const Seg*)segs0,
+                     (const Seg*)segs1, (const Seg*)segs2, scale0, scale1, scale2, (const Chunk*)chunks, nchunks, k, flag, stamp);
   return launched();
 }
 

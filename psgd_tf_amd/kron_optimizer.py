@@ -4,7 +4,8 @@ The reference has no such class: its Kron demos hand-write the step (mnist_with_
 lstm_with_xor_problem.py and the NMT demo).  The interface and the step(closure) contract are those of class UVd (psgd.py:630-764);
 the arithmetic is that of mnist_with_lenet5.py:43-57, with the finite-difference Hessian-vector product of psgd.py:716-727.
 
-    multi_sumsq, multi_param_update, multi_diff_scale     thin wrappers of the list kernels (csrc/psgd_multi_tail.hip)
+    multi_sumsq, multi_param_update, multi_diff_scale,
+    multi_blend, multi_scale_check                        thin wrappers of the list kernels (csrc/psgd_multi_tail.hip)
     kron_initial_factors                                  the initial factor pair of one layer
     Kron(...).step(closure)                               the optimizer
 """
@@ -32,6 +33,15 @@ class MultiTailPlan(_psgd.UVdTailPlan):
     def __init__(self, sizes, device):
         super().__init__(sizes, torch.float32, device)
         self.ws = torch.empty(_lib.MULTI_SUMSQ_WS_BYTES, dtype=torch.uint8, device=self.device)
+        # the flag word of the guarded step (multi_scale_check) and the stamp last stored to it.  The word is zeroed ONCE, here: the
+        # kernel stores a stamp that this word has not seen before, so nothing ever clears it again
+        self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.stamp = 0
+
+    def next_stamp(self):
+        """1 .. 2^31 - 1, then 1 again"""
+        self.stamp = self.stamp % (2 ** 31 - 1) + 1
+        return self.stamp
 
 
 _multi_plans = {}
@@ -104,7 +114,7 @@ def multi_sumsq(tensors, *, plan=None, out=None, ws=None):
     return out
 
 
-def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None, tiny=None, *, plan=None):
+def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None, tiny=None, *, plan=None, weight_decay=0.0):
     """For all parameters in ONE launch (psgd_multi_param_update_f32), every operation rounded to float32 on its own:
         p <- p - lr_eff * g                     vs None
         p <- p - (lr_eff * g + v)               vs given (the undo of the finite-difference perturbation, psgd.py:761)
@@ -112,11 +122,16 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
     lr_eff = float32(lr) when sumsq is None; with sumsq (a float64 device tensor of one element, what multi_sumsq left) and max_norm,
     lr_eff = float32(lr * min(max_norm / (sqrt(sumsq) + tiny), 1)) formed on the device in fp64: no host read; a NaN sumsq makes
     every parameter NaN, as torch.minimum does.  tiny defaults to the smallest normal float32.
+    weight_decay (decoupled; psgd_multi_param_update_wd_f32): with c = float32(lr_eff * weight_decay), the subtracted term gains
+    float32(c * p) after the vs term; 0 (default) adds no rounding step and calls the entry point without decay.
     The parameters are written through their pointers: autograd's version counters do not move."""
     what = "multi_param_update"
+    wd = float(weight_decay)
+    if not wd >= 0.0:
+        raise ValueError("%s: weight_decay must be >= 0, got %r" % (what, weight_decay))
     (params, grads, vs), plan = _lists(what, ("params", params), ("grads", grads), ("vs", vs), plan=plan)
-    if grads is None and (vs is None or sumsq is not None):
-        raise ValueError("%s: grads=None adds vs to the parameters; it needs vs and takes no sumsq" % what)
+    if grads is None and (vs is None or sumsq is not None or wd != 0.0):
+        raise ValueError("%s: grads=None adds vs to the parameters; it needs vs and takes no sumsq and no weight_decay" % what)
     if (sumsq is None) != (max_norm is None):
         raise ValueError("%s: sumsq and max_norm go together" % what)
     if sumsq is not None and (not isinstance(sumsq, torch.Tensor) or sumsq.dtype != torch.float64 or sumsq.device != plan.device
@@ -124,12 +139,16 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
         raise ValueError("%s: sumsq must be a float64 tensor of at least one element on %s" % (what, plan.device))
     if not plan.nchunks:
         return
-    rc = _lib.load().psgd_multi_param_update_f32(
-        plan.table("params", params, what), None if grads is None else plan.table("grads", grads, what),
-        None if vs is None else plan.table("vs", vs, what), len(params), plan.chunks.data_ptr(), plan.nchunks, float(lr),
-        None if sumsq is None else sumsq.data_ptr(), 0.0 if max_norm is None else float(max_norm),
-        _TINY if tiny is None else float(tiny), _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_param_update_f32")
+    args = (plan.table("params", params, what), None if grads is None else plan.table("grads", grads, what),
+            None if vs is None else plan.table("vs", vs, what), len(params), plan.chunks.data_ptr(), plan.nchunks, float(lr),
+            None if sumsq is None else sumsq.data_ptr(), 0.0 if max_norm is None else float(max_norm),
+            _TINY if tiny is None else float(tiny))
+    if wd == 0.0:
+        rc = _lib.load().psgd_multi_param_update_f32(*args, _psgd._stream_ptr(plan.device))
+        _lib.check(rc, "psgd_multi_param_update_f32")
+    else:
+        rc = _lib.load().psgd_multi_param_update_wd_f32(*args, wd, _psgd._stream_ptr(plan.device))
+        _lib.check(rc, "psgd_multi_param_update_wd_f32")
 
 
 def multi_diff_scale(a, b, h, v=None, x=None, s=1.0, *, plan=None):
@@ -147,6 +166,55 @@ def multi_diff_scale(a, b, h, v=None, x=None, s=1.0, *, plan=None):
         None if v is None else plan.table("v", v, what), None if x is None else plan.table("x", x, what),
         len(a), plan.chunks.data_ptr(), plan.nchunks, float(s), _psgd._stream_ptr(plan.device))
     _lib.check(rc, "psgd_multi_diff_scale_f32")
+
+
+def multi_blend(ms, gs, beta, omb, *, plan=None):
+    """m <- beta * m + omb * g for all tensors of the lists in ONE launch (psgd_multi_blend_f32), both products and the sum rounded
+    to float32 on their own: the momentum of class Kron.  beta and omb are the pair of uvd_momentum_coefficients (omb = float32(1) -
+    beta, rounded once); beta == 0 does not read m: whatever it held, NaN included, is replaced by omb * g."""
+    what = "multi_blend"
+    beta, omb = float(np.float32(beta)), float(np.float32(omb))
+    if not 0.0 <= beta < 1.0:
+        raise ValueError("%s: beta must be in [0, 1), got %r" % (what, beta))
+    (ms, gs), plan = _lists(what, ("ms", ms), ("gs", gs), plan=plan)
+    if gs is None:
+        raise ValueError("%s: gs is required" % what)
+    if not plan.nchunks:
+        return
+    rc = _lib.load().psgd_multi_blend_f32(plan.table("m", ms, what), plan.table("g", gs, what), len(ms), plan.chunks.data_ptr(),
+                                          plan.nchunks, beta, omb, _psgd._stream_ptr(plan.device))
+    _lib.check(rc, "psgd_multi_blend_f32")
+
+
+def multi_scale_check(lists, scales, *, flag=None, stamp=None, plan=None):
+    """One to three lists of tensors in ONE launch (psgd_multi_scale_check_f32): every element x of list j becomes float32(x *
+    scales[j]) in place where scales[j] != 1 (a list with scale 1 is only read), and with flag and stamp (both or neither) stamp is
+    stored to flag[0], an int32 device word, when any of these products -- of a scaled list or not -- is +-Inf or NaN.  The caller
+    passes a stamp it has not used on this word before (1 .. 2^31 - 1; plan.next_stamp() for plan.flag) and reads flag[0] == stamp
+    after the launch; nothing zeroes the word.  Without a flag the call only rescales, and all scales equal to 1 is an error."""
+    what = "multi_scale_check"
+    lists, scales = list(lists), [float(np.float32(s)) for s in scales]
+    if not 1 <= len(lists) <= 3 or len(scales) != len(lists):
+        raise ValueError("%s: one to three lists and one scale for each, got %d lists and %d scales" % (what, len(lists), len(scales)))
+    if (flag is None) != (stamp is None):
+        raise ValueError("%s: flag and stamp go together (got flag=%s, stamp=%r)" % (what, "None" if flag is None else "given", stamp))
+    if flag is None and all(s == 1.0 for s in scales):
+        raise ValueError("%s: no flag and every scale is 1: nothing to do" % what)
+    lists, plan = _lists(what, *[("lists[%d]" % j, ts) for j, ts in enumerate(lists)], plan=plan)
+    if any(ts is None for ts in lists):
+        raise ValueError("%s: a list is None" % what)
+    word = None
+    if flag is not None:
+        word = _psgd._flag_word(what, flag, stamp, plan.device)
+        if not 1 <= int(stamp) <= 2 ** 31 - 1:
+            raise ValueError("%s: stamp must be in 1 .. 2^31 - 1, got %r" % (what, stamp))
+    if not plan.nchunks:
+        return
+    tabs = [plan.table("check%d" % j, ts, what) for j, ts in enumerate(lists)] + [None] * (3 - len(lists))
+    rc = _lib.load().psgd_multi_scale_check_f32(*tabs, *(scales + [1.0] * (3 - len(scales))), len(lists[0]), plan.chunks.data_ptr(),
+                                                plan.nchunks, word, 0 if stamp is None else int(stamp),
+                                                _psgd._stream_ptr(plan.device))
+    _lib.check(rc, "psgd_multi_scale_check_f32")
 
 
 # --------------------------------------------------------------------------- formats and initial factors
@@ -267,6 +335,37 @@ def _decode_state(sd, formats, shapes):
     return factors, hyper, need("rng")
 
 
+def _encode_features(sd, momentum, weight_decay, buffers=None, momentum_step=0, guard=False, skipped_steps=0, loss_scale=None,
+                     good_steps=0):
+    """the keys that momentum, weight decay and the guard add to a state dict, as class UVd names them: 'hyper' always gains
+    momentum and weight_decay; momentum_buffers (CPU clones, one per parameter) and momentum_step only when momentum > 0;
+    nonfinite, skipped_steps, loss_scale, loss_scale_good_steps only when the optimizer is guarded.  Returns sd."""
+    sd["hyper"]["momentum"], sd["hyper"]["weight_decay"] = float(momentum), float(weight_decay)
+    if float(momentum) > 0.0:
+        sd["momentum_buffers"] = [m.detach().to("cpu", copy=True).contiguous() for m in buffers]
+        sd["momentum_step"] = int(momentum_step)
+    if guard:
+        sd["nonfinite"], sd["skipped_steps"] = "skip", int(skipped_steps)
+        sd["loss_scale"] = None if loss_scale is None else float(loss_scale)
+        sd["loss_scale_good_steps"] = int(good_steps)
+    return sd
+
+
+def _decode_features(sd, shapes):
+    """the optional keys of _encode_features, checked: (momentum buffers or None, momentum_step).  A dict from before them has
+    none and is valid."""
+    name = "Kron.load_state_dict"
+    bufs = sd.get("momentum_buffers")
+    if bufs is None:
+        return None, 0
+    if len(bufs) != len(shapes) or any(not isinstance(m, torch.Tensor) or m.dtype != _f32 or tuple(m.shape) != tuple(s)
+                                       for m, s in zip(bufs, shapes)):
+        raise ValueError("%s: 'momentum_buffers' must be one float32 tensor per parameter, of the parameter's shape" % name)
+    if "momentum_step" not in sd:
+        raise ValueError("%s: the state dict has 'momentum_buffers' but no 'momentum_step'" % name)
+    return bufs, int(sd["momentum_step"])
+
+
 # --------------------------------------------------------------------------- the optimizer
 def _flatten(params_with_grad):
     """the flattening order of class UVd (lists / tuples depth first, dict keys sorted); anything else is a leaf for the checks"""
@@ -291,13 +390,44 @@ class Kron:
     coin comes from the module's branch generator (psgd.manual_seed), the perturbations from the global device generator, as in
     class UVd.
 
-    Out of scope: half-precision parameters, parameters of rank 1 or 3, momentum, weight decay."""
+    momentum, weight_decay (off by default; _Hyper objects): one fp32 buffer per parameter, m <- beta_k m + (1 - beta_k) g with the
+    warm-up beta_k = min(k / (k + 1), momentum) of class UVd (uvd_momentum_coefficients), and m takes the place of g in
+    precond_grad_kron; decoupled weight decay adds float32(float32(lr_eff weight_decay) p) to what the update subtracts.
+    nonfinite="skip": a step whose gradients, Hessian-vector products (perturbed gradients) or probe vectors hold +-Inf or NaN
+    changes nothing (skipped_steps, last_step_skipped).  loss_scale (needs "skip"): None, a power of two, or "dynamic" (starts at
+    2^16, uvd_loss_scale_next with loss_scale_growth_interval); a _Hyper that holds the CURRENT scale.  See step().
+
+    Out of scope: half-precision parameters, parameters of rank 1 or 3."""
 
     def __init__(self, params_with_grad, preconditioner_formats="dense", preconditioner_init_scale=1.0, lr_params=0.01,
                  lr_preconditioner=0.01, grad_clip_max_norm=None, preconditioner_update_probability=1.0,
-                 exact_hessian_vector_product=True, *, layer_batch=True, step_tail="torch", generator=None):
+                 exact_hessian_vector_product=True, *, layer_batch=True, step_tail="torch", generator=None,
+                 momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000):
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
+        # momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval: the switches of class UVd with their meaning
+        # there (see step()); all off by default, and checked before anything touches a device
+        if not 0.0 <= float(momentum) < 1.0:
+            raise ValueError("Kron: momentum must be in [0, 1), got %r" % (momentum,))
+        if not float(weight_decay) >= 0.0:
+            raise ValueError("Kron: weight_decay must be >= 0, got %r" % (weight_decay,))
+        if nonfinite not in ("propagate", "skip"):
+            raise ValueError("Kron: nonfinite must be 'propagate' or 'skip', got %r" % (nonfinite,))
+        self._guard = nonfinite == "skip"
+        if loss_scale is not None and not self._guard:
+            raise ValueError("Kron: loss_scale needs nonfinite='skip' (a scaled gradient that overflows must not reach the state)")
+        self._dynamic_scale = isinstance(loss_scale, str)
+        if self._dynamic_scale and loss_scale != "dynamic":
+            raise ValueError("Kron: loss_scale must be None, a power of two or 'dynamic', got %r" % (loss_scale,))
+        self.momentum = _psgd._Hyper(momentum)
+        self.weight_decay = _psgd._Hyper(weight_decay)
+        self.loss_scale = _psgd._Hyper(2.0 ** 16 if self._dynamic_scale else loss_scale)
+        self._loss_scale_value()
+        self.loss_scale_growth_interval = int(loss_scale_growth_interval)
+        if self.loss_scale_growth_interval < 1:
+            raise ValueError("Kron: loss_scale_growth_interval must be >= 1, got %r" % (loss_scale_growth_interval,))
+        self._m, self._m_step, self._good_steps = None, 0, 0
+        self.skipped_steps, self.last_step_skipped = 0, False
         params = _flatten(params_with_grad)
         if not params:
             raise ValueError("Kron: no parameters")
@@ -350,21 +480,149 @@ class Kron:
         """Everything a bit-faithful resume needs except the parameters (the caller's): the factors (CPU clones), the formats and
         parameter shapes, the five hyper-parameters, and get_state() of the generator behind the coin and the perturbations
         (generator=None: of the module's branch generator; the global device generator that then draws the perturbations is the
-        caller's, as in class UVd)."""
-        return _encode_state(self._Qs, self._formats, self._shapes, {k: getattr(self, k) for k in _HYPER_KEYS},
-                             self._coin_generator().get_state())
+        caller's, as in class UVd).  'hyper' also holds momentum and weight_decay; with momentum > 0 the dict gains
+        momentum_buffers (CPU clones) and momentum_step, with nonfinite="skip" it gains nonfinite, skipped_steps, loss_scale (the
+        current one; None without loss scaling) and loss_scale_good_steps."""
+        sd = _encode_state(self._Qs, self._formats, self._shapes, {k: getattr(self, k) for k in _HYPER_KEYS},
+                           self._coin_generator().get_state())
+        mom = float(self.momentum)
+        return _encode_features(sd, mom, float(self.weight_decay), self._momentum_buffers() if mom > 0.0 else None, self._m_step,
+                                self._guard, self.skipped_steps, self.loss_scale.value, self._good_steps)
 
     def load_state_dict(self, sd):
         """Restore what state_dict() saved.  The factors become NEW device tensors (as after an update), the hyper-parameters are
-        assigned, the generator gets the saved state.  Formats and parameter shapes must be this optimizer's."""
+        assigned, the generator gets the saved state.  Formats and parameter shapes must be this optimizer's.
+        momentum and weight_decay are assigned when 'hyper' has them (a dict from before them leaves this object's values); the
+        momentum buffers and their step counter are restored, and a dict without them zeroes the buffers of a momentum optimizer
+        and restarts its warm-up.  A guarded optimizer restores skipped_steps, loss_scale_good_steps and, when both sides scale
+        the loss, loss_scale where the dict has them and starts them fresh where it has not; an unguarded one ignores them."""
         factors, hyper, rng = _decode_state(sd, self._formats, self._shapes)
+        bufs, m_step = _decode_features(sd, self._shapes)
         try:
             self._coin_generator().set_state(rng)
         except (RuntimeError, TypeError) as e:
             raise ValueError("Kron.load_state_dict: 'rng' does not fit this optimizer's generator: %s" % e)
         for k in _HYPER_KEYS:
             getattr(self, k).assign(hyper[k])
+        for k in ("momentum", "weight_decay"):
+            if k in hyper:
+                getattr(self, k).assign(hyper[k])
         self._Qs = [[q.to(self._device, copy=True) for q in pair] for pair in factors]
+        self._m_step = m_step
+        with torch.no_grad():
+            if bufs is not None:
+                for m, b in zip(self._momentum_buffers(), bufs):
+                    m.copy_(b)
+            elif float(self.momentum) > 0.0:             # no buffer saved: a momentum optimizer starts its warm-up again
+                for m in self._momentum_buffers():
+                    m.zero_()
+        if self._guard:                                  # a dict of an unguarded optimizer has none of these: the guard starts fresh
+            self.skipped_steps, self.last_step_skipped = int(sd.get("skipped_steps", 0)), False
+            self._good_steps = int(sd.get("loss_scale_good_steps", 0))
+            if sd.get("loss_scale") is not None and self.loss_scale.value is not None:
+                self.loss_scale.assign(float(sd["loss_scale"]))
+                self._loss_scale_value()
+
+    # ------------------------------------------------------------------------------------------------- momentum, guard
+    def _loss_scale_value(self):
+        """the current loss scale S as a float (1.0 without loss scaling), checked: a power of two"""
+        S = self.loss_scale.value
+        if S is None:
+            return 1.0
+        S = float(S)
+        if not (S > 0.0 and math.isfinite(S) and math.frexp(S)[0] == 0.5):
+            raise ValueError("Kron: loss_scale must be a power of two (1 / loss_scale must be exact), got %r" % (self.loss_scale.value,))
+        return S
+
+    def _hyper_momentum(self):
+        mom, wd = float(self.momentum), float(self.weight_decay)
+        if not 0.0 <= mom < 1.0:
+            raise ValueError("Kron: momentum must be in [0, 1), got %r" % (mom,))
+        if not wd >= 0.0:
+            raise ValueError("Kron: weight_decay must be >= 0, got %r" % (wd,))
+        return mom, wd
+
+    def _momentum_buffers(self):
+        """one zero-initialised fp32 buffer per parameter, created on first use"""
+        if self._m is None:
+            self._m = [torch.zeros_like(p, requires_grad=False) for p in self._params]
+        return self._m
+
+    @staticmethod
+    def _owned(tensors):
+        """detached contiguous tensors, no two of them the same memory (autograd may hand one tensor to two parameters): safe to
+        scale in place"""
+        out, seen = [], set()
+        for t in tensors:
+            t = t.detach().contiguous()
+            if t.data_ptr() in seen and t.numel():
+                t = t.clone()
+            seen.add(t.data_ptr())
+            out.append(t)
+        return out
+
+    def _judge(self, grads, second, vs, inv):
+        """The guard and the loss scale of one step, BEFORE anything else reads its inputs: the gradients and the second list (Hvs on
+        the exact route, the perturbed gradients on the finite-difference one; None on a step that leaves the factors alone) are
+        multiplied by inv = 1 / loss_scale (nothing when inv == 1), and they and the probe vectors vs (never scaled) are judged.
+        Returns (grads, second, bad).  Guarded fused tail: ONE multi_scale_check launch and ONE 4-byte host read; guarded torch
+        tail: per-tensor `* inv` and torch.isfinite(...).all(), one host read of one bool.  Unguarded (inv == 1): nothing runs."""
+        if not self._guard:
+            return grads, second, False
+        if self._tail is not None:
+            grads = self._owned(grads)
+            lists, scales = [grads], [inv]
+            if second is not None:
+                second = self._owned(second)
+                lists += [second, [v.contiguous() for v in vs]]
+                scales += [inv, 1.0]
+            plan = self._tail
+            stamp = plan.next_stamp()
+            multi_scale_check(lists, scales, flag=plan.flag, stamp=stamp, plan=plan)
+            return grads, second, int(plan.flag.item()) == stamp                            # the host read of a guarded step
+        if inv != 1.0:
+            grads = [g * inv for g in grads]
+            second = None if second is None else [h * inv for h in second]
+        ok = None
+        for x in list(grads) + list(second or ()) + list(vs or ()):
+            f = torch.isfinite(x).all()
+            ok = f if ok is None else ok & f
+        return grads, second, not bool(ok.item())                                           # ... and of the torch tail
+
+    def _guard_outcome(self, skipped, undo_vs=None):
+        """book-keeping of a guarded step once its decision is known; a skipped finite-difference step takes the perturbation of
+        psgd.py:723 back, p <- fl32(p - v): the reference's own undo, within one rounding of the parameters before the step"""
+        if undo_vs is not None:
+            with torch.no_grad():
+                for p, v in zip(self._params, undo_vs):
+                    p.sub_(v)
+        self.last_step_skipped = bool(skipped)
+        self.skipped_steps += int(bool(skipped))
+        if self._dynamic_scale:
+            S, self._good_steps = _psgd.uvd_loss_scale_next(self._loss_scale_value(), self._good_steps, skipped,
+                                                            growth_interval=self.loss_scale_growth_interval)
+            self.loss_scale.assign(S)
+
+    def _blend(self, grads, mom):
+        """the gradients that precond_grad_kron takes: with momentum the buffers after m <- fl32(fl32(beta_k m) + fl32((1 - beta_k) g))
+        (fused tail: one multi_blend launch; torch tail: the same three roundings per tensor; beta_k == 0 does not read m).  A
+        step with momentum == 0 sets the warm-up counter back."""
+        if mom == 0.0:
+            self._m_step = 0
+            return grads
+        beta, omb = _psgd.uvd_momentum_coefficients(self._m_step, mom)
+        self._m_step += 1
+        ms = self._momentum_buffers()
+        if self._tail is not None:
+            multi_blend(ms, [g.contiguous() for g in grads], beta, omb, plan=self._tail)
+            return ms
+        for m, g in zip(ms, grads):
+            if beta == 0.0:
+                m.copy_(g * omb)
+            else:
+                m.mul_(beta)
+                m.add_(g * omb)
+        return ms
 
     # ------------------------------------------------------------------------------------------------- step
     def _randn(self, p):
@@ -401,24 +659,53 @@ class Kron:
         6. with clipping, lr_eff = float32(lr_params * min(max_norm / (sqrt(S) + tiny), 1)) evaluated in fp64, S = the fp64 sum of
            the float32 squares of all preconditioned gradients.  tiny = finfo(float32).tiny follows psgd.py:753 (class UVd), not
            mnist_with_lenet5.py:54-55, which divides by the bare norm: a zero gradient gives a zero step, not NaN.
-        7. p <- p - float32(lr_eff * pg); after step 3, p <- p - float32(float32(lr_eff * pg) + v) (psgd.py:761)."""
+        7. p <- p - float32(lr_eff * pg); after step 3, p <- p - float32(float32(lr_eff * pg) + v) (psgd.py:761).
+
+        The switches of class UVd, with their meaning there; both tails round alike, and with all of them at their defaults none of
+        this runs (the same launches, the same bits, no host read):
+        loss_scale=S: every gradient the step takes is that of loss * S (the closure is unchanged and returns the unscaled loss);
+        inv = 1 / S, exact because S is a power of two, is applied once to the gradients and to the second list (Hvs in step 2, the
+        perturbed gradients in step 3) before anything else reads them; the probe vectors are never scaled.
+        nonfinite="skip": in that same pass the gradients, the second list and the probe vectors are judged, and a step with a
+        +-Inf or NaN among them is SKIPPED before the first update_precond_kron: factors, parameters, momentum buffers and the
+        warm-up counter keep their bits; after step 3 the perturbation is taken back by p <- float32(p - v), within one rounding of
+        the old parameters.  A skipped step has consumed the coin and the probe vectors and nothing else.  Fused tail: one
+        multi_scale_check launch and one 4-byte host read per guarded step; torch tail: per-tensor `* inv` and
+        torch.isfinite(...).all(), one host read of one bool.  "dynamic" halves S on a skip and doubles it after
+        loss_scale_growth_interval good steps in a row (uvd_loss_scale_next).
+        momentum: m <- float32(float32(beta_k m) + float32((1 - beta_k) g)) on the unscaled gradient, beta_k of
+        uvd_momentum_coefficients (k counts the steps blended so far; a step taken with momentum == 0 sets it back to 0), and step 5
+        is applied to m (fused tail: one multi_blend launch).  weight_decay: step 7 subtracts float32(delta + float32(c p)) with
+        c = float32(lr_eff weight_decay).  With everything on the fused tail issues at most seven launches besides the
+        preconditioner calls: perturbation, scale-check, difference, blend, two for the sum of squares, update."""
         params = self._params
         update_Q = self._coin()
         exact = bool(self.exact_hessian_vector_product)
         fused = self._tail is not None
+        mom, wd = self._hyper_momentum()
+        guard = self._guard
+        S = self._loss_scale_value() if guard else 1.0
+        inv = 1.0 / S                                           # exact: S is a power of two
+        scaled = (lambda loss: loss) if S == 1.0 else (lambda loss: loss * S)
         undo = None
         if update_Q and exact:
             with torch.enable_grad():
                 closure_returns = closure()
-                grads = torch.autograd.grad(self._loss_of(closure_returns), params, create_graph=True)
+                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params, create_graph=True)
                 vs = [self._randn(p) for p in params]
                 Hvs = torch.autograd.grad(grads, params, vs)
             grads = [g.detach() for g in grads]
             dXs, dGs = vs, [h.detach() for h in Hvs]
+            if guard:
+                with torch.no_grad():
+                    grads, dGs, bad = self._judge(grads, dGs, vs, inv)
+                self._guard_outcome(bad)
+                if bad:
+                    return closure_returns
         elif update_Q:
             with torch.enable_grad():
                 closure_returns = closure()
-                grads = torch.autograd.grad(self._loss_of(closure_returns), params)
+                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
             undo = vs = [self._randn(p) * _DELTA for p in params]
             with torch.no_grad():
                 if fused:
@@ -427,7 +714,13 @@ class Kron:
                     for p, v in zip(params, vs):
                         p.add_(v)
             with torch.enable_grad():
-                perturbed = torch.autograd.grad(self._loss_of(closure()), params)
+                perturbed = torch.autograd.grad(scaled(self._loss_of(closure())), params)
+            if guard:
+                with torch.no_grad():
+                    grads, perturbed, bad = self._judge(grads, perturbed, vs, inv)
+                self._guard_outcome(bad, vs if bad else None)
+                if bad:
+                    return closure_returns
             with torch.no_grad():
                 if fused:
                     dXs, dGs = self._fd_x, self._fd_h
@@ -439,13 +732,21 @@ class Kron:
         else:
             with torch.enable_grad():
                 closure_returns = closure()
-                grads = torch.autograd.grad(self._loss_of(closure_returns), params)
+                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
+            if guard:
+                with torch.no_grad():
+                    grads, _, bad = self._judge(grads, None, None, inv)
+                self._guard_outcome(bad)
+                if bad:
+                    return closure_returns
         with torch.no_grad():
             if update_Q:
                 lr_q = float(self.lr_preconditioner)
                 with self._block():
                     new = [_psgd.update_precond_kron(q[0], q[1], dX, dG, lr_q) for q, dX, dG in zip(self._Qs, dXs, dGs)]
                 self._Qs = [[a, b] for a, b in new]
+            if mom != 0.0 or self._m_step:
+                grads = self._blend(grads, mom)
             with self._block():
                 pre_grads = [_psgd.precond_grad_kron(q[0], q[1], g) for q, g in zip(self._Qs, grads)]
             lr, max_norm = float(self.lr_params), float(self.grad_clip_max_norm)
@@ -453,7 +754,8 @@ class Kron:
             if fused:
                 pre_grads = [g.contiguous() for g in pre_grads]          # (the mirrored formats return transposed views)
                 sumsq = multi_sumsq(pre_grads, plan=self._tail) if clip else None
-                multi_param_update(params, pre_grads, undo, lr, sumsq, max_norm if clip else None, _TINY, plan=self._tail)
+                multi_param_update(params, pre_grads, undo, lr, sumsq, max_norm if clip else None, _TINY, plan=self._tail,
+                                   weight_decay=wd)
                 return closure_returns
             if clip:
                 S = None
@@ -465,9 +767,14 @@ class Kron:
                 lr = (f64(lr) * ratio).float()
             else:
                 lr = float(np.float32(lr))
+            decay = None
+            if wd != 0.0:                                   # c = fl32(lr_eff * wd), as the kernel forms it
+                decay = lr * torch.tensor(wd, dtype=_f32, device=self._device) if clip else float(np.float32(lr) * np.float32(wd))
             for k, (p, g) in enumerate(zip(params, pre_grads)):
                 delta = g * lr
                 if undo is not None:
                     delta = delta + undo[k]
+                if decay is not None:
+                    delta = delta + p * decay
                 p.sub_(delta)
         return closure_returns

@@ -11,6 +11,16 @@ the range of the per-chunk step times over `--chunks` (>= 7) chunks.  A differen
 resolved, and the summary line says so.
 
     python tools/kron_step_timing.py [--chunks 9] [--steps 50] [--out profiles/kron_class.txt]
+
+--features times the switches of class Kron instead, same shapes and protocol, legs:
+
+    off       class Kron, step_tail="fused", momentum / weight decay / guard at their defaults
+    parent    the same, on the kron_optimizer.py of another commit given with --parent-module FILE (loaded beside this tree's; it
+              runs on this tree's library), when given: the cost of the switches while they are off
+    on-torch  momentum 0.9, weight decay 0.01, nonfinite="skip", loss_scale 2^8, step_tail="torch"
+    on-fused  the same with step_tail="fused"
+
+    python tools/kron_step_timing.py --features [--parent-module FILE] [--out profiles/kron_class_features.txt]
 """
 import argparse
 import os
@@ -62,12 +72,25 @@ def hand_leg(shapes, dev):
     return step
 
 
-def class_leg(tail):
+FEATURES_ON = dict(momentum=0.9, weight_decay=0.01, nonfinite="skip", loss_scale=2.0 ** 8)
+
+
+def class_leg(tail, cls=None, **kw):
     def make(shapes, dev):
         Ws, closure, clip = problem(shapes, dev)
-        opt = psgd.Kron(Ws, "dense", lr_params=LR, lr_preconditioner=LR_Q, grad_clip_max_norm=clip, step_tail=tail)
+        opt = (cls or psgd.Kron)(Ws, "dense", lr_params=LR, lr_preconditioner=LR_Q, grad_clip_max_norm=clip, step_tail=tail, **kw)
         return lambda: opt.step(closure)
     return make
+
+
+def parent_class(path):
+    """class Kron of the kron_optimizer.py at `path`, loaded as a sibling module of this tree's package"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("psgd_tf_amd._parent_kron_optimizer", path)
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules[spec.name] = mod
+    spec.loader.exec_module(mod)
+    return mod.Kron
 
 
 def timed(step, n):
@@ -84,14 +107,26 @@ def main():
     ap.add_argument("--chunks", type=int, default=9)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--features", action="store_true")
+    ap.add_argument("--parent-module", default=None)
     a = ap.parse_args()
     if a.chunks < 7:
         ap.error("--chunks must be at least 7")
     dev = torch.device("cuda:0")
-    lines = ["# tools/kron_step_timing.py --chunks %d --steps %d on %s" % (a.chunks, a.steps, torch.cuda.get_device_name(0)),
+    lines = ["# tools/kron_step_timing.py %s--chunks %d --steps %d on %s"
+             % ("--features " if a.features else "", a.chunks, a.steps, torch.cuda.get_device_name(0)),
              "# us per step (closure + preconditioner + tail), median [min .. max] over the chunks; legs alternate chunk by chunk"]
     for name, shapes in SETS.items():
-        legs = {"hand": hand_leg(shapes, dev), "torch": class_leg("torch")(shapes, dev), "fused": class_leg("fused")(shapes, dev)}
+        if a.features:
+            legs = {"off": class_leg("fused")(shapes, dev)}
+            if a.parent_module:
+                legs["parent"] = class_leg("fused", parent_class(a.parent_module))(shapes, dev)
+            legs["on-torch"] = class_leg("torch", **FEATURES_ON)(shapes, dev)
+            legs["on-fused"] = class_leg("fused", **FEATURES_ON)(shapes, dev)
+            pairs = ([("parent", "off")] if a.parent_module else []) + [("on-torch", "on-fused"), ("on-fused", "off")]
+        else:
+            legs = {"hand": hand_leg(shapes, dev), "torch": class_leg("torch")(shapes, dev), "fused": class_leg("fused")(shapes, dev)}
+            pairs = [("hand", "torch"), ("hand", "fused"), ("torch", "fused")]
         for step in legs.values():                                  # warm-up: at least 0.5 s each, measured with the device drained
             spent = 0.0
             while spent < 0.5:
@@ -102,14 +137,12 @@ def main():
                 times[k].append(timed(step, a.steps))
         med = {k: statistics.median(v) for k, v in times.items()}
         for k, v in times.items():
-            lines.append("%-10s %-6s %9.1f  [%9.1f .. %9.1f]" % (name, k, med[k], min(v), max(v)))
+            lines.append("%-10s %-8s %9.1f  [%9.1f .. %9.1f]" % (name, k, med[k], min(v), max(v)))
         spread = max(max(v) - min(v) for v in times.values())
-        for k in ("torch", "fused"):
-            d = med["hand"] - med[k]
-            lines.append("%-10s hand - %-5s = %+8.1f us: %s (largest range of a leg: %.1f us)"
-                         % (name, k, d, "resolved" if abs(d) > spread else "NOT resolved by this protocol", spread))
-        d = med["torch"] - med["fused"]
-        lines.append("%-10s torch - fused = %+8.1f us: %s" % (name, d, "resolved" if abs(d) > spread else "NOT resolved by this protocol"))
+        for x, y in pairs:
+            d = med[x] - med[y]
+            lines.append("%-10s %s - %s = %+8.1f us: %s (largest range of a leg: %.1f us)"
+                         % (name, x, y, d, "resolved" if abs(d) > spread else "NOT resolved by this protocol", spread))
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if a.out:
