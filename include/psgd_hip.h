@@ -62,6 +62,8 @@ extern "C" {
  *     class Kron (new symbols only: still 7).
  *     psgd_multi_blend_f32, psgd_multi_scale_check_f32 and psgd_multi_param_update_wd_f32: momentum, the non-finite guard with the
  *     loss scale, and decoupled weight decay of class Kron (additive, new symbols only: still 7).
+ *     psgd_multi_widen_check and psgd_multi_param_update_t: bfloat16 / float16 parameters of class Kron (additive, new symbols
+ *     only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -420,7 +422,9 @@ int psgd_uvd_param_update_multi_wd(const void *param_segs, const void *vs_segs, 
  * What an optimizer does around per-layer preconditioner calls (class Kron: mnist_with_lenet5.py:54-56 and the finite-difference
  * route of psgd.py:716-727, :734-736, :761) when NO operand is a flat vector: every operand is a list of k fp32 tensors with its own
  * segment table (psgd_multi_tail.hip).  Tables as above; `start` is not read.  All tables of one call describe tensors of the same
- * element counts and share one chunk table; a chunk never runs past the shortest of its segments.  fp32 only.
+ * element counts and share one chunk table; a chunk never runs past the shortest of its segments.  The _f32 entry points take fp32
+ * lists only; psgd_multi_widen_check and psgd_multi_param_update_t (below) take a PSGD_DTYPE_* code for the lists that hold parameters
+ * of another type.
  * Null tables, k < 0 and nchunks < 0 return PSGD_ERR_BAD_ARG before any HIP call; nchunks == 0 is a no-op (nothing is written).   */
 #define PSGD_MULTI_SUMSQ_WS_BYTES  8192   /* workspace of psgd_multi_sumsq_f32 (8-byte aligned, needs no initialisation) */
 
@@ -468,6 +472,31 @@ int psgd_multi_scale_check_f32(const void *segs0, const void *segs1, const void 
 int psgd_multi_param_update_wd_f32(const void *param_segs, const void *grad_segs, const void *vs_segs, int k, const void *chunks,
                                    int64_t nchunks, float lr, const double *sumsq, float max_norm, float tiny, float wd,
                                    void *stream);
+
+/* Parameters of type T = bfloat16 or float16 (dtype = PSGD_DTYPE_BF16 / PSGD_DTYPE_F16) in class Kron: factors, momentum buffers and
+ * everything the preconditioner reads stay fp32, so once per step the T lists of the step are widened, in ONE launch:
+ *     dst_j[i] = fl32(float(src_j[i]) * scale_j)          for one to three (src_j, dst_j) pairs of lists,
+ * src_j tensors of type T (aligned to their element), dst_j fp32 tensors of the same element counts.  An absent list passes NULL
+ * for BOTH of its tables (list 0 is required); a source without a destination, or the reverse, is PSGD_ERR_BAD_ARG.
+ * flag != NULL: when any value WRITTEN is +-Inf or NaN (a finite input that overflows under its scale counts, and so does an fp16
+ * +-Inf), stamp is stored to *flag -- the flag contract of psgd_multi_scale_check_f32: one 4-byte aligned device word that is never
+ * zeroed, every writer stores the same value with an ordinary store, no atomics, "bad" is *flag == stamp after the launch has
+ * completed.  flag != NULL with stamp <= 0 is PSGD_ERR_BAD_ARG.  flag == NULL only widens (stamp is ignored).
+ * dtype == PSGD_DTYPE_F32 is PSGD_ERR_BAD_ARG: fp32 lists are scaled and judged in place by psgd_multi_scale_check_f32.            */
+int psgd_multi_widen_check(const void *src0, const void *src1, const void *src2, const void *dst0, const void *dst1, const void *dst2,
+                           float scale0, float scale1, float scale2, int k, const void *chunks, int64_t nchunks, int dtype,
+                           int32_t *flag, int32_t stamp, void *stream);
+
+/* psgd_multi_param_update_wd_f32 on parameters and vs of type T with fp32 gradients, every operation rounded to nearest even on its
+ * own (the chain of psgd_uvd_param_update_multi_wd): with c = fl32(lr_eff * wd),
+ *     delta = T(fl32(lr_eff * g[i]));   vs_segs given: delta = T(delta + v[i]);
+ *     wd != 0: delta = T(delta + T(fl32(c * float(p[i]))));   p[i] = T(p[i] - delta).
+ * grad_segs == NULL (vs_segs required, sumsq NULL, wd == 0): p[i] = T(p[i] + v[i]).  lr_eff, sumsq, max_norm, tiny and the rejected
+ * combinations are those of psgd_multi_param_update_wd_f32; wd == 0 takes no extra rounding step.  dtype == PSGD_DTYPE_F32 forwards
+ * to psgd_multi_param_update_wd_f32 (every operand fp32); an unknown dtype is PSGD_ERR_BAD_ARG.                                   */
+int psgd_multi_param_update_t(const void *param_segs, const void *grad_segs, const void *vs_segs, int k, const void *chunks,
+                              int64_t nchunks, int dtype, float lr, const double *sumsq, float max_norm, float tiny, float wd,
+                              void *stream);
 
 /* Tuning knobs for experiments (not part of the stable ABI).
  * key 0: streaming policy (0 = automatic: non-temporal when U,V exceed the Infinity Cache,

@@ -8,6 +8,10 @@
 //   psgd_multi_scale_check_f32   one to three lists: x <- fl32(x s_j) where s_j != 1, and a stamp stored to a flag word when a
 //                                product is not finite                                                              (guarded step)
 //   psgd_multi_param_update_wd_f32  the update with decoupled weight decay: delta <- fl32(delta + fl32(fl32(lr_eff wd) p))
+// and, for parameters of type T = bf16 / fp16 (everything else of the step stays fp32):
+//   psgd_multi_widen_check       one to three lists of T tensors -> as many lists of fp32 tensors, dst <- fl32(float(src) s_j), with the
+//                                flag of psgd_multi_scale_check_f32 on the written values
+//   psgd_multi_param_update_t    the update on T parameters and vs, fp32 gradients: the rounding chain of psgd_uvd_param_update_multi_wd
 //
 // The tables are those of psgd_uvd_tail.hip: a SEGMENT is one tensor {pointer, start, count}, a CHUNK one piece of at most
 // PSGD_UVD_TAIL_CHUNK consecutive elements of one segment {segment index, offset}.  Here EVERY operand is a list: each has its own
@@ -26,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "psgd_hip.h"
+#include "tail_types.h"
 
 // The roundings are the contract (bit-equal to the torch expressions they replace): no product may be fused into a following sum.
 #pragma clang fp contract(off)
@@ -46,12 +51,17 @@ struct Chunk {
   int64_t seg, off;
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));       // 16 bytes from any fp32 element
+// the vector types, and F32 / BF16 / F16 (the PSGD_DTYPE_* codes) with their conversions and 16-byte accesses: tail_types.h
+using namespace psgdtt;
 
 // elements in front of the first 16-byte boundary at or after p, at most n
 __device__ __forceinline__ int head_of(const void* p, int n) {
   const int h = (int)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) / 4;
+  return h < n ? h : n;
+}
+// ... for elements of 2 bytes
+__device__ __forceinline__ int head_of_16bit(const void* p, int n) {
+  const int h = (int)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) / 2;
   return h < n ? h : n;
 }
 
@@ -341,7 +351,191 @@ __global__ __launch_bounds__(kT) void k_multi_scale_check(const Seg* __restrict_
   if (flag != nullptr && bad) *reinterpret_cast<volatile int32_t*>(flag) = stamp;
 }
 
+// ------------------------------------------------------------------------------------- half-precision parameters: widen and check
+// one list inside one chunk: dst = fl32(float(src) s), src of type T (bf16 / fp16), dst fp32; returns whether a value this lane
+// wrote is not finite.  The stored side is dst: head, body (4 floats = 16 bytes per lane and access, 8 bytes of src through the
+// element-aligned type) and tail are laid on its 16-byte boundaries.
+template <class T>
+__device__ __forceinline__ bool widen_list(const uint16_t* src, float* dst, int n, float s, int t) {
+  bool bad = false;
+  const int head = head_of(dst, n);
+  const int nvec = (n - head) / 4;
+  if (t < head) {
+    const float y = T::widen(src[t]) * s;
+    bad |= not_finite(y);
+    dst[t] = y;
+  }
+#pragma unroll 2
+  for (int q = t; q < nvec; q += kT) {
+    const int i = head + q * 4;
+    const u16x4_u v = *reinterpret_cast<const u16x4_u*>(src + i);
+    f32x4 y;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      y[e] = T::widen(v[e]) * s;
+      bad |= not_finite(y[e]);
+    }
+    *reinterpret_cast<f32x4*>(dst + i) = y;
+  }
+  const int i = head + nvec * 4 + t;
+  if (i < n) {
+    const float y = T::widen(src[i]) * s;
+    bad |= not_finite(y);
+    dst[i] = y;
+  }
+  return bad;
+}
+
+// One to three (source, destination) pairs of lists in one launch; the flag is that of k_multi_scale_check.  A chunk never runs
+// past the shortest of its segments, sources and destinations alike.
+template <class T>
+__global__ __launch_bounds__(kT) void k_multi_widen_check(const Seg* __restrict__ src0, const Seg* __restrict__ src1,
+                                                          const Seg* __restrict__ src2, const Seg* __restrict__ dst0,
+                                                          const Seg* __restrict__ dst1, const Seg* __restrict__ dst2, float s0,
+                                                          float s1, float s2, const Chunk* __restrict__ chunks, int64_t nchunks,
+                                                          int k, int32_t* flag, int32_t stamp) {
+  const int t = threadIdx.x;
+  bool bad = false;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Chunk ch = chunks[c];
+    if ((uint64_t)ch.seg >= (uint64_t)k || ch.off < 0) continue;     // a table that does not belong to these segments moves nothing
+    const Seg* const srcs[3] = {src0, src1, src2};
+    const Seg* const dsts[3] = {dst0, dst1, dst2};
+    const float scales[3] = {s0, s1, s2};
+    const uint16_t* sp[3] = {nullptr, nullptr, nullptr};
+    float* dp[3] = {nullptr, nullptr, nullptr};
+    int64_t left = kChunk;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (!srcs[j]) continue;
+      const Seg a = srcs[j][ch.seg];
+      const Seg b = dsts[j][ch.seg];
+      const int64_t l = (a.count < b.count ? a.count : b.count) - ch.off;
+      left = l < left ? l : left;
+      sp[j] = reinterpret_cast<const uint16_t*>(a.ptr) + ch.off;
+      dp[j] = reinterpret_cast<float*>(b.ptr) + ch.off;
+    }
+    if (left <= 0) continue;
+    const int n = (int)left;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (srcs[j]) bad |= widen_list<T>(sp[j], dp[j], n, scales[j], t);
+  }
+  if (flag != nullptr && bad) *reinterpret_cast<volatile int32_t*>(flag) = stamp;
+}
+
+// --------------------------------------------------------------------------------- half-precision parameters: the typed update
+// The rounding chain of psgd_uvd_param_update_multi_wd (k_uvd_param_update) with the gradients in a list of fp32 tensors:
+// delta = T(fl32(lr_eff g)); kVs: delta = T(delta + v); kWd: delta = T(delta + T(fl32(c p))), c = fl32(lr_eff wd); the caller
+// narrows p - delta.  !kPre: p + v.  kOpaque (the scalar head and tail): the products reach the narrowing as rounded fp32 values
+// in a register -- left to itself hipcc selects v_fma_mixlo_f16 x, y, 0 for the float16 narrow(x * y), and the +0 addend turns a -0
+// product into +0 (see psgd_uvd_tail.hip, where the same chain is tested for it).
+template <class T, bool kPre, bool kVs, bool kWd, bool kOpaque = false>
+__device__ __forceinline__ float update_one_t(float p, float g, float v, float lr_eff, float c) {
+  if constexpr (!kPre) {
+    return p + v;
+  } else {
+    float prod = lr_eff * g;
+    if constexpr (kOpaque) asm("" : "+v"(prod));
+    float delta = T::widen(T::narrow(prod));
+    if constexpr (kVs) delta = T::widen(T::narrow(delta + v));
+    if constexpr (kWd) {
+      float dec = c * p;
+      if constexpr (kOpaque) asm("" : "+v"(dec));
+      delta = T::widen(T::narrow(delta + T::widen(T::narrow(dec))));
+    }
+    return p - delta;
+  }
+}
+
+// parameters and vs of type T (bf16 / fp16), gradients fp32.  The stored side is p: a scalar head to its 16-byte boundary, a body of
+// 8 elements (16 bytes) per lane and access, a scalar tail; g (two 16-byte reads) and v go through the element-aligned types.
+template <class T, bool kPre, bool kVs, bool kWd>
+__global__ __launch_bounds__(kT) void k_multi_param_update_t(const Seg* __restrict__ psegs, const Seg* __restrict__ gsegs,
+                                                             const Seg* __restrict__ vsegs, const Chunk* __restrict__ chunks,
+                                                             int64_t nchunks, int k, float lr, const double* __restrict__ sumsq,
+                                                             float max_norm, float tiny, float wd) {
+  static_assert(T::E == 8, "bf16 / fp16 only: the fp32 lists keep k_multi_param_update");
+  const int t = threadIdx.x;
+  float lr_eff = lr;
+  if (kPre && sumsq) {        // as k_multi_param_update: fp64, one rounding, a NaN norm propagates
+    const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
+    lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
+  }
+  const float dc = kWd ? lr_eff * wd : 0.f;         // c = fl32(lr_eff wd)
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Chunk ch = chunks[c];
+    if ((uint64_t)ch.seg >= (uint64_t)k || ch.off < 0) continue;
+    const Seg ps = psegs[ch.seg];
+    int64_t left = ps.count - ch.off;
+    left = left < kChunk ? left : kChunk;
+    uint16_t* p = reinterpret_cast<uint16_t*>(ps.ptr) + ch.off;
+    const float* g = nullptr;
+    const uint16_t* v = nullptr;
+    if constexpr (kPre) {
+      const Seg gs = gsegs[ch.seg];
+      const int64_t l = gs.count - ch.off;
+      left = l < left ? l : left;
+      g = reinterpret_cast<const float*>(gs.ptr) + ch.off;
+    }
+    if constexpr (kVs) {
+      const Seg vsg = vsegs[ch.seg];
+      const int64_t l = vsg.count - ch.off;
+      left = l < left ? l : left;
+      v = reinterpret_cast<const uint16_t*>(vsg.ptr) + ch.off;
+    }
+    if (left <= 0) continue;
+    const int n = (int)left;
+    const int head = head_of_16bit(p, n);
+    const int nvec = (n - head) / 8;
+    if (t < head)
+      p[t] = T::narrow(update_one_t<T, kPre, kVs, kWd, true>(T::widen(p[t]), kPre ? g[t] : 0.f, kVs ? T::widen(v[t]) : 0.f, lr_eff, dc));
+#pragma unroll 2
+    for (int q = t; q < nvec; q += kT) {
+      const int i = head + q * 8;
+      float x[8], gg[8], vv[8];
+      load_16<T>(p + i, x);
+      if constexpr (kPre) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          const f32x4_u w = *reinterpret_cast<const f32x4_u*>(g + i + 4 * b);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) gg[4 * b + e] = w[e];
+        }
+      }
+      if constexpr (kVs) load_any<T>(v + i, vv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) x[e] = update_one_t<T, kPre, kVs, kWd>(x[e], kPre ? gg[e] : 0.f, kVs ? vv[e] : 0.f, lr_eff, dc);
+      store_16<T>(p + i, x);
+    }
+    const int i = head + nvec * 8 + t;
+    if (i < n)
+      p[i] = T::narrow(update_one_t<T, kPre, kVs, kWd, true>(T::widen(p[i]), kPre ? g[i] : 0.f, kVs ? T::widen(v[i]) : 0.f, lr_eff, dc));
+  }
+}
+
 static int grid_for(int64_t nchunks) { return (int)(nchunks < kMaxGrid ? nchunks : kMaxGrid); }
+
+template <class T>
+static void launch_update_t(int grid, hipStream_t st, const Seg* ps, const Seg* gs, const Seg* vsg, const Chunk* ch, int64_t nchunks,
+                            int k, float lr, const double* sumsq, float max_norm, float tiny, float wd) {
+#define PSGD_MULTI_UPDATE_T(PRE, VS, WD)                                                                                         \
+  hipLaunchKernelGGL((k_multi_param_update_t<T, PRE, VS, WD>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, \
+                     sumsq, max_norm, tiny, wd)
+  if (!gs)
+    PSGD_MULTI_UPDATE_T(false, true, false);
+  else if (wd != 0.f) {                      // (a NaN wd decays too: it propagates)
+    if (vsg)
+      PSGD_MULTI_UPDATE_T(true, true, true);
+    else
+      PSGD_MULTI_UPDATE_T(true, false, true);
+  } else if (vsg)
+    PSGD_MULTI_UPDATE_T(true, true, false);
+  else
+    PSGD_MULTI_UPDATE_T(true, false, false);
+#undef PSGD_MULTI_UPDATE_T
+}
+
 static int launched() { return hipGetLastError() == hipSuccess ? PSGD_OK : PSGD_ERR_LAUNCH; }
 
 }  // namespace psgdm
@@ -443,6 +637,48 @@ int psgd_multi_diff_scale_f32(const void* a_segs, const void* b_segs, const void
   else
     hipLaunchKernelGGL(k_multi_diff_scale<false>, dim3(grid), dim3(kT), 0, st, (const Seg*)a_segs, (const Seg*)b_segs,
                        (const Seg*)h_segs, (const Seg*)v_segs, (const Seg*)x_segs, ch, nchunks, k, s);
+  return launched();
+}
+
+int psgd_multi_widen_check(const void* src0, const void* src1, const void* src2, const void* dst0, const void* dst1, const void* dst2,
+                           float scale0, float scale1, float scale2, int k, const void* chunks, int64_t nchunks, int dtype,
+                           int32_t* flag, int32_t stamp, void* stream) {
+  if (!src0 || !dst0 || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
+  if ((src1 == nullptr) != (dst1 == nullptr) || (src2 == nullptr) != (dst2 == nullptr)) return PSGD_ERR_BAD_ARG;
+  if (dtype != PSGD_DTYPE_BF16 && dtype != PSGD_DTYPE_F16) return PSGD_ERR_BAD_ARG;      // fp32 lists: psgd_multi_scale_check_f32
+  if (flag && (stamp <= 0 || ((uintptr_t)flag & 3))) return PSGD_ERR_BAD_ARG;
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = grid_for(nchunks);
+  if (dtype == PSGD_DTYPE_BF16)
+    hipLaunchKernelGGL(k_multi_widen_check<BF16>, dim3(grid), dim3(kT), 0, st, (const Seg*)src0, (const Seg*)src1, (const Seg*)src2,
+                       (const Seg*)dst0, (const Seg*)dst1, (const Seg*)dst2, scale0, scale1, scale2, (const Chunk*)chunks, nchunks, k,
+                       flag, stamp);
+  else
+    hipLaunchKernelGGL(k_multi_widen_check<F16>, dim3(grid), dim3(kT), 0, st, (const Seg*)src0, (const Seg*)src1, (const Seg*)src2,
+                       (const Seg*)dst0, (const Seg*)dst1, (const Seg*)dst2, scale0, scale1, scale2, (const Chunk*)chunks, nchunks, k,
+                       flag, stamp);
+  return launched();
+}
+
+int psgd_multi_param_update_t(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
+                              int64_t nchunks, int dtype, float lr, const double* sumsq, float max_norm, float tiny, float wd,
+                              void* stream) {
+  if (dtype < PSGD_DTYPE_F32 || dtype > PSGD_DTYPE_F16) return PSGD_ERR_BAD_ARG;
+  if (dtype == PSGD_DTYPE_F32)                // every operand fp32: the same kernels, the same bits
+    return psgd_multi_param_update_wd_f32(param_segs, grad_segs, vs_segs, k, chunks, nchunks, lr, sumsq, max_norm, tiny, wd, stream);
+  if (!param_segs || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
+  if (!grad_segs && (!vs_segs || sumsq)) return PSGD_ERR_BAD_ARG;            // nothing to do, or a clip norm without a gradient
+  if (!grad_segs && wd != 0.f) return PSGD_ERR_BAD_ARG;                      // the perturbation p + v takes no decay
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = grid_for(nchunks);
+  if (dtype == PSGD_DTYPE_BF16)
+    launch_update_t<BF16>(grid, st, (const Seg*)param_segs, (const Seg*)grad_segs, (const Seg*)vs_segs, (const Chunk*)chunks, nchunks,
+                          k, lr, sumsq, max_norm, tiny, wd);
+  else
+    launch_update_t<F16>(grid, st, (const Seg*)param_segs, (const Seg*)grad_segs, (const Seg*)vs_segs, (const Chunk*)chunks, nchunks,
+                         k, lr, sumsq, max_norm, tiny, wd);
   return launched();
 }
 

@@ -5,7 +5,7 @@ lstm_with_xor_problem.py and the NMT demo).  The interface and the step(closure)
 the arithmetic is that of mnist_with_lenet5.py:43-57, with the finite-difference Hessian-vector product of psgd.py:716-727.
 
     multi_sumsq, multi_param_update, multi_diff_scale,
-    multi_blend, multi_scale_check                        thin wrappers of the list kernels (csrc/psgd_multi_tail.hip)
+    multi_blend, multi_scale_check, multi_widen_check     thin wrappers of the list kernels (csrc/psgd_multi_tail.hip)
     kron_initial_factors                                  the initial factor pair of one layer
     Kron(...).step(closure)                               the optimizer
 """
@@ -23,12 +23,25 @@ _f32 = torch.float32
 _TINY = float(np.finfo(np.float32).tiny)
 _DELTA = float(np.float32(np.sqrt(np.float32(np.finfo(np.float32).eps))))      # psgd.py:683 for fp32 parameters
 _FD_INV = float(np.float32(1.0) / np.float32(_DELTA))                           # the s of dG = (g' - g) s, dX = v s
+_HALF = (torch.bfloat16, torch.float16)
+_DTYPE_NAMES = {torch.float32: "float32", torch.bfloat16: "bfloat16", torch.float16: "float16"}
+
+
+def _dtype_constants(dtype):
+    """(delta, s, tiny) of parameters of this dtype: the perturbation scale of psgd.py:683, s = float32(1) / float32(delta) of
+    dG = (g' - g) s and dX = v s, and the tiny of the clip norm (psgd.py:682).  float32: the module's constants; bfloat16 /
+    float16: formed as class UVd forms its _delta_param_scale, _fd_inv_scale and _tiny."""
+    if dtype == _f32:
+        return _DELTA, _FD_INV, _TINY
+    delta = torch.finfo(dtype).eps ** 0.5
+    return delta, float(np.float32(1.0) / np.float32(delta)), torch.finfo(dtype).tiny
 
 
 # --------------------------------------------------------------------------- list kernels
 class MultiTailPlan(_psgd.UVdTailPlan):
     """The chunk table, the segment tables (one per role), the device double of the clip norm and the workspace of its reduction for
-    lists of fp32 tensors of fixed sizes.  Calls that share a plan must run on one stream."""
+    lists of tensors of fixed sizes.  The tables hold pointers and element counts only, so one plan serves the fp32 lists and
+    the bfloat16 / float16 lists of the typed entry points alike.  Calls that share a plan must run on one stream."""
 
     def __init__(self, sizes, device):
         super().__init__(sizes, torch.float32, device)
@@ -37,6 +50,22 @@ class MultiTailPlan(_psgd.UVdTailPlan):
         # kernel stores a stamp that this word has not seen before, so nothing ever clears it again
         self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.stamp = 0
+
+    def table(self, role, tensors, what, dtype=_f32):
+        """device pointer of the segment table of `tensors` (contiguous tensors of `dtype` with the plan's sizes) in this role"""
+        if dtype == self.dtype:
+            return super().table(role, tensors, what)
+        if len(tensors) != len(self.sizes):
+            raise ValueError("%s: %d tensors, the plan has %d" % (what, len(tensors), len(self.sizes)))
+        for t, n in zip(tensors, self.sizes):
+            if t.dtype != dtype or t.device != self.device or t.numel() != n or not t.is_contiguous():
+                raise ValueError("%s: every tensor must be a contiguous %s tensor on %s with the plan's element count (%d), got %s %s "
+                                 "%s%s" % (what, dtype, self.device, n, t.dtype, t.device, tuple(t.shape),
+                                           "" if t.is_contiguous() else " strided"))
+        tab = self._tables.get(role)
+        if tab is None:
+            tab = self._tables[role] = _psgd._SegTable(self.starts, self.sizes, self.device)
+        return tab.refresh([t.data_ptr() for t in tensors])
 
     def next_stamp(self):
         """1 .. 2^31 - 1, then 1 again"""
@@ -47,16 +76,17 @@ class MultiTailPlan(_psgd.UVdTailPlan):
 _multi_plans = {}
 
 
-def _check_list(what, name, tensors, sizes=None, device=None):
-    """one operand list of a list kernel: fp32 contiguous tensors on one HIP device, sizes[i] elements at position i"""
+def _check_list(what, name, tensors, sizes=None, device=None, dtype=_f32):
+    """one operand list of a list kernel: contiguous tensors of `dtype` (float32 unless the caller names another) on one HIP
+    device, sizes[i] elements at position i"""
     tensors = list(tensors)
     if sizes is not None and len(tensors) != len(sizes):
         raise ValueError("%s: %s has %d tensors, the first list has %d" % (what, name, len(tensors), len(sizes)))
     for i, t in enumerate(tensors):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s: %s[%d] is not a torch tensor (%r)" % (what, name, i, type(t)))
-        if t.dtype != _f32:
-            raise TypeError("%s: %s[%d] must be float32, got %s" % (what, name, i, t.dtype))
+        if t.dtype != dtype:
+            raise TypeError("%s: %s[%d] must be %s, got %s" % (what, name, i, _DTYPE_NAMES[dtype], t.dtype))
         if not t.is_cuda:
             raise _lib.PsgdHipError("%s runs on the HIP device only (%s[%d] is on %s); no CPU fallback" % (what, name, i, t.device))
         if device is None:
@@ -71,16 +101,17 @@ def _check_list(what, name, tensors, sizes=None, device=None):
     return tensors, device
 
 
-def _lists(what, first, *others, plan=None):
-    """checks every list against the first one; returns (lists, plan)"""
+def _lists(what, first, *others, plan=None, dtypes=None):
+    """checks every list against the first one; returns (lists, plan).  dtypes: {list name: dtype} of the lists that are not fp32"""
+    dtypes = dtypes or {}
     name0, t0 = first
-    t0, dev = _check_list(what, name0, t0)
+    t0, dev = _check_list(what, name0, t0, dtype=dtypes.get(name0, _f32))
     if not t0:
         raise ValueError("%s: empty tensor list" % what)
     sizes = tuple(int(t.numel()) for t in t0)
     out = [t0]
     for name, ts in others:
-        out.append(None if ts is None else _check_list(what, name, ts, sizes, dev)[0])
+        out.append(None if ts is None else _check_list(what, name, ts, sizes, dev, dtypes.get(name, _f32))[0])
     if plan is None:
         key = (dev, sizes)
         plan = _multi_plans.get(key)
@@ -124,12 +155,21 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
     every parameter NaN, as torch.minimum does.  tiny defaults to the smallest normal float32.
     weight_decay (decoupled; psgd_multi_param_update_wd_f32): with c = float32(lr_eff * weight_decay), the subtracted term gains
     float32(c * p) after the vs term; 0 (default) adds no rounding step and calls the entry point without decay.
-    The parameters are written through their pointers: autograd's version counters do not move."""
+    The parameters are written through their pointers: autograd's version counters do not move.
+    Half precision: when params[0] is a bfloat16 or float16 tensor on the HIP device, params and vs have that type T, grads stay
+    float32, and the call goes to psgd_multi_param_update_t: delta = T(float32(lr_eff * g)), then T(delta + v), then
+    T(delta + T(float32(c * float(p)))), p <- T(p - delta); p <- T(p + v) without grads.  tiny then defaults to finfo(T).tiny.
+    (A half-precision tensor that is not on the device is refused as before: params must be float32.)"""
     what = "multi_param_update"
     wd = float(weight_decay)
     if not wd >= 0.0:
         raise ValueError("%s: weight_decay must be >= 0, got %r" % (what, weight_decay))
-    (params, grads, vs), plan = _lists(what, ("params", params), ("grads", grads), ("vs", vs), plan=plan)
+    params = list(params)
+    T = _f32
+    if params and isinstance(params[0], torch.Tensor) and params[0].is_cuda and params[0].dtype in _HALF:
+        T = params[0].dtype
+    (params, grads, vs), plan = _lists(what, ("params", params), ("grads", grads), ("vs", vs), plan=plan,
+                                       dtypes={"params": T, "vs": T})
     if grads is None and (vs is None or sumsq is not None or wd != 0.0):
         raise ValueError("%s: grads=None adds vs to the parameters; it needs vs and takes no sumsq and no weight_decay" % what)
     if (sumsq is None) != (max_norm is None):
@@ -139,10 +179,15 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
         raise ValueError("%s: sumsq must be a float64 tensor of at least one element on %s" % (what, plan.device))
     if not plan.nchunks:
         return
-    args = (plan.table("params", params, what), None if grads is None else plan.table("grads", grads, what),
-            None if vs is None else plan.table("vs", vs, what), len(params), plan.chunks.data_ptr(), plan.nchunks, float(lr),
-            None if sumsq is None else sumsq.data_ptr(), 0.0 if max_norm is None else float(max_norm),
-            _TINY if tiny is None else float(tiny))
+    tabs = (plan.table("params", params, what, T), None if grads is None else plan.table("grads", grads, what),
+            None if vs is None else plan.table("vs", vs, what, T), len(params), plan.chunks.data_ptr(), plan.nchunks)
+    tail = (float(lr), None if sumsq is None else sumsq.data_ptr(), 0.0 if max_norm is None else float(max_norm),
+            float(_dtype_constants(T)[2] if tiny is None else tiny))
+    if T != _f32:
+        rc = _lib.load().psgd_multi_param_update_t(*tabs, _psgd._TAIL_DTYPES[T], *tail, wd, _psgd._stream_ptr(plan.device))
+        _lib.check(rc, "psgd_multi_param_update_t")
+        return
+    args = tabs + tail
     if wd == 0.0:
         rc = _lib.load().psgd_multi_param_update_f32(*args, _psgd._stream_ptr(plan.device))
         _lib.check(rc, "psgd_multi_param_update_f32")
@@ -215,6 +260,48 @@ def multi_scale_check(lists, scales, *, flag=None, stamp=None, plan=None):
                                                 plan.nchunks, word, 0 if stamp is None else int(stamp),
                                                 _psgd._stream_ptr(plan.device))
     _lib.check(rc, "psgd_multi_scale_check_f32")
+
+
+def multi_widen_check(srcs, dsts, scales, *, flag=None, stamp=None, plan=None):
+    """One to three lists of bfloat16 or float16 tensors widened into as many lists of float32 tensors in ONE launch
+    (psgd_multi_widen_check): dsts[j][i] <- float32(float(srcs[j][i]) * scales[j]).  All source tensors have the dtype of
+    srcs[0][0]; every destination is written whole.  With flag and stamp (both or neither) stamp is stored to flag[0], an int32
+    device word, when any value written is +-Inf or NaN -- the flag of multi_scale_check: the caller passes a stamp it has not
+    used on this word before (1 .. 2^31 - 1; plan.next_stamp() for plan.flag) and reads flag[0] == stamp after the launch;
+    nothing zeroes the word.  Without a flag the call only widens."""
+    what = "multi_widen_check"
+    srcs, dsts, scales = list(srcs), list(dsts), [float(np.float32(s)) for s in scales]
+    if not 1 <= len(srcs) <= 3 or len(dsts) != len(srcs) or len(scales) != len(srcs):
+        raise ValueError("%s: one to three source lists, a destination list and a scale for each, got %d, %d and %d"
+                         % (what, len(srcs), len(dsts), len(scales)))
+    if (flag is None) != (stamp is None):
+        raise ValueError("%s: flag and stamp go together (got flag=%s, stamp=%r)" % (what, "None" if flag is None else "given", stamp))
+    srcs = [None if ts is None else list(ts) for ts in srcs]
+    if any(ts is None for ts in srcs) or any(ts is None for ts in dsts):
+        raise ValueError("%s: a list is None" % what)
+    first = srcs[0][0] if srcs[0] else None
+    T = first.dtype if isinstance(first, torch.Tensor) else None
+    if isinstance(first, torch.Tensor) and T not in _HALF:
+        raise TypeError("%s: srcs[0][0] must be bfloat16 or float16, got %s (float32 lists are scaled in place by multi_scale_check)"
+                        % (what, T))
+    names = ["srcs[%d]" % j for j in range(len(srcs))]
+    lists, plan = _lists(what, *(list(zip(names, srcs)) + [("dsts[%d]" % j, ts) for j, ts in enumerate(dsts)]), plan=plan,
+                         dtypes={n: T for n in names})
+    srcs, dsts = lists[:len(srcs)], lists[len(srcs):]
+    word = None
+    if flag is not None:
+        word = _psgd._flag_word(what, flag, stamp, plan.device)
+        if not 1 <= int(stamp) <= 2 ** 31 - 1:
+            raise ValueError("%s: stamp must be in 1 .. 2^31 - 1, got %r" % (what, stamp))
+    if not plan.nchunks:
+        return
+    pad = [None] * (3 - len(srcs))
+    rc = _lib.load().psgd_multi_widen_check(*([plan.table("widen_src%d" % j, ts, what, T) for j, ts in enumerate(srcs)] + pad),
+                                            *([plan.table("widen_dst%d" % j, ts, what) for j, ts in enumerate(dsts)] + pad),
+                                            *(scales + [1.0] * len(pad)), len(srcs[0]), plan.chunks.data_ptr(), plan.nchunks,
+                                            _psgd._TAIL_DTYPES[T], word, 0 if stamp is None else int(stamp),
+                                            _psgd._stream_ptr(plan.device))
+    _lib.check(rc, "psgd_multi_widen_check")
 
 
 # --------------------------------------------------------------------------- formats and initial factors
@@ -380,8 +467,8 @@ class Kron:
     """Kronecker-product preconditioned SGD, one factor pair per rank-2 parameter: the train_step of mnist_with_lenet5.py:43-57 behind
     the interface of class UVd.
 
-    params_with_grad: contiguous float32 rank-2 tensors with requires_grad=True on one HIP device (nested lists / dicts are flattened
-    as class UVd does).  preconditioner_formats: "dense", a (left, right) pair of "dense" / "norm" / "scale", or one of either per
+    params_with_grad: contiguous rank-2 tensors of one dtype (float32, bfloat16 or float16) with requires_grad=True on one HIP
+    device (nested lists / dicts are flattened as class UVd does).  preconditioner_formats: "dense", a (left, right) pair of "dense" / "norm" / "scale", or one of either per
     parameter.  The five hyper-parameters are _Hyper objects (.assign()).  grad_clip_max_norm=None: no clipping.
     layer_batch: the per-layer calls of a step run inside kron.layer_batch() blocks (one for the updates, one for the applies).
     step_tail: "torch" = per-tensor torch expressions around the preconditioner calls; "fused" = the list kernels (at most five
@@ -397,7 +484,15 @@ class Kron:
     changes nothing (skipped_steps, last_step_skipped).  loss_scale (needs "skip"): None, a power of two, or "dynamic" (starts at
     2^16, uvd_loss_scale_next with loss_scale_growth_interval); a _Hyper that holds the CURRENT scale.  See step().
 
-    Out of scope: half-precision parameters, parameters of rank 1 or 3."""
+    Parameters of dtype T = bfloat16 or float16 (all of one optimizer share T): the factors, the momentum buffers, dX, dG, the
+    gradients given to precond_grad_kron, the preconditioned gradients and the clip norm stay float32; the gradients, the second
+    list and the probe vectors are widened once per step, and only the update is rounded in T, with the chain of class UVd's
+    psgd_uvd_param_update_multi_wd (see step()).  delta = finfo(T).eps ** 0.5 and tiny = finfo(T).tiny as in class UVd
+    (psgd.py:682-683).  A checkpoint has no dtype in it: a dict saved from a float32 optimizer loads into a bfloat16 one of the same
+    shapes and back.
+
+    Out of scope: feeding (dense, dense) layers to the bf16-operand Kron kernels from inside the class, mixed dtypes, parameters of
+    rank 1 or 3, a narrow (bfloat16) factor state."""
 
     def __init__(self, params_with_grad, preconditioner_formats="dense", preconditioner_init_scale=1.0, lr_params=0.01,
                  lr_preconditioner=0.01, grad_clip_max_norm=None, preconditioner_update_probability=1.0,
@@ -435,8 +530,10 @@ class Kron:
             if not isinstance(p, torch.Tensor):
                 raise TypeError("Kron: parameter %d is not a torch tensor (%r)" % (i, type(p)))
             tag = "parameter %d (shape %s, %s)" % (i, tuple(p.shape), p.dtype)
-            if p.dtype != _f32:
-                raise TypeError("Kron: %s must be float32; half-precision parameters are out of scope" % tag)
+            if p.dtype not in _DTYPE_NAMES:
+                raise TypeError("Kron: %s must be float32, bfloat16 or float16" % tag)
+            if p.dtype != params[0].dtype:
+                raise TypeError("Kron: %s must be %s like parameter 0" % (tag, params[0].dtype))     # one dtype per optimizer
             if p.dim() != 2:
                 raise ValueError("Kron: %s must have rank 2; reshape it (the reference's demos fold a bias into its matrix)" % tag)
             if not p.requires_grad:
@@ -451,6 +548,11 @@ class Kron:
                 raise ValueError("Kron: parameter %d (shape %s) is on %s; all parameters must be on one HIP device (parameter 0 is on %s)"
                                  % (i, tuple(p.shape), p.device, dev))
         self._params, self._device = params, dev
+        # T = the parameters' dtype.  Half precision: factors, momentum buffers and everything the preconditioner reads stay fp32;
+        # delta, s and tiny follow T as in class UVd (psgd.py:682-683)
+        self._dtype = params[0].dtype
+        self._half = self._dtype != _f32
+        self._delta, self._fd_inv, self._tiny = _dtype_constants(self._dtype)
         self._Qs = [kron_initial_factors(s, f, preconditioner_init_scale, dev, "parameter %d" % i)
                     for i, (s, f) in enumerate(zip(self._shapes, self._formats))]
         self.lr_params = _psgd._Hyper(lr_params)
@@ -464,8 +566,12 @@ class Kron:
         if step_tail == "fused":
             self._tail = MultiTailPlan([int(p.numel()) for p in params], dev)
             # dG and dX of the finite-difference route: written whole by multi_diff_scale before anything reads them
-            self._fd_h = [torch.empty_like(p, requires_grad=False) for p in params]
-            self._fd_x = [torch.empty_like(p, requires_grad=False) for p in params]
+            self._fd_h = [torch.empty_like(p, dtype=_f32, requires_grad=False) for p in params]
+            self._fd_x = [torch.empty_like(p, dtype=_f32, requires_grad=False) for p in params]
+            if self._half:
+                # the fp32 copies of the gradients, the second list and the probe vectors: written whole by the one
+                # multi_widen_check launch of a step before anything reads them
+                self._wide = [[torch.empty_like(p, dtype=_f32, requires_grad=False) for p in params] for _ in range(3)]
 
     # ------------------------------------------------------------------------------------------------- state
     @property
@@ -545,7 +651,7 @@ class Kron:
     def _momentum_buffers(self):
         """one zero-initialised fp32 buffer per parameter, created on first use"""
         if self._m is None:
-            self._m = [torch.zeros_like(p, requires_grad=False) for p in self._params]
+            self._m = [torch.zeros_like(p, dtype=_f32, requires_grad=False) for p in self._params]
         return self._m
 
     @staticmethod
@@ -589,6 +695,40 @@ class Kron:
             ok = f if ok is None else ok & f
         return grads, second, not bool(ok.item())                                           # ... and of the torch tail
 
+    def _widen(self, grads, second, vs, inv):
+        """The widening pass of a step on bfloat16 / float16 parameters, BEFORE anything else reads its inputs: the gradients and
+        the second list become float32(float(x) * inv), the probe vectors float(v); the guard, where on, judges exactly the values
+        written (a finite input that overflows under inv counts, and so does an fp16 +-Inf).  second and vs are None on a step
+        that leaves the factors alone.  Returns (grads, second, vs, bad), fp32 lists.  Fused tail: ONE multi_widen_check launch
+        into the preallocated lists, guarded or not, and ONE 4-byte host read when guarded; torch tail: per-tensor expressions and,
+        when guarded, torch.isfinite(...).all() with one host read of one bool."""
+        if self._tail is not None:
+            srcs, scales = [[g.contiguous() for g in grads]], [inv]
+            if second is not None:
+                srcs += [[h.contiguous() for h in second], [v.contiguous() for v in vs]]
+                scales += [inv, 1.0]
+            dsts = self._wide[:len(srcs)]
+            plan, bad = self._tail, False
+            if self._guard:
+                stamp = plan.next_stamp()
+                multi_widen_check(srcs, dsts, scales, flag=plan.flag, stamp=stamp, plan=plan)
+                bad = int(plan.flag.item()) == stamp                                            # the host read of a guarded step
+            else:
+                multi_widen_check(srcs, dsts, scales, plan=plan)
+            wide = dsts + [None] * (3 - len(dsts))
+            return wide[0], wide[1], wide[2], bad
+        grads = [g.float() * inv for g in grads]
+        if second is not None:
+            second, vs = [h.float() * inv for h in second], [v.float() for v in vs]
+        bad = False
+        if self._guard:
+            ok = None
+            for x in list(grads) + list(second or ()) + list(vs or ()):
+                f = torch.isfinite(x).all()
+                ok = f if ok is None else ok & f
+            bad = not bool(ok.item())                                                           # ... and of the torch tail
+        return grads, second, vs, bad
+
     def _guard_outcome(self, skipped, undo_vs=None):
         """book-keeping of a guarded step once its decision is known; a skipped finite-difference step takes the perturbation of
         psgd.py:723 back, p <- fl32(p - v): the reference's own undo, within one rounding of the parameters before the step"""
@@ -629,7 +769,7 @@ class Kron:
         gen = self._generator
         if gen is None:
             return torch.randn_like(p, requires_grad=False)
-        v = torch.randn(p.shape, dtype=_f32, device=gen.device, generator=gen)
+        v = torch.randn(p.shape, dtype=p.dtype, device=gen.device, generator=gen)
         return v if v.device == p.device else v.to(p.device)
 
     def _coin(self):
@@ -677,13 +817,26 @@ class Kron:
         uvd_momentum_coefficients (k counts the steps blended so far; a step taken with momentum == 0 sets it back to 0), and step 5
         is applied to m (fused tail: one multi_blend launch).  weight_decay: step 7 subtracts float32(delta + float32(c p)) with
         c = float32(lr_eff weight_decay).  With everything on the fused tail issues at most seven launches besides the
-        preconditioner calls: perturbation, scale-check, difference, blend, two for the sum of squares, update."""
+        preconditioner calls: perturbation, scale-check, difference, blend, two for the sum of squares, update.
+
+        Parameters of dtype T = bfloat16 / float16 (nothing of this runs for float32).  The probe vectors are drawn in T (step 3:
+        T(randn_T * delta), delta = finfo(T).eps ** 0.5; the perturbation is p <- T(p + v)).  A WIDENING PASS comes first, once per
+        step and before anything else reads its inputs: gradients and second list -> float32(float(x) * inv), probe vectors ->
+        float(v); the guard, where on, judges exactly these written values, so an fp16 gradient that is already +-Inf skips the
+        step.  Fused tail: one multi_widen_check launch into preallocated float32 lists (in the place of the scale-check; one
+        4-byte host read when guarded); torch tail: `g.float() * inv` per tensor.  Steps 3-6 then run on float32 lists as above,
+        with s = float32(1) / float32(delta): dG = fl32(fl32(g'_wide - g_wide) * s) subtracts in float32, where the reference and
+        class UVd subtract in T.  Step 7 rounds as psgd_uvd_param_update_multi_wd does, every operation to nearest even on its own:
+        delta = T(fl32(lr_eff * pg)); after step 3, delta = T(delta + v); with weight decay, delta = T(delta + T(fl32(c *
+        float(p)))), c = fl32(lr_eff * wd); p <- T(p - delta); tiny = finfo(T).tiny in step 6.  The torch tail is the same chain,
+        one torch op per rounding.  With everything on the fused tail still issues seven launches: perturbation, widen-check,
+        difference, blend, two for the sum of squares, update."""
         params = self._params
         update_Q = self._coin()
         exact = bool(self.exact_hessian_vector_product)
         fused = self._tail is not None
         mom, wd = self._hyper_momentum()
-        guard = self._guard
+        guard, half = self._guard, self._half
         S = self._loss_scale_value() if guard else 1.0
         inv = 1.0 / S                                           # exact: S is a power of two
         scaled = (lambda loss: loss) if S == 1.0 else (lambda loss: loss * S)
@@ -696,17 +849,21 @@ class Kron:
                 Hvs = torch.autograd.grad(grads, params, vs)
             grads = [g.detach() for g in grads]
             dXs, dGs = vs, [h.detach() for h in Hvs]
-            if guard:
+            if half or guard:
                 with torch.no_grad():
-                    grads, dGs, bad = self._judge(grads, dGs, vs, inv)
-                self._guard_outcome(bad)
+                    if half:
+                        grads, dGs, dXs, bad = self._widen(grads, dGs, vs, inv)
+                    else:
+                        grads, dGs, bad = self._judge(grads, dGs, vs, inv)
+                if guard:
+                    self._guard_outcome(bad)
                 if bad:
                     return closure_returns
         elif update_Q:
             with torch.enable_grad():
                 closure_returns = closure()
                 grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
-            undo = vs = [self._randn(p) * _DELTA for p in params]
+            undo = vs = [self._randn(p) * self._delta for p in params]          # in the parameters' dtype: T(randn_T * delta)
             with torch.no_grad():
                 if fused:
                     multi_param_update(params, None, vs, plan=self._tail)
@@ -715,28 +872,36 @@ class Kron:
                         p.add_(v)
             with torch.enable_grad():
                 perturbed = torch.autograd.grad(scaled(self._loss_of(closure())), params)
-            if guard:
+            if half or guard:
                 with torch.no_grad():
-                    grads, perturbed, bad = self._judge(grads, perturbed, vs, inv)
-                self._guard_outcome(bad, vs if bad else None)
+                    if half:                                # (vs stays the perturbation in T; the fp32 copy feeds dX)
+                        grads, perturbed, vs, bad = self._widen(grads, perturbed, vs, inv)
+                    else:
+                        grads, perturbed, bad = self._judge(grads, perturbed, vs, inv)
+                if guard:
+                    self._guard_outcome(bad, undo if bad else None)
                 if bad:
                     return closure_returns
             with torch.no_grad():
                 if fused:
                     dXs, dGs = self._fd_x, self._fd_h
-                    multi_diff_scale([g.contiguous() for g in perturbed], [g.contiguous() for g in grads], dGs, vs, dXs, _FD_INV,
-                                     plan=self._tail)
+                    multi_diff_scale([g.contiguous() for g in perturbed], [g.contiguous() for g in grads], dGs, vs, dXs,
+                                     self._fd_inv, plan=self._tail)
                 else:
-                    dGs = [(pg - g) * _FD_INV for pg, g in zip(perturbed, grads)]
-                    dXs = [v * _FD_INV for v in vs]
+                    dGs = [(pg - g) * self._fd_inv for pg, g in zip(perturbed, grads)]
+                    dXs = [v * self._fd_inv for v in vs]
         else:
             with torch.enable_grad():
                 closure_returns = closure()
                 grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
-            if guard:
+            if half or guard:
                 with torch.no_grad():
-                    grads, _, bad = self._judge(grads, None, None, inv)
-                self._guard_outcome(bad)
+                    if half:
+                        grads, _, _, bad = self._widen(grads, None, None, inv)
+                    else:
+                        grads, _, bad = self._judge(grads, None, None, inv)
+                if guard:
+                    self._guard_outcome(bad)
                 if bad:
                     return closure_returns
         with torch.no_grad():
@@ -754,7 +919,7 @@ class Kron:
             if fused:
                 pre_grads = [g.contiguous() for g in pre_grads]          # (the mirrored formats return transposed views)
                 sumsq = multi_sumsq(pre_grads, plan=self._tail) if clip else None
-                multi_param_update(params, pre_grads, undo, lr, sumsq, max_norm if clip else None, _TINY, plan=self._tail,
+                multi_param_update(params, pre_grads, undo, lr, sumsq, max_norm if clip else None, self._tiny, plan=self._tail,
                                    weight_decay=wd)
                 return closure_returns
             if clip:
@@ -763,18 +928,19 @@ class Kron:
                     s = torch.sum((g * g).double())
                     S = s if S is None else S + s
                 f64 = lambda x: torch.tensor(float(np.float32(x)), dtype=torch.float64, device=self._device)
-                ratio = torch.minimum(f64(max_norm) / (torch.sqrt(S) + f64(_TINY)), f64(1.0))
+                ratio = torch.minimum(f64(max_norm) / (torch.sqrt(S) + f64(self._tiny)), f64(1.0))
                 lr = (f64(lr) * ratio).float()
             else:
                 lr = float(np.float32(lr))
             decay = None
             if wd != 0.0:                                   # c = fl32(lr_eff * wd), as the kernel forms it
                 decay = lr * torch.tensor(wd, dtype=_f32, device=self._device) if clip else float(np.float32(lr) * np.float32(wd))
+            T = self._dtype                                 # one torch op per rounding; for float32 .to(T) and .float() do nothing
             for k, (p, g) in enumerate(zip(params, pre_grads)):
-                delta = g * lr
+                delta = (g * lr).to(T)
                 if undo is not None:
                     delta = delta + undo[k]
                 if decay is not None:
-                    delta = delta + p * decay
+                    delta = delta + (p.float() * decay).to(T)
                 p.sub_(delta)
         return closure_returns

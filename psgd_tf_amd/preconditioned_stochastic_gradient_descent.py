@@ -1636,4 +1636,4 @@ class UVd:
 # --------------------------------------------------------------------------- Kron optimizer (kron_optimizer.py)
 # (imported last: that module builds on the step-tail plan, _Hyper and the Kron entry points above)
 from .kron_optimizer import Kron, multi_sumsq, multi_param_update, multi_diff_scale, kron_initial_factors  # noqa: E402,F401
-from .kron_optimizer import multi_blend, multi_scale_check  # noqa: E402,F401
+from .kron_optimizer import multi_blend, multi_scale_check, multi_widen_check  # noqa: E402,F401

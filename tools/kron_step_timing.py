@@ -21,6 +21,15 @@ resolved, and the summary line says so.
     on-fused  the same with step_tail="fused"
 
     python tools/kron_step_timing.py --features [--parent-module FILE] [--out profiles/kron_class_features.txt]
+
+--dtype bf16 | fp16 times class Kron on parameters of that type (the closure widens them and computes in float32), legs:
+
+    torch     step_tail="torch", everything off          fused     the same with step_tail="fused"
+    on-torch  the switches of --features, torch tail      on-fused  the same with step_tail="fused"
+    fp32      class Kron on float32 parameters, fused tail, everything off (with --parent-module also "parent": the same on the
+              kron_optimizer.py of another commit): whether the float32 path moved
+
+    python tools/kron_step_timing.py --dtype bf16 [--parent-module FILE] [--out profiles/kron_class_half.txt]
 """
 import argparse
 import os
@@ -38,14 +47,17 @@ SETS = {"lenet5": [(26, 6), (151, 16), (257, 120), (121, 84), (85, 10)], "1024x4
 LR, LR_Q = 0.01, 0.01
 
 
-def problem(shapes, dev):
+DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+
+
+def problem(shapes, dev, dtype=torch.float32):
     g = torch.Generator(device=dev).manual_seed(0)
     Hl = [torch.diag(torch.exp(torch.empty(m, device=dev).uniform_(-1.0, 1.0, generator=g))) for m, n in shapes]
     Hr = [torch.diag(torch.exp(torch.empty(n, device=dev).uniform_(-1.0, 1.0, generator=g))) for m, n in shapes]
-    Ws = [torch.randn(m, n, device=dev, generator=g).requires_grad_(True) for m, n in shapes]
+    Ws = [torch.randn(m, n, device=dev, generator=g).to(dtype).requires_grad_(True) for m, n in shapes]
 
-    def closure():
-        return sum(0.5 * torch.sum(W * (hl @ W @ hr)) for W, hl, hr in zip(Ws, Hl, Hr))
+    def closure():                                  # (.float() of a float32 tensor is the tensor itself)
+        return sum(0.5 * torch.sum(W.float() * (hl @ W.float() @ hr)) for W, hl, hr in zip(Ws, Hl, Hr))
     return Ws, closure, 0.1 * sum(W.numel() for W in Ws) ** 0.5
 
 
@@ -75,9 +87,9 @@ def hand_leg(shapes, dev):
 FEATURES_ON = dict(momentum=0.9, weight_decay=0.01, nonfinite="skip", loss_scale=2.0 ** 8)
 
 
-def class_leg(tail, cls=None, **kw):
+def class_leg(tail, cls=None, dtype=torch.float32, **kw):
     def make(shapes, dev):
-        Ws, closure, clip = problem(shapes, dev)
+        Ws, closure, clip = problem(shapes, dev, dtype)
         opt = (cls or psgd.Kron)(Ws, "dense", lr_params=LR, lr_preconditioner=LR_Q, grad_clip_max_norm=clip, step_tail=tail, **kw)
         return lambda: opt.step(closure)
     return make
@@ -109,15 +121,26 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--features", action="store_true")
     ap.add_argument("--parent-module", default=None)
+    ap.add_argument("--dtype", choices=("bf16", "fp16"), default=None)
     a = ap.parse_args()
     if a.chunks < 7:
         ap.error("--chunks must be at least 7")
     dev = torch.device("cuda:0")
     lines = ["# tools/kron_step_timing.py %s--chunks %d --steps %d on %s"
-             % ("--features " if a.features else "", a.chunks, a.steps, torch.cuda.get_device_name(0)),
+             % ("--features " if a.features else "--dtype %s " % a.dtype if a.dtype else "", a.chunks, a.steps,
+                torch.cuda.get_device_name(0)),
              "# us per step (closure + preconditioner + tail), median [min .. max] over the chunks; legs alternate chunk by chunk"]
     for name, shapes in SETS.items():
-        if a.features:
+        if a.dtype:
+            T = DTYPES[a.dtype]
+            legs = {"torch": class_leg("torch", dtype=T)(shapes, dev), "fused": class_leg("fused", dtype=T)(shapes, dev),
+                    "on-torch": class_leg("torch", dtype=T, **FEATURES_ON)(shapes, dev),
+                    "on-fused": class_leg("fused", dtype=T, **FEATURES_ON)(shapes, dev), "fp32": class_leg("fused")(shapes, dev)}
+            pairs = [("torch", "fused"), ("on-torch", "on-fused"), ("fused", "fp32")]
+            if a.parent_module:
+                legs["parent"] = class_leg("fused", parent_class(a.parent_module))(shapes, dev)
+                pairs.append(("parent", "fp32"))
+        elif a.features:
             legs = {"off": class_leg("fused")(shapes, dev)}
             if a.parent_module:
                 legs["parent"] = class_leg("fused", parent_class(a.parent_module))(shapes, dev)
