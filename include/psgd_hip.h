@@ -64,6 +64,8 @@ extern "C" {
  *     loss scale, and decoupled weight decay of class Kron (additive, new symbols only: still 7).
  *     psgd_multi_widen_check and psgd_multi_param_update_t: bfloat16 / float16 parameters of class Kron (additive, new symbols
  *     only: still 7).
+ *     psgd_multi_vec_update_f32 and psgd_multi_vec_apply_f32: the vector layers of class Kron(any_rank=True) (additive, new symbols
+ *     only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -497,6 +499,31 @@ int psgd_multi_widen_check(const void *src0, const void *src1, const void *src2,
 int psgd_multi_param_update_t(const void *param_segs, const void *grad_segs, const void *vs_segs, int k, const void *chunks,
                               int64_t nchunks, int dtype, float lr, const double *sumsq, float max_norm, float tiny, float wd,
                               void *stream);
+
+/* Vector layers of class Kron.  A rank-1 parameter of length n is the reference's layer of shape [1, n] in the (dense, scaling)
+ * format: Ql is 1 x 1, qr is [1, n] (psgd.py:276-322).  All k vectors of a model in ONE launch each.  Four segment tables of k
+ * entries (the Seg of the step-tail kernels; `start` is not read): ql_segs names k tensors of one fp32 element, the other three k
+ * fp32 tensors of n_i >= 2 elements each.  One workgroup of 256 threads owns one vector (workgroup b takes vectors b, b + grid, ...
+ * under the grid cap of the step-tail kernels), so a vector's result depends on its own length and values only: not on k, not on
+ * its place in the list, not on where its tensors start.  min_count is the smallest n_i as the caller knows it: the tables live
+ * on the device and are not read on the host.  A null table, k < 1 or min_count < 2 is PSGD_ERR_BAD_ARG before any HIP call;
+ * whatever the caller says, a segment of fewer than 2 elements moves nothing.  Nothing allocates or synchronises.
+ *
+ * Update, in place, fp32 in the reference's order (psgd.py:288-307 with M = 1):
+ *     rho = sqrt(ql / max(qr));   ql' = ql / rho;   qr' = rho * qr;
+ *     A = (ql' * dG) * qr';   Bt = (dX / ql') * (1 / qr');   grad1 = sum(A A) - sum(Bt Bt);   grad2 = A A - Bt Bt;
+ *     ql = ql' - (step1 * grad1) * ql',  step1 = step / (|grad1| + tiny);
+ *     qr = qr' - (step2 * grad2) * qr',  step2 = step / (max|grad2| + tiny).
+ * The two sums add the fp32 squares in fp64, per lane and then lanes -> waves -> workgroup in a fixed order (no atomics: the same
+ * bits on every call), and grad1 is their fp64 difference rounded once; the maxima propagate NaN as tf.reduce_max does.  A vector
+ * of a million elements is correct and slow (one workgroup): long vectors are not what this is for.                              */
+int psgd_multi_vec_update_f32(const void *ql_segs, const void *qr_segs, const void *dx_segs, const void *dg_segs, int k,
+                              int64_t min_count, float step, float tiny, void *stream);
+
+/* out[i] = fl32(fl32(fl32(ql * ql) * g[i]) * fl32(qr[i] * qr[i])) for every vector: precond_grad_kron on the [1, n] layer, the M < N
+ * branch of psgd.py:318-319 and :322.  out_segs may name the tensors of g_segs (in place).                                          */
+int psgd_multi_vec_apply_f32(const void *ql_segs, const void *qr_segs, const void *g_segs, const void *out_segs, int k,
+                             int64_t min_count, void *stream);
 
 /* Tuning knobs for experiments (not part of the stable ABI).
  * key 0: streaming policy (0 = automatic: non-temporal when U,V exceed the Infinity Cache,

@@ -12,6 +12,10 @@
 //   psgd_multi_widen_check       one to three lists of T tensors -> as many lists of fp32 tensors, dst <- fl32(float(src) s_j), with the
 //                                flag of psgd_multi_scale_check_f32 on the written values
 //   psgd_multi_param_update_t    the update on T parameters and vs, fp32 gradients: the rounding chain of psgd_uvd_param_update_multi_wd
+// and, for the VECTOR LAYERS of class Kron (a rank-1 parameter of length n is the [1, n] layer of the (dense, scaling) format:
+// Ql is 1 x 1, qr is [1, n]; psgd.py:276-322), all k of them in one launch each:
+//   psgd_multi_vec_update_f32    the factor update of psgd.py:276-307 on every (ql, qr), in place
+//   psgd_multi_vec_apply_f32     out <- fl32(fl32(fl32(ql ql) g) fl32(qr qr)), the M < N branch of psgd.py:318-319, :322
 //
 // The tables are those of psgd_uvd_tail.hip: a SEGMENT is one tensor {pointer, start, count}, a CHUNK one piece of at most
 // PSGD_UVD_TAIL_CHUNK consecutive elements of one segment {segment index, offset}.  Here EVERY operand is a list: each has its own
@@ -31,6 +35,7 @@
 #include <stdint.h>
 #include "psgd_hip.h"
 #include "tail_types.h"
+#include "nanmax.h"
 
 // The roundings are the contract (bit-equal to the torch expressions they replace): no product may be fused into a following sum.
 #pragma clang fp contract(off)
@@ -514,6 +519,195 @@ __global__ __launch_bounds__(kT) void k_multi_param_update_t(const Seg* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- vector layers
+// A vector of length n is the reference's layer of shape [1, n] in the (dense, scaling) format: Ql = [[ql]], qr = [1, n].  One
+// workgroup owns one vector (workgroup b takes vectors b, b + grid, ...): what a vector gets depends on its own n and values only,
+// never on k, on its place in the list or on where its tensors start.  Segments of the tables: ql has one element, the others n; a
+// vector shorter than 2 (or a table whose counts disagree below 2) moves nothing.
+//
+// Update (psgd.py:276-307 with M = 1), fp32 in the reference's order, three phases between two workgroup barriers; the vector is
+// read again from cache in every phase, so any n works (a vector of a million elements is correct and slow: one workgroup):
+//   1. m = max(qr);  rho = sqrt(ql / m);  ql' = ql / rho;  qr' = rho qr                                              (:288-292)
+//   2. A = (ql' dG) qr';  Bt = (dX / ql') (1 / qr');  sum A^2, sum Bt^2 (fp64 sums of the fp32 squares);  max |A^2 - Bt^2|
+//   3. grad1 = sum A^2 - sum Bt^2;  ql <- ql' - (step1 grad1) ql';  qr <- qr' - (step2 grad2) qr'                   (:301-307)
+//      step1 = step / (|grad1| + tiny),  step2 = step / (max |grad2| + tiny)
+// Lane t takes the elements 4 (t + 256 j) .. + 3 and the last n mod 4 go to lanes 0 .. 2, whatever the alignment (every access is
+// through the element-aligned vector type), each lane accumulates its squares in fp64 in index order, and the lanes are folded
+// lanes -> waves -> workgroup in a fixed order: no atomics, the same bits on every call.  The maxima propagate NaN (nanmax.h).
+struct VecFold {
+  float m1[kT / 64];        // phase 1: max(qr)
+  double sa[kT / 64];       // phase 2: sum A^2, sum Bt^2, max |grad2|
+  double sb[kT / 64];
+  float m2[kT / 64];
+};
+
+// every lane runs `one(i)` for its single elements and `four(i)` for its groups of four consecutive ones
+template <class F1, class F4>
+__device__ __forceinline__ void vec_sweep(int n, int head, int t, F1 one, F4 four) {
+  const int nvec = (n - head) / 4;
+  if (t < head) one(t);
+#pragma unroll 2
+  for (int q = t; q < nvec; q += kT) four(head + 4 * q);
+  const int i = head + nvec * 4 + t;
+  if (i < n) one(i);
+}
+
+__device__ __forceinline__ float wave_nmax(float v) {
+  for (int o = 32; o > 0; o >>= 1) v = psgd::nmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// A^2, Bt^2 of one element as the reference forms them
+__device__ __forceinline__ void vec_squares(float qlp, float rho, float qr, float dx, float dg, float& qrp, float& a2, float& b2) {
+  qrp = rho * qr;
+  const float a = (qlp * dg) * qrp;
+  const float inv = 1.0f / qrp;
+  const float bt = (dx / qlp) * inv;
+  a2 = a * a;
+  b2 = bt * bt;
+}
+
+__global__ __launch_bounds__(kT) void k_multi_vec_update(const Seg* __restrict__ qlsegs, const Seg* __restrict__ qrsegs,
+                                                         const Seg* __restrict__ dxsegs, const Seg* __restrict__ dgsegs, int k,
+                                                         float step, float tiny) {
+  __shared__ VecFold lds;
+  const int t = threadIdx.x;
+  const int w = t >> 6;
+  for (int s = blockIdx.x; s < k; s += gridDim.x) {
+    const Seg sl = qlsegs[s], sr = qrsegs[s], sx = dxsegs[s], sg = dgsegs[s];
+    int64_t cnt = sr.count < sx.count ? sr.count : sx.count;
+    cnt = sg.count < cnt ? sg.count : cnt;
+    if (sl.count < 1 || cnt < 2 || cnt > 0x7fffffff) continue;      // (the same for every lane of the workgroup)
+    const int n = (int)cnt;
+    float* qlptr = reinterpret_cast<float*>(sl.ptr);
+    float* qr = reinterpret_cast<float*>(sr.ptr);
+    const float* dX = reinterpret_cast<const float*>(sx.ptr);
+    const float* dG = reinterpret_cast<const float*>(sg.ptr);
+    const float ql = qlptr[0];
+    // ---- phase 1: max(qr)
+    float m = __uint_as_float(0xff800000u);                         // -inf
+    vec_sweep(n, 0, t, [&](int i) { m = psgd::nmaxf(m, qr[i]); },
+              [&](int i) {
+                const f32x4_u v = *reinterpret_cast<const f32x4_u*>(qr + i);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) m = psgd::nmaxf(m, v[e]);
+              });
+    m = wave_nmax(m);
+    if ((t & 63) == 0) lds.m1[w] = m;
+    __syncthreads();
+    m = lds.m1[0];
+#pragma unroll
+    for (int j = 1; j < kT / 64; ++j) m = psgd::nmaxf(m, lds.m1[j]);
+    const float rho = sqrtf(ql / m);                                // :288-290
+    const float qlp = ql / rho;                                     // :291
+    // ---- phase 2: the two sums and max |grad2|
+    double sa = 0.0, sb = 0.0;
+    float mx = 0.f;
+    vec_sweep(n, 0, t,
+              [&](int i) {
+                float qrp, a2, b2;
+                vec_squares(qlp, rho, qr[i], dX[i], dG[i], qrp, a2, b2);
+                sa += (double)a2;
+                sb += (double)b2;
+                mx = psgd::amaxf(mx, fabsf(a2 - b2));
+              },
+              [&](int i) {
+                const f32x4_u vr = *reinterpret_cast<const f32x4_u*>(qr + i);
+                const f32x4_u vx = *reinterpret_cast<const f32x4_u*>(dX + i);
+                const f32x4_u vg = *reinterpret_cast<const f32x4_u*>(dG + i);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                  float qrp, a2, b2;
+                  vec_squares(qlp, rho, vr[e], vx[e], vg[e], qrp, a2, b2);
+                  sa += (double)a2;
+                  sb += (double)b2;
+                  mx = psgd::amaxf(mx, fabsf(a2 - b2));
+                }
+              });
+    sa = wave_sum(sa);
+    sb = wave_sum(sb);
+    for (int o = 32; o > 0; o >>= 1) mx = psgd::amaxf(mx, __shfl_xor(mx, o, 64));
+    if ((t & 63) == 0) {
+      lds.sa[w] = sa;
+      lds.sb[w] = sb;
+      lds.m2[w] = mx;
+    }
+    __syncthreads();
+    sa = lds.sa[0];
+    sb = lds.sb[0];
+    mx = lds.m2[0];
+#pragma unroll
+    for (int j = 1; j < kT / 64; ++j) {
+      sa += lds.sa[j];
+      sb += lds.sb[j];
+      mx = psgd::amaxf(mx, lds.m2[j]);
+    }
+    // ---- phase 3: the new factors                                  (:301-307)
+    const float grad1 = (float)(sa - sb);
+    const float step1 = step / (fabsf(grad1) + tiny);
+    const float step2 = step / (mx + tiny);
+    vec_sweep(n, 0, t,
+              [&](int i) {
+                float qrp, a2, b2;
+                vec_squares(qlp, rho, qr[i], dX[i], dG[i], qrp, a2, b2);
+                const float g2 = a2 - b2;
+                qr[i] = qrp - (step2 * g2) * qrp;
+              },
+              [&](int i) {
+                f32x4_u vr = *reinterpret_cast<const f32x4_u*>(qr + i);
+                const f32x4_u vx = *reinterpret_cast<const f32x4_u*>(dX + i);
+                const f32x4_u vg = *reinterpret_cast<const f32x4_u*>(dG + i);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                  float qrp, a2, b2;
+                  vec_squares(qlp, rho, vr[e], vx[e], vg[e], qrp, a2, b2);
+                  const float g2 = a2 - b2;
+                  vr[e] = qrp - (step2 * g2) * qrp;
+                }
+                *reinterpret_cast<f32x4_u*>(qr + i) = vr;
+              });
+    // every lane read ql before the first barrier; lds.m1 is next written after this vector's second barrier, lds.sa / sb / m2
+    // after the next vector's first one: two barriers per vector are enough
+    if (t == 0) qlptr[0] = qlp - (step1 * grad1) * qlp;
+  }
+}
+
+// out = fl32(fl32(fl32(ql ql) g) fl32(qr qr)).  Streaming: a scalar head to the 16-byte boundary of out, 4 floats per lane and access,
+// a scalar tail; g and qr through the element-aligned type.  out may be g: every element is read and written by one lane.
+__global__ __launch_bounds__(kT) void k_multi_vec_apply(const Seg* __restrict__ qlsegs, const Seg* __restrict__ qrsegs,
+                                                        const Seg* __restrict__ gsegs, const Seg* __restrict__ osegs, int k) {
+  const int t = threadIdx.x;
+  for (int s = blockIdx.x; s < k; s += gridDim.x) {
+    const Seg sl = qlsegs[s], sr = qrsegs[s], sg = gsegs[s], so = osegs[s];
+    int64_t cnt = sr.count < sg.count ? sr.count : sg.count;
+    cnt = so.count < cnt ? so.count : cnt;
+    if (sl.count < 1 || cnt < 2 || cnt > 0x7fffffff) continue;
+    const int n = (int)cnt;
+    const float* qr = reinterpret_cast<const float*>(sr.ptr);
+    const float* g = reinterpret_cast<const float*>(sg.ptr);
+    float* out = reinterpret_cast<float*>(so.ptr);
+    const float ql = reinterpret_cast<const float*>(sl.ptr)[0];
+    const float ql2 = ql * ql;
+    vec_sweep(n, head_of(out, n), t,
+              [&](int i) {
+                const float r = qr[i];
+                out[i] = (ql2 * g[i]) * (r * r);
+              },
+              [&](int i) {
+                const f32x4_u vr = *reinterpret_cast<const f32x4_u*>(qr + i);
+                const f32x4_u vg = *reinterpret_cast<const f32x4_u*>(g + i);
+                f32x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = (ql2 * vg[e]) * (vr[e] * vr[e]);
+                *reinterpret_cast<f32x4*>(out + i) = o;
+              });
+  }
+}
+
 static int grid_for(int64_t nchunks) { return (int)(nchunks < kMaxGrid ? nchunks : kMaxGrid); }
 
 template <class T>
@@ -679,6 +873,22 @@ int psgd_multi_param_update_t(const void* param_segs, const void* grad_segs, con
   else
     launch_update_t<F16>(grid, st, (const Seg*)param_segs, (const Seg*)grad_segs, (const Seg*)vs_segs, (const Chunk*)chunks, nchunks,
                          k, lr, sumsq, max_norm, tiny, wd);
+  return launched();
+}
+
+int psgd_multi_vec_update_f32(const void* ql_segs, const void* qr_segs, const void* dx_segs, const void* dg_segs, int k,
+                              int64_t min_count, float step, float tiny, void* stream) {
+  if (!ql_segs || !qr_segs || !dx_segs || !dg_segs || k < 1 || min_count < 2) return PSGD_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_multi_vec_update, dim3(grid_for(k)), dim3(kT), 0, (hipStream_t)stream, (const Seg*)ql_segs,
+                     (const Seg*)qr_segs, (const Seg*)dx_segs, (const Seg*)dg_segs, k, step, tiny);
+  return launched();
+}
+
+int psgd_multi_vec_apply_f32(const void* ql_segs, const void* qr_segs, const void* g_segs, const void* out_segs, int k,
+                             int64_t min_count, void* stream) {
+  if (!ql_segs || !qr_segs || !g_segs || !out_segs || k < 1 || min_count < 2) return PSGD_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_multi_vec_apply, dim3(grid_for(k)), dim3(kT), 0, (hipStream_t)stream, (const Seg*)ql_segs,
+                     (const Seg*)qr_segs, (const Seg*)g_segs, (const Seg*)out_segs, k);
   return launched();
 }
 

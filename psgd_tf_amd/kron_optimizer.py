@@ -304,6 +304,53 @@ def multi_widen_check(srcs, dsts, scales, *, flag=None, stamp=None, plan=None):
     _lib.check(rc, "psgd_multi_widen_check")
 
 
+# --------------------------------------------------------------------------- vector layers
+def _vec_lists(what, qls, first, *others, plan=None):
+    """the operand lists of a vector-layer kernel: `first` and `others` as _lists checks them, every tensor of at least 2 elements,
+    and qls, one fp32 tensor of ONE element per vector.  Returns (qls, lists, plan, device pointer of the table of qls)."""
+    lists, plan = _lists(what, first, *others, plan=plan)
+    if any(ts is None for ts in lists):
+        raise ValueError("%s: a list is None" % what)
+    for i, n in enumerate(plan.sizes):
+        if n < 2:
+            raise ValueError("%s: %s[%d] has %d element%s; a vector layer has at least 2 (a scaling factor of length 1 is square, and "
+                             "the reference's dispatcher would run it as a dense one)" % (what, first[0], i, n, "" if n == 1 else "s"))
+    qls, _ = _check_list(what, "qls", qls, (1,) * len(plan.sizes), plan.device)
+    tab = plan._tables.get("vec_ql")
+    if tab is None:
+        tab = plan._tables["vec_ql"] = _psgd._SegTable(list(range(len(qls))), [1] * len(qls), plan.device)
+    return qls, lists, plan, tab.refresh([t.data_ptr() for t in qls])
+
+
+def multi_vec_precond_update(qls, qrs, dXs, dGs, step, tiny=None, *, plan=None):
+    """update_precond_kron on k vector layers in ONE launch (psgd_multi_vec_update_f32), IN PLACE.  Vector i of length n_i >= 2 is
+    the reference's layer of shape [1, n_i] in the (dense, scaling) format (psgd.py:276-307): qls[i] holds the 1 x 1 left factor,
+    qrs[i] the [1, n_i] scaling factor, dXs[i] and dGs[i] the pair (dx, dg), all contiguous fp32 tensors on one HIP device with these
+    element counts, of any shape.  fp32 in the reference's order -- the balance rho = sqrt(ql / max(qr)) is performed, not cancelled
+    -- with the two sums of squares accumulated in fp64 in a fixed order (the same bits on every call, whatever k and the vector's
+    place in the list) and NaN-propagating maxima.  tiny defaults to the smallest normal float32.  One workgroup per vector: a
+    vector of a million elements is correct but slow."""
+    what = "multi_vec_precond_update"
+    qls, (qrs, dXs, dGs), plan, ql_tab = _vec_lists(what, qls, ("qrs", qrs), ("dXs", dXs), ("dGs", dGs), plan=plan)
+    rc = _lib.load().psgd_multi_vec_update_f32(ql_tab, plan.table("vec_qr", qrs, what), plan.table("vec_dx", dXs, what),
+                                               plan.table("vec_dg", dGs, what), len(qrs), min(plan.sizes), float(step),
+                                               float(_TINY if tiny is None else tiny), _psgd._stream_ptr(plan.device))
+    _lib.check(rc, "psgd_multi_vec_update_f32")
+
+
+def multi_vec_precond_grad(qls, qrs, gs, outs, *, plan=None):
+    """precond_grad_kron on k vector layers in ONE launch (psgd_multi_vec_apply_f32): outs[i] <- ((ql ql) g) (qr qr), the M < N branch of
+    psgd.py:318-319 and :322 on the [1, n_i] layer, every product rounded to float32 on its own.  Lists as in
+    multi_vec_precond_update; outs may be gs itself (in place).  Returns outs."""
+    what = "multi_vec_precond_grad"
+    qls, (qrs, gs, outs), plan, ql_tab = _vec_lists(what, qls, ("qrs", qrs), ("gs", gs), ("outs", outs), plan=plan)
+    rc = _lib.load().psgd_multi_vec_apply_f32(ql_tab, plan.table("vec_qr", qrs, what), plan.table("vec_g", gs, what),
+                                              plan.table("vec_out", outs, what), len(qrs), min(plan.sizes),
+                                              _psgd._stream_ptr(plan.device))
+    _lib.check(rc, "psgd_multi_vec_apply_f32")
+    return outs
+
+
 # --------------------------------------------------------------------------- formats and initial factors
 KRON_SIDES = ("dense", "norm", "scale")
 KRON_PAIRS = (("dense", "dense"), ("dense", "norm"), ("dense", "scale"), ("norm", "dense"), ("norm", "scale"), ("scale", "dense"),
@@ -375,6 +422,56 @@ def _factor_shape(side, n):
     return (n, n) if side == "dense" else (1, n) if side == "scale" else (2, n)
 
 
+VECTOR_FORMAT = ("dense", "scale")      # a vector of length n is the reference's [1, n] layer in this format (psgd.py:87-88, :129-130)
+
+
+def kron_layers(shapes, preconditioner_formats="dense", any_rank=False):
+    """How class Kron(any_rank=...) lays parameters of these shapes out as layers: one (kind, (M, N), (left, right)) per parameter.
+        rank 2                     "matrix", the shape itself, the format asked for
+        rank >= 3                  "matrix", (shape[0], prod(shape[1:])): the usual folding of a conv kernel
+        rank 1, length n >= 2      "vector", (1, n), ("dense", "scale"): Ql is 1 x 1, Qr is [1, n]
+        rank 0, rank 1 length 1    "scalar", (1, 1), ("dense", "dense"): a scaling side of length 1 does not exist
+    One format given for all parameters applies to the matrix layers only.  In a per-parameter list the entry of a vector must be
+    ("dense", "scale") or the default name "dense", that of a scalar ("dense", "dense") or "dense"; anything else is a ValueError
+    that names the parameter.  With any_rank off, or when every shape has rank 2, this is kron_formats on the shapes as they are."""
+    shapes = [tuple(int(n) for n in s) for s in shapes]
+    k = len(shapes)
+    if not any_rank or all(len(s) == 2 for s in shapes):
+        return [("matrix", s, f) for s, f in zip(shapes, kron_formats(preconditioner_formats, k))]
+    f = preconditioner_formats
+    if isinstance(f, str) or (isinstance(f, (tuple, list)) and len(f) == 2 and all(isinstance(s, str) for s in f)):
+        entries = [None] * k
+        matrix_pair = _format_pair(f, "Kron")
+    else:
+        try:
+            entries = list(f)
+        except TypeError:
+            raise ValueError("Kron: preconditioner_formats must be a side name, a (left, right) pair or one of either per parameter, "
+                             "got %r" % (f,))
+        if len(entries) != k:
+            raise ValueError("Kron: preconditioner_formats lists %d formats for %d parameters" % (len(entries), k))
+        matrix_pair = None
+
+    def fixed(i, entry, kind, pair):
+        """the entry of a vector or scalar layer: nothing, the default name, or the one pair such a layer has"""
+        if entry is None or entry == "dense":
+            return pair
+        if isinstance(entry, (tuple, list)) and tuple(entry) == pair:
+            return pair
+        raise ValueError("Kron: parameter %d (shape %s) is a %s layer; its preconditioner format is %r (or the default name 'dense'), "
+                         "got %r" % (i, shapes[i], kind, pair, entry))
+    out = []
+    for i, (s, e) in enumerate(zip(shapes, entries)):
+        if len(s) >= 2:
+            shape2d = s if len(s) == 2 else (s[0], int(np.prod(s[1:], dtype=np.int64)))
+            out.append(("matrix", shape2d, matrix_pair if e is None else _format_pair(e, "Kron (parameter %d)" % i)))
+        elif len(s) == 1 and s[0] >= 2:
+            out.append(("vector", (1, s[0]), fixed(i, e, "vector", VECTOR_FORMAT)))
+        else:
+            out.append(("scalar", (1, s[0] if s else 1), fixed(i, e, "scalar", ("dense", "dense"))))
+    return out
+
+
 # --------------------------------------------------------------------------- checkpoint, host part
 _HYPER_KEYS = ("lr_params", "lr_preconditioner", "grad_clip_max_norm", "preconditioner_update_probability",
                "exact_hessian_vector_product")
@@ -389,10 +486,12 @@ def _encode_state(factors, formats, shapes, hyper, rng_state):
             "rng": rng_state.clone()}
 
 
-def _decode_state(sd, formats, shapes):
+def _decode_state(sd, formats, shapes, layer_shapes=None):
     """the checks of load_state_dict(): returns (factors, hyper, rng_state) of a dict that fits an optimizer with these formats and
-    parameter shapes; ValueError naming the key otherwise"""
+    parameter shapes; ValueError naming the key otherwise.  layer_shapes: the (M, N) of every layer where they are not the
+    parameters' own shapes (Kron(any_rank=True): 'param_shapes' holds the true shapes, the factors have those of the layers)"""
     name = "Kron.load_state_dict"
+    layer_shapes = shapes if layer_shapes is None else layer_shapes
 
     def need(key):
         if key not in sd:
@@ -410,7 +509,7 @@ def _decode_state(sd, formats, shapes):
     factors = need("factors")
     if len(factors) != len(shapes):
         raise ValueError("%s: 'factors' holds %d pairs for %d parameters" % (name, len(factors), len(shapes)))
-    for i, (pair, fmt, (M, N)) in enumerate(zip(factors, formats, shapes)):
+    for i, (pair, fmt, (M, N)) in enumerate(zip(factors, formats, layer_shapes)):
         want = (_factor_shape(fmt[0], M), _factor_shape(fmt[1], N))
         if len(pair) != 2 or any(not isinstance(q, torch.Tensor) or q.dtype != _f32 or tuple(q.shape) != w
                                  for q, w in zip(pair, want)):
@@ -491,15 +590,33 @@ class Kron:
     (psgd.py:682-683).  A checkpoint has no dtype in it: a dict saved from a float32 optimizer loads into a bfloat16 one of the same
     shapes and back.
 
-    Out of scope: feeding (dense, dense) layers to the bf16-operand Kron kernels from inside the class, mixed dtypes, parameters of
-    rank 1 or 3, a narrow (bfloat16) factor state."""
+    any_rank=True (keyword-only, off by default: nothing changes) takes the parameters of an ordinary torch.nn.Module, laid out as
+    kron_layers says.  A rank-1 parameter of length n >= 2 is a VECTOR LAYER: the reference's layer of shape [1, n] in the
+    ("dense", "scale") format (psgd.py:87-88, :129-130), Ql of shape (1, 1) equal to preconditioner_init_scale and Qr = ones(1, n)
+    -- a diagonal preconditioner with one scalar of balance; a per-parameter format list may name it ("dense", "scale") or "dense"
+    and nothing else.  Rank 0 and rank 1 of length 1 are [1, 1] layers in ("dense", "dense").  Rank >= 3 is the matrix layer
+    [shape[0], prod(shape[1:])] in the format asked for, a view that shares the parameter's storage (the usual folding of a conv
+    kernel).  One format given for all parameters applies to the matrix layers only.  factors, state_dict() and
+    load_state_dict() carry every layer's pair in parameter order; 'param_shapes' holds the parameters' true shapes.  Every other
+    switch keeps its meaning; the step-tail kernels work on element counts and do not see the shapes.
+    vector_route="list" (default): all vector layers of a step are updated by ONE launch and applied by ONE launch
+    (multi_vec_precond_update, in place, and multi_vec_precond_grad; one workgroup per vector, so a vector of a million elements is
+    correct but slow).  vector_route="layer": they go through update_precond_kron / precond_grad_kron on [1, n] views like any
+    other layer, about ten launches each -- the comparison leg.  The two routes round differently and need not agree bit for bit.
+
+    Out of scope: feeding (dense, dense) layers to the bf16-operand Kron kernels from inside the class, mixed dtypes, a narrow
+    (bfloat16) factor state, a format for vectors other than the reference's (dense, scale)."""
 
     def __init__(self, params_with_grad, preconditioner_formats="dense", preconditioner_init_scale=1.0, lr_params=0.01,
                  lr_preconditioner=0.01, grad_clip_max_norm=None, preconditioner_update_probability=1.0,
                  exact_hessian_vector_product=True, *, layer_batch=True, step_tail="torch", generator=None,
-                 momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000):
+                 momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
+                 any_rank=False, vector_route="list"):
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
+        if vector_route not in ("list", "layer"):
+            raise ValueError("Kron: vector_route must be 'list' or 'layer', got %r" % (vector_route,))
+        any_rank = bool(any_rank)
         # momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval: the switches of class UVd with their meaning
         # there (see step()); all off by default, and checked before anything touches a device
         if not 0.0 <= float(momentum) < 1.0:
@@ -534,14 +651,19 @@ class Kron:
                 raise TypeError("Kron: %s must be float32, bfloat16 or float16" % tag)
             if p.dtype != params[0].dtype:
                 raise TypeError("Kron: %s must be %s like parameter 0" % (tag, params[0].dtype))     # one dtype per optimizer
-            if p.dim() != 2:
+            if p.dim() != 2 and not any_rank:
                 raise ValueError("Kron: %s must have rank 2; reshape it (the reference's demos fold a bias into its matrix)" % tag)
             if not p.requires_grad:
                 raise ValueError("Kron: %s does not require grad" % tag)
             if not p.is_contiguous():
                 raise ValueError("Kron: %s is not contiguous" % tag)
-        self._formats = kron_formats(preconditioner_formats, len(params))
         self._shapes = [tuple(int(s) for s in p.shape) for p in params]
+        layers = kron_layers(self._shapes, preconditioner_formats, any_rank)
+        self._formats = [f for _, _, f in layers]
+        # the (M, N) of every layer; _reshape: some parameter is not its own layer (any_rank), so what the preconditioner calls take
+        # and return is brought to the layers' shapes and back
+        self._layer_shapes = [s for _, s, _ in layers]
+        self._reshape = self._layer_shapes != self._shapes
         dev = params[0].device
         for i, p in enumerate(params):
             if not p.is_cuda or p.device != dev:
@@ -554,7 +676,15 @@ class Kron:
         self._half = self._dtype != _f32
         self._delta, self._fd_inv, self._tiny = _dtype_constants(self._dtype)
         self._Qs = [kron_initial_factors(s, f, preconditioner_init_scale, dev, "parameter %d" % i)
-                    for i, (s, f) in enumerate(zip(self._shapes, self._formats))]
+                    for i, (s, f) in enumerate(zip(self._layer_shapes, self._formats))]
+        # the vector layers of the list route (none with any_rank off or vector_route="layer") and all other layers; the applies of
+        # the vectors write into buffers made once: the pointers of their table never move
+        self._vec = [i for i, (kind, _, _) in enumerate(layers) if kind == "vector" and vector_route == "list"]
+        self._mat = sorted(set(range(len(params))) - set(self._vec))
+        self._vec_plan, self._vec_out = None, None
+        if self._vec:
+            self._vec_plan = MultiTailPlan([self._layer_shapes[i][1] for i in self._vec], dev)
+            self._vec_out = [torch.empty(self._layer_shapes[i], dtype=_f32, device=dev) for i in self._vec]
         self.lr_params = _psgd._Hyper(lr_params)
         self.lr_preconditioner = _psgd._Hyper(lr_preconditioner)
         self.grad_clip_max_norm = _psgd._Hyper(math.inf if grad_clip_max_norm is None else grad_clip_max_norm)
@@ -602,7 +732,7 @@ class Kron:
         momentum buffers and their step counter are restored, and a dict without them zeroes the buffers of a momentum optimizer
         and restarts its warm-up.  A guarded optimizer restores skipped_steps, loss_scale_good_steps and, when both sides scale
         the loss, loss_scale where the dict has them and starts them fresh where it has not; an unguarded one ignores them."""
-        factors, hyper, rng = _decode_state(sd, self._formats, self._shapes)
+        factors, hyper, rng = _decode_state(sd, self._formats, self._shapes, self._layer_shapes)
         bufs, m_step = _decode_features(sd, self._shapes)
         try:
             self._coin_generator().set_state(rng)
@@ -786,6 +916,54 @@ class Kron:
     def _loss_of(closure_returns):
         return closure_returns if isinstance(closure_returns, torch.Tensor) else closure_returns[0]
 
+    def _as_layers(self, tensors):
+        """parameter-shaped tensors in the (M, N) of their layers (views where the memory allows); nothing without any_rank"""
+        if not self._reshape:
+            return tensors
+        return [t.reshape(s) for t, s in zip(tensors, self._layer_shapes)]
+
+    def _update_factors(self, dXs, dGs, lr_q):
+        """step 4: one update_precond_kron per layer inside one block, the factor references rebound to the returned tensors; the
+        vector layers of the list route in ONE multi_vec_precond_update launch, in place"""
+        dXs, dGs = self._as_layers(dXs), self._as_layers(dGs)
+        Qs = self._Qs
+        if not self._vec:
+            with self._block():
+                new = [_psgd.update_precond_kron(q[0], q[1], dX, dG, lr_q) for q, dX, dG in zip(Qs, dXs, dGs)]
+            self._Qs = [[a, b] for a, b in new]
+            return
+        Qs = list(Qs)
+        if self._mat:
+            with self._block():
+                new = [_psgd.update_precond_kron(Qs[i][0], Qs[i][1], dXs[i], dGs[i], lr_q) for i in self._mat]
+            for i, (a, b) in zip(self._mat, new):
+                Qs[i] = [a, b]
+        vec = self._vec
+        multi_vec_precond_update([Qs[i][0] for i in vec], [Qs[i][1] for i in vec], [dXs[i].contiguous() for i in vec],
+                                 [dGs[i].contiguous() for i in vec], lr_q, plan=self._vec_plan)
+        self._Qs = Qs
+
+    def _precondition(self, grads):
+        """step 5: one precond_grad_kron per layer inside a second block; the vector layers of the list route in ONE
+        multi_vec_precond_grad launch.  Returns the preconditioned gradients in the layers' shapes."""
+        grads = self._as_layers(grads)
+        Qs = self._Qs
+        if not self._vec:
+            with self._block():
+                return [_psgd.precond_grad_kron(q[0], q[1], g) for q, g in zip(Qs, grads)]
+        pre = [None] * len(grads)
+        if self._mat:
+            with self._block():
+                out = [_psgd.precond_grad_kron(Qs[i][0], Qs[i][1], grads[i]) for i in self._mat]
+            for i, g in zip(self._mat, out):
+                pre[i] = g
+        vec = self._vec
+        multi_vec_precond_grad([Qs[i][0] for i in vec], [Qs[i][1] for i in vec], [grads[i].contiguous() for i in vec],
+                               self._vec_out, plan=self._vec_plan)
+        for i, g in zip(vec, self._vec_out):
+            pre[i] = g
+        return pre
+
     def step(self, closure):
         """One step; returns what closure() returns (the loss is its first element when it is an iterable).
 
@@ -795,7 +973,9 @@ class Kron:
            second time; dG = (g' - g) * s, dX = v * s with s = float32(1) / float32(delta); the perturbation is undone in step 7.
         4. one update_precond_kron per layer (inside one kron.layer_batch() block); the factor references are rebound to the returned
            tensors, nothing is copied.
-        5. one precond_grad_kron per layer (a second block).
+        5. one precond_grad_kron per layer (a second block).  any_rank: dX, dG and the gradients are taken in the shapes of the
+           layers (views), and with vector_route="list" the vector layers leave steps 4 and 5 for one multi_vec_precond_update launch
+           (in place: these factor tensors are not rebound) and one multi_vec_precond_grad launch.
         6. with clipping, lr_eff = float32(lr_params * min(max_norm / (sqrt(S) + tiny), 1)) evaluated in fp64, S = the fp64 sum of
            the float32 squares of all preconditioned gradients.  tiny = finfo(float32).tiny follows psgd.py:753 (class UVd), not
            mnist_with_lenet5.py:54-55, which divides by the bare norm: a zero gradient gives a zero step, not NaN.
@@ -906,14 +1086,10 @@ class Kron:
                     return closure_returns
         with torch.no_grad():
             if update_Q:
-                lr_q = float(self.lr_preconditioner)
-                with self._block():
-                    new = [_psgd.update_precond_kron(q[0], q[1], dX, dG, lr_q) for q, dX, dG in zip(self._Qs, dXs, dGs)]
-                self._Qs = [[a, b] for a, b in new]
+                self._update_factors(dXs, dGs, float(self.lr_preconditioner))
             if mom != 0.0 or self._m_step:
                 grads = self._blend(grads, mom)
-            with self._block():
-                pre_grads = [_psgd.precond_grad_kron(q[0], q[1], g) for q, g in zip(self._Qs, grads)]
+            pre_grads = self._precondition(grads)
             lr, max_norm = float(self.lr_params), float(self.grad_clip_max_norm)
             clip = not math.isinf(max_norm)
             if fused:
@@ -937,6 +1113,8 @@ class Kron:
                 decay = lr * torch.tensor(wd, dtype=_f32, device=self._device) if clip else float(np.float32(lr) * np.float32(wd))
             T = self._dtype                                 # one torch op per rounding; for float32 .to(T) and .float() do nothing
             for k, (p, g) in enumerate(zip(params, pre_grads)):
+                if self._reshape:
+                    g = g.reshape(p.shape)
                 delta = (g * lr).to(T)
                 if undo is not None:
                     delta = delta + undo[k]
