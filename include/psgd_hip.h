@@ -66,6 +66,8 @@ extern "C" {
  *     only: still 7).
  *     psgd_multi_vec_update_f32 and psgd_multi_vec_apply_f32: the vector layers of class Kron(any_rank=True) (additive, new symbols
  *     only: still 7).
+ *     psgd_multi_narrow_bf16, psgd_multi_sumsq_mixed and psgd_multi_param_update_mixed: the bf16-operand layers of class
+ *     Kron(operands="bfloat16") (additive, new symbols only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -426,7 +428,8 @@ int psgd_uvd_param_update_multi_wd(const void *param_segs, const void *vs_segs, 
  * segment table (psgd_multi_tail.hip).  Tables as above; `start` is not read.  All tables of one call describe tensors of the same
  * element counts and share one chunk table; a chunk never runs past the shortest of its segments.  The _f32 entry points take fp32
  * lists only; psgd_multi_widen_check and psgd_multi_param_update_t (below) take a PSGD_DTYPE_* code for the lists that hold parameters
- * of another type.
+ * of another type, and psgd_multi_narrow_bf16, psgd_multi_sumsq_mixed and psgd_multi_param_update_mixed (further below) serve the
+ * layers whose preconditioner runs on bf16 operands.
  * Null tables, k < 0 and nchunks < 0 return PSGD_ERR_BAD_ARG before any HIP call; nchunks == 0 is a no-op (nothing is written).   */
 #define PSGD_MULTI_SUMSQ_WS_BYTES  8192   /* workspace of psgd_multi_sumsq_f32 (8-byte aligned, needs no initialisation) */
 
@@ -524,6 +527,41 @@ int psgd_multi_vec_update_f32(const void *ql_segs, const void *qr_segs, const vo
  * branch of psgd.py:318-319 and :322.  out_segs may name the tensors of g_segs (in place).                                          */
 int psgd_multi_vec_apply_f32(const void *ql_segs, const void *qr_segs, const void *g_segs, const void *out_segs, int k,
                              int64_t min_count, void *stream);
+
+/* bf16-operand layers of class Kron(operands="bfloat16"): large (dense, dense) layers take dX, dG and the gradient as bf16 tensors
+ * (psgd_kron_dd_update_bf16, psgd_kron_dd_apply_bf16) and return a bf16 preconditioned gradient; everything else stays fp32.
+ *
+ * psgd_multi_narrow_bf16 is psgd_multi_widen_check in the other direction, without a flag: in ONE launch
+ *     dst_j[i] = bf16(src_j[i])          for one to three (src_j, dst_j) pairs of lists,
+ * src_j fp32 tensors, dst_j bf16 tensors of the same element counts, each aligned to its element only.  Round to nearest even,
+ * the bits of torch's .to(torch.bfloat16): NaN -> the quiet NaN 0x7FC0, a finite value beyond the bf16 range -> +-Inf, subnormals
+ * kept.  An absent list passes NULL for BOTH of its tables (list 0 is required); a source without a destination, or the reverse,
+ * is PSGD_ERR_BAD_ARG.  Nothing is judged: the guard of a step has seen the fp32 values.                                          */
+int psgd_multi_narrow_bf16(const void *src0, const void *src1, const void *src2, const void *dst0, const void *dst1, const void *dst2,
+                           int k, const void *chunks, int64_t nchunks, void *stream);
+
+/* MIXED lists: a list whose tensors are fp32 or bf16, tensor by tensor.  The `start` field of a segment, which no entry point of
+ * this section reads otherwise, holds that segment's PSGD_DTYPE_F32 or PSGD_DTYPE_BF16; its pointer is aligned to its element and
+ * its count is in elements.  The table lives on the device, so the host cannot judge the codes: a segment with any other code is
+ * skipped (it adds nothing to the sum, and its parameters are not touched).
+ *
+ * psgd_multi_sumsq_mixed: psgd_multi_sumsq_f32 on a mixed list, sum of fl32(float(x) * float(x)) in fp64: the same partial / fold
+ * structure, workspace (PSGD_MULTI_SUMSQ_WS_BYTES), argument checks and fixed order.  Two bit contracts: with every segment fp32
+ * the result has the bits of psgd_multi_sumsq_f32 on the same tensors; a bf16 segment is summed in the order in which
+ * psgd_multi_sumsq_f32 sums a 16-byte aligned fp32 tensor holding the widened values (what psgd_multi_widen_check with scale 1
+ * writes into a fresh buffer), wherever the bf16 tensor itself starts.                                                            */
+int psgd_multi_sumsq_mixed(const void *segs, int k, const void *chunks, int64_t nchunks, double *out, void *ws, int64_t ws_bytes,
+                           void *stream);
+
+/* psgd_multi_param_update_t with a mixed list as the gradients: parameters and vs of type T = dtype (PSGD_DTYPE_F32, _BF16 or
+ * _F16; for F32 the chain is that of psgd_multi_param_update_wd_f32), gradient segment i fp32 or bf16 as grad_segs[i].start says,
+ * read as float(g): delta = T(fl32(lr_eff * float(g[i]))), and everything after it as in psgd_multi_param_update_t.  With every
+ * segment fp32 the bits are those of psgd_multi_param_update_t; with bf16 segments those of widening them exactly first.
+ * grad_segs == NULL is PSGD_ERR_BAD_ARG (the perturbation p + v has no gradient and keeps psgd_multi_param_update_t), and so is
+ * an unknown dtype; lr_eff, sumsq, max_norm, tiny and wd as in psgd_multi_param_update_wd_f32.                                    */
+int psgd_multi_param_update_mixed(const void *param_segs, const void *grad_segs, const void *vs_segs, int k, const void *chunks,
+                                  int64_t nchunks, int dtype, float lr, const double *sumsq, float max_norm, float tiny, float wd,
+                                  void *stream);
 
 /* Tuning knobs for experiments (not part of the stable ABI).
  * key 0: streaming policy (0 = automatic: non-temporal when U,V exceed the Infinity Cache,

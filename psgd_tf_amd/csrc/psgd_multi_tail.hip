@@ -16,6 +16,10 @@
 // Ql is 1 x 1, qr is [1, n]; psgd.py:276-322), all k of them in one launch each:
 //   psgd_multi_vec_update_f32    the factor update of psgd.py:276-307 on every (ql, qr), in place
 //   psgd_multi_vec_apply_f32     out <- fl32(fl32(fl32(ql ql) g) fl32(qr qr)), the M < N branch of psgd.py:318-319, :322
+// and, for the layers of class Kron(operands="bfloat16") that run on the bf16-operand Kron kernels (psgd_kron_bf16.hip):
+//   psgd_multi_narrow_bf16       one to three lists of fp32 tensors -> as many lists of bf16 tensors, round to nearest even
+//   psgd_multi_sumsq_mixed       psgd_multi_sumsq_f32 on a list whose tensors are fp32 or bf16, tensor by tensor
+//   psgd_multi_param_update_mixed  psgd_multi_param_update_t (for fp32 parameters: _wd_f32) with such a list as the gradients
 //
 // The tables are those of psgd_uvd_tail.hip: a SEGMENT is one tensor {pointer, start, count}, a CHUNK one piece of at most
 // PSGD_UVD_TAIL_CHUNK consecutive elements of one segment {segment index, offset}.  Here EVERY operand is a list: each has its own
@@ -708,7 +712,229 @@ __global__ __launch_bounds__(kT) void k_multi_vec_apply(const Seg* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------------------ bf16 operands of class Kron: narrow, mixed lists
+// one list inside one chunk: dst = bf16(src), round to nearest even (BF16::narrow: NaN -> quiet NaN, a finite value beyond the bf16
+// range -> +-Inf).  The stored side is dst: a scalar head to its 16-byte boundary, a body of 8 elements per lane and access (two
+// 16-byte reads of src through the element-aligned type, one 16-byte store), a scalar tail.
+__device__ __forceinline__ void narrow_list(const float* src, uint16_t* dst, int n, int t) {
+  const int head = head_of_16bit(dst, n);
+  const int nvec = (n - head) / 8;
+  if (t < head) dst[t] = BF16::narrow(src[t]);
+#pragma unroll 2
+  for (int q = t; q < nvec; q += kT) {
+    const int i = head + q * 8;
+    u16x8 y;
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const f32x4_u w = *reinterpret_cast<const f32x4_u*>(src + i + 4 * b);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) y[4 * b + e] = BF16::narrow(w[e]);
+    }
+    *reinterpret_cast<u16x8*>(dst + i) = y;
+  }
+  const int i = head + nvec * 8 + t;
+  if (i < n) dst[i] = BF16::narrow(src[i]);
+}
+
+// One to three (source, destination) pairs of lists in one launch: k_multi_widen_check in the other direction, without a flag.
+__global__ __launch_bounds__(kT) void k_multi_narrow_bf16(const Seg* __restrict__ src0, const Seg* __restrict__ src1,
+                                                          const Seg* __restrict__ src2, const Seg* __restrict__ dst0,
+                                                          const Seg* __restrict__ dst1, const Seg* __restrict__ dst2,
+                                                          const Chunk* __restrict__ chunks, int64_t nchunks, int k) {
+  const int t = threadIdx.x;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Chunk ch = chunks[c];
+    if ((uint64_t)ch.seg >= (uint64_t)k || ch.off < 0) continue;     // a table that does not belong to these segments moves nothing
+    const Seg* const srcs[3] = {src0, src1, src2};
+    const Seg* const dsts[3] = {dst0, dst1, dst2};
+    const float* sp[3] = {nullptr, nullptr, nullptr};
+    uint16_t* dp[3] = {nullptr, nullptr, nullptr};
+    int64_t left = kChunk;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (!srcs[j]) continue;
+      const Seg a = srcs[j][ch.seg];
+      const Seg b = dsts[j][ch.seg];
+      const int64_t l = (a.count < b.count ? a.count : b.count) - ch.off;
+      left = l < left ? l : left;
+      sp[j] = reinterpret_cast<const float*>(a.ptr) + ch.off;
+      dp[j] = reinterpret_cast<uint16_t*>(b.ptr) + ch.off;
+    }
+    if (left <= 0) continue;
+    const int n = (int)left;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (srcs[j]) narrow_list(sp[j], dp[j], n, t);
+  }
+}
+
+// The MIXED lists: every segment of the gradient list is fp32 or bf16, and its `start` field -- which no list kernel reads --
+// holds its PSGD_DTYPE_* code.  A segment with any other code moves nothing: the tables live on the device and the host cannot
+// judge them.
+
+// k_multi_sumsq_partial on a mixed list.  An fp32 segment is summed exactly as there (the same lanes take the same elements in the
+// same order: the same bits).  A bf16 segment is summed as that kernel sums a 16-BYTE ALIGNED fp32 tensor of the widened values --
+// no head, lane t takes the groups of four at 4 (t + 256 j), then the tail -- wherever the bf16 tensor starts: 8 bytes per lane
+// and access through the element-aligned type.
+__global__ __launch_bounds__(kT) void k_multi_sumsq_partial_mixed(const Seg* __restrict__ segs, const Chunk* __restrict__ chunks,
+                                                                  int64_t nchunks, int k, double* __restrict__ partial) {
+  __shared__ double lds[kT / 64];
+  const int t = threadIdx.x;
+  double acc = 0.0;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Chunk ch = chunks[c];
+    if ((uint64_t)ch.seg >= (uint64_t)k || ch.off < 0) continue;
+    const Seg s = segs[ch.seg];
+    int64_t left = s.count - ch.off;
+    left = left < kChunk ? left : kChunk;
+    if (left <= 0) continue;
+    const int n = (int)left;
+    if (s.start == PSGD_DTYPE_F32) {
+      const float* x = reinterpret_cast<const float*>(s.ptr) + ch.off;
+      const int head = head_of(x, n);
+      const int nvec = (n - head) / 4;
+      if (t < head) acc += (double)(x[t] * x[t]);
+#pragma unroll 2
+      for (int g = t; g < nvec; g += kT) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + head + 4 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc += (double)(v[e] * v[e]);
+      }
+      const int i = head + nvec * 4 + t;
+      if (i < n) acc += (double)(x[i] * x[i]);
+    } else if (s.start == PSGD_DTYPE_BF16) {
+      const uint16_t* x = reinterpret_cast<const uint16_t*>(s.ptr) + ch.off;
+      const int nvec = n / 4;
+#pragma unroll 2
+      for (int g = t; g < nvec; g += kT) {
+        const u16x4_u v = *reinterpret_cast<const u16x4_u*>(x + 4 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float w = BF16::widen(v[e]);
+          acc += (double)(w * w);
+        }
+      }
+      const int i = nvec * 4 + t;
+      if (i < n) {
+        const float w = BF16::widen(x[i]);
+        acc += (double)(w * w);
+      }
+    }
+  }
+  const double s = block_sum(acc, lds);
+  if (t == 0) partial[blockIdx.x] = s;
+}
+
+// elements in front of the first 16-byte boundary at or after p for elements of type T, at most n
+template <class T>
+__device__ __forceinline__ int head_of_t(const void* p, int n) {
+  const int h = (int)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) / (int)sizeof(typename T::raw);
+  return h < n ? h : n;
+}
+
+// one gradient element, and E consecutive ones from an address aligned to the element only, of a mixed segment as floats
+__device__ __forceinline__ float grad_at(const void* g, bool bf, int i) {
+  return bf ? BF16::widen(reinterpret_cast<const uint16_t*>(g)[i]) : reinterpret_cast<const float*>(g)[i];
+}
+template <int E>
+__device__ __forceinline__ void load_grad(const void* g, bool bf, int i, float (&gg)[E]) {
+  if (!bf) {
+#pragma unroll
+    for (int b = 0; b < E / 4; ++b) {
+      const f32x4_u w = *reinterpret_cast<const f32x4_u*>(reinterpret_cast<const float*>(g) + i + 4 * b);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) gg[4 * b + e] = w[e];
+    }
+  } else if constexpr (E == 8) {
+    load_any<BF16>(reinterpret_cast<const uint16_t*>(g) + i, gg);
+  } else {
+    const u16x4_u w = *reinterpret_cast<const u16x4_u*>(reinterpret_cast<const uint16_t*>(g) + i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gg[e] = BF16::widen(w[e]);
+  }
+}
+
+// k_multi_param_update (T = F32) and k_multi_param_update_t (T = BF16 / F16) with a mixed gradient list: the rounding chain of
+// update_one_t on float(g), which for T = F32 (widen and narrow are the identity) is that of update_one.  Every product reaches its
+// rounding as an fp32 value in a register (kOpaque, head, body and tail alike).  Parameters and vs of type T; the stored side is p.
+template <class T, bool kVs, bool kWd>
+__global__ __launch_bounds__(kT) void k_multi_param_update_mixed(const Seg* __restrict__ psegs, const Seg* __restrict__ gsegs,
+                                                                 const Seg* __restrict__ vsegs, const Chunk* __restrict__ chunks,
+                                                                 int64_t nchunks, int k, float lr, const double* __restrict__ sumsq,
+                                                                 float max_norm, float tiny, float wd) {
+  using raw = typename T::raw;
+  constexpr int E = T::E;
+  const int t = threadIdx.x;
+  float lr_eff = lr;
+  if (sumsq) {                // as k_multi_param_update: fp64, one rounding, a NaN norm propagates
+    const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
+    lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
+  }
+  const float dc = kWd ? lr_eff * wd : 0.f;         // c = fl32(lr_eff wd)
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Chunk ch = chunks[c];
+    if ((uint64_t)ch.seg >= (uint64_t)k || ch.off < 0) continue;
+    const Seg ps = psegs[ch.seg];
+    const Seg gs = gsegs[ch.seg];
+    if (gs.start != PSGD_DTYPE_F32 && gs.start != PSGD_DTYPE_BF16) continue;
+    const bool bf = gs.start == PSGD_DTYPE_BF16;
+    int64_t left = ps.count - ch.off;
+    left = left < kChunk ? left : kChunk;
+    {
+      const int64_t l = gs.count - ch.off;
+      left = l < left ? l : left;
+    }
+    raw* p = reinterpret_cast<raw*>(ps.ptr) + ch.off;
+    const void* g = reinterpret_cast<const char*>(gs.ptr) + ch.off * (bf ? 2 : 4);
+    const raw* v = nullptr;
+    if constexpr (kVs) {
+      const Seg vsg = vsegs[ch.seg];
+      const int64_t l = vsg.count - ch.off;
+      left = l < left ? l : left;
+      v = reinterpret_cast<const raw*>(vsg.ptr) + ch.off;
+    }
+    if (left <= 0) continue;
+    const int n = (int)left;
+    const int head = head_of_t<T>(p, n);
+    const int nvec = (n - head) / E;
+    if (t < head)
+      p[t] = T::narrow(update_one_t<T, true, kVs, kWd, true>(T::widen(p[t]), grad_at(g, bf, t), kVs ? T::widen(v[t]) : 0.f, lr_eff, dc));
+#pragma unroll 2
+    for (int q = t; q < nvec; q += kT) {
+      const int i = head + q * E;
+      float x[E], gg[E], vv[E];
+      load_16<T>(p + i, x);
+      load_grad<E>(g, bf, i, gg);
+      if constexpr (kVs) load_any<T>(v + i, vv);
+#pragma unroll
+      for (int e = 0; e < E; ++e) x[e] = update_one_t<T, true, kVs, kWd, true>(x[e], gg[e], kVs ? vv[e] : 0.f, lr_eff, dc);
+      store_16<T>(p + i, x);
+    }
+    const int i = head + nvec * E + t;
+    if (i < n)
+      p[i] = T::narrow(update_one_t<T, true, kVs, kWd, true>(T::widen(p[i]), grad_at(g, bf, i), kVs ? T::widen(v[i]) : 0.f, lr_eff, dc));
+  }
+}
+
 static int grid_for(int64_t nchunks) { return (int)(nchunks < kMaxGrid ? nchunks : kMaxGrid); }
+
+template <class T>
+static void launch_update_mixed(int grid, hipStream_t st, const Seg* ps, const Seg* gs, const Seg* vsg, const Chunk* ch,
+                                int64_t nchunks, int k, float lr, const double* sumsq, float max_norm, float tiny, float wd) {
+#define PSGD_MULTI_UPDATE_MIXED(VS, WD)                                                                                         \
+  hipLaunchKernelGGL((k_multi_param_update_mixed<T, VS, WD>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, \
+                     sumsq, max_norm, tiny, wd)
+  if (wd != 0.f) {                           // (a NaN wd decays too: it propagates)
+    if (vsg)
+      PSGD_MULTI_UPDATE_MIXED(true, true);
+    else
+      PSGD_MULTI_UPDATE_MIXED(false, true);
+  } else if (vsg)
+    PSGD_MULTI_UPDATE_MIXED(true, false);
+  else
+    PSGD_MULTI_UPDATE_MIXED(false, false);
+#undef PSGD_MULTI_UPDATE_MIXED
+}
 
 template <class T>
 static void launch_update_t(int grid, hipStream_t st, const Seg* ps, const Seg* gs, const Seg* vsg, const Chunk* ch, int64_t nchunks,
@@ -889,6 +1115,51 @@ int psgd_multi_vec_apply_f32(const void* ql_segs, const void* qr_segs, const voi
   if (!ql_segs || !qr_segs || !g_segs || !out_segs || k < 1 || min_count < 2) return PSGD_ERR_BAD_ARG;
   hipLaunchKernelGGL(k_multi_vec_apply, dim3(grid_for(k)), dim3(kT), 0, (hipStream_t)stream, (const Seg*)ql_segs,
                      (const Seg*)qr_segs, (const Seg*)g_segs, (const Seg*)out_segs, k);
+  return launched();
+}
+
+int psgd_multi_narrow_bf16(const void* src0, const void* src1, const void* src2, const void* dst0, const void* dst1, const void* dst2,
+                           int k, const void* chunks, int64_t nchunks, void* stream) {
+  if (!src0 || !dst0 || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
+  if ((src1 == nullptr) != (dst1 == nullptr) || (src2 == nullptr) != (dst2 == nullptr)) return PSGD_ERR_BAD_ARG;
+  if (nchunks == 0) return PSGD_OK;
+  hipLaunchKernelGGL(k_multi_narrow_bf16, dim3(grid_for(nchunks)), dim3(kT), 0, (hipStream_t)stream, (const Seg*)src0,
+                     (const Seg*)src1, (const Seg*)src2, (const Seg*)dst0, (const Seg*)dst1, (const Seg*)dst2, (const Chunk*)chunks,
+                     nchunks, k);
+  return launched();
+}
+
+int psgd_multi_sumsq_mixed(const void* segs, int k, const void* chunks, int64_t nchunks, double* out, void* ws, int64_t ws_bytes,
+                           void* stream) {
+  if (!segs || !chunks || !out || ((uintptr_t)out & 7) || !ws || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
+  if (ws_bytes < PSGD_MULTI_SUMSQ_WS_BYTES || ((uintptr_t)ws & 7)) return PSGD_ERR_WORKSPACE;
+  if (nchunks == 0) return PSGD_OK;                                           // out is NOT written, as in psgd_multi_sumsq_f32
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = (int)(nchunks < kSumsqBlocks ? nchunks : kSumsqBlocks);      // the partition of psgd_multi_sumsq_f32
+  hipLaunchKernelGGL(k_multi_sumsq_partial_mixed, dim3(nb), dim3(kT), 0, st, (const Seg*)segs, (const Chunk*)chunks, nchunks, k,
+                     (double*)ws);
+  hipLaunchKernelGGL(k_multi_sumsq_fold, dim3(1), dim3(kT), 0, st, (const double*)ws, nb, out);
+  return launched();
+}
+
+int psgd_multi_param_update_mixed(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
+                                  int64_t nchunks, int dtype, float lr, const double* sumsq, float max_norm, float tiny, float wd,
+                                  void* stream) {
+  if (dtype < PSGD_DTYPE_F32 || dtype > PSGD_DTYPE_F16) return PSGD_ERR_BAD_ARG;
+  if (!param_segs || !grad_segs || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;   // (p + v keeps its entry points)
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = grid_for(nchunks);
+  const Seg* ps = (const Seg*)param_segs;
+  const Seg* gs = (const Seg*)grad_segs;
+  const Seg* vsg = (const Seg*)vs_segs;
+  const Chunk* ch = (const Chunk*)chunks;
+  if (dtype == PSGD_DTYPE_F32)
+    launch_update_mixed<F32>(grid, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq, max_norm, tiny, wd);
+  else if (dtype == PSGD_DTYPE_BF16)
+    launch_update_mixed<BF16>(grid, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq, max_norm, tiny, wd);
+  else
+    launch_update_mixed<F16>(grid, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq, max_norm, tiny, wd);
   return launched();
 }
 

@@ -5,7 +5,9 @@ lstm_with_xor_problem.py and the NMT demo).  The interface and the step(closure)
 the arithmetic is that of mnist_with_lenet5.py:43-57, with the finite-difference Hessian-vector product of psgd.py:716-727.
 
     multi_sumsq, multi_param_update, multi_diff_scale,
-    multi_blend, multi_scale_check, multi_widen_check     thin wrappers of the list kernels (csrc/psgd_multi_tail.hip)
+    multi_blend, multi_scale_check, multi_widen_check,
+    multi_narrow                                          thin wrappers of the list kernels (csrc/psgd_multi_tail.hip)
+    kron_layers, kron_operand_layers                      how the parameters become layers, and which run on bf16 operands
     kron_initial_factors                                  the initial factor pair of one layer
     Kron(...).step(closure)                               the optimizer
 """
@@ -24,6 +26,7 @@ _TINY = float(np.finfo(np.float32).tiny)
 _DELTA = float(np.float32(np.sqrt(np.float32(np.finfo(np.float32).eps))))      # psgd.py:683 for fp32 parameters
 _FD_INV = float(np.float32(1.0) / np.float32(_DELTA))                           # the s of dG = (g' - g) s, dX = v s
 _HALF = (torch.bfloat16, torch.float16)
+_MIXED = (torch.float32, torch.bfloat16)            # the dtypes of a mixed list: a preconditioned gradient is one or the other
 _DTYPE_NAMES = {torch.float32: "float32", torch.bfloat16: "bfloat16", torch.float16: "float16"}
 
 
@@ -67,6 +70,28 @@ class MultiTailPlan(_psgd.UVdTailPlan):
             tab = self._tables[role] = _psgd._SegTable(self.starts, self.sizes, self.device)
         return tab.refresh([t.data_ptr() for t in tensors])
 
+    def mixed_table(self, role, tensors, what):
+        """device pointer of the segment table of a MIXED list in this role: contiguous tensors with the plan's sizes, each float32
+        or bfloat16; the `start` field of a segment holds its PSGD_DTYPE_* code (include/psgd_hip.h)"""
+        if len(tensors) != len(self.sizes):
+            raise ValueError("%s: %d tensors, the plan has %d" % (what, len(tensors), len(self.sizes)))
+        for t, n in zip(tensors, self.sizes):
+            if t.dtype not in _MIXED or t.device != self.device or t.numel() != n or not t.is_contiguous():
+                raise ValueError("%s: every tensor must be a contiguous float32 or bfloat16 tensor on %s with the plan's element "
+                                 "count (%d), got %s %s %s%s" % (what, self.device, n, t.dtype, t.device, tuple(t.shape),
+                                                                 "" if t.is_contiguous() else " strided"))
+        codes = [_psgd._TAIL_DTYPES[t.dtype] for t in tensors]
+        tab = self._tables.get(role)
+        if tab is None:
+            tab = self._tables[role] = _psgd._SegTable(codes, self.sizes, self.device)
+            tab.codes = codes
+        elif tab.codes != codes:                               # another pattern of dtypes in this role: rewrite and upload again
+            if tab.uploaded is not None:
+                tab.uploaded.synchronize()
+            tab.rows[:, 1] = codes
+            tab.codes, tab.ptrs = codes, None
+        return tab.refresh([t.data_ptr() for t in tensors])
+
     def next_stamp(self):
         """1 .. 2^31 - 1, then 1 again"""
         self.stamp = self.stamp % (2 ** 31 - 1) + 1
@@ -85,8 +110,9 @@ def _check_list(what, name, tensors, sizes=None, device=None, dtype=_f32):
     for i, t in enumerate(tensors):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s: %s[%d] is not a torch tensor (%r)" % (what, name, i, type(t)))
-        if t.dtype != dtype:
-            raise TypeError("%s: %s[%d] must be %s, got %s" % (what, name, i, _DTYPE_NAMES[dtype], t.dtype))
+        if t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):          # (a tuple: a mixed list)
+            raise TypeError("%s: %s[%d] must be %s, got %s" % (what, name, i, " or ".join(
+                _DTYPE_NAMES[d] for d in (dtype if isinstance(dtype, tuple) else (dtype,))), t.dtype))
         if not t.is_cuda:
             raise _lib.PsgdHipError("%s runs on the HIP device only (%s[%d] is on %s); no CPU fallback" % (what, name, i, t.device))
         if device is None:
@@ -124,12 +150,22 @@ def _lists(what, first, *others, plan=None, dtypes=None):
     return out, plan
 
 
+def _has_bf16(tensors):
+    """a list of gradients with a bfloat16 device tensor in it is a MIXED list (the preconditioned gradients of an optimizer with
+    bf16-operand layers); anything else takes the checks and the entry points of the fp32 lists"""
+    return any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 and t.is_cuda for t in tensors)
+
+
 def multi_sumsq(tensors, *, plan=None, out=None, ws=None):
     """out[0] = sum of fl32(x * x) over every element of every tensor, in fp64 and in a fixed order (psgd_multi_sumsq_f32: two launches
     whatever len(tensors), the same bits on every call).  tensors: contiguous fp32 tensors on one HIP device, empty ones allowed.
     out: a float64 device tensor of one element (default: the plan's); ws: a uint8 device tensor of at least
-    _lib.MULTI_SUMSQ_WS_BYTES bytes (default: the plan's).  Returns out."""
-    (tensors,), plan = _lists("multi_sumsq", ("tensors", tensors), plan=plan)
+    _lib.MULTI_SUMSQ_WS_BYTES bytes (default: the plan's).  Returns out.
+    A MIXED list -- some tensors bfloat16, the others float32 -- goes to psgd_multi_sumsq_mixed: the squares are those of float(x),
+    the structure and the fixed order are the same; a list without a bfloat16 tensor calls psgd_multi_sumsq_f32 as before."""
+    tensors = list(tensors)
+    mixed = _has_bf16(tensors)
+    (tensors,), plan = _lists("multi_sumsq", ("tensors", tensors), plan=plan, dtypes={"tensors": _MIXED} if mixed else None)
     out = plan.sumsq if out is None else out
     ws = plan.ws if ws is None else ws
     if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != plan.device or out.numel() < 1:
@@ -138,6 +174,12 @@ def multi_sumsq(tensors, *, plan=None, out=None, ws=None):
         raise ValueError("multi_sumsq: ws must be a contiguous uint8 tensor on %s" % (plan.device,))
     if not plan.nchunks:
         out[:1].zero_()                                              # the kernel launches nothing: the sum of nothing is 0
+        return out
+    if mixed:
+        rc = _lib.load().psgd_multi_sumsq_mixed(plan.mixed_table("sumsq_mixed", tensors, "multi_sumsq"), len(tensors),
+                                                plan.chunks.data_ptr(), plan.nchunks, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                _psgd._stream_ptr(plan.device))
+        _lib.check(rc, "psgd_multi_sumsq_mixed")
         return out
     rc = _lib.load().psgd_multi_sumsq_f32(plan.table("sumsq", tensors, "multi_sumsq"), len(tensors), plan.chunks.data_ptr(),
                                           plan.nchunks, out.data_ptr(), ws.data_ptr(), ws.numel(), _psgd._stream_ptr(plan.device))
@@ -159,7 +201,10 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
     Half precision: when params[0] is a bfloat16 or float16 tensor on the HIP device, params and vs have that type T, grads stay
     float32, and the call goes to psgd_multi_param_update_t: delta = T(float32(lr_eff * g)), then T(delta + v), then
     T(delta + T(float32(c * float(p)))), p <- T(p - delta); p <- T(p + v) without grads.  tiny then defaults to finfo(T).tiny.
-    (A half-precision tensor that is not on the device is refused as before: params must be float32.)"""
+    (A half-precision tensor that is not on the device is refused as before: params must be float32.)
+    MIXED gradients: when some tensors of grads are bfloat16 device tensors and the others float32 (the preconditioned gradients
+    of bf16-operand layers), the call goes to psgd_multi_param_update_mixed, which reads every gradient as float(g) and rounds as
+    above for the parameters' dtype, float32 included.  A list without a bfloat16 tensor calls the entry points of before."""
     what = "multi_param_update"
     wd = float(weight_decay)
     if not wd >= 0.0:
@@ -168,8 +213,12 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
     T = _f32
     if params and isinstance(params[0], torch.Tensor) and params[0].is_cuda and params[0].dtype in _HALF:
         T = params[0].dtype
-    (params, grads, vs), plan = _lists(what, ("params", params), ("grads", grads), ("vs", vs), plan=plan,
-                                       dtypes={"params": T, "vs": T})
+    grads = None if grads is None else list(grads)
+    mixed = grads is not None and _has_bf16(grads)
+    dtypes = {"params": T, "vs": T}
+    if mixed:
+        dtypes["grads"] = _MIXED
+    (params, grads, vs), plan = _lists(what, ("params", params), ("grads", grads), ("vs", vs), plan=plan, dtypes=dtypes)
     if grads is None and (vs is None or sumsq is not None or wd != 0.0):
         raise ValueError("%s: grads=None adds vs to the parameters; it needs vs and takes no sumsq and no weight_decay" % what)
     if (sumsq is None) != (max_norm is None):
@@ -178,6 +227,15 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
                               or sumsq.numel() < 1):
         raise ValueError("%s: sumsq must be a float64 tensor of at least one element on %s" % (what, plan.device))
     if not plan.nchunks:
+        return
+    if mixed:
+        rc = _lib.load().psgd_multi_param_update_mixed(
+            plan.table("params", params, what, T), plan.mixed_table("grads_mixed", grads, what),
+            None if vs is None else plan.table("vs", vs, what, T), len(params), plan.chunks.data_ptr(), plan.nchunks,
+            _psgd._TAIL_DTYPES[T], float(lr), None if sumsq is None else sumsq.data_ptr(),
+            0.0 if max_norm is None else float(max_norm), float(_dtype_constants(T)[2] if tiny is None else tiny), wd,
+            _psgd._stream_ptr(plan.device))
+        _lib.check(rc, "psgd_multi_param_update_mixed")
         return
     tabs = (plan.table("params", params, what, T), None if grads is None else plan.table("grads", grads, what),
             None if vs is None else plan.table("vs", vs, what, T), len(params), plan.chunks.data_ptr(), plan.nchunks)
@@ -302,6 +360,33 @@ def multi_widen_check(srcs, dsts, scales, *, flag=None, stamp=None, plan=None):
                                             _psgd._TAIL_DTYPES[T], word, 0 if stamp is None else int(stamp),
                                             _psgd._stream_ptr(plan.device))
     _lib.check(rc, "psgd_multi_widen_check")
+
+
+def multi_narrow(srcs, dsts, *, plan=None):
+    """One to three lists of float32 tensors narrowed into as many lists of bfloat16 tensors in ONE launch (psgd_multi_narrow_bf16):
+    dsts[j][i] <- srcs[j][i].to(torch.bfloat16), bit for bit -- round to nearest even, NaN stays NaN, a finite value beyond the
+    bfloat16 range becomes +-Inf.  multi_widen_check in the other direction, without a scale and without a flag: every destination
+    is written whole and nothing is judged.  All tensors contiguous on one HIP device, dsts[j][i] with the element count of
+    srcs[j][i].  Returns dsts."""
+    what = "multi_narrow"
+    srcs, dsts = list(srcs), list(dsts)
+    if not 1 <= len(srcs) <= 3 or len(dsts) != len(srcs):
+        raise ValueError("%s: one to three source lists and a destination list for each, got %d and %d" % (what, len(srcs), len(dsts)))
+    if any(ts is None for ts in srcs) or any(ts is None for ts in dsts):
+        raise ValueError("%s: a list is None" % what)
+    names = ["dsts[%d]" % j for j in range(len(dsts))]
+    lists, plan = _lists(what, *([("srcs[%d]" % j, ts) for j, ts in enumerate(srcs)] + list(zip(names, dsts))), plan=plan,
+                         dtypes={n: torch.bfloat16 for n in names})
+    srcs, dsts = lists[:len(srcs)], lists[len(srcs):]
+    if not plan.nchunks:
+        return dsts
+    pad = [None] * (3 - len(srcs))
+    rc = _lib.load().psgd_multi_narrow_bf16(*([plan.table("narrow_src%d" % j, ts, what) for j, ts in enumerate(srcs)] + pad),
+                                            *([plan.table("narrow_dst%d" % j, ts, what, torch.bfloat16)
+                                               for j, ts in enumerate(dsts)] + pad),
+                                            len(srcs[0]), plan.chunks.data_ptr(), plan.nchunks, _psgd._stream_ptr(plan.device))
+    _lib.check(rc, "psgd_multi_narrow_bf16")
+    return dsts
 
 
 # --------------------------------------------------------------------------- vector layers
@@ -472,6 +557,51 @@ def kron_layers(shapes, preconditioner_formats="dense", any_rank=False):
     return out
 
 
+# operand_min_dim of class Kron when none is given: the smallest short side at which narrow + bf16 update + narrow + bf16 apply beat
+# the fp32 update + apply by more than the spread of the legs, on the square and on the 1:4 layer, and at every larger side measured
+# (profiles/kron_class_operands.txt: 768 x 768 by 36 us of 431, 768 x 3072 by 54 us of 892; at 512 x 512 the legs are not resolved,
+# at 256 x 256 the fp32 route wins).
+OPERAND_MIN_DIM = 768
+
+
+def _operands_dtype(operands):
+    """`operands` of class Kron: None, or torch.bfloat16 for "bfloat16" / torch.bfloat16; ValueError otherwise"""
+    if operands is None:
+        return None
+    if operands is torch.bfloat16 or (isinstance(operands, str) and operands == "bfloat16"):
+        return torch.bfloat16
+    raise ValueError("Kron: operands must be None, 'bfloat16' or torch.bfloat16, got %r" % (operands,))
+
+
+def _operand_min_dim(operand_min_dim):
+    if isinstance(operand_min_dim, bool) or not isinstance(operand_min_dim, (int, np.integer)) or operand_min_dim < 1:
+        raise ValueError("Kron: operand_min_dim must be an integer >= 1, got %r" % (operand_min_dim,))
+    return int(operand_min_dim)
+
+
+def kron_operand_layers(layer_shapes, formats, operands=None, operand_min_dim=OPERAND_MIN_DIM):
+    """The indices of the OPERAND LAYERS of class Kron(operands=..., operand_min_dim=...): the layers whose factor update and
+    apply run on the bf16-operand kernels.  layer_shapes: the (M, N) of every layer, as kron_layers gives them (with any_rank the
+    [shape[0], prod(shape[1:])] view, not the parameter's own shape); formats: one (left, right) pair per layer.  A layer is chosen
+    when operands is bfloat16, its format is ("dense", "dense") and min(M, N) >= operand_min_dim; sizes that are no multiple of 8
+    qualify (the functional calls pad them).  Vector layers (("dense", "scale")), the other sparse formats and smaller layers are
+    never chosen; operands=None gives []."""
+    op = _operands_dtype(operands)
+    min_dim = _operand_min_dim(operand_min_dim)
+    layer_shapes, formats = list(layer_shapes), list(formats)
+    if len(layer_shapes) != len(formats):
+        raise ValueError("kron_operand_layers: %d layer shapes and %d formats" % (len(layer_shapes), len(formats)))
+    if op is None:
+        return []
+    out = []
+    for i, (s, f) in enumerate(zip(layer_shapes, formats)):
+        if len(s) != 2:
+            raise ValueError("kron_operand_layers: layer %d has shape %r; a layer shape is (M, N)" % (i, tuple(s)))
+        if _format_pair(f, "kron_operand_layers (layer %d)" % i) == ("dense", "dense") and min(int(s[0]), int(s[1])) >= min_dim:
+            out.append(i)
+    return out
+
+
 # --------------------------------------------------------------------------- checkpoint, host part
 _HYPER_KEYS = ("lr_params", "lr_preconditioner", "grad_clip_max_norm", "preconditioner_update_probability",
                "exact_hessian_vector_product")
@@ -604,16 +734,34 @@ class Kron:
     correct but slow).  vector_route="layer": they go through update_precond_kron / precond_grad_kron on [1, n] views like any
     other layer, about ten launches each -- the comparison leg.  The two routes round differently and need not agree bit for bit.
 
-    Out of scope: feeding (dense, dense) layers to the bf16-operand Kron kernels from inside the class, mixed dtypes, a narrow
-    (bfloat16) factor state, a format for vectors other than the reference's (dense, scale)."""
+    operands="bfloat16" (or torch.bfloat16; keyword-only, None by default: nothing changes) runs the large (dense, dense) layers on
+    the bf16-operand Kron kernels (psgd_kron_dd_update_bf16, psgd_kron_dd_apply_bf16[_prepared]), whatever the parameters' dtype.
+    A layer is an OPERAND LAYER when its format is ("dense", "dense") and min(M, N) >= operand_min_dim on its layer shape (with
+    any_rank the [shape[0], prod(shape[1:])] view); kron_operand_layers is the rule, opt.operand_layers the indices chosen.  Sizes
+    that are no multiple of 8 qualify (the functional calls pad them); vector layers, the sparse formats and smaller layers keep
+    the fp32 path.  For an operand layer step 4 is update_precond_kron(Ql, Qr, bf16(dX), bf16(dG), lr_q) and step 5
+    precond_grad_kron(Ql, Qr, bf16(g)), g the momentum buffer after the blend when momentum is on; the factors stay float32, the
+    preconditioned gradient is a bfloat16 tensor, and steps 6 and 7 read it as float(pg) and round as they always do (see step()).
+    The fused tail keeps three bfloat16 buffers per operand layer, in the layer's shape, for the gradient, dX and dG: 6 bytes per
+    element of those layers (the torch tail makes them per step).  operands is a constructor choice like step_tail: it is not in
+    state_dict(), and a checkpoint loads into an optimizer with either setting.
+    operand_min_dim defaults to 768 (OPERAND_MIN_DIM): the smallest short side at which the bf16 route (narrow + update + narrow +
+    apply) beats the fp32 update + apply by more than the spread of the legs on both the square and the 1:4 layer, and at every
+    larger side measured (1024, 2048); at 512 the square layer is not resolved and at 256 the fp32 route wins
+    (profiles/kron_class_operands.txt).
+    Known limitation: kron.py keeps ONE prepared bf16 factor slot per (device, M, N, stream), so several operand layers of one
+    shape convert their factors again on every apply of a step that did not update them.
+
+    Out of scope: mixed dtypes, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale)."""
 
     def __init__(self, params_with_grad, preconditioner_formats="dense", preconditioner_init_scale=1.0, lr_params=0.01,
                  lr_preconditioner=0.01, grad_clip_max_norm=None, preconditioner_update_probability=1.0,
                  exact_hessian_vector_product=True, *, layer_batch=True, step_tail="torch", generator=None,
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
-                 any_rank=False, vector_route="list"):
+                 any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM):
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
+        self._operands, self._operand_min_dim = _operands_dtype(operands), _operand_min_dim(operand_min_dim)
         if vector_route not in ("list", "layer"):
             raise ValueError("Kron: vector_route must be 'list' or 'layer', got %r" % (vector_route,))
         any_rank = bool(any_rank)
@@ -681,6 +829,11 @@ class Kron:
         # the vectors write into buffers made once: the pointers of their table never move
         self._vec = [i for i, (kind, _, _) in enumerate(layers) if kind == "vector" and vector_route == "list"]
         self._mat = sorted(set(range(len(params))) - set(self._vec))
+        # the operand layers (none with operands=None): (dense, dense) matrix layers, never one of self._vec; self._f32: the layers
+        # of self._mat that keep the fp32 calls
+        self._ops = kron_operand_layers(self._layer_shapes, self._formats, self._operands, self._operand_min_dim)
+        self._f32 = [i for i in self._mat if i not in set(self._ops)]
+        self._op_plan, self._op_bufs = None, None
         self._vec_plan, self._vec_out = None, None
         if self._vec:
             self._vec_plan = MultiTailPlan([self._layer_shapes[i][1] for i in self._vec], dev)
@@ -702,12 +855,23 @@ class Kron:
                 # the fp32 copies of the gradients, the second list and the probe vectors: written whole by the one
                 # multi_widen_check launch of a step before anything reads them
                 self._wide = [[torch.empty_like(p, dtype=_f32, requires_grad=False) for p in params] for _ in range(3)]
+            if self._ops:
+                # the bf16 copies of the gradient, dX and dG of every operand layer, in the layer's shape (6 bytes per element of
+                # these layers): each is written whole by a multi_narrow launch before the preconditioner call that reads it
+                self._op_plan = MultiTailPlan([int(params[i].numel()) for i in self._ops], dev)
+                self._op_bufs = [[torch.empty(self._layer_shapes[i], dtype=torch.bfloat16, device=dev) for i in self._ops]
+                                 for _ in range(3)]
 
     # ------------------------------------------------------------------------------------------------- state
     @property
     def factors(self):
         """[[Ql, Qr], ...] in parameter order: the tensors the last update returned (never copies)"""
         return self._Qs
+
+    @property
+    def operand_layers(self):
+        """the indices (parameter order) of the layers that run on the bf16-operand kernels: kron_operand_layers of this optimizer"""
+        return list(self._ops)
 
     def _coin_generator(self):
         return self._generator if self._generator is not None else _psgd._branch_rng
@@ -927,41 +1091,65 @@ class Kron:
         vector layers of the list route in ONE multi_vec_precond_update launch, in place"""
         dXs, dGs = self._as_layers(dXs), self._as_layers(dGs)
         Qs = self._Qs
-        if not self._vec:
+        if not self._vec and not self._ops:
             with self._block():
                 new = [_psgd.update_precond_kron(q[0], q[1], dX, dG, lr_q) for q, dX, dG in zip(Qs, dXs, dGs)]
             self._Qs = [[a, b] for a, b in new]
             return
         Qs = list(Qs)
-        if self._mat:
+        if self._ops:
+            # the operand layers: bf16(dX), bf16(dG) -- ONE multi_narrow launch for all of them (torch tail: .to(bfloat16) per
+            # tensor) -- into update_precond_kron, which runs them at once on the bf16-operand kernel: outside the block, so that
+            # the queue of the small fp32 layers stays whole
+            ops = self._ops
+            bX, bG = self._narrow([[dXs[i] for i in ops], [dGs[i] for i in ops]], self._op_bufs and self._op_bufs[1:])
+            for i, x, g in zip(ops, bX, bG):
+                Qs[i] = list(_psgd.update_precond_kron(Qs[i][0], Qs[i][1], x, g, lr_q))
+        if self._f32:
             with self._block():
-                new = [_psgd.update_precond_kron(Qs[i][0], Qs[i][1], dXs[i], dGs[i], lr_q) for i in self._mat]
-            for i, (a, b) in zip(self._mat, new):
+                new = [_psgd.update_precond_kron(Qs[i][0], Qs[i][1], dXs[i], dGs[i], lr_q) for i in self._f32]
+            for i, (a, b) in zip(self._f32, new):
                 Qs[i] = [a, b]
         vec = self._vec
-        multi_vec_precond_update([Qs[i][0] for i in vec], [Qs[i][1] for i in vec], [dXs[i].contiguous() for i in vec],
-                                 [dGs[i].contiguous() for i in vec], lr_q, plan=self._vec_plan)
+        if vec:
+            multi_vec_precond_update([Qs[i][0] for i in vec], [Qs[i][1] for i in vec], [dXs[i].contiguous() for i in vec],
+                                     [dGs[i].contiguous() for i in vec], lr_q, plan=self._vec_plan)
         self._Qs = Qs
+
+    def _narrow(self, lists, bufs):
+        """bf16(x) of the fp32 tensors of one to three lists, one list per role of the operand layers: round to nearest even of the
+        values the step already has; nothing is judged again (the guard has seen the fp32 values).  Fused tail: ONE multi_narrow
+        launch into the preallocated buffers; torch tail: x.to(torch.bfloat16) per tensor."""
+        if self._tail is not None:
+            return multi_narrow([[x.contiguous() for x in xs] for xs in lists], bufs, plan=self._op_plan)
+        return [[x.to(torch.bfloat16) for x in xs] for xs in lists]
 
     def _precondition(self, grads):
         """step 5: one precond_grad_kron per layer inside a second block; the vector layers of the list route in ONE
         multi_vec_precond_grad launch.  Returns the preconditioned gradients in the layers' shapes."""
         grads = self._as_layers(grads)
         Qs = self._Qs
-        if not self._vec:
+        if not self._vec and not self._ops:
             with self._block():
                 return [_psgd.precond_grad_kron(q[0], q[1], g) for q, g in zip(Qs, grads)]
         pre = [None] * len(grads)
-        if self._mat:
+        if self._ops:
+            # the operand layers: bf16(g) (one multi_narrow launch) into precond_grad_kron; their preconditioned gradient is bf16
+            ops = self._ops
+            (bg,) = self._narrow([[grads[i] for i in ops]], self._op_bufs and self._op_bufs[:1])
+            for i, g in zip(ops, bg):
+                pre[i] = _psgd.precond_grad_kron(Qs[i][0], Qs[i][1], g)
+        if self._f32:
             with self._block():
-                out = [_psgd.precond_grad_kron(Qs[i][0], Qs[i][1], grads[i]) for i in self._mat]
-            for i, g in zip(self._mat, out):
+                out = [_psgd.precond_grad_kron(Qs[i][0], Qs[i][1], grads[i]) for i in self._f32]
+            for i, g in zip(self._f32, out):
                 pre[i] = g
         vec = self._vec
-        multi_vec_precond_grad([Qs[i][0] for i in vec], [Qs[i][1] for i in vec], [grads[i].contiguous() for i in vec],
-                               self._vec_out, plan=self._vec_plan)
-        for i, g in zip(vec, self._vec_out):
-            pre[i] = g
+        if vec:
+            multi_vec_precond_grad([Qs[i][0] for i in vec], [Qs[i][1] for i in vec], [grads[i].contiguous() for i in vec],
+                                   self._vec_out, plan=self._vec_plan)
+            for i, g in zip(vec, self._vec_out):
+                pre[i] = g
         return pre
 
     def step(self, closure):
@@ -1010,7 +1198,20 @@ class Kron:
         delta = T(fl32(lr_eff * pg)); after step 3, delta = T(delta + v); with weight decay, delta = T(delta + T(fl32(c *
         float(p)))), c = fl32(lr_eff * wd); p <- T(p - delta); tiny = finfo(T).tiny in step 6.  The torch tail is the same chain,
         one torch op per rounding.  With everything on the fused tail still issues seven launches: perturbation, widen-check,
-        difference, blend, two for the sum of squares, update."""
+        difference, blend, two for the sum of squares, update.
+
+        operands="bfloat16" (nothing of this runs without operand layers).  bf16(x) is round-to-nearest-even of the float32 value
+        the step already has -- after the widening / scale / guard pass and, for the gradient, after the blend: NaN stays NaN, a
+        finite value beyond the bfloat16 range becomes +-Inf, exactly as tensor.to(torch.bfloat16) does.  The guard has judged the
+        float32 values: the narrowing is not judged again and there is no second host read, so a finite float32 value beyond
+        3.39e38 that overflows HERE propagates into the factors or the parameters, under the "propagate silently" contract of an
+        unguarded step.  Fused tail: at most two multi_narrow launches per step whatever the number of layers -- one before the
+        updates (dX and dG, on steps that update the factors), one before the applies (gradients or momentum buffers) -- so at
+        most nine launches with everything on; the sum of squares and the update then go through psgd_multi_sumsq_mixed and
+        psgd_multi_param_update_mixed, which read a bf16 preconditioned gradient as float(pg): S adds fl32(float(pg) float(pg)) in
+        fp64 and delta = T(fl32(lr_eff float(pg))), everything after that unchanged.  Torch tail: x.to(torch.bfloat16) and
+        pg.float() per tensor, the definition the kernels match.  Inside layer_batch blocks the operand layers run at once, as
+        outside a block; the class issues them before the block so that the queue of the small layers stays whole."""
         params = self._params
         update_Q = self._coin()
         exact = bool(self.exact_hessian_vector_product)
@@ -1098,6 +1299,8 @@ class Kron:
                 multi_param_update(params, pre_grads, undo, lr, sumsq, max_norm if clip else None, self._tiny, plan=self._tail,
                                    weight_decay=wd)
                 return closure_returns
+            if self._ops:                                   # float(pg) of the bf16 preconditioned gradients, exact
+                pre_grads = [g.float() if g.dtype != _f32 else g for g in pre_grads]
             if clip:
                 S = None
                 for g in pre_grads:

@@ -1638,3 +1638,4 @@ class UVd:
 from .kron_optimizer import Kron, multi_sumsq, multi_param_update, multi_diff_scale, kron_initial_factors  # noqa: E402,F401
 from .kron_optimizer import multi_blend, multi_scale_check, multi_widen_check  # noqa: E402,F401
 from .kron_optimizer import multi_vec_precond_update, multi_vec_precond_grad, kron_layers  # noqa: E402,F401
+from .kron_optimizer import multi_narrow, kron_operand_layers  # noqa: E402,F401

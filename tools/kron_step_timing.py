@@ -30,6 +30,18 @@ resolved, and the summary line says so.
               kron_optimizer.py of another commit): whether the float32 path moved
 
     python tools/kron_step_timing.py --dtype bf16 [--parent-module FILE] [--out profiles/kron_class_half.txt]
+
+--operands measures Kron(operands="bfloat16"), two tables:
+
+    threshold   per layer shape (square and 1:4, short side 256 .. 2048), DEVICE time (events around a chunk of 20 rounds) of
+                "bf16": one multi_narrow of dX and dG + the bf16-operand update + one multi_narrow of g + the bf16-operand apply,
+                against "fp32": the fp32 update + apply; new factors every round, as on a step that updates them
+    step        whole steps, fused tail, exact products, the switches off, an elementwise quadratic loss (so that the
+                preconditioner dominates), float32 and bfloat16 parameters, legs "none" (operands=None), "bf16"
+                (operands="bfloat16", operand_min_dim=1024) and, with --parent-module, "parent" (as "none", on the
+                kron_optimizer.py of another commit)
+
+    python tools/kron_step_timing.py --operands [--parent-module FILE] [--out profiles/kron_class_operands.txt]
 """
 import argparse
 import os
@@ -114,8 +126,115 @@ def timed(step, n):
     return (time.perf_counter() - t0) / n * 1e6
 
 
+OPERAND_SHORT_SIDES = (256, 512, 768, 1024, 2048)
+OPERAND_SETS = {"4096x4096": [(4096, 4096)], "1024x4096": [(1024, 4096)],
+                "8x(1024x4096)+8x(1024x1024)": [(1024, 4096)] * 8 + [(1024, 1024)] * 8}
+
+
+def device_timed(fn, n):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n * 1e3
+
+
+def alternate(legs, chunks, n, timer, warm):
+    """warm every leg up for `warm` seconds, then `chunks` rounds over the legs of n calls each: {leg: [us per call]}"""
+    for fn in legs.values():
+        spent = 0.0
+        while spent < warm:
+            spent += timed(fn, 10) * 10e-6
+    times = {k: [] for k in legs}
+    for _ in range(chunks):
+        for k, fn in legs.items():
+            times[k].append(timer(fn, n))
+    return times
+
+
+def threshold_legs(M, N, dev):
+    g = torch.Generator(device=dev).manual_seed(7 * M + N)
+    dX, G = torch.randn(M, N, device=dev, generator=g), torch.randn(M, N, device=dev, generator=g)
+    dG = dX * torch.exp(torch.empty(M, N, device=dev).uniform_(-1.0, 1.0, generator=g))
+    Q = {k: [torch.eye(M, device=dev), torch.eye(N, device=dev)] for k in ("fp32", "bf16")}
+    bg, bx, bh = (torch.empty(M, N, dtype=torch.bfloat16, device=dev) for _ in range(3))
+
+    def fp32():
+        q = Q["fp32"]
+        q[:] = psgd.update_precond_kron(q[0], q[1], dX, dG, LR_Q)
+        psgd.precond_grad_kron(q[0], q[1], G)
+
+    def bf16():
+        q = Q["bf16"]
+        psgd.multi_narrow([[dX], [dG]], [[bx], [bh]])
+        q[:] = psgd.update_precond_kron(q[0], q[1], bx, bh, LR_Q)
+        psgd.multi_narrow([[G]], [[bg]])
+        psgd.precond_grad_kron(q[0], q[1], bg)
+    return {"fp32": fp32, "bf16": bf16}
+
+
+def operand_leg(shapes, dev, dtype, cls=None, **kw):
+    g = torch.Generator(device=dev).manual_seed(0)
+    H = [torch.exp(torch.empty(m, n, device=dev).uniform_(-1.0, 1.0, generator=g)) for m, n in shapes]
+    Ws = [torch.randn(m, n, device=dev, generator=g).to(dtype).requires_grad_(True) for m, n in shapes]
+    closure = lambda: sum(0.5 * torch.sum(h * W.float() * W.float()) for W, h in zip(Ws, H))
+    clip = 0.1 * sum(W.numel() for W in Ws) ** 0.5
+    opt = (cls or psgd.Kron)(Ws, "dense", lr_params=LR, lr_preconditioner=LR_Q, grad_clip_max_norm=clip, step_tail="fused", **kw)
+    return lambda: opt.step(closure)
+
+
+def report(lines, name, times, pairs):
+    med = {k: statistics.median(v) for k, v in times.items()}
+    for k, v in times.items():
+        lines.append("%-28s %-7s %9.1f  [%9.1f .. %9.1f]" % (name, k, med[k], min(v), max(v)))
+    spread = max(max(v) - min(v) for v in times.values())
+    for x, y in pairs:
+        d = med[x] - med[y]
+        lines.append("%-28s %s - %s = %+8.1f us: %s (largest range of a leg: %.1f us)"
+                     % (name, x, y, d, "resolved" if abs(d) > spread else "NOT resolved by this protocol", spread))
+    print("\n".join(lines[-len(times) - len(pairs):]), flush=True)
+    return med, spread
+
+
+def operands_main(a, dev):
+    lines = ["# tools/kron_step_timing.py --operands --chunks %d --steps %d on %s" % (a.chunks, a.steps, torch.cuda.get_device_name(0)),
+             "# threshold: us of DEVICE time per round (narrow + update + narrow + apply on bf16 operands against the fp32 update + "
+             "apply), median [min .. max] over the chunks of 20 rounds; legs alternate chunk by chunk"]
+    wins = {}
+    for short in OPERAND_SHORT_SIDES:
+        for M, N in ((short, short), (short, 4 * short)):
+            med, spread = report(lines, "threshold %dx%d" % (M, N), alternate(threshold_legs(M, N, dev), a.chunks, 20, device_timed, 0.2),
+                                 [("fp32", "bf16")])
+            wins.setdefault(short, []).append(med["fp32"] - med["bf16"] > spread)
+            torch.cuda.empty_cache()
+    ok = [s for s in OPERAND_SHORT_SIDES if all(all(wins[t]) for t in OPERAND_SHORT_SIDES if t >= s)]
+    lines.append("# smallest short side from which the bf16 route wins by more than the spread on both shapes, and on every larger "
+                 "side measured: %s" % (min(ok) if ok else "none"))
+    lines.append("# step: us per step on the host clock (closure + preconditioner + tail), fused tail, exact products, median "
+                 "[min .. max] over the chunks of %d steps; legs alternate chunk by chunk" % a.steps)
+    parent = parent_class(a.parent_module) if a.parent_module else None
+    for name, shapes in OPERAND_SETS.items():
+        for tag, T in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+            legs = {"none": operand_leg(shapes, dev, T), "bf16": operand_leg(shapes, dev, T, operands="bfloat16", operand_min_dim=1024)}
+            pairs = [("none", "bf16")]
+            if parent is not None:
+                legs["parent"] = operand_leg(shapes, dev, T, parent)
+                pairs.append(("parent", "none"))
+            report(lines, "step %s %s" % (name, tag), alternate(legs, a.chunks, a.steps, timed, 0.5), pairs)
+            del legs
+            torch.cuda.empty_cache()
+    text = "\n".join(lines) + "\n"
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--operands", action="store_true")
     ap.add_argument("--chunks", type=int, default=9)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--out", default=None)
@@ -126,6 +245,8 @@ def main():
     if a.chunks < 7:
         ap.error("--chunks must be at least 7")
     dev = torch.device("cuda:0")
+    if a.operands:
+        return operands_main(a, dev)
     lines = ["# tools/kron_step_timing.py %s--chunks %d --steps %d on %s"
              % ("--features " if a.features else "--dtype %s " % a.dtype if a.dtype else "", a.chunks, a.steps,
                 torch.cuda.get_device_name(0)),
