@@ -68,6 +68,8 @@ extern "C" {
  *     only: still 7).
  *     psgd_multi_narrow_bf16, psgd_multi_sumsq_mixed and psgd_multi_param_update_mixed: the bf16-operand layers of class
  *     Kron(operands="bfloat16") (additive, new symbols only: still 7).
+ *     psgd_uvd_param_update_multi_sr, psgd_multi_param_update_sr and psgd_multi_param_update_mixed_sr: stochastic rounding of the
+ *     bf16 parameter update of class UVd and class Kron (additive, new symbols only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -562,6 +564,37 @@ int psgd_multi_sumsq_mixed(const void *segs, int k, const void *chunks, int64_t 
 int psgd_multi_param_update_mixed(const void *param_segs, const void *grad_segs, const void *vs_segs, int k, const void *chunks,
                                   int64_t nchunks, int dtype, float lr, const double *sumsq, float max_norm, float tiny, float wd,
                                   void *stream);
+
+/* ------------------------------------------------- bf16 parameters written with stochastic rounding ---
+ * param_rounding="stochastic" of class UVd and class Kron.  A bf16 parameter under round to nearest ignores every update below half
+ * its spacing; these three entry points form the update ONCE in fp32 and narrow it ONCE, stochastically.  With w = float(p[i]) and
+ * c = fl32(lr_eff * wd), every operation rounded to fp32 on its own:
+ *     d = fl32(lr_eff * float(g[i]));   vs_segs given: d = fl32(d + float(v[i]));   wd != 0: d = fl32(d + fl32(c * w));
+ *     x = fl32(w - d);   p[i] = SR(x).
+ * SR(x) is the stochastic narrowing of the bf16-stored states, (bits(x) + u) >> 16 with u the top 16 bits of their counter hash of
+ * (key, idx), where key is the rounding stream of (seed, tensor id 16 = "parameters") and idx = index0 + start + i, start being
+ * the `start` field of the PARAMETER segment (which the psgd_multi_* entry points above never read): the element's index in the
+ * optimizer's flat parameter order.  The stored bits therefore do not depend on the grid, the chunk table, where a tensor starts
+ * or how a flat vector is split over ranks (index0 = the rank's first row).  A NaN x is stored as 0x7FC0; +-Inf stays +-Inf; an x
+ * that is exactly a bf16 value is never changed; a finite x beyond the largest finite bf16 value may carry into +-Inf -- its upper
+ * neighbour, so the correct stochastic outcome.  lr_eff, sumsq, max_norm and tiny are evaluated exactly as in the siblings (a NaN
+ * *sumsq makes every parameter NaN).  Same tables, launch shape and accesses as the siblings; one hash per written element.
+ * dtype must be PSGD_DTYPE_BF16 (float16 needs its own narrowing for its subnormal range) and index0 >= 0: anything else is
+ * PSGD_ERR_BAD_ARG, and so is a missing gradient -- the perturbation p + v and its undo round to nearest and keep the siblings.
+ * Other argument checks as in the siblings.  Nothing allocates or synchronises.
+ *
+ * psgd_uvd_param_update_multi_sr: psgd_uvd_param_update_multi_wd (flat fp32 pre_grad, g[i] = pre_grad[start + i]).
+ * psgd_multi_param_update_sr: psgd_multi_param_update_t (a list of fp32 gradients).
+ * psgd_multi_param_update_mixed_sr: psgd_multi_param_update_mixed (gradient segment i fp32 or bf16 as grad_segs[i].start says).   */
+int psgd_uvd_param_update_multi_sr(const void *param_segs, const void *vs_segs, int k, const void *chunks, int64_t nchunks, int dtype,
+                                   const float *pre_grad, float lr, const double *sumsq, float max_norm, float tiny, float wd,
+                                   uint64_t seed, int64_t index0, void *stream);
+int psgd_multi_param_update_sr(const void *param_segs, const void *grad_segs, const void *vs_segs, int k, const void *chunks,
+                               int64_t nchunks, int dtype, float lr, const double *sumsq, float max_norm, float tiny, float wd,
+                               uint64_t seed, int64_t index0, void *stream);
+int psgd_multi_param_update_mixed_sr(const void *param_segs, const void *grad_segs, const void *vs_segs, int k, const void *chunks,
+                                     int64_t nchunks, int dtype, float lr, const double *sumsq, float max_norm, float tiny, float wd,
+                                     uint64_t seed, int64_t index0, void *stream);
 
 /* Tuning knobs for experiments (not part of the stable ABI).
  * key 0: streaming policy (0 = automatic: non-temporal when U,V exceed the Infinity Cache,

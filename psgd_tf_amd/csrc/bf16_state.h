@@ -2,7 +2,8 @@
 // the widening and the one narrowing of an element (round to nearest even or stochastic, a counter hash keyed by seed,
 // tensor id and flat element index), the rounding-stream keys, the exact three-piece bf16 split of an fp32 value, and the
 // tile copies of an [N, r] row-major bf16 matrix with 16-byte loads and stores whatever the rank.
-// Tensor ids of the rounding streams: 0, 1, 2 = U, V, d of UVd; 8, 9, 10, 11 = L12, l3, U12, u3 of the sparse-LU state.
+// Tensor ids of the rounding streams: 0, 1, 2 = U, V, d of UVd; 8, 9, 10, 11 = L12, l3, U12, u3 of the sparse-LU state;
+// 16 = the bf16 PARAMETERS of class UVd / class Kron (param_rounding="stochastic": narrow_param below, the step-tail kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -73,6 +74,17 @@ __device__ __forceinline__ unsigned narrow(float x, int mode, SrKey key, unsigne
     add = z >> 16;
   }
   return (b + add) >> 16;
+}
+
+// fp32 -> bf16 code of a PARAMETER written by the stochastic step-tail kernels (tensor id 16): the mode-1 narrowing above on the
+// element's index in the optimizer's flat parameter order, except that a NaN becomes the quiet NaN 0x7FC0 (what
+// psgdtt::BF16::narrow and torch store).  +-Inf stays +-Inf.  A value that is exactly a bf16 code is never changed (its low 16 bits
+// are 0 and the addend is below 2^16).  A finite x beyond the largest finite bf16 value (low 16 bits f of 0x7F7Fffff's neighbourhood)
+// carries into +-Inf with probability f / 2^16: that IS the stochastic outcome -- the two neighbours of such an x are the largest
+// finite bf16 value and Inf -- and round to nearest does the same from the midpoint on.
+__device__ __forceinline__ unsigned narrow_param(float x, SrKey key, unsigned long long idx) {
+  if (x != x) return 0x7FC0u;
+  return narrow(x, 1, key, idx);
 }
 
 // x = h + m + l, each an exact bf16 value kept as fp32

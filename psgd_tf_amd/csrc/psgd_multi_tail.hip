@@ -20,6 +20,10 @@
 //   psgd_multi_narrow_bf16       one to three lists of fp32 tensors -> as many lists of bf16 tensors, round to nearest even
 //   psgd_multi_sumsq_mixed       psgd_multi_sumsq_f32 on a list whose tensors are fp32 or bf16, tensor by tensor
 //   psgd_multi_param_update_mixed  psgd_multi_param_update_t (for fp32 parameters: _wd_f32) with such a list as the gradients
+// and, for bf16 parameters written with STOCHASTIC rounding (param_rounding="stochastic" of class Kron; these two read `start` of
+// the parameter table):
+//   psgd_multi_param_update_sr        the update formed once in fp32 and narrowed once, fp32 gradients
+//   psgd_multi_param_update_mixed_sr  the same with a mixed list as the gradients
 //
 // The tables are those of psgd_uvd_tail.hip: a SEGMENT is one tensor {pointer, start, count}, a CHUNK one piece of at most
 // PSGD_UVD_TAIL_CHUNK consecutive elements of one segment {segment index, offset}.  Here EVERY operand is a list: each has its own
@@ -39,6 +43,7 @@
 #include <stdint.h>
 #include "psgd_hip.h"
 #include "tail_types.h"
+#include "bf16_state.h"
 #include "nanmax.h"
 
 // The roundings are the contract (bit-equal to the torch expressions they replace): no product may be fused into a following sum.
@@ -916,7 +921,125 @@ __global__ __launch_bounds__(kT) void k_multi_param_update_mixed(const Seg* __re
   }
 }
 
+// ------------------------------------------------------------------------- bf16 parameters: the update with stochastic rounding
+// psgd_multi_param_update_sr (kMixed false: gradients fp32) and psgd_multi_param_update_mixed_sr (kMixed true: every gradient
+// segment fp32 or bf16 as its `start` says) in ONE kernel, so that the tables are handled in one place.  The update is formed ONCE
+// in fp32 and narrowed ONCE: with w = float(p),  d = fl32(lr_eff * float(g));  kVs: d = fl32(d + float(v));
+// kWd: d = fl32(d + fl32(c * w)), c = fl32(lr_eff * wd);  x = fl32(w - d);  p = narrow_param(x, key, idx)  (bf16_state.h).
+// idx = index0 + the PARAMETER segment's start + the offset inside it -- these kernels, unlike every other list kernel, read
+// `start` of the parameter table: the element's place in the optimizer's flat parameter order.  The launch shape, the chunk loop
+// and the accesses are those of k_multi_param_update_t<BF16> / k_multi_param_update_mixed<BF16>; one hash per element.
+template <bool kVs, bool kWd>
+__device__ __forceinline__ float update_one_sr(float w, float g, float v, float lr_eff, float c) {
+  float d = lr_eff * g;
+  if constexpr (kVs) d = d + v;
+  if constexpr (kWd) {
+    const float dec = c * w;
+    d = d + dec;
+  }
+  return w - d;
+}
+
+template <bool kMixed, bool kVs, bool kWd>
+__global__ __launch_bounds__(kT) void k_multi_param_update_sr(const Seg* __restrict__ psegs, const Seg* __restrict__ gsegs,
+                                                              const Seg* __restrict__ vsegs, const Chunk* __restrict__ chunks,
+                                                              int64_t nchunks, int k, float lr, const double* __restrict__ sumsq,
+                                                              float max_norm, float tiny, float wd, psgd::bf16s::SrKey key,
+                                                              unsigned long long index0) {
+  using T = BF16;
+  constexpr int E = 8;
+  const int t = threadIdx.x;
+  float lr_eff = lr;
+  if (sumsq) {                // as k_multi_param_update: fp64, one rounding, a NaN norm propagates
+    const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
+    lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
+  }
+  const float dc = kWd ? lr_eff * wd : 0.f;         // c = fl32(lr_eff wd)
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Chunk ch = chunks[c];
+    if ((uint64_t)ch.seg >= (uint64_t)k || ch.off < 0) continue;
+    const Seg ps = psegs[ch.seg];
+    const Seg gs = gsegs[ch.seg];
+    if (kMixed && gs.start != PSGD_DTYPE_F32 && gs.start != PSGD_DTYPE_BF16) continue;
+    const bool bf = kMixed && gs.start == PSGD_DTYPE_BF16;
+    int64_t left = ps.count - ch.off;
+    left = left < kChunk ? left : kChunk;
+    {
+      const int64_t l = gs.count - ch.off;
+      left = l < left ? l : left;
+    }
+    uint16_t* p = reinterpret_cast<uint16_t*>(ps.ptr) + ch.off;
+    const void* g = reinterpret_cast<const char*>(gs.ptr) + ch.off * (bf ? 2 : 4);
+    const uint16_t* v = nullptr;
+    if constexpr (kVs) {
+      const Seg vsg = vsegs[ch.seg];
+      const int64_t l = vsg.count - ch.off;
+      left = l < left ? l : left;
+      v = reinterpret_cast<const uint16_t*>(vsg.ptr) + ch.off;
+    }
+    if (left <= 0) continue;
+    const int n = (int)left;
+    const unsigned long long idx0 = index0 + (unsigned long long)(ps.start + ch.off);
+    const int head = head_of_16bit(p, n);
+    const int nvec = (n - head) / E;
+    if (t < head)
+      p[t] = (uint16_t)psgd::bf16s::narrow_param(
+          update_one_sr<kVs, kWd>(T::widen(p[t]), grad_at(g, bf, t), kVs ? T::widen(v[t]) : 0.f, lr_eff, dc), key, idx0 + t);
+#pragma unroll 2
+    for (int q = t; q < nvec; q += kT) {
+      const int i = head + q * E;
+      float x[E], gg[E], vv[E];
+      load_16<T>(p + i, x);
+      load_grad<E>(g, bf, i, gg);
+      if constexpr (kVs) load_any<T>(v + i, vv);
+      u16x8 y;
+#pragma unroll
+      for (int e = 0; e < E; ++e)
+        y[e] = (uint16_t)psgd::bf16s::narrow_param(update_one_sr<kVs, kWd>(x[e], gg[e], kVs ? vv[e] : 0.f, lr_eff, dc), key,
+                                                   idx0 + (unsigned)(i + e));
+      *reinterpret_cast<u16x8*>(p + i) = y;
+    }
+    const int i = head + nvec * E + t;
+    if (i < n)
+      p[i] = (uint16_t)psgd::bf16s::narrow_param(
+          update_one_sr<kVs, kWd>(T::widen(p[i]), grad_at(g, bf, i), kVs ? T::widen(v[i]) : 0.f, lr_eff, dc), key, idx0 + (unsigned)i);
+  }
+}
+
 static int grid_for(int64_t nchunks) { return (int)(nchunks < kMaxGrid ? nchunks : kMaxGrid); }
+
+// the two stochastic entry points: argument checks of psgd_multi_param_update_mixed (a gradient list is required: the perturbation
+// p + v and its undo round to nearest), bf16 parameters only, index0 >= 0
+template <bool kMixed>
+static int update_sr_entry(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
+                           int64_t nchunks, int dtype, float lr, const double* sumsq, float max_norm, float tiny, float wd,
+                           uint64_t seed, int64_t index0, void* stream) {
+  if (dtype != PSGD_DTYPE_BF16 || index0 < 0) return PSGD_ERR_BAD_ARG;
+  if (!param_segs || !grad_segs || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = grid_for(nchunks);
+  const Seg* ps = (const Seg*)param_segs;
+  const Seg* gs = (const Seg*)grad_segs;
+  const Seg* vsg = (const Seg*)vs_segs;
+  const Chunk* ch = (const Chunk*)chunks;
+  const psgd::bf16s::SrKey key = psgd::bf16s::make_key(seed, 16u);          // tensor id 16: the parameters (bf16_state.h)
+  const unsigned long long i0 = (unsigned long long)index0;
+#define PSGD_MULTI_UPDATE_SR(VS, WD)                                                                                             \
+  hipLaunchKernelGGL((k_multi_param_update_sr<kMixed, VS, WD>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, \
+                     sumsq, max_norm, tiny, wd, key, i0)
+  if (wd != 0.f) {                           // (a NaN wd decays too: it propagates)
+    if (vsg)
+      PSGD_MULTI_UPDATE_SR(true, true);
+    else
+      PSGD_MULTI_UPDATE_SR(false, true);
+  } else if (vsg)
+    PSGD_MULTI_UPDATE_SR(true, false);
+  else
+    PSGD_MULTI_UPDATE_SR(false, false);
+#undef PSGD_MULTI_UPDATE_SR
+  return hipGetLastError() == hipSuccess ? PSGD_OK : PSGD_ERR_LAUNCH;
+}
 
 template <class T>
 static void launch_update_mixed(int grid, hipStream_t st, const Seg* ps, const Seg* gs, const Seg* vsg, const Chunk* ch,
@@ -1161,6 +1284,20 @@ int psgd_multi_param_update_mixed(const void* param_segs, const void* grad_segs,
   else
     launch_update_mixed<F16>(grid, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq, max_norm, tiny, wd);
   return launched();
+}
+
+int psgd_multi_param_update_sr(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
+                               int64_t nchunks, int dtype, float lr, const double* sumsq, float max_norm, float tiny, float wd,
+                               uint64_t seed, int64_t index0, void* stream) {
+  return update_sr_entry<false>(param_segs, grad_segs, vs_segs, k, chunks, nchunks, dtype, lr, sumsq, max_norm, tiny, wd, seed, index0,
+                                stream);
+}
+
+int psgd_multi_param_update_mixed_sr(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
+                                     int64_t nchunks, int dtype, float lr, const double* sumsq, float max_norm, float tiny, float wd,
+                                     uint64_t seed, int64_t index0, void* stream) {
+  return update_sr_entry<true>(param_segs, grad_segs, vs_segs, k, chunks, nchunks, dtype, lr, sumsq, max_norm, tiny, wd, seed, index0,
+                               stream);
 }
 
 }  // extern "C"

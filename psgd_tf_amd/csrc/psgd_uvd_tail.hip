@@ -7,6 +7,7 @@
 //   psgd_uvd_sumsq_f32           sum x^2 of a flat fp32 vector -> one device double (the clip norm's square)              (:753)
 //   psgd_uvd_param_update_multi  p <- T(p - [T(T(fl32(lr_eff pre_grad)) + v)])  for every element of every parameter      (:757-762)
 //   psgd_uvd_param_update_multi_wd  ... with decoupled weight decay: delta <- T(delta + T(fl32(fl32(lr_eff wd) p)))
+//   psgd_uvd_param_update_multi_sr  bf16 parameters, the update formed once in fp32 and narrowed once, stochastically
 //
 // The work of pack and update is described by two device tables.  A SEGMENT is one tensor: {pointer, start offset in the flat vector,
 // element count}.  A CHUNK is one piece of at most kChunk consecutive elements of one segment: {segment index, offset inside it}; the
@@ -27,6 +28,7 @@
 #include <stdint.h>
 #include "psgd_hip.h"
 #include "tail_types.h"
+#include "bf16_state.h"
 
 // The roundings of this file are its contract (bit-equal to the torch expressions it replaces): no product may be fused into a
 // following sum.  hipcc contracts by default, and the header's __fmul_rn / __fadd_rn are compiled under that default: plain
@@ -291,6 +293,82 @@ __global__ __launch_bounds__(kT) void k_uvd_param_update(const Seg* __restrict__
   }
 }
 
+// ------------------------------------------------------------------------------ parameter update, stochastic rounding (bf16)
+// psgd_uvd_param_update_multi_sr: the update of k_uvd_param_update formed ONCE in fp32 and narrowed ONCE, stochastically.  With
+// w = float(p):  d = fl32(lr_eff * g);  kVs: d = fl32(d + float(v));  kWd: d = fl32(d + fl32(c * w)), c = fl32(lr_eff * wd);
+// x = fl32(w - d);  p = narrow_param(x, key, idx)  (bf16_state.h: (bits(x) + u) >> 16, u the top 16 bits of the counter hash of
+// (key, idx); NaN -> 0x7FC0).  idx = index0 + the segment's start + the offset inside it: the element's place in the optimizer's
+// flat parameter order, so what is stored depends on neither the grid, the chunks nor where a tensor starts.  No contraction.
+template <bool kVs, bool kWd>
+__device__ __forceinline__ float update_one_sr(float w, float g, float v, float lr_eff, float c) {
+  float d = lr_eff * g;
+  if constexpr (kVs) d = d + v;
+  if constexpr (kWd) {
+    const float dec = c * w;
+    d = d + dec;
+  }
+  return w - d;
+}
+
+// The launch shape, the chunk loop and the accesses of k_uvd_param_update<BF16, true, ., .>: a scalar head to the 16-byte boundary
+// of p, a body of 8 elements (16 bytes of p, two 16-byte reads of g) per lane and access, a scalar tail; one hash per element.
+template <bool kVs, bool kWd>
+__global__ __launch_bounds__(kT) void k_uvd_param_update_sr(const Seg* __restrict__ psegs, const Seg* __restrict__ vsegs,
+                                                            const Chunk* __restrict__ chunks, int64_t nchunks, int k,
+                                                            const float* __restrict__ pre_grad, float lr,
+                                                            const double* __restrict__ sumsq, float max_norm, float tiny, float wd,
+                                                            psgd::bf16s::SrKey key, unsigned long long index0) {
+  using T = BF16;
+  constexpr int E = 8;
+  const int t = threadIdx.x;
+  float lr_eff = lr;
+  if (sumsq) {                // as k_uvd_param_update: fp64, one rounding, a NaN norm propagates
+    const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
+    lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
+  }
+  const float dc = kWd ? lr_eff * wd : 0.f;      // c = fl32(lr_eff * wd)
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Chunk ch = chunks[c];
+    if ((uint64_t)ch.seg >= (uint64_t)k) continue;
+    const Seg s = psegs[ch.seg];
+    const int64_t left = s.count - ch.off;
+    if (ch.off < 0 || left <= 0) continue;
+    const int n = (int)(left < kChunk ? left : kChunk);
+    uint16_t* p = reinterpret_cast<uint16_t*>(s.ptr) + ch.off;
+    const float* g = pre_grad + s.start + ch.off;
+    const uint16_t* v = kVs ? reinterpret_cast<const uint16_t*>(vsegs[ch.seg].ptr) + ch.off : nullptr;
+    const unsigned long long idx0 = index0 + (unsigned long long)(s.start + ch.off);
+    const int head = head_of(p, 2, n);
+    const int nvec = (n - head) / E;
+    if (t < head)
+      p[t] = (uint16_t)psgd::bf16s::narrow_param(
+          update_one_sr<kVs, kWd>(T::widen(p[t]), g[t], kVs ? T::widen(v[t]) : 0.f, lr_eff, dc), key, idx0 + t);
+#pragma unroll 2
+    for (int q = t; q < nvec; q += kT) {
+      const int i = head + q * E;
+      float x[E], gg[E], vv[E];
+      load_16<T>(p + i, x);
+#pragma unroll
+      for (int b = 0; b < E / 4; ++b) {
+        const f32x4_u w = *reinterpret_cast<const f32x4_u*>(g + i + 4 * b);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gg[4 * b + e] = w[e];
+      }
+      if constexpr (kVs) load_any<T>(v + i, vv);
+      u16x8 y;
+#pragma unroll
+      for (int e = 0; e < E; ++e)
+        y[e] = (uint16_t)psgd::bf16s::narrow_param(update_one_sr<kVs, kWd>(x[e], gg[e], kVs ? vv[e] : 0.f, lr_eff, dc), key,
+                                                   idx0 + (unsigned)(i + e));
+      *reinterpret_cast<u16x8*>(p + i) = y;
+    }
+    const int i = head + nvec * E + t;
+    if (i < n)
+      p[i] = (uint16_t)psgd::bf16s::narrow_param(
+          update_one_sr<kVs, kWd>(T::widen(p[i]), g[i], kVs ? T::widen(v[i]) : 0.f, lr_eff, dc), key, idx0 + (unsigned)i);
+  }
+}
+
 static int grid_for(int64_t nchunks) { return (int)(nchunks < kMaxGrid ? nchunks : kMaxGrid); }
 static bool bad_dtype(int dtype) { return dtype < PSGD_DTYPE_F32 || dtype > PSGD_DTYPE_F16; }
 static int launched() { return hipGetLastError() == hipSuccess ? PSGD_OK : PSGD_ERR_LAUNCH; }
@@ -420,6 +498,35 @@ int psgd_uvd_param_update_multi_wd(const void* param_segs, const void* vs_segs, 
     launch_update<BF16>(pre, vs, grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny, wd);
   else
     launch_update<F16>(pre, vs, grid, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, max_norm, tiny, wd);
+  return launched();
+}
+
+int psgd_uvd_param_update_multi_sr(const void* param_segs, const void* vs_segs, int k, const void* chunks, int64_t nchunks, int dtype,
+                                   const float* pre_grad, float lr, const double* sumsq, float max_norm, float tiny, float wd,
+                                   uint64_t seed, int64_t index0, void* stream) {
+  if (!param_segs || !chunks || k < 0 || nchunks < 0 || dtype != PSGD_DTYPE_BF16 || index0 < 0) return PSGD_ERR_BAD_ARG;
+  if (!pre_grad) return PSGD_ERR_BAD_ARG;                                   // the perturbation of :723 and its undo round to nearest
+  if (nchunks == 0) return PSGD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const Seg* ps = (const Seg*)param_segs;
+  const Seg* vsg = (const Seg*)vs_segs;
+  const Chunk* ch = (const Chunk*)chunks;
+  const int grid = grid_for(nchunks);
+  const psgd::bf16s::SrKey key = psgd::bf16s::make_key(seed, 16u);          // tensor id 16: the parameters (bf16_state.h)
+  const unsigned long long i0 = (unsigned long long)index0;
+#define PSGD_UVD_UPDATE_SR(VS, WD)                                                                                              \
+  hipLaunchKernelGGL((k_uvd_param_update_sr<VS, WD>), dim3(grid), dim3(kT), 0, st, ps, vsg, ch, nchunks, k, pre_grad, lr, sumsq, \
+                     max_norm, tiny, wd, key, i0)
+  if (wd != 0.f) {                           // (a NaN wd decays too: it propagates)
+    if (vsg)
+      PSGD_UVD_UPDATE_SR(true, true);
+    else
+      PSGD_UVD_UPDATE_SR(false, true);
+  } else if (vsg)
+    PSGD_UVD_UPDATE_SR(true, false);
+  else
+    PSGD_UVD_UPDATE_SR(false, false);
+#undef PSGD_UVD_UPDATE_SR
   return launched();
 }
 

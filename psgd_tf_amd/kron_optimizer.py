@@ -187,7 +187,8 @@ def multi_sumsq(tensors, *, plan=None, out=None, ws=None):
     return out
 
 
-def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None, tiny=None, *, plan=None, weight_decay=0.0):
+def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None, tiny=None, *, plan=None, weight_decay=0.0,
+                       rounding="nearest", rounding_seed=None, index0=0):
     """For all parameters in ONE launch (psgd_multi_param_update_f32), every operation rounded to float32 on its own:
         p <- p - lr_eff * g                     vs None
         p <- p - (lr_eff * g + v)               vs given (the undo of the finite-difference perturbation, psgd.py:761)
@@ -204,11 +205,24 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
     (A half-precision tensor that is not on the device is refused as before: params must be float32.)
     MIXED gradients: when some tensors of grads are bfloat16 device tensors and the others float32 (the preconditioned gradients
     of bf16-operand layers), the call goes to psgd_multi_param_update_mixed, which reads every gradient as float(g) and rounds as
-    above for the parameters' dtype, float32 included.  A list without a bfloat16 tensor calls the entry points of before."""
+    above for the parameters' dtype, float32 included.  A list without a bfloat16 tensor calls the entry points of before.
+    rounding="stochastic" (bfloat16 parameters, grads required; psgd_multi_param_update_sr, with mixed gradients
+    psgd_multi_param_update_mixed_sr): the update is formed once in float32 and narrowed once -- w = float(p),
+    d = fl32(lr_eff * float(g)), d = fl32(d + float(v)), d = fl32(d + fl32(c * w)), p <- SR(fl32(w - d)) -- with the stochastic
+    narrowing of stochastic_narrow_bf16 under rounding_seed (None: drawn from the module's branch generator) on the flat index
+    index0 + the element's place in the concatenation of params.  "nearest" (default): nothing changes, and rounding_seed / index0
+    must be left alone."""
     what = "multi_param_update"
     wd = float(weight_decay)
     if not wd >= 0.0:
         raise ValueError("%s: weight_decay must be >= 0, got %r" % (what, weight_decay))
+    if rounding not in _psgd._PARAM_ROUNDINGS:
+        raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (what, rounding))
+    sr = rounding == "stochastic"
+    if not sr and (rounding_seed is not None or index0 != 0):
+        raise ValueError("%s: rounding_seed and index0 apply to rounding='stochastic' only" % what)
+    if sr and (grads is None or int(index0) < 0):
+        raise ValueError("%s: rounding='stochastic' needs grads (the perturbation p + v rounds to nearest) and index0 >= 0" % what)
     params = list(params)
     T = _f32
     if params and isinstance(params[0], torch.Tensor) and params[0].is_cuda and params[0].dtype in _HALF:
@@ -226,7 +240,22 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
     if sumsq is not None and (not isinstance(sumsq, torch.Tensor) or sumsq.dtype != torch.float64 or sumsq.device != plan.device
                               or sumsq.numel() < 1):
         raise ValueError("%s: sumsq must be a float64 tensor of at least one element on %s" % (what, plan.device))
+    if sr and T != torch.bfloat16:
+        raise ValueError("%s: rounding='stochastic' needs bfloat16 parameters on the HIP device, got %s" % (what, params[0].dtype))
     if not plan.nchunks:
+        return
+    if sr:
+        if rounding_seed is None:
+            rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=_psgd._branch_rng).item())
+        name = "psgd_multi_param_update_mixed_sr" if mixed else "psgd_multi_param_update_sr"
+        rc = getattr(_lib.load(), name)(
+            plan.table("params", params, what, T),
+            plan.mixed_table("grads_mixed", grads, what) if mixed else plan.table("grads", grads, what),
+            None if vs is None else plan.table("vs", vs, what, T), len(params), plan.chunks.data_ptr(), plan.nchunks,
+            _psgd._TAIL_DTYPES[T], float(lr), None if sumsq is None else sumsq.data_ptr(),
+            0.0 if max_norm is None else float(max_norm), float(_dtype_constants(T)[2] if tiny is None else tiny), wd,
+            int(rounding_seed) & (2 ** 64 - 1), int(index0), _psgd._stream_ptr(plan.device))
+        _lib.check(rc, name)
         return
     if mixed:
         rc = _lib.load().psgd_multi_param_update_mixed(
@@ -752,13 +781,27 @@ class Kron:
     Known limitation: kron.py keeps ONE prepared bf16 factor slot per (device, M, N, stream), so several operand layers of one
     shape convert their factors again on every apply of a step that did not update them.
 
-    Out of scope: mixed dtypes, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale)."""
+    param_rounding="stochastic" (keyword-only, "nearest" by default: nothing changes; bfloat16 parameters only, anything else is a
+    ValueError before a device is touched).  The parameters are the only copy of the weights, and under round to nearest a
+    bfloat16 weight ignores every update below half its spacing (2^-9 for a weight near 1): late in training most updates are
+    lost without a sign of it.  With "stochastic" step 7 forms the update once in float32 and narrows it once with the stochastic
+    rounding of the bf16-stored UVd / sparse-LU states: w = float(p), d = fl32(lr_eff * float(pg)), after step 3 d = fl32(d +
+    float(v)), with weight decay d = fl32(d + fl32(c * w)), p <- SR(fl32(w - d)) (psgd_multi_param_update_sr / _mixed_sr on the
+    fused tail, param_update_stochastic_ on the torch tail: the same bits).  SR is unbiased, so small updates accumulate in
+    expectation.  The stream of step k is keyed by uvd_step_rounding_seed(seed0, k) and the element's index in the flat
+    parameter order; seed0 = param_rounding_seed, or a draw from the generator behind the coin; k counts the steps that wrote the
+    parameters (a skipped step does not advance it).  The perturbation of step 3 and its undo on a skipped step stay
+    round-to-nearest.  state_dict() carries param_round_seed0 / param_round_step; param_rounding itself is a constructor choice.
+
+    Out of scope: mixed dtypes, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale),
+    float16 stochastic rounding."""
 
     def __init__(self, params_with_grad, preconditioner_formats="dense", preconditioner_init_scale=1.0, lr_params=0.01,
                  lr_preconditioner=0.01, grad_clip_max_norm=None, preconditioner_update_probability=1.0,
                  exact_hessian_vector_product=True, *, layer_batch=True, step_tail="torch", generator=None,
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
-                 any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM):
+                 any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM,
+                 param_rounding="nearest", param_rounding_seed=None):
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
         self._operands, self._operand_min_dim = _operands_dtype(operands), _operand_min_dim(operand_min_dim)
@@ -805,6 +848,9 @@ class Kron:
                 raise ValueError("Kron: %s does not require grad" % tag)
             if not p.is_contiguous():
                 raise ValueError("Kron: %s is not contiguous" % tag)
+        # param_rounding (see the class docstring): judged before the parameters' device is looked at
+        self._param_sr = _psgd._param_rounding("Kron", param_rounding, params[0].dtype)
+        self._param_round_seed0, self._param_round_step = None, 0
         self._shapes = [tuple(int(s) for s in p.shape) for p in params]
         layers = kron_layers(self._shapes, preconditioner_formats, any_rank)
         self._formats = [f for _, _, f in layers]
@@ -845,6 +891,15 @@ class Kron:
         self.exact_hessian_vector_product = _psgd._Hyper(bool(exact_hessian_vector_product))
         self._layer_batch = bool(layer_batch)
         self._generator = generator
+        if self._param_sr:
+            if param_rounding_seed is not None:
+                self._param_round_seed0 = int(param_rounding_seed) & (2 ** 64 - 1)
+            else:                    # drawn from the generator behind the coin, as class UVd draws the seed of its native state
+                gen = self._coin_generator()
+                self._param_round_seed0 = int(torch.randint(0, 2 ** 62, (), generator=gen, device=gen.device).item())
+            self._param_starts = [0]
+            for p in params[:-1]:
+                self._param_starts.append(self._param_starts[-1] + int(p.numel()))
         self._tail = None
         if step_tail == "fused":
             self._tail = MultiTailPlan([int(p.numel()) for p in params], dev)
@@ -882,12 +937,14 @@ class Kron:
         (generator=None: of the module's branch generator; the global device generator that then draws the perturbations is the
         caller's, as in class UVd).  'hyper' also holds momentum and weight_decay; with momentum > 0 the dict gains
         momentum_buffers (CPU clones) and momentum_step, with nonfinite="skip" it gains nonfinite, skipped_steps, loss_scale (the
-        current one; None without loss scaling) and loss_scale_good_steps."""
+        current one; None without loss scaling) and loss_scale_good_steps, with param_rounding="stochastic" param_round_seed0 and
+        param_round_step (param_rounding itself is a constructor choice and is not saved)."""
         sd = _encode_state(self._Qs, self._formats, self._shapes, {k: getattr(self, k) for k in _HYPER_KEYS},
                            self._coin_generator().get_state())
         mom = float(self.momentum)
-        return _encode_features(sd, mom, float(self.weight_decay), self._momentum_buffers() if mom > 0.0 else None, self._m_step,
-                                self._guard, self.skipped_steps, self.loss_scale.value, self._good_steps)
+        sd = _encode_features(sd, mom, float(self.weight_decay), self._momentum_buffers() if mom > 0.0 else None, self._m_step,
+                              self._guard, self.skipped_steps, self.loss_scale.value, self._good_steps)
+        return _psgd._param_rounding_encode(sd, self._param_sr, self._param_round_seed0, self._param_round_step)
 
     def load_state_dict(self, sd):
         """Restore what state_dict() saved.  The factors become NEW device tensors (as after an update), the hyper-parameters are
@@ -895,9 +952,12 @@ class Kron:
         momentum and weight_decay are assigned when 'hyper' has them (a dict from before them leaves this object's values); the
         momentum buffers and their step counter are restored, and a dict without them zeroes the buffers of a momentum optimizer
         and restarts its warm-up.  A guarded optimizer restores skipped_steps, loss_scale_good_steps and, when both sides scale
-        the loss, loss_scale where the dict has them and starts them fresh where it has not; an unguarded one ignores them."""
+        the loss, loss_scale where the dict has them and starts them fresh where it has not; an unguarded one ignores them.
+        param_rounding="stochastic": param_round_seed0 / param_round_step are restored where the dict has them; a dict without them
+        leaves this object's seed and sets the counter to 0; a nearest optimizer ignores them."""
         factors, hyper, rng = _decode_state(sd, self._formats, self._shapes, self._layer_shapes)
         bufs, m_step = _decode_features(sd, self._shapes)
+        sr_state = _psgd._param_rounding_decode("Kron.load_state_dict", sd, self._param_sr, self._param_round_seed0)
         try:
             self._coin_generator().set_state(rng)
         except (RuntimeError, TypeError) as e:
@@ -909,6 +969,7 @@ class Kron:
                 getattr(self, k).assign(hyper[k])
         self._Qs = [[q.to(self._device, copy=True) for q in pair] for pair in factors]
         self._m_step = m_step
+        self._param_round_seed0, self._param_round_step = sr_state
         with torch.no_grad():
             if bufs is not None:
                 for m, b in zip(self._momentum_buffers(), bufs):
@@ -1293,11 +1354,16 @@ class Kron:
             pre_grads = self._precondition(grads)
             lr, max_norm = float(self.lr_params), float(self.grad_clip_max_norm)
             clip = not math.isinf(max_norm)
+            sr = self._param_sr
+            if sr:                                          # this step writes the parameters: the seed of its rounding stream
+                sr_seed = _psgd.uvd_step_rounding_seed(self._param_round_seed0, self._param_round_step)
+                self._param_round_step += 1
             if fused:
                 pre_grads = [g.contiguous() for g in pre_grads]          # (the mirrored formats return transposed views)
                 sumsq = multi_sumsq(pre_grads, plan=self._tail) if clip else None
+                sr_kw = dict(rounding="stochastic", rounding_seed=sr_seed) if sr else {}
                 multi_param_update(params, pre_grads, undo, lr, sumsq, max_norm if clip else None, self._tiny, plan=self._tail,
-                                   weight_decay=wd)
+                                   weight_decay=wd, **sr_kw)
                 return closure_returns
             if self._ops:                                   # float(pg) of the bf16 preconditioned gradients, exact
                 pre_grads = [g.float() if g.dtype != _f32 else g for g in pre_grads]
@@ -1318,6 +1384,9 @@ class Kron:
             for k, (p, g) in enumerate(zip(params, pre_grads)):
                 if self._reshape:
                     g = g.reshape(p.shape)
+                if sr:                                      # formed once in fp32, narrowed once: psgd_multi_param_update_sr
+                    _psgd.param_update_stochastic_(p, g, None if undo is None else undo[k], lr, decay, sr_seed, self._param_starts[k])
+                    continue
                 delta = (g * lr).to(T)
                 if undo is not None:
                     delta = delta + undo[k]

@@ -204,6 +204,93 @@ def uvd_step_rounding_seed(seed0, k):
     return _mix64(_mix64(int(seed0)) + 0x9E3779B97F4A7C15 * (int(k) + 1))
 
 
+# --------------------------------------------------------------------------- stochastic rounding of bf16 parameters
+# param_rounding="stochastic" of class UVd and class Kron: the narrowing of the step-tail kernels psgd_uvd_param_update_multi_sr,
+# psgd_multi_param_update_sr and psgd_multi_param_update_mixed_sr (bf16_state.h: narrow_param) restated with torch integer ops, bit
+# for bit -- what step_tail="torch" runs and what the tests hold the kernels against.
+_PARAM_TENSOR_ID = 16                                # the rounding stream "parameters" (bf16_state.h)
+_PARAM_ROUNDINGS = ("nearest", "stochastic")
+_M32 = 0xFFFFFFFF
+
+
+def rounding_stream_key(seed, tensor):
+    """(a, b): the two 32-bit halves of the key of one tensor's rounding stream, bf16s::make_key(seed, tensor) in Python"""
+    z = _mix64(_mix64(int(seed) + 0x9E3779B97F4A7C15) ^ ((0xD1B54A32D192ED03 * (int(tensor) + 1)) & (2 ** 64 - 1)))
+    return z & _M32, z >> 32
+
+
+def param_rounding_addend(seed, index):
+    """u of SR(x) = (bits(x) + u) >> 16 for the parameter elements whose flat indices are `index` (an int64 tensor, >= 0): the top
+    16 bits of the counter hash of bf16s::narrow's mode 1 under the key of (seed, tensor id 16).  int64 arithmetic with 32-bit
+    masks (a product of two 32-bit values may wrap in int64: its low 32 bits, all that is kept, are right)."""
+    a, b = rounding_stream_key(seed, _PARAM_TENSOR_ID)
+    index = index.to(torch.int64)
+    z = ((index & _M32) * 0x9E3779B1 + a + ((index >> 32) & _M32) * 0x85EBCA77) & _M32
+    z = z ^ (z >> 16)
+    z = (z * 0x7FEB352D) & _M32
+    z = z ^ b
+    z = z ^ (z >> 15)
+    z = (z * 0x846CA68B) & _M32
+    z = z ^ (z >> 16)
+    return z >> 16
+
+
+def stochastic_narrow_bf16(x, seed, index0=0):
+    """SR(x): the bfloat16 tensor the stochastic step-tail kernels store for the float32 values x, element j of x.reshape(-1)
+    being the parameter element of flat index index0 + j.  (bits(x) + u) >> 16; a NaN becomes 0x7FC0, +-Inf stays, a value that
+    is a bfloat16 value is unchanged, a finite value beyond the bfloat16 range may carry into +-Inf.  Any device."""
+    if x.dtype != torch.float32:
+        raise TypeError("stochastic_narrow_bf16: x must be float32, got %s" % (x.dtype,))
+    flat = x.detach().contiguous().view(-1)
+    index = torch.arange(flat.numel(), dtype=torch.int64, device=flat.device) + int(index0)
+    bits = flat.view(torch.int32).to(torch.int64) & _M32
+    code = ((bits + param_rounding_addend(seed, index)) >> 16) & 0xFFFF
+    code = torch.where(torch.isnan(flat), torch.full_like(code, 0x7FC0), code)
+    code = torch.where(code >= 2 ** 15, code - 2 ** 16, code).to(torch.int16)      # the 16 bits as they are: nothing converts
+    return code.view(torch.bfloat16).view(x.shape)
+
+
+def param_update_stochastic_(p, g, v, lr_eff, c, seed, index0):
+    """One bfloat16 parameter tensor of the stochastic step tail, in place, as the kernels compute it: w = float(p),
+    d = fl32(lr_eff * float(g)); v given: d = fl32(d + float(v)); c given: d = fl32(d + fl32(c * w)); p <- SR(fl32(w - d)) with the
+    flat indices index0, index0 + 1, ...  lr_eff and c: Python floats that hold float32 values, or 0-dim float32 tensors."""
+    w = p.detach().float()
+    d = g.reshape(p.shape).float() * lr_eff
+    if v is not None:
+        d = d + v.float()
+    if c is not None:
+        d = d + w * c
+    p.detach().copy_(stochastic_narrow_bf16(w - d, seed, index0))
+    return p
+
+
+def _param_rounding(name, param_rounding, dtype):
+    """the param_rounding argument of a constructor, judged before anything touches a device: True for "stochastic" """
+    if param_rounding not in _PARAM_ROUNDINGS:
+        raise ValueError("%s: param_rounding must be 'nearest' or 'stochastic', got %r" % (name, param_rounding))
+    if param_rounding == "stochastic" and dtype != torch.bfloat16:
+        raise ValueError("%s: param_rounding='stochastic' needs bfloat16 parameters, got %s (float32 parameters are not rounded; "
+                         "float16 stochastic rounding is not supported)" % (name, dtype))
+    return param_rounding == "stochastic"
+
+
+def _param_rounding_encode(sd, stochastic, seed0, step):
+    """the checkpoint keys of the parameters' rounding stream, added to sd when the switch is on (both classes); returns sd"""
+    if stochastic:
+        sd["param_round_seed0"], sd["param_round_step"] = int(seed0), int(step)
+    return sd
+
+
+def _param_rounding_decode(name, sd, stochastic, seed0):
+    """(seed0, step) after loading sd into an optimizer whose own seed is seed0: the dict's pair where it has one; the
+    optimizer's seed with the counter at 0 where it has none; a nearest optimizer ignores the keys and gets (seed0, 0)"""
+    if not stochastic or "param_round_seed0" not in sd:
+        return seed0, 0
+    if "param_round_step" not in sd:
+        raise ValueError("%s: the state dict has 'param_round_seed0' but no 'param_round_step'" % name)
+    return int(sd["param_round_seed0"]), int(sd["param_round_step"])
+
+
 _UVD_TENSOR_IDS = {"U": 0, "V": 1, "d": 2}           # the tensor ids of psgd_uvd_bf16_rounding_key
 _NARROW_STAGING_BYTES = 64 << 20                     # UVd.load_state_dict: the fp32 staging buffer of an fp32 -> native bf16 load
 
@@ -870,7 +957,8 @@ def uvd_sumsq(x, *, plan):
     return plan.sumsq
 
 
-def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group=None, *, plan=None, weight_decay=0.0):
+def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group=None, *, plan=None, weight_decay=0.0,
+                  rounding="nearest", rounding_seed=None, index0=0):
     """psgd.py:750-762 on all parameters in place, in launches that do not depend on len(params):
         lr_eff = lr                                                         (max_norm None or inf, :750-751)
                  lr * min(max_norm / (||pre_grad|| + tiny), 1)              (:753-754; the norm never reaches the host)
@@ -881,9 +969,23 @@ def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group
     scalar, the collective sharded.global_norm uses).  pre_grad None (vs required): p <- T(p + v), the perturbation of :723.
     weight_decay (extension, decoupled): with c = fl32(lr_eff * weight_decay), delta = T(delta + T(fl32(c * p))) after the vs term;
     0 (default) adds no rounding step.
+    rounding="stochastic" (bfloat16 parameters, pre_grad required; psgd_uvd_param_update_multi_sr): the update is formed once in
+    float32 and narrowed once, with w = float(p): d = fl32(lr_eff * g); d = fl32(d + float(v)); d = fl32(d + fl32(c * w));
+    p <- SR(fl32(w - d)), SR the stochastic narrowing of stochastic_narrow_bf16 under rounding_seed (None: drawn from the module's
+    branch generator) on the flat index index0 + the element's place in the concatenation of params (index0: this rank's first
+    row on a row-sharded vector).  With "nearest" (default) nothing changes, and rounding_seed / index0 must be left alone.
     The parameters are written through their pointers: autograd's version counters do not move."""
     params = list(params)
+    if rounding not in _PARAM_ROUNDINGS:
+        raise ValueError("uvd_step_tail: rounding must be 'nearest' or 'stochastic', got %r" % (rounding,))
+    sr = rounding == "stochastic"
+    if not sr and (rounding_seed is not None or index0 != 0):
+        raise ValueError("uvd_step_tail: rounding_seed and index0 apply to rounding='stochastic' only")
+    if sr and (pre_grad is None or int(index0) < 0):
+        raise ValueError("uvd_step_tail: rounding='stochastic' needs pre_grad (the perturbation p + v rounds to nearest) and index0 >= 0")
     plan = plan if plan is not None else _tail_plan(params, "uvd_step_tail")
+    if sr and plan.dtype != torch.bfloat16:
+        raise ValueError("uvd_step_tail: rounding='stochastic' needs bfloat16 parameters, got %s" % (plan.dtype,))
     dev = plan.device
     psegs = plan.table("params", params, "uvd_step_tail")
     vsegs = plan.table("vs", list(vs), "uvd_step_tail (vs)") if vs is not None else None
@@ -910,7 +1012,12 @@ def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group
         args = (psegs, vsegs, len(params), plan.chunks.data_ptr(), plan.nchunks, plan.code,
                 None if pre_grad is None else pre_grad.data_ptr(), float(lr), None if sumsq is None else sumsq.data_ptr(),
                 float(max_norm) if clip else 0.0, float(tiny))
-        if wd == 0.0:
+        if sr:
+            if rounding_seed is None:
+                rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=_branch_rng).item())
+            rc = _lib.load().psgd_uvd_param_update_multi_sr(*args, wd, int(rounding_seed) & (2 ** 64 - 1), int(index0), _stream_ptr(dev))
+            _lib.check(rc, "psgd_uvd_param_update_multi_sr")
+        elif wd == 0.0:
             rc = _lib.load().psgd_uvd_param_update_multi(*args, _stream_ptr(dev))
             _lib.check(rc, "psgd_uvd_param_update_multi")
         else:
@@ -977,14 +1084,25 @@ class UVd:
 
     Same constructor arguments and defaults as the reference (psgd.py:663-666).  Parameters are
     torch tensors with requires_grad=True on a ROCm device (the reference's `.trainable` filter,
-    :670, maps to requires_grad).  `step(closure)` returns whatever closure returns (:764)."""
+    :670, maps to requires_grad).  `step(closure)` returns whatever closure returns (:764).
+
+    param_rounding="stochastic" (extension, keyword-only; "nearest" by default: nothing changes; bfloat16 parameters only, anything
+    else is a ValueError before a device is touched).  There is no float32 master copy: the parameter is the bfloat16 tensor, and
+    under round to nearest a weight ignores every update below half its spacing.  With "stochastic" the update of :757-762 is
+    formed once in float32 and narrowed once with the stochastic rounding of the bf16-stored states -- w = float(p),
+    d = fl32(lr_eff g), d = fl32(d + float(v)), d = fl32(d + fl32(c w)), p <- SR(fl32(w - d)) -- on a stream keyed by
+    uvd_step_rounding_seed(seed0, k) and the element's global flat index (psgd_uvd_param_update_multi_sr on the fused tail,
+    param_update_stochastic_ on the torch tail: the same bits).  seed0: param_rounding_seed, or a draw from the generator behind
+    the coins; k counts the steps that wrote the parameters.  The perturbation of :723 and its undo stay round-to-nearest.
+    state_dict() carries param_round_seed0 / param_round_step; param_rounding itself is a constructor choice, like step_tail."""
 
     def __init__(self, params_with_grad, rank_of_modification: int = 10, preconditioner_init_scale=1.0,
                  lr_params=0.01, lr_preconditioner=0.01,
                  grad_clip_max_norm=None, preconditioner_update_probability=1.0,
                  exact_hessian_vector_product: bool = True, generator=None, state_dtype=None, group=None,
                  stage_backend=None, placement="auto", state_route="widen", state_rounding=None, step_tail="torch",
-                 momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000):
+                 momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
+                 *, param_rounding="nearest", param_rounding_seed=None):
         # group (extension, SURVEY 8e): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
         # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the
         # concatenation of the ranks' vectors in rank order, and U, V, d hold this rank's rows only.  A step then costs three
@@ -998,6 +1116,17 @@ class UVd:
         self._dtype = p0.dtype                                                               # :671
         if self._dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise TypeError("UVd: parameters must be float32, float16 or bfloat16, got %s" % self._dtype)
+        # param_rounding (extension, keyword-only; "nearest" = nothing changes).  The parameters are the only copy of the weights:
+        # there is no fp32 master.  Under round to nearest a bfloat16 weight ignores every update below half its spacing (2^-9 for
+        # a weight near 1), so late in training most updates are lost without a sign of it.  "stochastic" (bfloat16 parameters
+        # only) forms the update of :757-762 once in float32 and narrows it once with the stochastic rounding of the bf16-stored
+        # states (uvd_step_tail(rounding="stochastic"); param_update_stochastic_ on the torch tail, the same bits): unbiased, so
+        # small updates accumulate in expectation.  The stream of step k is keyed by uvd_step_rounding_seed(seed0, k) and the
+        # element's GLOBAL flat index, seed0 = param_rounding_seed or a draw from the generator behind the coins; k counts the steps
+        # that wrote the parameters (a skipped step does not advance it).  The finite-difference perturbation and its undo on a
+        # skipped step stay round-to-nearest.  Judged here, before anything touches a device.
+        self._param_sr = _param_rounding("UVd", param_rounding, self._dtype)
+        self._param_round_seed0, self._param_round_step = None, 0
         # psgd.py:657-658 allows half-precision parameters.  The preconditioner state U, V, d and all of its arithmetic
         # stay fp32 here (mixed precision: the HIP kernels compute in fp32; v, Hv and the gradient are widened on the
         # way in, the preconditioned gradient is narrowed on the way out).  _tiny and the finite-difference scale follow
@@ -1054,6 +1183,16 @@ class UVd:
         elif state_rounding is not None:
             raise ValueError("UVd: state_rounding applies to state_route='native' only")
         self._state_rounding = state_rounding
+        if self._param_sr:
+            if param_rounding_seed is not None:
+                self._param_round_seed0 = int(param_rounding_seed) & (2 ** 64 - 1)
+            else:                    # drawn as the native route's seed is: row-sharded, from the generator all ranks share
+                if group is None:
+                    gen = generator if generator is not None else _branch_rng
+                else:
+                    from . import sharded as _sharded
+                    gen = _sharded.branch_rng_for(generator, group, p0.device).gen
+                self._param_round_seed0 = int(torch.randint(0, 2 ** 62, (), generator=gen).item())
         self.lr_params = _Hyper(lr_params)                                                   # :673
         self.lr_preconditioner = _Hyper(lr_preconditioner)                                   # :674
         self.grad_clip_max_norm = _Hyper(math.inf if grad_clip_max_norm is None else grad_clip_max_norm)  # :675-678
@@ -1322,6 +1461,8 @@ class UVd:
             param_sizes              the element counts of this rank's parameter tensors
             state_dtype, state_route, state_rounding    strings ("torch.bfloat16", "native" / "widen", "stochastic" / "nearest" / "none")
             round_seed0, round_step  native route only: together they fix every stored code of every later step
+            param_round_seed0, param_round_step    param_rounding="stochastic" only: the seed and the step counter of the
+                                     parameters' rounding stream (param_rounding itself is a constructor choice and is not saved)
             hyper                    lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability (floats),
                                      exact_hessian_vector_product (bool)
                                      and, optional when loading, momentum and weight_decay (floats)
@@ -1353,6 +1494,7 @@ class UVd:
             sd["momentum_buffer"], sd["momentum_step"] = host(self._momentum_buffer()), int(self._m_step)
         if self._native:
             sd["round_seed0"], sd["round_step"] = int(self._round_seed0), int(self._round_step)
+        _param_rounding_encode(sd, self._param_sr, self._param_round_seed0, self._param_round_step)
         if self._guard:
             sd["nonfinite"], sd["skipped_steps"] = "skip", int(self.skipped_steps)
             sd["loss_scale"] = None if self.loss_scale.value is None else float(self.loss_scale)
@@ -1365,7 +1507,9 @@ class UVd:
         assigned (momentum and weight_decay when the dict has them; momentum_buffer / momentum_step are restored, and a dict
         without them zeroes the buffer of a momentum optimizer and restarts its warm-up), the generator behind the coins gets the
         saved state (row-sharded: every rank loads the same bytes into the
-        synchronised generator; nothing is broadcast again) and, on the native route, so do round_seed0 / round_step.  A guarded
+        synchronised generator; nothing is broadcast again) and, on the native route, so do round_seed0 / round_step.  With
+        param_rounding="stochastic", param_round_seed0 / param_round_step are restored where the dict has them; a dict without
+        them leaves this object's seed and sets the counter to 0; a nearest optimizer ignores them.  A guarded
         optimizer (nonfinite="skip") restores skipped_steps, loss_scale_good_steps and, when both sides scale the loss, loss_scale
         where the dict has them and starts them fresh where it has not (a dict of an unguarded optimizer); an unguarded one
         ignores them.
@@ -1453,6 +1597,7 @@ class UVd:
                     self._momentum_buffer().zero_()
         if self._native and "round_seed0" in sd:
             self._round_seed0, self._round_step = int(sd["round_seed0"]), int(need("round_step"))
+        self._param_round_seed0, self._param_round_step = _param_rounding_decode(name, sd, self._param_sr, self._param_round_seed0)
         if self._guard:                  # a dict from an unguarded optimizer has none of these: the guard starts fresh
             self.skipped_steps, self.last_step_skipped = int(sd.get("skipped_steps", 0)), False
             self._good_steps = int(sd.get("loss_scale_good_steps", 0))
@@ -1597,12 +1742,18 @@ class UVd:
                 grad = self._grad_flat(grads, mom)
             pre_grad = self._precondition(None, None, grad)                                   # :747-748
         max_norm = float(self.grad_clip_max_norm)
+        sr = self._param_sr
+        if sr:                           # this step writes the parameters: the seed of its rounding stream, the GLOBAL first index
+            sr_seed = uvd_step_rounding_seed(self._param_round_seed0, self._param_round_step)
+            self._param_round_step += 1
+            sr_index0 = int(self._row0()) if self._group is not None else 0
         if fused:                                                                             # :750-762 in the step-tail kernels
+            sr_kw = dict(rounding="stochastic", rounding_seed=sr_seed, index0=sr_index0) if sr else {}
             uvd_step_tail(params, pre_grad, float(self.lr_params), max_norm, self._tiny, vs if (not exact) and update_Q else None,
-                          self._group, plan=self._tail, weight_decay=wd)
+                          self._group, plan=self._tail, weight_decay=wd, **sr_kw)
             return closure_returns
         decay = None
-        if mom != 0.0 or wd != 0.0:      # the torch tail of the extensions: lr_eff as the step-tail kernel forms it, one op per rounding
+        if mom != 0.0 or wd != 0.0 or sr:      # the torch tail of the extensions: lr_eff as the step-tail kernel forms it, one op per rounding
             lr = torch.tensor(float(self.lr_params), dtype=torch.float32, device=pre_grad.device)
             if not math.isinf(max_norm):
                 sq = torch.sum((pre_grad * pre_grad).double()).reshape(1)
@@ -1624,6 +1775,9 @@ class UVd:
         with torch.no_grad():                                                                 # :757-762
             undo = (not exact) and update_Q
             for k, (p, i, j) in enumerate(zip(params, self._param_sizes, self._param_cumsizes)):
+                if sr:                   # formed once in fp32, narrowed once: the chain of psgd_uvd_param_update_multi_sr
+                    param_update_stochastic_(p, pre_grad[j - i:j], vs[k] if undo else None, lr, decay, sr_seed, sr_index0 + j - i)
+                    continue
                 delta = (lr * torch.reshape(pre_grad[j - i:j], p.shape)).to(p.dtype)
                 if undo:
                     delta = delta + vs[k]
