@@ -70,6 +70,8 @@ extern "C" {
  *     Kron(operands="bfloat16") (additive, new symbols only: still 7).
  *     psgd_uvd_param_update_multi_sr, psgd_multi_param_update_sr and psgd_multi_param_update_mixed_sr: stochastic rounding of the
  *     bf16 parameter update of class UVd and class Kron (additive, new symbols only: still 7).
+ *     psgd_multi_randn_f32: the counter-based probe vectors of class Kron(preconditioner_fit="whitening") (additive, a new symbol
+ *     only: still 7).
  * psgd_tf_amd/_lib.py refuses a library whose psgd_abi_version() differs from the one it was written for. */
 #define PSGD_ABI_VERSION 7
 
@@ -595,6 +597,20 @@ int psgd_multi_param_update_sr(const void *param_segs, const void *grad_segs, co
 int psgd_multi_param_update_mixed_sr(const void *param_segs, const void *grad_segs, const void *vs_segs, int k, const void *chunks,
                                      int64_t nchunks, int dtype, float lr, const double *sumsq, float max_norm, float tiny, float wd,
                                      uint64_t seed, int64_t index0, void *stream);
+
+/* The probe vectors of class Kron(preconditioner_fit="whitening"): k contiguous fp32 tensors filled with standard normal draws in
+ * ONE launch (psgd_multi_tail.hip).  Element i of segment s gets fl32(scale * z_g), g = index0 + out_segs[s].start + i: the
+ * element's index in the concatenation of the list (this entry point reads `start`, as the stochastic updates above do), and z_g
+ * depends on (seed, g) alone -- not on how the list is cut into tensors, where they start, the chunk table or the grid.
+ * Stream: K = the key of (seed, tensor id 17 = "probe vectors") built as for the rounding streams; pair j = g >> 1 takes one 64-bit
+ * hash h = mix64(K + 0x9E3779B97F4A7C15 * (j + 1)) (mix64: the splitmix64 finaliser); u1 = ((h >> 32) + 1) * 2^-32 in (0, 1],
+ * r = sqrt(-2 ln u1) <= 6.67, theta = 2 pi (h & 0xFFFFFFFF) 2^-32; even g takes r cos theta, odd g takes r sin theta.  fp32
+ * arithmetic with the full-precision logf / log1pf / sqrtf / sincospif (within a few fp32 ulps of the float64 evaluation,
+ * counter_randn in Python).  Every value written is finite for a scale of ordinary size: no Inf and no NaN whatever the seed.
+ * Argument checks before any HIP call: null tables, k < 1, nchunks < 0, index0 < 0 or a scale that is not finite are
+ * PSGD_ERR_BAD_ARG.  nchunks == 0 is PSGD_OK and writes nothing.  Nothing allocates or synchronises. */
+int psgd_multi_randn_f32(const void *out_segs, int k, const void *chunks, int64_t nchunks, uint64_t seed, int64_t index0, float scale,
+                         void *stream);
 
 /* Tuning knobs for experiments (not part of the stable ABI).
  * key 0: streaming policy (0 = automatic: non-temporal when U,V exceed the Infinity Cache,

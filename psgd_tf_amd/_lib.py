@@ -151,6 +151,7 @@ SIGNATURES = {
                                           ctypes.c_uint64, _i64, _strm]),
     "psgd_multi_param_update_mixed_sr": (_int, [_c_f32p, _c_f32p, _c_f32p, _int, _c_f32p, _i64, _int, _flt, _c_f32p, _flt, _flt, _flt,
                                                 ctypes.c_uint64, _i64, _strm]),
+    "psgd_multi_randn_f32": (_int, [_c_f32p, _int, _c_f32p, _i64, ctypes.c_uint64, _i64, _flt, _strm]),
     "psgd_splu_workspace_bytes": (_i64, [_i64, _int]),
     "psgd_splu_apply_f32": (_int, [_c_f32p] * 6 + [_i64, _int, _c_ws, _i64, _strm]),
     "psgd_splu_update_f32": (_int, [_c_f32p] * 10 + [_i64, _int, ctypes.c_float, ctypes.c_float, _c_ws, _i64, _strm]),

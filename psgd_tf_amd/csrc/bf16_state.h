@@ -3,7 +3,9 @@
 // tensor id and flat element index), the rounding-stream keys, the exact three-piece bf16 split of an fp32 value, and the
 // tile copies of an [N, r] row-major bf16 matrix with 16-byte loads and stores whatever the rank.
 // Tensor ids of the rounding streams: 0, 1, 2 = U, V, d of UVd; 8, 9, 10, 11 = L12, l3, U12, u3 of the sparse-LU state;
-// 16 = the bf16 PARAMETERS of class UVd / class Kron (param_rounding="stochastic": narrow_param below, the step-tail kernels).
+// 16 = the bf16 PARAMETERS of class UVd / class Kron (param_rounding="stochastic": narrow_param below, the step-tail kernels);
+// 17 = the PROBE VECTORS of class Kron(preconditioner_fit="whitening"): not a rounding stream but the standard normal draws of
+// psgd_multi_randn_f32 (psgd_multi_tail.hip), keyed the same way -- key64(seed, 17) and the element's flat index.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,7 +40,7 @@ inline Geo make_geo(int r) {
 
 struct SrKey { unsigned a, b; };
 
-inline uint64_t mix64(uint64_t z) {   // the splitmix64 finaliser
+__host__ __device__ inline uint64_t mix64(uint64_t z) {   // the splitmix64 finaliser
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);

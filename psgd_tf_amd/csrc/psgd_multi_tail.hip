@@ -24,6 +24,8 @@
 // the parameter table):
 //   psgd_multi_param_update_sr        the update formed once in fp32 and narrowed once, fp32 gradients
 //   psgd_multi_param_update_mixed_sr  the same with a mixed list as the gradients
+// and, for the probe vectors of class Kron(preconditioner_fit="whitening") (this one reads `start` of its table too):
+//   psgd_multi_randn_f32         out <- fl32(scale z), z standard normal, a counter-based draw keyed by (seed, flat element index)
 //
 // The tables are those of psgd_uvd_tail.hip: a SEGMENT is one tensor {pointer, start, count}, a CHUNK one piece of at most
 // PSGD_UVD_TAIL_CHUNK consecutive elements of one segment {segment index, offset}.  Here EVERY operand is a list: each has its own
@@ -1006,6 +1008,86 @@ __global__ __launch_bounds__(kT) void k_multi_param_update_sr(const Seg* __restr
   }
 }
 
+// ------------------------------------------------------------------------------------------- probe vectors: counter-based normals
+// psgd_multi_randn_f32: element i of the concatenation of the list (i = index0 + the segment's `start` + the offset inside it) gets
+// fl32(scale * z_i), z_i a function of (seed, i) alone.  Stream: K = key64(seed, tensor id 17) (bf16_state.h); pair j = i >> 1 takes
+// ONE 64-bit hash h = mix64(K + 0x9E3779B97F4A7C15 (j + 1)) -- the splitmix64 sequence started at K -- and Box-Muller on its words:
+//   hi = h >> 32:   u1 = (hi + 1) 2^-32, in (0, 1];   r = sqrt(-2 ln u1), in [0, 6.67]
+//   lo = h & M32:   theta = 2 pi lo 2^-32
+//   z_{2j} = fl32(r cos theta),   z_{2j+1} = fl32(r sin theta)         (parity of the GLOBAL index: a segment that starts on an odd
+//                                                                       index starts with the sine half of a pair)
+// Evaluated in fp32 with the full-precision logf / log1pf / sqrtf / sincospif, arranged so that no input rounding is amplified:
+// for u1 <= 1/2, ln u1 = logf(fl32(hi + 1) 2^-32) (a relative error of 2^-24 in u1 moves r by less than 1e-7); for u1 > 1/2,
+// ln u1 = log1pf(-w) with w = 1 - u1 = fl32(2^32 - 1 - hi) 2^-32 <= 1/2, which keeps r's RELATIVE accuracy down to r = 0 (logf of
+// a u1 rounded to 24 bits would not: near u1 = 1 it loses r altogether); theta enters as sincospif(x), x = int32(lo) 2^-31 in
+// [-1, 1), the same angle modulo 2 pi with |x| small where fl32(lo) would round.  FINITE BY CONSTRUCTION: u1 > 0, so ln u1 >= -32 ln 2
+// and r <= 6.67; u1 <= 1, so the radicand is >= 0 (never NaN); sin and cos are in [-1, 1]: no Inf and no NaN whatever the seed --
+// with a finite scale of ordinary size class Kron's guard does not judge these vectors, and relies on this.
+// The value of an element does not depend on the lane, the chunk, the grid, where a tensor starts or how the list is cut: every
+// path below calls the one randn_pair.  A lane that owns both halves of a pair hashes once.  Accesses: a scalar head to the 16-byte
+// boundary of the segment's piece, 4 floats per lane and store, a scalar tail.  The kernel only writes.
+__device__ __forceinline__ void randn_pair(uint64_t K, uint64_t j, float& zc, float& zs) {
+  const uint64_t h = psgd::bf16s::mix64(K + 0x9E3779B97F4A7C15ull * (j + 1ull));
+  const uint32_t hi = (uint32_t)(h >> 32), lo = (uint32_t)h;
+  float nl;                                                              // -ln u1 >= 0
+  if (hi < 0x80000000u)
+    nl = -logf((float)(hi + 1u) * 0x1p-32f);
+  else
+    nl = -log1pf(-((float)(~hi) * 0x1p-32f));
+  const float r = sqrtf(2.0f * nl);
+  float s, c;
+  sincospif((float)(int32_t)lo * 0x1p-31f, &s, &c);
+  zc = r * c;
+  zs = r * s;
+}
+
+__device__ __forceinline__ float randn_one(uint64_t K, uint64_t i, float scale) {
+  float zc, zs;
+  randn_pair(K, i >> 1, zc, zs);
+  return scale * ((i & 1ull) ? zs : zc);
+}
+
+__global__ __launch_bounds__(kT) void k_multi_randn(const Seg* __restrict__ segs, const Chunk* __restrict__ chunks, int64_t nchunks,
+                                                    int k, uint64_t K, unsigned long long index0, float scale) {
+  const int t = threadIdx.x;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const Chunk ch = chunks[c];
+    if ((uint64_t)ch.seg >= (uint64_t)k || ch.off < 0) continue;     // a table that does not belong to these segments moves nothing
+    const Seg sg = segs[ch.seg];
+    int64_t left = sg.count - ch.off;
+    left = left < kChunk ? left : kChunk;
+    if (left <= 0) continue;
+    const int n = (int)left;
+    float* out = reinterpret_cast<float*>(sg.ptr) + ch.off;
+    const uint64_t i0 = index0 + (uint64_t)(sg.start + ch.off);
+    const int head = head_of(out, n);
+    const int nvec = (n - head) / 4;
+    if (t < head) out[t] = randn_one(K, i0 + (unsigned)t, scale);
+    const bool odd = ((i0 + (unsigned)head) & 1ull) != 0;              // the same for every group of four of this piece
+#pragma unroll 2
+    for (int q = t; q < nvec; q += kT) {
+      const int i = head + q * 4;
+      const uint64_t j = (i0 + (unsigned)i) >> 1;
+      float c0, s0, c1, s1;
+      randn_pair(K, j, c0, s0);
+      randn_pair(K, j + 1, c1, s1);
+      f32x4 v;
+      if (!odd) {                       // two whole pairs
+        v[0] = c0; v[1] = s0; v[2] = c1; v[3] = s1;
+      } else {                          // the sine half of pair j, pair j + 1, the cosine half of pair j + 2
+        float c2, s2;
+        randn_pair(K, j + 2, c2, s2);
+        v[0] = s0; v[1] = c1; v[2] = s1; v[3] = c2;
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = scale * v[e];
+      *reinterpret_cast<f32x4*>(out + i) = v;
+    }
+    const int i = head + nvec * 4 + t;
+    if (i < n) out[i] = randn_one(K, i0 + (unsigned)i, scale);
+  }
+}
+
 static int grid_for(int64_t nchunks) { return (int)(nchunks < kMaxGrid ? nchunks : kMaxGrid); }
 
 // the two stochastic entry points: argument checks of psgd_multi_param_update_mixed (a gradient list is required: the perturbation
@@ -1298,6 +1380,17 @@ int psgd_multi_param_update_mixed_sr(const void* param_segs, const void* grad_se
                                      uint64_t seed, int64_t index0, void* stream) {
   return update_sr_entry<true>(param_segs, grad_segs, vs_segs, k, chunks, nchunks, dtype, lr, sumsq, max_norm, tiny, wd, seed, index0,
                                stream);
+}
+
+int psgd_multi_randn_f32(const void* out_segs, int k, const void* chunks, int64_t nchunks, uint64_t seed, int64_t index0, float scale,
+                         void* stream) {
+  if (!out_segs || !chunks || k < 1 || nchunks < 0 || index0 < 0) return PSGD_ERR_BAD_ARG;
+  if ((__builtin_bit_cast(uint32_t, scale) & 0x7F800000u) == 0x7F800000u) return PSGD_ERR_BAD_ARG;      // +-Inf, NaN
+  if (nchunks == 0) return PSGD_OK;
+  const uint64_t K = psgd::bf16s::key64(seed, 17u);                          // tensor id 17: the probe vectors (bf16_state.h)
+  hipLaunchKernelGGL(k_multi_randn, dim3(grid_for(nchunks)), dim3(kT), 0, (hipStream_t)stream, (const Seg*)out_segs,
+                     (const Chunk*)chunks, nchunks, k, K, (unsigned long long)index0, scale);
+  return launched();
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@ the arithmetic is that of mnist_with_lenet5.py:43-57, with the finite-difference
 
     multi_sumsq, multi_param_update, multi_diff_scale,
     multi_blend, multi_scale_check, multi_widen_check,
-    multi_narrow                                          thin wrappers of the list kernels (csrc/psgd_multi_tail.hip)
+    multi_narrow, multi_randn                             thin wrappers of the list kernels (csrc/psgd_multi_tail.hip)
     kron_layers, kron_operand_layers                      how the parameters become layers, and which run on bf16 operands
     kron_initial_factors                                  the initial factor pair of one layer
     Kron(...).step(closure)                               the optimizer
@@ -418,6 +418,28 @@ def multi_narrow(srcs, dsts, *, plan=None):
     return dsts
 
 
+def multi_randn(outs, seed, index0=0, scale=1.0, *, plan=None):
+    """Standard normal draws into all tensors of a list in ONE launch (psgd_multi_randn_f32): element j of the concatenation of outs
+    (contiguous float32 tensors on one HIP device, empty ones allowed) becomes float32(scale) * z_i, i = index0 + j, and z_i is a
+    function of (seed, i) alone -- a counter hash and Box-Muller on pairs, the stream psgd.counter_randn restates in float64; the
+    two agree to a few float32 ulps (profiles/kron_whitening.txt).  The draws do not depend on how the list is cut into tensors,
+    on where the tensors start, on the launch shape or on any torch generator, and every value is finite.  seed: any integer (its
+    low 64 bits); index0 >= 0; scale finite.  Returns outs."""
+    what = "multi_randn"
+    if int(index0) != index0 or int(index0) < 0 or int(index0) >= 2 ** 63:
+        raise ValueError("%s: index0 must be an integer in [0, 2^63), got %r" % (what, index0))
+    scale = float(np.float32(scale))
+    if not math.isfinite(scale):
+        raise ValueError("%s: scale must be a finite float32 value, got %r" % (what, scale))
+    (outs,), plan = _lists(what, ("outs", outs), plan=plan)
+    if not plan.nchunks:
+        return outs
+    rc = _lib.load().psgd_multi_randn_f32(plan.table("randn", outs, what), len(outs), plan.chunks.data_ptr(), plan.nchunks,
+                                          int(seed) & (2 ** 64 - 1), int(index0), scale, _psgd._stream_ptr(plan.device))
+    _lib.check(rc, "psgd_multi_randn_f32")
+    return outs
+
+
 # --------------------------------------------------------------------------- vector layers
 def _vec_lists(what, qls, first, *others, plan=None):
     """the operand lists of a vector-layer kernel: `first` and `others` as _lists checks them, every tensor of at least 2 elements,
@@ -696,6 +718,34 @@ def _encode_features(sd, momentum, weight_decay, buffers=None, momentum_step=0, 
     return sd
 
 
+_PRECONDITIONER_FITS = ("hessian", "whitening")
+
+
+def _preconditioner_fit(preconditioner_fit):
+    """the preconditioner_fit argument of the constructor, judged before anything touches a device: True for "whitening" """
+    if preconditioner_fit not in _PRECONDITIONER_FITS:
+        raise ValueError("Kron: preconditioner_fit must be 'hessian' or 'whitening', got %r" % (preconditioner_fit,))
+    return preconditioner_fit == "whitening"
+
+
+def _probe_encode(sd, whitening, seed0, step):
+    """the checkpoint keys of the probe stream, added to sd when the optimizer fits by gradient whitening; returns sd"""
+    if whitening:
+        sd["probe_seed0"], sd["probe_step"] = int(seed0), int(step)
+    return sd
+
+
+def _probe_decode(sd, whitening, seed0):
+    """(seed0, step) after loading sd into an optimizer whose own probe seed is seed0: the dict's pair where it has one; the
+    optimizer's seed with the counter at 0 where it has none (a dict of a hessian-fit optimizer); a hessian-fit optimizer ignores
+    the keys and gets (seed0, 0)"""
+    if not whitening or "probe_seed0" not in sd:
+        return seed0, 0
+    if "probe_step" not in sd:
+        raise ValueError("Kron.load_state_dict: the state dict has 'probe_seed0' but no 'probe_step'")
+    return int(sd["probe_seed0"]), int(sd["probe_step"])
+
+
 def _decode_features(sd, shapes):
     """the optional keys of _encode_features, checked: (momentum buffers or None, momentum_step).  A dict from before them has
     none and is valid."""
@@ -793,6 +843,23 @@ class Kron:
     parameters (a skipped step does not advance it).  The perturbation of step 3 and its undo on a skipped step stay
     round-to-nearest.  state_dict() carries param_round_seed0 / param_round_step; param_rounding itself is a constructor choice.
 
+    preconditioner_fit="whitening" (keyword-only, "hessian" by default: nothing changes, no new entry point is called; any other
+    value is a ValueError before a device is touched) fits the factors to the GRADIENTS instead of to Hessian-vector products:
+    the update rule of step 4 is fed the pair (dX, dG) = (v, g), v ~ N(0, I) drawn fresh on every updating step and g the raw
+    float32 gradient of this step (unscaled, widened; never the momentum buffer).  The criterion E[dG' P dG + dX' P^-1 dX] is then
+    minimised by P = Q'Q = (E[g g'])^(-1/2): the preconditioner whitens the gradient (the gradient-whitening fit of the PSGD
+    papers).  A step needs ONE ordinary backward pass: no create_graph, no second closure call, no perturbation of the
+    parameters -- so closures whose backward cannot be differentiated again (fused attention kernels, custom Functions marked
+    once_differentiable) train, at about half the autograd cost.  exact_hessian_vector_product is ignored on this route (nothing
+    is rejected).  The probe vectors are float32 tensors in the parameters' shapes, made once, and filled by ONE multi_randn
+    launch per updating step on BOTH step tails (there is no torch.randn on this route): the stream of updating step k is keyed
+    by uvd_step_rounding_seed(probe_seed0, k) and the element's index in the flat parameter order, whatever `generator` is;
+    probe_seed0 = probe_seed, or a draw from the generator behind the coin (after the draw of param_rounding_seed where that
+    happens); k = probe_step counts the steps that drew a probe.  The probe is finite by construction and is not judged by the
+    guard; a skipped step returns before it is drawn and leaves probe_step alone.  state_dict() carries probe_seed0 / probe_step;
+    preconditioner_fit itself is a constructor choice like step_tail.  The whitened gradient has roughly unit scale per element,
+    as Adam's update has: lr_params and grad_clip_max_norm tuned for the Hessian fit do NOT carry over.
+
     Out of scope: mixed dtypes, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale),
     float16 stochastic rounding."""
 
@@ -801,9 +868,12 @@ class Kron:
                  exact_hessian_vector_product=True, *, layer_batch=True, step_tail="torch", generator=None,
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
                  any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM,
-                 param_rounding="nearest", param_rounding_seed=None):
+                 param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None):
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
+        self._whiten = _preconditioner_fit(preconditioner_fit)
+        self.preconditioner_fit = preconditioner_fit
+        self._probe_seed0, self._probe_step, self._probe, self._probe_plan = None, 0, None, None
         self._operands, self._operand_min_dim = _operands_dtype(operands), _operand_min_dim(operand_min_dim)
         if vector_route not in ("list", "layer"):
             raise ValueError("Kron: vector_route must be 'list' or 'layer', got %r" % (vector_route,))
@@ -900,6 +970,12 @@ class Kron:
             self._param_starts = [0]
             for p in params[:-1]:
                 self._param_starts.append(self._param_starts[-1] + int(p.numel()))
+        if self._whiten:
+            if probe_seed is not None:
+                self._probe_seed0 = int(probe_seed) & (2 ** 64 - 1)
+            else:                    # drawn as param_rounding_seed is, and after it
+                gen = self._coin_generator()
+                self._probe_seed0 = int(torch.randint(0, 2 ** 62, (), generator=gen, device=gen.device).item())
         self._tail = None
         if step_tail == "fused":
             self._tail = MultiTailPlan([int(p.numel()) for p in params], dev)
@@ -916,6 +992,11 @@ class Kron:
                 self._op_plan = MultiTailPlan([int(params[i].numel()) for i in self._ops], dev)
                 self._op_bufs = [[torch.empty(self._layer_shapes[i], dtype=torch.bfloat16, device=dev) for i in self._ops]
                                  for _ in range(3)]
+        if self._whiten:
+            # the probe vectors of the whitening fit, fp32 whatever the parameters' dtype: written whole by the one multi_randn
+            # launch of an updating step before anything reads them; the torch tail has no list plan of its own, so it gets one
+            self._probe = [torch.empty_like(p, dtype=_f32, requires_grad=False) for p in params]
+            self._probe_plan = self._tail if self._tail is not None else MultiTailPlan([int(p.numel()) for p in params], dev)
 
     # ------------------------------------------------------------------------------------------------- state
     @property
@@ -928,6 +1009,16 @@ class Kron:
         """the indices (parameter order) of the layers that run on the bf16-operand kernels: kron_operand_layers of this optimizer"""
         return list(self._ops)
 
+    @property
+    def probe_seed0(self):
+        """the construction seed of the probe stream (None with preconditioner_fit="hessian")"""
+        return self._probe_seed0
+
+    @property
+    def probe_step(self):
+        """the number of steps that drew a probe so far: the k of uvd_step_rounding_seed(probe_seed0, k) of the next draw"""
+        return self._probe_step
+
     def _coin_generator(self):
         return self._generator if self._generator is not None else _psgd._branch_rng
 
@@ -938,13 +1029,16 @@ class Kron:
         caller's, as in class UVd).  'hyper' also holds momentum and weight_decay; with momentum > 0 the dict gains
         momentum_buffers (CPU clones) and momentum_step, with nonfinite="skip" it gains nonfinite, skipped_steps, loss_scale (the
         current one; None without loss scaling) and loss_scale_good_steps, with param_rounding="stochastic" param_round_seed0 and
-        param_round_step (param_rounding itself is a constructor choice and is not saved)."""
+        param_round_step (param_rounding itself is a constructor choice and is not saved), with preconditioner_fit="whitening"
+        probe_seed0 and probe_step (preconditioner_fit itself is a constructor choice too).  The 'rng' entry keeps its meaning on
+        every route: the coin comes from that generator; the probe of the whitening fit does not."""
         sd = _encode_state(self._Qs, self._formats, self._shapes, {k: getattr(self, k) for k in _HYPER_KEYS},
                            self._coin_generator().get_state())
         mom = float(self.momentum)
         sd = _encode_features(sd, mom, float(self.weight_decay), self._momentum_buffers() if mom > 0.0 else None, self._m_step,
                               self._guard, self.skipped_steps, self.loss_scale.value, self._good_steps)
-        return _psgd._param_rounding_encode(sd, self._param_sr, self._param_round_seed0, self._param_round_step)
+        sd = _psgd._param_rounding_encode(sd, self._param_sr, self._param_round_seed0, self._param_round_step)
+        return _probe_encode(sd, self._whiten, self._probe_seed0, self._probe_step)
 
     def load_state_dict(self, sd):
         """Restore what state_dict() saved.  The factors become NEW device tensors (as after an update), the hyper-parameters are
@@ -954,10 +1048,13 @@ class Kron:
         and restarts its warm-up.  A guarded optimizer restores skipped_steps, loss_scale_good_steps and, when both sides scale
         the loss, loss_scale where the dict has them and starts them fresh where it has not; an unguarded one ignores them.
         param_rounding="stochastic": param_round_seed0 / param_round_step are restored where the dict has them; a dict without them
-        leaves this object's seed and sets the counter to 0; a nearest optimizer ignores them."""
+        leaves this object's seed and sets the counter to 0; a nearest optimizer ignores them.
+        preconditioner_fit="whitening": probe_seed0 / probe_step likewise -- restored where the dict has them, this object's seed
+        and a counter of 0 where it has not (a dict of a hessian-fit optimizer); a hessian-fit optimizer ignores them."""
         factors, hyper, rng = _decode_state(sd, self._formats, self._shapes, self._layer_shapes)
         bufs, m_step = _decode_features(sd, self._shapes)
         sr_state = _psgd._param_rounding_decode("Kron.load_state_dict", sd, self._param_sr, self._param_round_seed0)
+        probe_state = _probe_decode(sd, self._whiten, self._probe_seed0)
         try:
             self._coin_generator().set_state(rng)
         except (RuntimeError, TypeError) as e:
@@ -970,6 +1067,7 @@ class Kron:
         self._Qs = [[q.to(self._device, copy=True) for q in pair] for pair in factors]
         self._m_step = m_step
         self._param_round_seed0, self._param_round_step = sr_state
+        self._probe_seed0, self._probe_step = probe_state
         with torch.no_grad():
             if bufs is not None:
                 for m, b in zip(self._momentum_buffers(), bufs):
@@ -1272,7 +1370,19 @@ class Kron:
         psgd_multi_param_update_mixed, which read a bf16 preconditioned gradient as float(pg): S adds fl32(float(pg) float(pg)) in
         fp64 and delta = T(fl32(lr_eff float(pg))), everything after that unchanged.  Torch tail: x.to(torch.bfloat16) and
         pg.float() per tensor, the definition the kernels match.  Inside layer_batch blocks the operand layers run at once, as
-        outside a block; the class issues them before the block so that the queue of the small layers stays whole."""
+        outside a block; the class issues them before the block so that the queue of the small layers stays whole.
+
+        preconditioner_fit="whitening" (nothing of this runs with "hessian").  Steps 2 and 3 are replaced: the closure runs ONCE,
+        grads = autograd.grad(scaled(loss), params) without create_graph, and the parameters are not perturbed (nothing to undo in
+        step 7); exact_hessian_vector_product is not read.  The widening / scale / guard pass is that of a step that leaves the
+        factors alone: it sees the gradients only (inv is applied once), the probe is not judged because it is finite by
+        construction, and a skipped step returns before the probe is drawn: probe_step, factors, parameters, momentum buffers
+        and the warm-up counter keep their bits, and the next step draws the stream the skipped one would have drawn.  When the
+        coin says update: ONE multi_randn launch (seed uvd_step_rounding_seed(probe_seed0, probe_step), index0 = 0, scale = 1)
+        fills the float32 probe buffers on either tail, probe_step advances, and step 4 runs with dX = the probe, dG = the float32
+        gradients of this step -- raw, unscaled, widened; not the momentum buffer.  From step 4 on nothing differs: operand
+        layers narrow dX / dG by multi_narrow, vector layers of the list route go to multi_vec_precond_update, then the blend,
+        step 5, the clip, weight decay and param_rounding.  Nothing on this route differs between the tails before step 6."""
         params = self._params
         update_Q = self._coin()
         exact = bool(self.exact_hessian_vector_product)
@@ -1283,7 +1393,27 @@ class Kron:
         inv = 1.0 / S                                           # exact: S is a power of two
         scaled = (lambda loss: loss) if S == 1.0 else (lambda loss: loss * S)
         undo = None
-        if update_Q and exact:
+        if self._whiten:
+            with torch.enable_grad():
+                closure_returns = closure()
+                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
+            if half or guard:
+                with torch.no_grad():
+                    if half:
+                        grads, _, _, bad = self._widen(grads, None, None, inv)
+                    else:
+                        grads, _, bad = self._judge(grads, None, None, inv)
+                if guard:
+                    self._guard_outcome(bad)
+                if bad:                                     # before the probe is drawn: probe_step does not move
+                    return closure_returns
+            if update_Q:
+                with torch.no_grad():
+                    multi_randn(self._probe, _psgd.uvd_step_rounding_seed(self._probe_seed0, self._probe_step),
+                                plan=self._probe_plan)
+                self._probe_step += 1
+                dXs, dGs = self._probe, list(grads)
+        elif update_Q and exact:
             with torch.enable_grad():
                 closure_returns = closure()
                 grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params, create_graph=True)

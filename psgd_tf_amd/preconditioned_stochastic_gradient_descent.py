@@ -291,6 +291,43 @@ def _param_rounding_decode(name, sd, stochastic, seed0):
     return int(sd["param_round_seed0"]), int(sd["param_round_step"])
 
 
+# --------------------------------------------------------------------------- counter-based probe vectors
+# The draws of psgd_multi_randn_f32 (class Kron(preconditioner_fit="whitening"), kron_optimizer.multi_randn) restated in numpy: the
+# hash in integer arithmetic, Box-Muller in float64.  The kernel evaluates the same expressions in float32, so the two agree to a
+# few float32 ulps, not bit for bit (profiles/kron_whitening.txt has the measured distance).
+_PROBE_TENSOR_ID = 17                                # the stream "probe vectors" (bf16_state.h)
+_GOLDEN64 = 0x9E3779B97F4A7C15
+
+
+def counter_randn(seed, index0, n, scale=1.0):
+    """The n float32 values psgd_multi_randn_f32 defines for the flat indices index0 .. index0 + n - 1 under `seed`, as a numpy
+    array, evaluated in float64 and rounded to float32 once: element i is float32(scale) * float32(z_i) with, for the pair
+    j = i >> 1 and K = the 64-bit key of (seed, tensor id 17),
+        h = mix64(K + 0x9E3779B97F4A7C15 * (j + 1));  u1 = ((h >> 32) + 1) * 2^-32;  theta = 2 pi (h & 0xFFFFFFFF) * 2^-32
+        z_{2j} = sqrt(-2 ln u1) cos(theta),  z_{2j+1} = sqrt(-2 ln u1) sin(theta).
+    The draw of an element depends on (seed, i) alone: counter_randn(s, i0, n)[a:b] == counter_randn(s, i0 + a, b - a).  The
+    per-step seed of class Kron is uvd_step_rounding_seed(probe_seed0, probe_step)."""
+    import numpy as np
+    index0, n = int(index0), int(n)
+    if index0 < 0 or n < 0:
+        raise ValueError("counter_randn: index0 and n must be >= 0, got %r and %r" % (index0, n))
+    if not math.isfinite(float(scale)):
+        raise ValueError("counter_randn: scale must be finite, got %r" % (scale,))
+    a, b = rounding_stream_key(seed, _PROBE_TENSOR_ID)
+    K = a | (b << 32)
+    j0, j1 = index0 >> 1, (index0 + n + 1) >> 1                       # the pairs that cover the range
+    # Python integers in an object array: _mix64 itself, element by element, with no width to overflow
+    j = np.arange(j1 - j0, dtype=np.int64).astype(object) + j0
+    h = _mix64(K + _GOLDEN64 * (j + 1))
+    hi = (h >> 32).astype(np.float64)
+    lo = (h & _M32).astype(np.float64)
+    r = np.sqrt(-2.0 * np.log((hi + 1.0) * 2.0 ** -32))
+    theta = (2.0 * np.pi) * (lo * 2.0 ** -32)
+    z = np.stack([r * np.cos(theta), r * np.sin(theta)], axis=1).reshape(-1)
+    z = z[index0 - 2 * j0: index0 - 2 * j0 + n].astype(np.float32)
+    return np.float32(scale) * z
+
+
 _UVD_TENSOR_IDS = {"U": 0, "V": 1, "d": 2}           # the tensor ids of psgd_uvd_bf16_rounding_key
 _NARROW_STAGING_BYTES = 64 << 20                     # UVd.load_state_dict: the fp32 staging buffer of an fp32 -> native bf16 load
 
@@ -1793,3 +1830,4 @@ from .kron_optimizer import Kron, multi_sumsq, multi_param_update, multi_diff_sc
 from .kron_optimizer import multi_blend, multi_scale_check, multi_widen_check  # noqa: E402,F401
 from .kron_optimizer import multi_vec_precond_update, multi_vec_precond_grad, kron_layers  # noqa: E402,F401
 from .kron_optimizer import multi_narrow, kron_operand_layers  # noqa: E402,F401
+from .kron_optimizer import multi_randn  # noqa: E402,F401

@@ -42,6 +42,17 @@ resolved, and the summary line says so.
                 kron_optimizer.py of another commit)
 
     python tools/kron_step_timing.py --operands [--parent-module FILE] [--out profiles/kron_class_operands.txt]
+
+--whitening compares the three fits of class Kron, fused tail, clipping on, everything else off, on the LeNet5 set, on one
+1024 x 4096 layer and on 200 vectors of length 1024 + one 1024 x 4096 layer with any_rank=True, two tables:
+
+    step     whole steps on the host clock, legs "exact" (exact_hessian_vector_product=True), "fd" (finite differences),
+             "whitening" (preconditioner_fit="whitening") and, with --parent-module, "parent" (as "exact", on the
+             kron_optimizer.py of another commit): whether the default path moved
+    probe    DEVICE time (events around a chunk of 20 rounds) of ONE multi_randn launch against the k torch.randn launches it
+             replaces, on the probe buffers of the same three parameter sets
+
+    python tools/kron_step_timing.py --whitening [--parent-module FILE] [--out profiles/kron_whitening.txt]
 """
 import argparse
 import os
@@ -232,8 +243,55 @@ def operands_main(a, dev):
             f.write(text)
 
 
+WHITENING_SETS = {"lenet5": (SETS["lenet5"], False), "1024x4096": (SETS["1024x4096"], False),
+                  "200x(1024,)+1024x4096": ([(1024,)] * 200 + [(1024, 4096)], True)}
+
+
+def whitening_leg(shapes, any_rank, dev, cls=None, **kw):
+    """an elementwise quadratic loss (any rank; its backward is cheap, so the legs differ by the passes they run, not by the model)"""
+    g = torch.Generator(device=dev).manual_seed(0)
+    H = [torch.exp(torch.empty(s, device=dev).uniform_(-1.0, 1.0, generator=g)) for s in shapes]
+    Ws = [torch.randn(s, device=dev, generator=g).requires_grad_(True) for s in shapes]
+    closure = lambda: sum(0.5 * torch.sum(h * W * W) for W, h in zip(Ws, H))
+    clip = 0.1 * sum(W.numel() for W in Ws) ** 0.5
+    if any_rank:
+        kw = dict(kw, any_rank=True)
+    opt = (cls or psgd.Kron)(Ws, "dense", lr_params=LR, lr_preconditioner=LR_Q, grad_clip_max_norm=clip, step_tail="fused", **kw)
+    return lambda: opt.step(closure)
+
+
+def whitening_main(a, dev):
+    lines = ["# tools/kron_step_timing.py --whitening --chunks %d --steps %d on %s" % (a.chunks, a.steps, torch.cuda.get_device_name(0)),
+             "# step: us per step on the host clock (closure + preconditioner + tail), fused tail, clipping on, median [min .. max] "
+             "over the chunks of %d steps; legs alternate chunk by chunk" % a.steps]
+    parent = parent_class(a.parent_module) if a.parent_module else None
+    for name, (shapes, any_rank) in WHITENING_SETS.items():
+        legs = {"exact": whitening_leg(shapes, any_rank, dev, exact_hessian_vector_product=True),
+                "fd": whitening_leg(shapes, any_rank, dev, exact_hessian_vector_product=False),
+                "whitening": whitening_leg(shapes, any_rank, dev, preconditioner_fit="whitening")}
+        pairs = [("exact", "whitening"), ("fd", "whitening")]
+        if parent is not None:
+            legs["parent"] = whitening_leg(shapes, any_rank, dev, parent, exact_hessian_vector_product=True)
+            pairs.append(("parent", "exact"))
+        report(lines, "step %s" % name, alternate(legs, a.chunks, a.steps, timed, 0.5), pairs)
+        del legs
+        torch.cuda.empty_cache()
+    lines.append("# probe: us of DEVICE time per round, ONE multi_randn launch over k float32 buffers against k torch.randn launches "
+                 "(out=) into the same buffers; median [min .. max] over the chunks of 20 rounds; legs alternate chunk by chunk")
+    for name, (shapes, _) in WHITENING_SETS.items():
+        bufs = [torch.empty(s, device=dev) for s in shapes]
+        legs = {"randn-k": lambda bufs=bufs: [torch.randn(b.shape, device=dev, out=b) for b in bufs],
+                "multi-1": lambda bufs=bufs: psgd.multi_randn(bufs, 12345)}
+        report(lines, "probe %s (k = %d)" % (name, len(bufs)), alternate(legs, a.chunks, 20, device_timed, 0.2), [("randn-k", "multi-1")])
+    text = "\n".join(lines) + "\n"
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--whitening", action="store_true")
     ap.add_argument("--operands", action="store_true")
     ap.add_argument("--chunks", type=int, default=9)
     ap.add_argument("--steps", type=int, default=50)
@@ -247,6 +305,8 @@ def main():
     dev = torch.device("cuda:0")
     if a.operands:
         return operands_main(a, dev)
+    if a.whitening:
+        return whitening_main(a, dev)
     lines = ["# tools/kron_step_timing.py %s--chunks %d --steps %d on %s"
              % ("--features " if a.features else "--dtype %s " % a.dtype if a.dtype else "", a.chunks, a.steps,
                 torch.cuda.get_device_name(0)),
