@@ -5,7 +5,8 @@ Contents (only what the hot path needs):
   _lib.py                                          ctypes binding / in-tree build
   preconditioned_stochastic_gradient_descent.py    host-side mirror of the reference module
   kron.py                                          Kronecker dispatch + formats
-  kron_optimizer.py                                class Kron and the multi-tensor kernels of its step tail
+  kron_optimizer.py                                class Kron
+  multi_tail.py                                    the multi-tensor (list) kernels of its step tail as functions
   sharded.py                                       row-sharded multi-GPU UVd (torch.distributed / RCCL)
 """
 from . import preconditioned_stochastic_gradient_descent as psgd  # noqa: F401

@@ -1,15 +1,15 @@
-"""class Kron: the per-layer Kronecker-product preconditioner as an optimizer, and the multi-tensor kernels of its step tail.
+"""class Kron: the per-layer Kronecker-product preconditioner as an optimizer.
 
 The reference has no such class: its Kron demos hand-write the step (mnist_with_lenet5.py:43-57, repeated in
 lstm_with_xor_problem.py and the NMT demo).  The interface and the step(closure) contract are those of class UVd (psgd.py:630-764);
 the arithmetic is that of mnist_with_lenet5.py:43-57, with the finite-difference Hessian-vector product of psgd.py:716-727.
 
-    multi_sumsq, multi_param_update, multi_diff_scale,
-    multi_blend, multi_scale_check, multi_widen_check,
-    multi_narrow, multi_randn                             thin wrappers of the list kernels (csrc/psgd_multi_tail.hip)
     kron_layers, kron_operand_layers                      how the parameters become layers, and which run on bf16 operands
     kron_initial_factors                                  the initial factor pair of one layer
     Kron(...).step(closure)                               the optimizer
+
+The list kernels of its step tail (multi_sumsq, multi_param_update, ...) are the functions of multi_tail.py, imported here by name:
+the class calls them as globals of this module.  The switches it shares with class UVd are _StepFeatures of the UVd module.
 """
 import contextlib
 import math
@@ -17,17 +17,14 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
 from . import kron as _kron
 from . import preconditioned_stochastic_gradient_descent as _psgd
+from .multi_tail import MultiTailPlan, _lists, _f32, _TINY, _HALF, _MIXED, _DTYPE_NAMES  # noqa: F401
+from .multi_tail import multi_sumsq, multi_param_update, multi_diff_scale, multi_blend, multi_scale_check  # noqa: F401
+from .multi_tail import multi_widen_check, multi_narrow, multi_randn, multi_vec_precond_update, multi_vec_precond_grad  # noqa: F401
 
-_f32 = torch.float32
-_TINY = float(np.finfo(np.float32).tiny)
 _DELTA = float(np.float32(np.sqrt(np.float32(np.finfo(np.float32).eps))))      # psgd.py:683 for fp32 parameters
 _FD_INV = float(np.float32(1.0) / np.float32(_DELTA))                           # the s of dG = (g' - g) s, dX = v s
-_HALF = (torch.bfloat16, torch.float16)
-_MIXED = (torch.float32, torch.bfloat16)            # the dtypes of a mixed list: a preconditioned gradient is one or the other
-_DTYPE_NAMES = {torch.float32: "float32", torch.bfloat16: "bfloat16", torch.float16: "float16"}
 
 
 def _dtype_constants(dtype):
@@ -38,453 +35,6 @@ def _dtype_constants(dtype):
         return _DELTA, _FD_INV, _TINY
     delta = torch.finfo(dtype).eps ** 0.5
     return delta, float(np.float32(1.0) / np.float32(delta)), torch.finfo(dtype).tiny
-
-
-# --------------------------------------------------------------------------- list kernels
-class MultiTailPlan(_psgd.UVdTailPlan):
-    """The chunk table, the segment tables (one per role), the device double of the clip norm and the workspace of its reduction for
-    lists of tensors of fixed sizes.  The tables hold pointers and element counts only, so one plan serves the fp32 lists and
-    the bfloat16 / float16 lists of the typed entry points alike.  Calls that share a plan must run on one stream."""
-
-    def __init__(self, sizes, device):
-        super().__init__(sizes, torch.float32, device)
-        self.ws = torch.empty(_lib.MULTI_SUMSQ_WS_BYTES, dtype=torch.uint8, device=self.device)
-        # the flag word of the guarded step (multi_scale_check) and the stamp last stored to it.  The word is zeroed ONCE, here: the
-        # kernel stores a stamp that this word has not seen before, so nothing ever clears it again
-        self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.stamp = 0
-
-    def table(self, role, tensors, what, dtype=_f32):
-        """device pointer of the segment table of `tensors` (contiguous tensors of `dtype` with the plan's sizes) in this role"""
-        if dtype == self.dtype:
-            return super().table(role, tensors, what)
-        if len(tensors) != len(self.sizes):
-            raise ValueError("%s: %d tensors, the plan has %d" % (what, len(tensors), len(self.sizes)))
-        for t, n in zip(tensors, self.sizes):
-            if t.dtype != dtype or t.device != self.device or t.numel() != n or not t.is_contiguous():
-                raise ValueError("%s: every tensor must be a contiguous %s tensor on %s with the plan's element count (%d), got %s %s "
-                                 "%s%s" % (what, dtype, self.device, n, t.dtype, t.device, tuple(t.shape),
-                                           "" if t.is_contiguous() else " strided"))
-        tab = self._tables.get(role)
-        if tab is None:
-            tab = self._tables[role] = _psgd._SegTable(self.starts, self.sizes, self.device)
-        return tab.refresh([t.data_ptr() for t in tensors])
-
-    def mixed_table(self, role, tensors, what):
-        """device pointer of the segment table of a MIXED list in this role: contiguous tensors with the plan's sizes, each float32
-        or bfloat16; the `start` field of a segment holds its PSGD_DTYPE_* code (include/psgd_hip.h)"""
-        if len(tensors) != len(self.sizes):
-            raise ValueError("%s: %d tensors, the plan has %d" % (what, len(tensors), len(self.sizes)))
-        for t, n in zip(tensors, self.sizes):
-            if t.dtype not in _MIXED or t.device != self.device or t.numel() != n or not t.is_contiguous():
-                raise ValueError("%s: every tensor must be a contiguous float32 or bfloat16 tensor on %s with the plan's element "
-                                 "count (%d), got %s %s %s%s" % (what, self.device, n, t.dtype, t.device, tuple(t.shape),
-                                                                 "" if t.is_contiguous() else " strided"))
-        codes = [_psgd._TAIL_DTYPES[t.dtype] for t in tensors]
-        tab = self._tables.get(role)
-        if tab is None:
-            tab = self._tables[role] = _psgd._SegTable(codes, self.sizes, self.device)
-            tab.codes = codes
-        elif tab.codes != codes:                               # another pattern of dtypes in this role: rewrite and upload again
-            if tab.uploaded is not None:
-                tab.uploaded.synchronize()
-            tab.rows[:, 1] = codes
-            tab.codes, tab.ptrs = codes, None
-        return tab.refresh([t.data_ptr() for t in tensors])
-
-    def next_stamp(self):
-        """1 .. 2^31 - 1, then 1 again"""
-        self.stamp = self.stamp % (2 ** 31 - 1) + 1
-        return self.stamp
-
-
-_multi_plans = {}
-
-
-def _check_list(what, name, tensors, sizes=None, device=None, dtype=_f32):
-    """one operand list of a list kernel: contiguous tensors of `dtype` (float32 unless the caller names another) on one HIP
-    device, sizes[i] elements at position i"""
-    tensors = list(tensors)
-    if sizes is not None and len(tensors) != len(sizes):
-        raise ValueError("%s: %s has %d tensors, the first list has %d" % (what, name, len(tensors), len(sizes)))
-    for i, t in enumerate(tensors):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s: %s[%d] is not a torch tensor (%r)" % (what, name, i, type(t)))
-        if t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):          # (a tuple: a mixed list)
-            raise TypeError("%s: %s[%d] must be %s, got %s" % (what, name, i, " or ".join(
-                _DTYPE_NAMES[d] for d in (dtype if isinstance(dtype, tuple) else (dtype,))), t.dtype))
-        if not t.is_cuda:
-            raise _lib.PsgdHipError("%s runs on the HIP device only (%s[%d] is on %s); no CPU fallback" % (what, name, i, t.device))
-        if device is None:
-            device = t.device
-        if t.device != device:
-            raise ValueError("%s: all tensors must be on one device, %s[%d] is on %s, not %s" % (what, name, i, t.device, device))
-        if not t.is_contiguous():
-            raise ValueError("%s: %s[%d] (shape %s) is not contiguous" % (what, name, i, tuple(t.shape)))
-        if sizes is not None and int(t.numel()) != sizes[i]:
-            raise ValueError("%s: %s[%d] has %d elements, position %d of the first list has %d"
-                             % (what, name, i, t.numel(), i, sizes[i]))
-    return tensors, device
-
-
-def _lists(what, first, *others, plan=None, dtypes=None):
-    """checks every list against the first one; returns (lists, plan).  dtypes: {list name: dtype} of the lists that are not fp32"""
-    dtypes = dtypes or {}
-    name0, t0 = first
-    t0, dev = _check_list(what, name0, t0, dtype=dtypes.get(name0, _f32))
-    if not t0:
-        raise ValueError("%s: empty tensor list" % what)
-    sizes = tuple(int(t.numel()) for t in t0)
-    out = [t0]
-    for name, ts in others:
-        out.append(None if ts is None else _check_list(what, name, ts, sizes, dev, dtypes.get(name, _f32))[0])
-    if plan is None:
-        key = (dev, sizes)
-        plan = _multi_plans.get(key)
-        if plan is None:
-            while len(_multi_plans) >= 16:
-                _multi_plans.pop(next(iter(_multi_plans)))
-            plan = _multi_plans[key] = MultiTailPlan(sizes, dev)
-    elif plan.sizes != sizes or plan.device != dev:
-        raise ValueError("%s: the plan is for sizes %r on %s, the tensors have %r on %s" % (what, plan.sizes, plan.device, sizes, dev))
-    return out, plan
-
-
-def _has_bf16(tensors):
-    """a list of gradients with a bfloat16 device tensor in it is a MIXED list (the preconditioned gradients of an optimizer with
-    bf16-operand layers); anything else takes the checks and the entry points of the fp32 lists"""
-    return any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 and t.is_cuda for t in tensors)
-
-
-def multi_sumsq(tensors, *, plan=None, out=None, ws=None):
-    """out[0] = sum of fl32(x * x) over every element of every tensor, in fp64 and in a fixed order (psgd_multi_sumsq_f32: two launches
-    whatever len(tensors), the same bits on every call).  tensors: contiguous fp32 tensors on one HIP device, empty ones allowed.
-    out: a float64 device tensor of one element (default: the plan's); ws: a uint8 device tensor of at least
-    _lib.MULTI_SUMSQ_WS_BYTES bytes (default: the plan's).  Returns out.
-    A MIXED list -- some tensors bfloat16, the others float32 -- goes to psgd_multi_sumsq_mixed: the squares are those of float(x),
-    the structure and the fixed order are the same; a list without a bfloat16 tensor calls psgd_multi_sumsq_f32 as before."""
-    tensors = list(tensors)
-    mixed = _has_bf16(tensors)
-    (tensors,), plan = _lists("multi_sumsq", ("tensors", tensors), plan=plan, dtypes={"tensors": _MIXED} if mixed else None)
-    out = plan.sumsq if out is None else out
-    ws = plan.ws if ws is None else ws
-    if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != plan.device or out.numel() < 1:
-        raise ValueError("multi_sumsq: out must be a float64 tensor of at least one element on %s" % (plan.device,))
-    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != plan.device or not ws.is_contiguous():
-        raise ValueError("multi_sumsq: ws must be a contiguous uint8 tensor on %s" % (plan.device,))
-    if not plan.nchunks:
-        out[:1].zero_()                                              # the kernel launches nothing: the sum of nothing is 0
-        return out
-    if mixed:
-        rc = _lib.load().psgd_multi_sumsq_mixed(plan.mixed_table("sumsq_mixed", tensors, "multi_sumsq"), len(tensors),
-                                                plan.chunks.data_ptr(), plan.nchunks, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                _psgd._stream_ptr(plan.device))
-        _lib.check(rc, "psgd_multi_sumsq_mixed")
-        return out
-    rc = _lib.load().psgd_multi_sumsq_f32(plan.table("sumsq", tensors, "multi_sumsq"), len(tensors), plan.chunks.data_ptr(),
-                                          plan.nchunks, out.data_ptr(), ws.data_ptr(), ws.numel(), _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_sumsq_f32")
-    return out
-
-
-def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None, tiny=None, *, plan=None, weight_decay=0.0,
-                       rounding="nearest", rounding_seed=None, index0=0):
-    """For all parameters in ONE launch (psgd_multi_param_update_f32), every operation rounded to float32 on its own:
-        p <- p - lr_eff * g                     vs None
-        p <- p - (lr_eff * g + v)               vs given (the undo of the finite-difference perturbation, psgd.py:761)
-        p <- p + v                              grads None (the perturbation itself, psgd.py:723; lr, sumsq are not used)
-    lr_eff = float32(lr) when sumsq is None; with sumsq (a float64 device tensor of one element, what multi_sumsq left) and max_norm,
-    lr_eff = float32(lr * min(max_norm / (sqrt(sumsq) + tiny), 1)) formed on the device in fp64: no host read; a NaN sumsq makes
-    every parameter NaN, as torch.minimum does.  tiny defaults to the smallest normal float32.
-    weight_decay (decoupled; psgd_multi_param_update_wd_f32): with c = float32(lr_eff * weight_decay), the subtracted term gains
-    float32(c * p) after the vs term; 0 (default) adds no rounding step and calls the entry point without decay.
-    The parameters are written through their pointers: autograd's version counters do not move.
-    Half precision: when params[0] is a bfloat16 or float16 tensor on the HIP device, params and vs have that type T, grads stay
-    float32, and the call goes to psgd_multi_param_update_t: delta = T(float32(lr_eff * g)), then T(delta + v), then
-    T(delta + T(float32(c * float(p)))), p <- T(p - delta); p <- T(p + v) without grads.  tiny then defaults to finfo(T).tiny.
-    (A half-precision tensor that is not on the device is refused as before: params must be float32.)
-    MIXED gradients: when some tensors of grads are bfloat16 device tensors and the others float32 (the preconditioned gradients
-    of bf16-operand layers), the call goes to psgd_multi_param_update_mixed, which reads every gradient as float(g) and rounds as
-    above for the parameters' dtype, float32 included.  A list without a bfloat16 tensor calls the entry points of before.
-    rounding="stochastic" (bfloat16 parameters, grads required; psgd_multi_param_update_sr, with mixed gradients
-    psgd_multi_param_update_mixed_sr): the update is formed once in float32 and narrowed once -- w = float(p),
-    d = fl32(lr_eff * float(g)), d = fl32(d + float(v)), d = fl32(d + fl32(c * w)), p <- SR(fl32(w - d)) -- with the stochastic
-    narrowing of stochastic_narrow_bf16 under rounding_seed (None: drawn from the module's branch generator) on the flat index
-    index0 + the element's place in the concatenation of params.  "nearest" (default): nothing changes, and rounding_seed / index0
-    must be left alone."""
-    what = "multi_param_update"
-    wd = float(weight_decay)
-    if not wd >= 0.0:
-        raise ValueError("%s: weight_decay must be >= 0, got %r" % (what, weight_decay))
-    if rounding not in _psgd._PARAM_ROUNDINGS:
-        raise ValueError("%s: rounding must be 'nearest' or 'stochastic', got %r" % (what, rounding))
-    sr = rounding == "stochastic"
-    if not sr and (rounding_seed is not None or index0 != 0):
-        raise ValueError("%s: rounding_seed and index0 apply to rounding='stochastic' only" % what)
-    if sr and (grads is None or int(index0) < 0):
-        raise ValueError("%s: rounding='stochastic' needs grads (the perturbation p + v rounds to nearest) and index0 >= 0" % what)
-    params = list(params)
-    T = _f32
-    if params and isinstance(params[0], torch.Tensor) and params[0].is_cuda and params[0].dtype in _HALF:
-        T = params[0].dtype
-    grads = None if grads is None else list(grads)
-    mixed = grads is not None and _has_bf16(grads)
-    dtypes = {"params": T, "vs": T}
-    if mixed:
-        dtypes["grads"] = _MIXED
-    (params, grads, vs), plan = _lists(what, ("params", params), ("grads", grads), ("vs", vs), plan=plan, dtypes=dtypes)
-    if grads is None and (vs is None or sumsq is not None or wd != 0.0):
-        raise ValueError("%s: grads=None adds vs to the parameters; it needs vs and takes no sumsq and no weight_decay" % what)
-    if (sumsq is None) != (max_norm is None):
-        raise ValueError("%s: sumsq and max_norm go together" % what)
-    if sumsq is not None and (not isinstance(sumsq, torch.Tensor) or sumsq.dtype != torch.float64 or sumsq.device != plan.device
-                              or sumsq.numel() < 1):
-        raise ValueError("%s: sumsq must be a float64 tensor of at least one element on %s" % (what, plan.device))
-    if sr and T != torch.bfloat16:
-        raise ValueError("%s: rounding='stochastic' needs bfloat16 parameters on the HIP device, got %s" % (what, params[0].dtype))
-    if not plan.nchunks:
-        return
-    if sr:
-        if rounding_seed is None:
-            rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=_psgd._branch_rng).item())
-        name = "psgd_multi_param_update_mixed_sr" if mixed else "psgd_multi_param_update_sr"
-        rc = getattr(_lib.load(), name)(
-            plan.table("params", params, what, T),
-            plan.mixed_table("grads_mixed", grads, what) if mixed else plan.table("grads", grads, what),
-            None if vs is None else plan.table("vs", vs, what, T), len(params), plan.chunks.data_ptr(), plan.nchunks,
-            _psgd._TAIL_DTYPES[T], float(lr), None if sumsq is None else sumsq.data_ptr(),
-            0.0 if max_norm is None else float(max_norm), float(_dtype_constants(T)[2] if tiny is None else tiny), wd,
-            int(rounding_seed) & (2 ** 64 - 1), int(index0), _psgd._stream_ptr(plan.device))
-        _lib.check(rc, name)
-        return
-    if mixed:
-        rc = _lib.load().psgd_multi_param_update_mixed(
-            plan.table("params", params, what, T), plan.mixed_table("grads_mixed", grads, what),
-            None if vs is None else plan.table("vs", vs, what, T), len(params), plan.chunks.data_ptr(), plan.nchunks,
-            _psgd._TAIL_DTYPES[T], float(lr), None if sumsq is None else sumsq.data_ptr(),
-            0.0 if max_norm is None else float(max_norm), float(_dtype_constants(T)[2] if tiny is None else tiny), wd,
-            _psgd._stream_ptr(plan.device))
-        _lib.check(rc, "psgd_multi_param_update_mixed")
-        return
-    tabs = (plan.table("params", params, what, T), None if grads is None else plan.table("grads", grads, what),
-            None if vs is None else plan.table("vs", vs, what, T), len(params), plan.chunks.data_ptr(), plan.nchunks)
-    tail = (float(lr), None if sumsq is None else sumsq.data_ptr(), 0.0 if max_norm is None else float(max_norm),
-            float(_dtype_constants(T)[2] if tiny is None else tiny))
-    if T != _f32:
-        rc = _lib.load().psgd_multi_param_update_t(*tabs, _psgd._TAIL_DTYPES[T], *tail, wd, _psgd._stream_ptr(plan.device))
-        _lib.check(rc, "psgd_multi_param_update_t")
-        return
-    args = tabs + tail
-    if wd == 0.0:
-        rc = _lib.load().psgd_multi_param_update_f32(*args, _psgd._stream_ptr(plan.device))
-        _lib.check(rc, "psgd_multi_param_update_f32")
-    else:
-        rc = _lib.load().psgd_multi_param_update_wd_f32(*args, wd, _psgd._stream_ptr(plan.device))
-        _lib.check(rc, "psgd_multi_param_update_wd_f32")
-
-
-def multi_diff_scale(a, b, h, v=None, x=None, s=1.0, *, plan=None):
-    """h <- (a - b) * s and, with v and x (both or neither), x <- v * s for all tensors of the lists in ONE launch
-    (psgd_multi_diff_scale_f32), the difference and each product rounded to float32 on its own: the finite-difference
-    dG = (g' - g) / delta, dX = v / delta of psgd.py:727, :734-736 with s = 1 / delta."""
-    what = "multi_diff_scale"
-    if (v is None) != (x is None):
-        raise ValueError("%s: v and x go together" % what)
-    (a, b, h, v, x), plan = _lists(what, ("a", a), ("b", b), ("h", h), ("v", v), ("x", x), plan=plan)
-    if not plan.nchunks:
-        return
-    rc = _lib.load().psgd_multi_diff_scale_f32(
-        plan.table("a", a, what), plan.table("b", b, what), plan.table("h", h, what),
-        None if v is None else plan.table("v", v, what), None if x is None else plan.table("x", x, what),
-        len(a), plan.chunks.data_ptr(), plan.nchunks, float(s), _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_diff_scale_f32")
-
-
-def multi_blend(ms, gs, beta, omb, *, plan=None):
-    """m <- beta * m + omb * g for all tensors of the lists in ONE launch (psgd_multi_blend_f32), both products and the sum rounded
-    to float32 on their own: the momentum of class Kron.  beta and omb are the pair of uvd_momentum_coefficients (omb = float32(1) -
-    beta, rounded once); beta == 0 does not read m: whatever it held, NaN included, is replaced by omb * g."""
-    what = "multi_blend"
-    beta, omb = float(np.float32(beta)), float(np.float32(omb))
-    if not 0.0 <= beta < 1.0:
-        raise ValueError("%s: beta must be in [0, 1), got %r" % (what, beta))
-    (ms, gs), plan = _lists(what, ("ms", ms), ("gs", gs), plan=plan)
-    if gs is None:
-        raise ValueError("%s: gs is required" % what)
-    if not plan.nchunks:
-        return
-    rc = _lib.load().psgd_multi_blend_f32(plan.table("m", ms, what), plan.table("g", gs, what), len(ms), plan.chunks.data_ptr(),
-                                          plan.nchunks, beta, omb, _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_blend_f32")
-
-
-def multi_scale_check(lists, scales, *, flag=None, stamp=None, plan=None):
-    """One to three lists of tensors in ONE launch (psgd_multi_scale_check_f32): every element x of list j becomes float32(x *
-    scales[j]) in place where scales[j] != 1 (a list with scale 1 is only read), and with flag and stamp (both or neither) stamp is
-    stored to flag[0], an int32 device word, when any of these products -- of a scaled list or not -- is +-Inf or NaN.  The caller
-    passes a stamp it has not used on this word before (1 .. 2^31 - 1; plan.next_stamp() for plan.flag) and reads flag[0] == stamp
-    after the launch; nothing zeroes the word.  Without a flag the call only rescales, and all scales equal to 1 is an error."""
-    what = "multi_scale_check"
-    lists, scales = list(lists), [float(np.float32(s)) for s in scales]
-    if not 1 <= len(lists) <= 3 or len(scales) != len(lists):
-        raise ValueError("%s: one to three lists and one scale for each, got %d lists and %d scales" % (what, len(lists), len(scales)))
-    if (flag is None) != (stamp is None):
-        raise ValueError("%s: flag and stamp go together (got flag=%s, stamp=%r)" % (what, "None" if flag is None else "given", stamp))
-    if flag is None and all(s == 1.0 for s in scales):
-        raise ValueError("%s: no flag and every scale is 1: nothing to do" % what)
-    lists, plan = _lists(what, *[("lists[%d]" % j, ts) for j, ts in enumerate(lists)], plan=plan)
-    if any(ts is None for ts in lists):
-        raise ValueError("%s: a list is None" % what)
-    word = None
-    if flag is not None:
-        word = _psgd._flag_word(what, flag, stamp, plan.device)
-        if not 1 <= int(stamp) <= 2 ** 31 - 1:
-            raise ValueError("%s: stamp must be in 1 .. 2^31 - 1, got %r" % (what, stamp))
-    if not plan.nchunks:
-        return
-    tabs = [plan.table("check%d" % j, ts, what) for j, ts in enumerate(lists)] + [None] * (3 - len(lists))
-    rc = _lib.load().psgd_multi_scale_check_f32(*tabs, *(scales + [1.0] * (3 - len(scales))), len(lists[0]), plan.chunks.data_ptr(),
-                                                plan.nchunks, word, 0 if stamp is None else int(stamp),
-                                                _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_scale_check_f32")
-
-
-def multi_widen_check(srcs, dsts, scales, *, flag=None, stamp=None, plan=None):
-    """One to three lists of bfloat16 or float16 tensors widened into as many lists of float32 tensors in ONE launch
-    (psgd_multi_widen_check): dsts[j][i] <- float32(float(srcs[j][i]) * scales[j]).  All source tensors have the dtype of
-    srcs[0][0]; every destination is written whole.  With flag and stamp (both or neither) stamp is stored to flag[0], an int32
-    device word, when any value written is +-Inf or NaN -- the flag of multi_scale_check: the caller passes a stamp it has not
-    used on this word before (1 .. 2^31 - 1; plan.next_stamp() for plan.flag) and reads flag[0] == stamp after the launch;
-    nothing zeroes the word.  Without a flag the call only widens."""
-    what = "multi_widen_check"
-    srcs, dsts, scales = list(srcs), list(dsts), [float(np.float32(s)) for s in scales]
-    if not 1 <= len(srcs) <= 3 or len(dsts) != len(srcs) or len(scales) != len(srcs):
-        raise ValueError("%s: one to three source lists, a destination list and a scale for each, got %d, %d and %d"
-                         % (what, len(srcs), len(dsts), len(scales)))
-    if (flag is None) != (stamp is None):
-        raise ValueError("%s: flag and stamp go together (got flag=%s, stamp=%r)" % (what, "None" if flag is None else "given", stamp))
-    srcs = [None if ts is None else list(ts) for ts in srcs]
-    if any(ts is None for ts in srcs) or any(ts is None for ts in dsts):
-        raise ValueError("%s: a list is None" % what)
-    first = srcs[0][0] if srcs[0] else None
-    T = first.dtype if isinstance(first, torch.Tensor) else None
-    if isinstance(first, torch.Tensor) and T not in _HALF:
-        raise TypeError("%s: srcs[0][0] must be bfloat16 or float16, got %s (float32 lists are scaled in place by multi_scale_check)"
-                        % (what, T))
-    names = ["srcs[%d]" % j for j in range(len(srcs))]
-    lists, plan = _lists(what, *(list(zip(names, srcs)) + [("dsts[%d]" % j, ts) for j, ts in enumerate(dsts)]), plan=plan,
-                         dtypes={n: T for n in names})
-    srcs, dsts = lists[:len(srcs)], lists[len(srcs):]
-    word = None
-    if flag is not None:
-        word = _psgd._flag_word(what, flag, stamp, plan.device)
-        if not 1 <= int(stamp) <= 2 ** 31 - 1:
-            raise ValueError("%s: stamp must be in 1 .. 2^31 - 1, got %r" % (what, stamp))
-    if not plan.nchunks:
-        return
-    pad = [None] * (3 - len(srcs))
-    rc = _lib.load().psgd_multi_widen_check(*([plan.table("widen_src%d" % j, ts, what, T) for j, ts in enumerate(srcs)] + pad),
-                                            *([plan.table("widen_dst%d" % j, ts, what) for j, ts in enumerate(dsts)] + pad),
-                                            *(scales + [1.0] * len(pad)), len(srcs[0]), plan.chunks.data_ptr(), plan.nchunks,
-                                            _psgd._TAIL_DTYPES[T], word, 0 if stamp is None else int(stamp),
-                                            _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_widen_check")
-
-
-def multi_narrow(srcs, dsts, *, plan=None):
-    """One to three lists of float32 tensors narrowed into as many lists of bfloat16 tensors in ONE launch (psgd_multi_narrow_bf16):
-    dsts[j][i] <- srcs[j][i].to(torch.bfloat16), bit for bit -- round to nearest even, NaN stays NaN, a finite value beyond the
-    bfloat16 range becomes +-Inf.  multi_widen_check in the other direction, without a scale and without a flag: every destination
-    is written whole and nothing is judged.  All tensors contiguous on one HIP device, dsts[j][i] with the element count of
-    srcs[j][i].  Returns dsts."""
-    what = "multi_narrow"
-    srcs, dsts = list(srcs), list(dsts)
-    if not 1 <= len(srcs) <= 3 or len(dsts) != len(srcs):
-        raise ValueError("%s: one to three source lists and a destination list for each, got %d and %d" % (what, len(srcs), len(dsts)))
-    if any(ts is None for ts in srcs) or any(ts is None for ts in dsts):
-        raise ValueError("%s: a list is None" % what)
-    names = ["dsts[%d]" % j for j in range(len(dsts))]
-    lists, plan = _lists(what, *([("srcs[%d]" % j, ts) for j, ts in enumerate(srcs)] + list(zip(names, dsts))), plan=plan,
-                         dtypes={n: torch.bfloat16 for n in names})
-    srcs, dsts = lists[:len(srcs)], lists[len(srcs):]
-    if not plan.nchunks:
-        return dsts
-    pad = [None] * (3 - len(srcs))
-    rc = _lib.load().psgd_multi_narrow_bf16(*([plan.table("narrow_src%d" % j, ts, what) for j, ts in enumerate(srcs)] + pad),
-                                            *([plan.table("narrow_dst%d" % j, ts, what, torch.bfloat16)
-                                               for j, ts in enumerate(dsts)] + pad),
-                                            len(srcs[0]), plan.chunks.data_ptr(), plan.nchunks, _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_narrow_bf16")
-    return dsts
-
-
-def multi_randn(outs, seed, index0=0, scale=1.0, *, plan=None):
-    """Standard normal draws into all tensors of a list in ONE launch (psgd_multi_randn_f32): element j of the concatenation of outs
-    (contiguous float32 tensors on one HIP device, empty ones allowed) becomes float32(scale) * z_i, i = index0 + j, and z_i is a
-    function of (seed, i) alone -- a counter hash and Box-Muller on pairs, the stream psgd.counter_randn restates in float64; the
-    two agree to a few float32 ulps (profiles/kron_whitening.txt).  The draws do not depend on how the list is cut into tensors,
-    on where the tensors start, on the launch shape or on any torch generator, and every value is finite.  seed: any integer (its
-    low 64 bits); index0 >= 0; scale finite.  Returns outs."""
-    what = "multi_randn"
-    if int(index0) != index0 or int(index0) < 0 or int(index0) >= 2 ** 63:
-        raise ValueError("%s: index0 must be an integer in [0, 2^63), got %r" % (what, index0))
-    scale = float(np.float32(scale))
-    if not math.isfinite(scale):
-        raise ValueError("%s: scale must be a finite float32 value, got %r" % (what, scale))
-    (outs,), plan = _lists(what, ("outs", outs), plan=plan)
-    if not plan.nchunks:
-        return outs
-    rc = _lib.load().psgd_multi_randn_f32(plan.table("randn", outs, what), len(outs), plan.chunks.data_ptr(), plan.nchunks,
-                                          int(seed) & (2 ** 64 - 1), int(index0), scale, _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_randn_f32")
-    return outs
-
-
-# --------------------------------------------------------------------------- vector layers
-def _vec_lists(what, qls, first, *others, plan=None):
-    """the operand lists of a vector-layer kernel: `first` and `others` as _lists checks them, every tensor of at least 2 elements,
-    and qls, one fp32 tensor of ONE element per vector.  Returns (qls, lists, plan, device pointer of the table of qls)."""
-    lists, plan = _lists(what, first, *others, plan=plan)
-    if any(ts is None for ts in lists):
-        raise ValueError("%s: a list is None" % what)
-    for i, n in enumerate(plan.sizes):
-        if n < 2:
-            raise ValueError("%s: %s[%d] has %d element%s; a vector layer has at least 2 (a scaling factor of length 1 is square, and "
-                             "the reference's dispatcher would run it as a dense one)" % (what, first[0], i, n, "" if n == 1 else "s"))
-    qls, _ = _check_list(what, "qls", qls, (1,) * len(plan.sizes), plan.device)
-    tab = plan._tables.get("vec_ql")
-    if tab is None:
-        tab = plan._tables["vec_ql"] = _psgd._SegTable(list(range(len(qls))), [1] * len(qls), plan.device)
-    return qls, lists, plan, tab.refresh([t.data_ptr() for t in qls])
-
-
-def multi_vec_precond_update(qls, qrs, dXs, dGs, step, tiny=None, *, plan=None):
-    """update_precond_kron on k vector layers in ONE launch (psgd_multi_vec_update_f32), IN PLACE.  Vector i of length n_i >= 2 is
-    the reference's layer of shape [1, n_i] in the (dense, scaling) format (psgd.py:276-307): qls[i] holds the 1 x 1 left factor,
-    qrs[i] the [1, n_i] scaling factor, dXs[i] and dGs[i] the pair (dx, dg), all contiguous fp32 tensors on one HIP device with these
-    element counts, of any shape.  fp32 in the reference's order -- the balance rho = sqrt(ql / max(qr)) is performed, not cancelled
-    -- with the two sums of squares accumulated in fp64 in a fixed order (the same bits on every call, whatever k and the vector's
-    place in the list) and NaN-propagating maxima.  tiny defaults to the smallest normal float32.  One workgroup per vector: a
-    vector of a million elements is correct but slow."""
-    what = "multi_vec_precond_update"
-    qls, (qrs, dXs, dGs), plan, ql_tab = _vec_lists(what, qls, ("qrs", qrs), ("dXs", dXs), ("dGs", dGs), plan=plan)
-    rc = _lib.load().psgd_multi_vec_update_f32(ql_tab, plan.table("vec_qr", qrs, what), plan.table("vec_dx", dXs, what),
-                                               plan.table("vec_dg", dGs, what), len(qrs), min(plan.sizes), float(step),
-                                               float(_TINY if tiny is None else tiny), _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_vec_update_f32")
-
-
-def multi_vec_precond_grad(qls, qrs, gs, outs, *, plan=None):
-    """precond_grad_kron on k vector layers in ONE launch (psgd_multi_vec_apply_f32): outs[i] <- ((ql ql) g) (qr qr), the M < N branch of
-    psgd.py:318-319 and :322 on the [1, n_i] layer, every product rounded to float32 on its own.  Lists as in
-    multi_vec_precond_update; outs may be gs itself (in place).  Returns outs."""
-    what = "multi_vec_precond_grad"
-    qls, (qrs, gs, outs), plan, ql_tab = _vec_lists(what, qls, ("qrs", qrs), ("gs", gs), ("outs", outs), plan=plan)
-    rc = _lib.load().psgd_multi_vec_apply_f32(ql_tab, plan.table("vec_qr", qrs, what), plan.table("vec_g", gs, what),
-                                              plan.table("vec_out", outs, what), len(qrs), min(plan.sizes),
-                                              _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_vec_apply_f32")
-    return outs
 
 
 # --------------------------------------------------------------------------- formats and initial factors
@@ -711,11 +261,7 @@ def _encode_features(sd, momentum, weight_decay, buffers=None, momentum_step=0, 
     if float(momentum) > 0.0:
         sd["momentum_buffers"] = [m.detach().to("cpu", copy=True).contiguous() for m in buffers]
         sd["momentum_step"] = int(momentum_step)
-    if guard:
-        sd["nonfinite"], sd["skipped_steps"] = "skip", int(skipped_steps)
-        sd["loss_scale"] = None if loss_scale is None else float(loss_scale)
-        sd["loss_scale_good_steps"] = int(good_steps)
-    return sd
+    return _psgd._guard_encode(sd, guard, skipped_steps, loss_scale, good_steps)
 
 
 _PRECONDITIONER_FITS = ("hessian", "whitening")
@@ -771,7 +317,7 @@ def _flatten(params_with_grad):
     return [params_with_grad]
 
 
-class Kron:
+class Kron(_psgd._StepFeatures):
     """Kronecker-product preconditioned SGD, one factor pair per rank-2 parameter: the train_step of mnist_with_lenet5.py:43-57 behind
     the interface of class UVd.
 
@@ -880,27 +426,7 @@ class Kron:
         any_rank = bool(any_rank)
         # momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval: the switches of class UVd with their meaning
         # there (see step()); all off by default, and checked before anything touches a device
-        if not 0.0 <= float(momentum) < 1.0:
-            raise ValueError("Kron: momentum must be in [0, 1), got %r" % (momentum,))
-        if not float(weight_decay) >= 0.0:
-            raise ValueError("Kron: weight_decay must be >= 0, got %r" % (weight_decay,))
-        if nonfinite not in ("propagate", "skip"):
-            raise ValueError("Kron: nonfinite must be 'propagate' or 'skip', got %r" % (nonfinite,))
-        self._guard = nonfinite == "skip"
-        if loss_scale is not None and not self._guard:
-            raise ValueError("Kron: loss_scale needs nonfinite='skip' (a scaled gradient that overflows must not reach the state)")
-        self._dynamic_scale = isinstance(loss_scale, str)
-        if self._dynamic_scale and loss_scale != "dynamic":
-            raise ValueError("Kron: loss_scale must be None, a power of two or 'dynamic', got %r" % (loss_scale,))
-        self.momentum = _psgd._Hyper(momentum)
-        self.weight_decay = _psgd._Hyper(weight_decay)
-        self.loss_scale = _psgd._Hyper(2.0 ** 16 if self._dynamic_scale else loss_scale)
-        self._loss_scale_value()
-        self.loss_scale_growth_interval = int(loss_scale_growth_interval)
-        if self.loss_scale_growth_interval < 1:
-            raise ValueError("Kron: loss_scale_growth_interval must be >= 1, got %r" % (loss_scale_growth_interval,))
-        self._m, self._m_step, self._good_steps = None, 0, 0
-        self.skipped_steps, self.last_step_skipped = 0, False
+        self._init_features(momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval)
         params = _flatten(params_with_grad)
         if not params:
             raise ValueError("Kron: no parameters")
@@ -961,21 +487,14 @@ class Kron:
         self.exact_hessian_vector_product = _psgd._Hyper(bool(exact_hessian_vector_product))
         self._layer_batch = bool(layer_batch)
         self._generator = generator
+        # the construction seeds, from the generator behind the coin: the parameters' first, then the probe's
         if self._param_sr:
-            if param_rounding_seed is not None:
-                self._param_round_seed0 = int(param_rounding_seed) & (2 ** 64 - 1)
-            else:                    # drawn from the generator behind the coin, as class UVd draws the seed of its native state
-                gen = self._coin_generator()
-                self._param_round_seed0 = int(torch.randint(0, 2 ** 62, (), generator=gen, device=gen.device).item())
+            self._param_round_seed0 = self._draw_seed(param_rounding_seed)
             self._param_starts = [0]
             for p in params[:-1]:
                 self._param_starts.append(self._param_starts[-1] + int(p.numel()))
         if self._whiten:
-            if probe_seed is not None:
-                self._probe_seed0 = int(probe_seed) & (2 ** 64 - 1)
-            else:                    # drawn as param_rounding_seed is, and after it
-                gen = self._coin_generator()
-                self._probe_seed0 = int(torch.randint(0, 2 ** 62, (), generator=gen, device=gen.device).item())
+            self._probe_seed0 = self._draw_seed(probe_seed)
         self._tail = None
         if step_tail == "fused":
             self._tail = MultiTailPlan([int(p.numel()) for p in params], dev)
@@ -1018,9 +537,6 @@ class Kron:
     def probe_step(self):
         """the number of steps that drew a probe so far: the k of uvd_step_rounding_seed(probe_seed0, k) of the next draw"""
         return self._probe_step
-
-    def _coin_generator(self):
-        return self._generator if self._generator is not None else _psgd._branch_rng
 
     def state_dict(self):
         """Everything a bit-faithful resume needs except the parameters (the caller's): the factors (CPU clones), the formats and
@@ -1075,32 +591,9 @@ class Kron:
             elif float(self.momentum) > 0.0:             # no buffer saved: a momentum optimizer starts its warm-up again
                 for m in self._momentum_buffers():
                     m.zero_()
-        if self._guard:                                  # a dict of an unguarded optimizer has none of these: the guard starts fresh
-            self.skipped_steps, self.last_step_skipped = int(sd.get("skipped_steps", 0)), False
-            self._good_steps = int(sd.get("loss_scale_good_steps", 0))
-            if sd.get("loss_scale") is not None and self.loss_scale.value is not None:
-                self.loss_scale.assign(float(sd["loss_scale"]))
-                self._loss_scale_value()
+        self._guard_decode(sd)
 
     # ------------------------------------------------------------------------------------------------- momentum, guard
-    def _loss_scale_value(self):
-        """the current loss scale S as a float (1.0 without loss scaling), checked: a power of two"""
-        S = self.loss_scale.value
-        if S is None:
-            return 1.0
-        S = float(S)
-        if not (S > 0.0 and math.isfinite(S) and math.frexp(S)[0] == 0.5):
-            raise ValueError("Kron: loss_scale must be a power of two (1 / loss_scale must be exact), got %r" % (self.loss_scale.value,))
-        return S
-
-    def _hyper_momentum(self):
-        mom, wd = float(self.momentum), float(self.weight_decay)
-        if not 0.0 <= mom < 1.0:
-            raise ValueError("Kron: momentum must be in [0, 1), got %r" % (mom,))
-        if not wd >= 0.0:
-            raise ValueError("Kron: weight_decay must be >= 0, got %r" % (wd,))
-        return mom, wd
-
     def _momentum_buffers(self):
         """one zero-initialised fp32 buffer per parameter, created on first use"""
         if self._m is None:
@@ -1182,19 +675,21 @@ class Kron:
             bad = not bool(ok.item())                                                           # ... and of the torch tail
         return grads, second, vs, bad
 
-    def _guard_outcome(self, skipped, undo_vs=None):
-        """book-keeping of a guarded step once its decision is known; a skipped finite-difference step takes the perturbation of
-        psgd.py:723 back, p <- fl32(p - v): the reference's own undo, within one rounding of the parameters before the step"""
-        if undo_vs is not None:
-            with torch.no_grad():
-                for p, v in zip(self._params, undo_vs):
-                    p.sub_(v)
-        self.last_step_skipped = bool(skipped)
-        self.skipped_steps += int(bool(skipped))
-        if self._dynamic_scale:
-            S, self._good_steps = _psgd.uvd_loss_scale_next(self._loss_scale_value(), self._good_steps, skipped,
-                                                            growth_interval=self.loss_scale_growth_interval)
-            self.loss_scale.assign(S)
+    def _screen(self, grads, second, vs, inv, undo=None):
+        """The one pass of a step over its inputs, BEFORE anything else reads them: _widen for bfloat16 / float16 parameters, else
+        _judge for a guarded step, then the guard's book-keeping (a skipped finite-difference step takes the perturbation `undo`
+        back).  Returns (grads, second, vs, bad); bad: the caller returns at once.  Neither half nor guarded: the inputs come
+        back untouched -- nothing runs, no host read."""
+        if not (self._half or self._guard):
+            return grads, second, vs, False
+        with torch.no_grad():
+            if self._half:
+                grads, second, vs, bad = self._widen(grads, second, vs, inv)
+            else:
+                grads, second, bad = self._judge(grads, second, vs, inv)
+        if self._guard:
+            self._guard_outcome(bad, undo if bad else None)
+        return grads, second, vs, bad
 
     def _blend(self, grads, mom):
         """the gradients that precond_grad_kron takes: with momentum the buffers after m <- fl32(fl32(beta_k m) + fl32((1 - beta_k) g))
@@ -1234,10 +729,6 @@ class Kron:
 
     def _block(self):
         return _kron.layer_batch() if self._layer_batch else contextlib.nullcontext()
-
-    @staticmethod
-    def _loss_of(closure_returns):
-        return closure_returns if isinstance(closure_returns, torch.Tensor) else closure_returns[0]
 
     def _as_layers(self, tensors):
         """parameter-shaped tensors in the (M, N) of their layers (views where the memory allows); nothing without any_rank"""
@@ -1387,54 +878,21 @@ class Kron:
         update_Q = self._coin()
         exact = bool(self.exact_hessian_vector_product)
         fused = self._tail is not None
-        mom, wd = self._hyper_momentum()
-        guard, half = self._guard, self._half
-        S = self._loss_scale_value() if guard else 1.0
-        inv = 1.0 / S                                           # exact: S is a power of two
-        scaled = (lambda loss: loss) if S == 1.0 else (lambda loss: loss * S)
-        undo = None
-        if self._whiten:
-            with torch.enable_grad():
-                closure_returns = closure()
-                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
-            if half or guard:
-                with torch.no_grad():
-                    if half:
-                        grads, _, _, bad = self._widen(grads, None, None, inv)
-                    else:
-                        grads, _, bad = self._judge(grads, None, None, inv)
-                if guard:
-                    self._guard_outcome(bad)
-                if bad:                                     # before the probe is drawn: probe_step does not move
-                    return closure_returns
-            if update_Q:
-                with torch.no_grad():
-                    multi_randn(self._probe, _psgd.uvd_step_rounding_seed(self._probe_seed0, self._probe_step),
-                                plan=self._probe_plan)
-                self._probe_step += 1
-                dXs, dGs = self._probe, list(grads)
-        elif update_Q and exact:
-            with torch.enable_grad():
-                closure_returns = closure()
+        mom, wd, S, inv, scaled = self._step_scales()
+        # how this step feeds step 4: None leaves the factors alone.  The branches differ in what they hand to _screen and in
+        # what becomes (dX, dG) after it; "whitening" and None take their gradients alike
+        route = None if not update_Q else "whitening" if self._whiten else "exact" if exact else "fd"
+        undo = second = vs = None
+        with torch.enable_grad():
+            closure_returns = closure()
+            if route == "exact":
                 grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params, create_graph=True)
                 vs = [self._randn(p) for p in params]
-                Hvs = torch.autograd.grad(grads, params, vs)
-            grads = [g.detach() for g in grads]
-            dXs, dGs = vs, [h.detach() for h in Hvs]
-            if half or guard:
-                with torch.no_grad():
-                    if half:
-                        grads, dGs, dXs, bad = self._widen(grads, dGs, vs, inv)
-                    else:
-                        grads, dGs, bad = self._judge(grads, dGs, vs, inv)
-                if guard:
-                    self._guard_outcome(bad)
-                if bad:
-                    return closure_returns
-        elif update_Q:
-            with torch.enable_grad():
-                closure_returns = closure()
+                second = [h.detach() for h in torch.autograd.grad(grads, params, vs)]                    # the Hvs
+                grads = [g.detach() for g in grads]
+            else:
                 grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
+        if route == "fd":
             undo = vs = [self._randn(p) * self._delta for p in params]          # in the parameters' dtype: T(randn_T * delta)
             with torch.no_grad():
                 if fused:
@@ -1443,39 +901,27 @@ class Kron:
                     for p, v in zip(params, vs):
                         p.add_(v)
             with torch.enable_grad():
-                perturbed = torch.autograd.grad(scaled(self._loss_of(closure())), params)
-            if half or guard:
-                with torch.no_grad():
-                    if half:                                # (vs stays the perturbation in T; the fp32 copy feeds dX)
-                        grads, perturbed, vs, bad = self._widen(grads, perturbed, vs, inv)
-                    else:
-                        grads, perturbed, bad = self._judge(grads, perturbed, vs, inv)
-                if guard:
-                    self._guard_outcome(bad, undo if bad else None)
-                if bad:
-                    return closure_returns
+                second = torch.autograd.grad(scaled(self._loss_of(closure())), params)                   # the perturbed gradients
+        # (after a half-precision widening undo stays the perturbation in T; the fp32 copy in vs feeds dX)
+        grads, second, vs, bad = self._screen(grads, second, vs, inv, undo)
+        if bad:                                                 # before a probe is drawn: probe_step does not move
+            return closure_returns
+        if route == "whitening":
+            with torch.no_grad():
+                multi_randn(self._probe, _psgd.uvd_step_rounding_seed(self._probe_seed0, self._probe_step), plan=self._probe_plan)
+            self._probe_step += 1
+            dXs, dGs = self._probe, list(grads)
+        elif route == "exact":
+            dXs, dGs = vs, second
+        elif route == "fd":
             with torch.no_grad():
                 if fused:
                     dXs, dGs = self._fd_x, self._fd_h
-                    multi_diff_scale([g.contiguous() for g in perturbed], [g.contiguous() for g in grads], dGs, vs, dXs,
+                    multi_diff_scale([g.contiguous() for g in second], [g.contiguous() for g in grads], dGs, vs, dXs,
                                      self._fd_inv, plan=self._tail)
                 else:
-                    dGs = [(pg - g) * self._fd_inv for pg, g in zip(perturbed, grads)]
+                    dGs = [(pg - g) * self._fd_inv for pg, g in zip(second, grads)]
                     dXs = [v * self._fd_inv for v in vs]
-        else:
-            with torch.enable_grad():
-                closure_returns = closure()
-                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
-            if half or guard:
-                with torch.no_grad():
-                    if half:
-                        grads, _, _, bad = self._widen(grads, None, None, inv)
-                    else:
-                        grads, _, bad = self._judge(grads, None, None, inv)
-                if guard:
-                    self._guard_outcome(bad)
-                if bad:
-                    return closure_returns
         with torch.no_grad():
             if update_Q:
                 self._update_factors(dXs, dGs, float(self.lr_preconditioner))
@@ -1484,10 +930,8 @@ class Kron:
             pre_grads = self._precondition(grads)
             lr, max_norm = float(self.lr_params), float(self.grad_clip_max_norm)
             clip = not math.isinf(max_norm)
-            sr = self._param_sr
-            if sr:                                          # this step writes the parameters: the seed of its rounding stream
-                sr_seed = _psgd.uvd_step_rounding_seed(self._param_round_seed0, self._param_round_step)
-                self._param_round_step += 1
+            sr = self._param_sr                             # this step writes the parameters: the seed of its rounding stream
+            sr_seed = self._next_param_round_seed() if sr else None
             if fused:
                 pre_grads = [g.contiguous() for g in pre_grads]          # (the mirrored formats return transposed views)
                 sumsq = multi_sumsq(pre_grads, plan=self._tail) if clip else None
@@ -1510,17 +954,9 @@ class Kron:
             decay = None
             if wd != 0.0:                                   # c = fl32(lr_eff * wd), as the kernel forms it
                 decay = lr * torch.tensor(wd, dtype=_f32, device=self._device) if clip else float(np.float32(lr) * np.float32(wd))
-            T = self._dtype                                 # one torch op per rounding; for float32 .to(T) and .float() do nothing
             for k, (p, g) in enumerate(zip(params, pre_grads)):
                 if self._reshape:
                     g = g.reshape(p.shape)
-                if sr:                                      # formed once in fp32, narrowed once: psgd_multi_param_update_sr
-                    _psgd.param_update_stochastic_(p, g, None if undo is None else undo[k], lr, decay, sr_seed, self._param_starts[k])
-                    continue
-                delta = (g * lr).to(T)
-                if undo is not None:
-                    delta = delta + undo[k]
-                if decay is not None:
-                    delta = delta + (p.float() * decay).to(T)
-                p.sub_(delta)
+                _psgd._torch_param_update_(p, g, None if undo is None else undo[k], lr, decay, sr_seed,
+                                           self._param_starts[k] if sr else 0)
         return closure_returns

@@ -292,7 +292,7 @@ def _param_rounding_decode(name, sd, stochastic, seed0):
 
 
 # --------------------------------------------------------------------------- counter-based probe vectors
-# The draws of psgd_multi_randn_f32 (class Kron(preconditioner_fit="whitening"), kron_optimizer.multi_randn) restated in numpy: the
+# The draws of psgd_multi_randn_f32 (class Kron(preconditioner_fit="whitening"), multi_tail.multi_randn) restated in numpy: the
 # hash in integer arithmetic, Box-Muller in float64.  The kernel evaluates the same expressions in float32, so the two agree to a
 # few float32 ulps, not bit for bit (profiles/kron_whitening.txt has the measured distance).
 _PROBE_TENSOR_ID = 17                                # the stream "probe vectors" (bf16_state.h)
@@ -1087,6 +1087,149 @@ class _Hyper:
         return "_Hyper(%r)" % (self.value,)
 
 
+class _StepFeatures:
+    """The switches that class UVd and class Kron share, written once: momentum, weight decay, nonfinite="skip", the loss scale,
+    the seeds drawn at construction, the stream of param_rounding="stochastic" and the guard's checkpoint keys.  The class that
+    inherits this provides self._params (the parameters, in order), self._generator and, where param_rounding is on,
+    _param_round_seed0 / _param_round_step.  Messages carry the name of that class.  The schedules (uvd_loss_scale_next,
+    uvd_momentum_coefficients, uvd_step_rounding_seed) are looked up in this module at the call."""
+
+    def _init_features(self, momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval):
+        """momentum, weight_decay (off by default; _Hyper objects like the others), nonfinite, loss_scale,
+        loss_scale_growth_interval of a constructor, checked in this order before anything touches a device.  nonfinite="propagate"
+        is the code path from before the guard; "skip": a step with a non-finite input changes nothing.  loss_scale: None, a power
+        of two, or "dynamic" (starts at 2^16, uvd_loss_scale_next); a _Hyper that holds the CURRENT scale."""
+        name = type(self).__name__
+        if not 0.0 <= float(momentum) < 1.0:
+            raise ValueError("%s: momentum must be in [0, 1), got %r" % (name, momentum))
+        if not float(weight_decay) >= 0.0:
+            raise ValueError("%s: weight_decay must be >= 0, got %r" % (name, weight_decay))
+        if nonfinite not in ("propagate", "skip"):
+            raise ValueError("%s: nonfinite must be 'propagate' or 'skip', got %r" % (name, nonfinite))
+        self._guard = nonfinite == "skip"
+        if loss_scale is not None and not self._guard:
+            raise ValueError("%s: loss_scale needs nonfinite='skip' (a scaled gradient that overflows must not reach the state)" % name)
+        self._dynamic_scale = isinstance(loss_scale, str)
+        if self._dynamic_scale and loss_scale != "dynamic":
+            raise ValueError("%s: loss_scale must be None, a power of two or 'dynamic', got %r" % (name, loss_scale))
+        self.momentum = _Hyper(momentum)
+        self.weight_decay = _Hyper(weight_decay)
+        self.loss_scale = _Hyper(2.0 ** 16 if self._dynamic_scale else loss_scale)
+        self._loss_scale_value()
+        self.loss_scale_growth_interval = int(loss_scale_growth_interval)
+        if self.loss_scale_growth_interval < 1:
+            raise ValueError("%s: loss_scale_growth_interval must be >= 1, got %r" % (name, loss_scale_growth_interval))
+        self._m, self._m_step, self._good_steps = None, 0, 0
+        self.skipped_steps, self.last_step_skipped = 0, False
+
+    def _loss_scale_value(self):
+        """the current loss scale S as a float (1.0 without loss scaling), checked: a power of two"""
+        S = self.loss_scale.value
+        if S is None:
+            return 1.0
+        S = float(S)
+        if not (S > 0.0 and math.isfinite(S) and math.frexp(S)[0] == 0.5):
+            raise ValueError("%s: loss_scale must be a power of two (1 / loss_scale must be exact), got %r"
+                             % (type(self).__name__, self.loss_scale.value))
+        return S
+
+    def _hyper_momentum(self):
+        mom, wd = float(self.momentum), float(self.weight_decay)
+        if not 0.0 <= mom < 1.0:
+            raise ValueError("%s: momentum must be in [0, 1), got %r" % (type(self).__name__, mom))
+        if not wd >= 0.0:
+            raise ValueError("%s: weight_decay must be >= 0, got %r" % (type(self).__name__, wd))
+        return mom, wd
+
+    def _step_scales(self):
+        """(mom, wd, S, inv, scaled) of one step: the checked momentum and weight decay, the loss scale S (1.0 unguarded),
+        inv = 1 / S and the function that scales the loss"""
+        mom, wd = self._hyper_momentum()
+        S = self._loss_scale_value() if self._guard else 1.0
+        inv = 1.0 / S                                           # exact: S is a power of two
+        return mom, wd, S, inv, (lambda loss: loss) if S == 1.0 else (lambda loss: loss * S)
+
+    def _guard_outcome(self, skipped, undo_vs=None):
+        """book-keeping of a guarded step once its decision is known; a skipped finite-difference step takes the perturbation of
+        psgd.py:723 back, p <- T(p - v): the reference's own undo, within one rounding of T of the parameters before the step"""
+        if undo_vs is not None:
+            with torch.no_grad():
+                for p, v in zip(self._params, undo_vs):
+                    p.sub_(v)
+        self.last_step_skipped = bool(skipped)
+        self.skipped_steps += int(bool(skipped))
+        if self._dynamic_scale:
+            S, self._good_steps = uvd_loss_scale_next(self._loss_scale_value(), self._good_steps, skipped,
+                                                      growth_interval=self.loss_scale_growth_interval)
+            self.loss_scale.assign(S)
+
+    @staticmethod
+    def _loss_of(closure_returns):
+        return closure_returns if isinstance(closure_returns, torch.Tensor) else closure_returns[0]
+
+    _group = None                        # class UVd(group=...) sets it, and _coins: the generator all ranks share
+
+    def _coin_generator(self):
+        """the generator behind the coins (psgd.py:703, :562, :588) and the construction seeds: the generator= argument, else the
+        module's branch generator; row-sharded, the synchronised generator all ranks draw from"""
+        if self._group is not None:
+            return self._coins.gen
+        return self._generator if self._generator is not None else _branch_rng
+
+    def _draw_seed(self, explicit):
+        """a construction seed (native state, param_rounding, probe): the low 64 bits of `explicit`, or, for None, one draw from
+        the generator behind the coin.  The order of these draws is part of the checkpoint contract."""
+        if explicit is not None:
+            return int(explicit) & (2 ** 64 - 1)
+        gen = self._coin_generator()
+        return int(torch.randint(0, 2 ** 62, (), generator=gen, device=gen.device).item())
+
+    def _next_param_round_seed(self):
+        """the seed of the rounding stream of a step that writes the parameters (param_rounding="stochastic"); advances the counter"""
+        seed = uvd_step_rounding_seed(self._param_round_seed0, self._param_round_step)
+        self._param_round_step += 1
+        return seed
+
+    def _guard_decode(self, sd):
+        """restores what _guard_encode saved into a guarded optimizer.  A dict of an unguarded optimizer has none of the keys: the
+        guard starts fresh; loss_scale is taken only when both sides scale the loss.  An unguarded optimizer ignores the keys."""
+        if not self._guard:
+            return
+        self.skipped_steps, self.last_step_skipped = int(sd.get("skipped_steps", 0)), False
+        self._good_steps = int(sd.get("loss_scale_good_steps", 0))
+        if sd.get("loss_scale") is not None and self.loss_scale.value is not None:
+            self.loss_scale.assign(float(sd["loss_scale"]))
+            self._loss_scale_value()
+
+
+def _guard_encode(sd, guard, skipped_steps, loss_scale, good_steps):
+    """the checkpoint keys of the guard, added to sd when the optimizer is guarded (both classes): nonfinite, skipped_steps,
+    loss_scale (the current one; None without loss scaling) and loss_scale_good_steps; returns sd"""
+    if guard:
+        sd["nonfinite"], sd["skipped_steps"] = "skip", int(skipped_steps)
+        sd["loss_scale"] = None if loss_scale is None else float(loss_scale)
+        sd["loss_scale_good_steps"] = int(good_steps)
+    return sd
+
+
+def _torch_param_update_(p, g, v, lr, decay, sr_seed, index0):
+    """One parameter tensor of the torch tail of either class, in place, one torch op per rounding: delta = T(lr g); v given (the
+    undo of the finite-difference perturbation): delta = T(delta + v); decay given (c = fl32(lr_eff wd)): delta = T(delta +
+    T(c float(p))); p <- T(p - delta).  For float32 .to(T) and .float() do nothing.  g: float32, in p's shape; lr and decay:
+    Python floats that hold float32 values, or 0-dim float32 tensors.  The products are written scalar first; class Kron wrote
+    them tensor first, and since a floating-point product does not depend on the order of its operands these are the same bits.
+    sr_seed not None (param_rounding="stochastic"): param_update_stochastic_ on the flat indices index0, index0 + 1, ..."""
+    if sr_seed is not None:                                     # formed once in fp32, narrowed once
+        param_update_stochastic_(p, g, v, lr, decay, sr_seed, index0)
+        return
+    delta = (lr * g).to(p.dtype)
+    if v is not None:
+        delta = delta + v
+    if decay is not None:
+        delta = delta + (decay * p.float()).to(p.dtype)
+    p.sub_(delta)
+
+
 def _randn_like(p):
     """The draw of psgd.py:713 / :721 (one place, so that a test can supply the global vector's slices)."""
     return torch.randn_like(p)
@@ -1116,7 +1259,7 @@ def _flatten_params(params_with_grad):
     return out
 
 
-class UVd:
+class UVd(_StepFeatures):
     """Low-rank modification (UVd) preconditioner as an optimizer, psgd.py:630-764.
 
     Same constructor arguments and defaults as the reference (psgd.py:663-666).  Parameters are
@@ -1148,7 +1291,7 @@ class UVd:
         # from one generator whose state rank 0 broadcasts once.  The closure returns this rank's loss; its gradient and
         # Hessian-vector product with respect to this rank's parameters are what a model-parallel closure computes.
         params = _flatten_params(params_with_grad)
-        self._params_with_grad = [p for p in params if p.requires_grad]                      # :670
+        self._params = self._params_with_grad = [p for p in params if p.requires_grad]       # :670 (one list under both names)
         p0 = self._params_with_grad[0]
         self._dtype = p0.dtype                                                               # :671
         if self._dtype not in (torch.float32, torch.float16, torch.bfloat16):
@@ -1210,26 +1353,19 @@ class UVd:
             state_rounding = "stochastic" if state_rounding is None else state_rounding
             if state_rounding not in _ROUNDINGS:
                 raise ValueError("UVd: state_rounding must be 'stochastic' or 'nearest', got %r" % (state_rounding,))
-            if group is None:
-                gen = generator if generator is not None else _branch_rng
-            else:       # the generator whose state rank 0 broadcasts: one seed for all ranks
-                from . import sharded as _sharded
-                gen = _sharded.branch_rng_for(generator, group, p0.device).gen
-            self._round_seed0 = int(torch.randint(0, 2 ** 62, (), generator=gen).item())
-            self._round_step = 0
         elif state_rounding is not None:
             raise ValueError("UVd: state_rounding applies to state_route='native' only")
         self._state_rounding = state_rounding
+        self._group, self._generator = group, generator
+        if group is not None:       # the generator whose state rank 0 broadcasts, once, here: the coins and one seed for all ranks
+            from . import sharded as _sharded
+            self._sharded = _sharded
+            self._coins = _sharded.branch_rng_for(generator, group, self._device)
+        # the construction seeds, from the generator behind the coins: the native state's first, then the parameters'
+        if self._native:
+            self._round_seed0, self._round_step = self._draw_seed(None), 0
         if self._param_sr:
-            if param_rounding_seed is not None:
-                self._param_round_seed0 = int(param_rounding_seed) & (2 ** 64 - 1)
-            else:                    # drawn as the native route's seed is: row-sharded, from the generator all ranks share
-                if group is None:
-                    gen = generator if generator is not None else _branch_rng
-                else:
-                    from . import sharded as _sharded
-                    gen = _sharded.branch_rng_for(generator, group, p0.device).gen
-                self._param_round_seed0 = int(torch.randint(0, 2 ** 62, (), generator=gen).item())
+            self._param_round_seed0 = self._draw_seed(param_rounding_seed)
         self.lr_params = _Hyper(lr_params)                                                   # :673
         self.lr_preconditioner = _Hyper(lr_preconditioner)                                   # :674
         self.grad_clip_max_norm = _Hyper(math.inf if grad_clip_max_norm is None else grad_clip_max_norm)  # :675-678
@@ -1243,36 +1379,14 @@ class UVd:
         # the fused tail the blend rides on the pack of g (uvd_pack_blend: no flat g exists).  weight_decay (decoupled): the update
         # of :757-762 gains delta <- T(delta + T(fl32(fl32(lr_eff wd) p))).  Both tails round alike (every operation on its own);
         # with either one on, the torch tail forms the clipped lr as the kernel does (fp64 from the fp32 squares, one rounding).
-        if not 0.0 <= float(momentum) < 1.0:
-            raise ValueError("UVd: momentum must be in [0, 1), got %r" % (momentum,))
-        if not float(weight_decay) >= 0.0:
-            raise ValueError("UVd: weight_decay must be >= 0, got %r" % (weight_decay,))
-        self.momentum = _Hyper(momentum)
-        self.weight_decay = _Hyper(weight_decay)
-        self._m, self._m_step = None, 0
-        # nonfinite, loss_scale, loss_scale_growth_interval (extensions, off by default; see step()).  nonfinite="propagate" is the
-        # code path from before them.  "skip": a step whose v, h or g holds a non-finite value changes nothing.  loss_scale: None, a
-        # power of two, or "dynamic" (starts at 2^16, uvd_loss_scale_next); a _Hyper that holds the CURRENT scale.
-        if nonfinite not in ("propagate", "skip"):
-            raise ValueError("UVd: nonfinite must be 'propagate' or 'skip', got %r" % (nonfinite,))
-        self._guard = nonfinite == "skip"
-        if loss_scale is not None and not self._guard:
-            raise ValueError("UVd: loss_scale needs nonfinite='skip' (a scaled gradient that overflows must not reach the state)")
-        self._dynamic_scale = isinstance(loss_scale, str)
-        if self._dynamic_scale and loss_scale != "dynamic":
-            raise ValueError("UVd: loss_scale must be None, a power of two or 'dynamic', got %r" % (loss_scale,))
-        self.loss_scale = _Hyper(2.0 ** 16 if self._dynamic_scale else loss_scale)
-        self._loss_scale_value()
-        self.loss_scale_growth_interval = int(loss_scale_growth_interval)
-        if self.loss_scale_growth_interval < 1:
-            raise ValueError("UVd: loss_scale_growth_interval must be >= 1, got %r" % (loss_scale_growth_interval,))
-        self._good_steps, self._stamp = 0, 0
-        self.skipped_steps, self.last_step_skipped = 0, False
+        # nonfinite, loss_scale, loss_scale_growth_interval (extensions, off by default; see step()): "skip" = a step whose v, h or
+        # g holds a non-finite value changes nothing.  All five are checked and stored by _init_features.
+        self._init_features(momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval)
+        self._stamp = 0
         self._tiny = torch.finfo(self._dtype).tiny                                           # :682
         self._delta_param_scale = torch.finfo(self._dtype).eps ** 0.5                        # :683
         self._param_sizes, self._param_cumsizes = uvd_param_index(self._params_with_grad)    # :684-685
         num_params = self._param_cumsizes[-1]                                                # :686
-        self._generator = generator
         # step_tail (extension): "torch" (default) = the tail of step() as torch expressions, a handful of launches per parameter tensor;
         # "fused" = the step-tail kernels (uvd_pack, uvd_step_tail): the lists of :729-730, :747 packed into flat vectors that this
         # object owns (the arena's when the state is placed), the clip norm of :753 and the update of :757-762 in a number of launches
@@ -1289,12 +1403,9 @@ class UVd:
             else:
                 import warnings
                 warnings.warn("UVd: step_tail='fused' needs contiguous parameters of one dtype; this optimizer keeps the torch tail")
-        self._group, self._stage_backend, self._num_params_global = group, stage_backend, num_params
+        self._stage_backend, self._num_params_global = stage_backend, num_params
         if group is not None:
-            from . import sharded as _sharded
-            self._sharded = _sharded
-            self._num_params_global = _sharded.global_rows(num_params, self._device, group)  # :686 over all ranks (set-up time)
-            self._coins = _sharded.branch_rng_for(generator, group, self._device)
+            self._num_params_global = self._sharded.global_rows(num_params, self._device, group)  # :686 over all ranks (set-up time)
         uv_scale = (1.0 / (self._num_params_global * r)) ** 0.5                              # :687 (the GLOBAL N)
         sd = self._state_dtype
         # placement (extension): "probe" / "packed" carve U, V, d, the workspace, the output and the flat v / h / g vectors of :729-730,
@@ -1342,16 +1453,6 @@ class UVd:
             self._V.copy_(V)
             self._d.copy_(d)
 
-    def _loss_scale_value(self):
-        """the current loss scale S as a float (1.0 without loss scaling), checked: a power of two"""
-        S = self.loss_scale.value
-        if S is None:
-            return 1.0
-        S = float(S)
-        if not (S > 0.0 and math.isfinite(S) and math.frexp(S)[0] == 0.5):
-            raise ValueError("UVd: loss_scale must be a power of two (1 / loss_scale must be exact), got %r" % (self.loss_scale.value,))
-        return S
-
     def _pack_scale(self, fd_scaled, inv):
         """the scale of a pack: 1 / delta_param_scale (:734-736) where fd_scaled, times inv = 1 / loss_scale, rounded once to fp32"""
         base = self._fd_inv_scale if fd_scaled else 1.0
@@ -1389,14 +1490,6 @@ class UVd:
         if self._m is None:
             self._m = torch.zeros(self._param_cumsizes[-1], dtype=torch.float32, device=self._device)
         return self._m
-
-    def _hyper_momentum(self):
-        mom, wd = float(self.momentum), float(self.weight_decay)
-        if not 0.0 <= mom < 1.0:
-            raise ValueError("UVd: momentum must be in [0, 1), got %r" % (mom,))
-        if not wd >= 0.0:
-            raise ValueError("UVd: weight_decay must be >= 0, got %r" % (wd,))
-        return mom, wd
 
     def _grad_flat(self, grads, mom, inv=1.0, flat=None):
         """psgd.py:747; with momentum the gradients blended into the momentum buffer, which is returned in their place.  inv:
@@ -1454,32 +1547,9 @@ class UVd:
             return None
         return self._grad_flat(grads, mom, inv, flat)
 
-    def _guard_outcome(self, skipped, undo_vs=None):
-        """book-keeping of a guarded step once its decision is known; a skipped finite-difference step takes the perturbation of
-        :723 back, p <- T(p - v): the reference's own undo, within one rounding of T of the parameters before the step"""
-        if undo_vs is not None:
-            with torch.no_grad():
-                for p, v in zip(self._params_with_grad, undo_vs):
-                    p.sub_(v)
-        self.last_step_skipped = bool(skipped)
-        self.skipped_steps += int(bool(skipped))
-        if self._dynamic_scale:
-            S, self._good_steps = uvd_loss_scale_next(self._loss_scale_value(), self._good_steps, skipped,
-                                                      growth_interval=self.loss_scale_growth_interval)
-            self.loss_scale.assign(S)
-
-    def _loss_of(self, closure_returns):
-        return closure_returns if isinstance(closure_returns, torch.Tensor) else closure_returns[0]
-
     # ------------------------------------------------------------------------------------------------- checkpoint / resume
     _HYPER_KEYS = ("lr_params", "lr_preconditioner", "grad_clip_max_norm", "preconditioner_update_probability",
                    "exact_hessian_vector_product")
-
-    def _coin_generator(self):
-        """the generator behind the coins of :703, :562, :588 (and the construction seed of the native route)"""
-        if self._group is not None:
-            return self._coins.gen
-        return self._generator if self._generator is not None else _branch_rng
 
     def _row0(self):
         if self._group is None:
@@ -1532,11 +1602,7 @@ class UVd:
         if self._native:
             sd["round_seed0"], sd["round_step"] = int(self._round_seed0), int(self._round_step)
         _param_rounding_encode(sd, self._param_sr, self._param_round_seed0, self._param_round_step)
-        if self._guard:
-            sd["nonfinite"], sd["skipped_steps"] = "skip", int(self.skipped_steps)
-            sd["loss_scale"] = None if self.loss_scale.value is None else float(self.loss_scale)
-            sd["loss_scale_good_steps"] = int(self._good_steps)
-        return sd
+        return _guard_encode(sd, self._guard, self.skipped_steps, self.loss_scale.value, self._good_steps)
 
     def load_state_dict(self, sd, *, strict=True, narrow_rounding=None, narrow_seed=None):
         """Restore what state_dict() saved, IN PLACE: U, V, d are written into the tensors this object already holds (a placed
@@ -1635,12 +1701,7 @@ class UVd:
         if self._native and "round_seed0" in sd:
             self._round_seed0, self._round_step = int(sd["round_seed0"]), int(need("round_step"))
         self._param_round_seed0, self._param_round_step = _param_rounding_decode(name, sd, self._param_sr, self._param_round_seed0)
-        if self._guard:                  # a dict from an unguarded optimizer has none of these: the guard starts fresh
-            self.skipped_steps, self.last_step_skipped = int(sd.get("skipped_steps", 0)), False
-            self._good_steps = int(sd.get("loss_scale_good_steps", 0))
-            if sd.get("loss_scale") is not None and self.loss_scale.value is not None:
-                self.loss_scale.assign(float(sd["loss_scale"]))
-                self._loss_scale_value()
+        self._guard_decode(sd)
         with torch.no_grad():
             if how == "copy":
                 for k, mine in (("U", self._U), ("V", self._V), ("d", self._d)):
@@ -1722,11 +1783,8 @@ class UVd:
         else:
             update_Q = self._coins.draw(float(self.preconditioner_update_probability))       # the same coin on every rank
         exact = bool(self.exact_hessian_vector_product)
-        mom, wd = self._hyper_momentum()
+        mom, wd, S, inv, scaled = self._step_scales()
         guard, fused = self._guard, self._tail is not None
-        S = self._loss_scale_value() if guard else 1.0
-        inv = 1.0 / S                                           # exact: S is a power of two
-        scaled = (lambda loss: loss) if S == 1.0 else (lambda loss: loss * S)
         if guard:
             self._stamp = self._stamp % (2 ** 31 - 1) + 1       # 1 .. 2^31 - 1, then 1 again: the flags are never zeroed
         vs = None
@@ -1779,10 +1837,9 @@ class UVd:
                 grad = self._grad_flat(grads, mom)
             pre_grad = self._precondition(None, None, grad)                                   # :747-748
         max_norm = float(self.grad_clip_max_norm)
-        sr = self._param_sr
+        sr, sr_seed, sr_index0 = self._param_sr, None, 0
         if sr:                           # this step writes the parameters: the seed of its rounding stream, the GLOBAL first index
-            sr_seed = uvd_step_rounding_seed(self._param_round_seed0, self._param_round_step)
-            self._param_round_step += 1
+            sr_seed = self._next_param_round_seed()
             sr_index0 = int(self._row0()) if self._group is not None else 0
         if fused:                                                                             # :750-762 in the step-tail kernels
             sr_kw = dict(rounding="stochastic", rounding_seed=sr_seed, index0=sr_index0) if sr else {}
@@ -1812,20 +1869,14 @@ class UVd:
         with torch.no_grad():                                                                 # :757-762
             undo = (not exact) and update_Q
             for k, (p, i, j) in enumerate(zip(params, self._param_sizes, self._param_cumsizes)):
-                if sr:                   # formed once in fp32, narrowed once: the chain of psgd_uvd_param_update_multi_sr
-                    param_update_stochastic_(p, pre_grad[j - i:j], vs[k] if undo else None, lr, decay, sr_seed, sr_index0 + j - i)
-                    continue
-                delta = (lr * torch.reshape(pre_grad[j - i:j], p.shape)).to(p.dtype)
-                if undo:
-                    delta = delta + vs[k]
-                if decay is not None:
-                    delta = delta + (decay * p.float()).to(p.dtype)
-                p.sub_(delta)
-        return closure_returns                                                                # :764
+                _torch_param_update_(p, torch.reshape(pre_grad[j - i:j], p.shape), vs[k] if undo else None, lr, decay, sr_seed,
+                                     sr_index0 + j - i)
+        return closure_returns                                                              # :764
 
 
-# --------------------------------------------------------------------------- Kron optimizer (kron_optimizer.py)
-# (imported last: that module builds on the step-tail plan, _Hyper and the Kron entry points above)
+# --------------------------------------------------------------------------- Kron optimizer (kron_optimizer.py, multi_tail.py)
+# (imported last: those modules build on the step-tail plan, _Hyper, _StepFeatures and the Kron entry points above; the multi_*
+# functions live in multi_tail.py and come through kron_optimizer, which imports them by name)
 from .kron_optimizer import Kron, multi_sumsq, multi_param_update, multi_diff_scale, kron_initial_factors  # noqa: E402,F401
 from .kron_optimizer import multi_blend, multi_scale_check, multi_widen_check  # noqa: E402,F401
 from .kron_optimizer import multi_vec_precond_update, multi_vec_precond_grad, kron_layers  # noqa: E402,F401

@@ -1,0 +1,134 @@
+"""One sha256 per configuration of class UVd and class Kron after 6 steps: a refactor of the classes' host layer must leave every
+digest that repeats from run to run as it was.
+
+    python tools/class_step_digest.py [--out FILE]
+
+Three parameters of shapes (5, 7), (4, 3) and (7,) -- Kron(any_rank=True), UVd(rank_of_modification=3) -- a seeded CPU generator
+behind the coin and preconditioner_update_probability=0.5.  The configurations are the cross product of
+
+    class      UVd, Kron                       tail     torch, fused             hvp     exact, fd (finite differences)
+    dtype      float32, bfloat16 with param_rounding="nearest", bfloat16 with param_rounding="stochastic"
+    features   off, or momentum 0.9 + weight decay + nonfinite="skip" + loss_scale="dynamic" with an Inf gradient in step 3
+
+and class Kron(preconditioner_fit="whitening") on every tail, dtype and feature setting.  The digest covers the parameters, the
+preconditioner state (U, V, d or the factors), the momentum buffers, skipped_steps, the current loss scale and the counters of
+the rounding and probe streams.  Before anything runs on the device the coins of every configuration are replayed on the CPU
+from the generator alone, and a configuration whose coins (the step with the Inf gradient left out) do not hold both outcomes is
+an error; after the run the replay is compared with what the steps did (a step updated the preconditioner when its state
+changed), and a line that disagrees says so.
+
+Run it twice on the commit before the change and once after, and compare the lines: this tool takes no part in the test suite.
+"""
+import argparse
+import hashlib
+import itertools
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import preconditioned_stochastic_gradient_descent as psgd  # noqa: E402
+
+SHAPES = [(5, 7), (4, 3), (7,)]
+STEPS, INF_STEP, P_UPDATE, SEED = 6, 2, 0.5, 1
+FEATURES_ON = dict(momentum=0.9, weight_decay=0.01, nonfinite="skip", loss_scale="dynamic")
+DTYPES = {"fp32": (torch.float32, "nearest"), "bf16": (torch.bfloat16, "nearest"), "bf16sr": (torch.bfloat16, "stochastic")}
+
+
+def configurations():
+    for cls, tail, hvp, dt, feat in itertools.product(("UVd", "Kron"), ("torch", "fused"), ("exact", "fd"), DTYPES, ("off", "on")):
+        yield cls, tail, hvp, dt, feat
+    for tail, dt, feat in itertools.product(("torch", "fused"), DTYPES, ("off", "on")):
+        yield "Kron", tail, "whitening", dt, feat
+
+
+def replayed_coins(cls, hvp, dt, feat):
+    """the coins of the six steps, from the CPU generator alone: the draws of the constructor (the seed of the parameters'
+    rounding stream, then the probe seed), then per step the coin and what the class draws after it from the same generator --
+    class UVd the two branches of an update that runs, class Kron its probe vectors in the parameters' dtype"""
+    gen = torch.Generator().manual_seed(SEED)
+    dtype, rounding = DTYPES[dt]
+    for _ in range((rounding == "stochastic") + (hvp == "whitening")):
+        torch.randint(0, 2 ** 62, (), generator=gen)
+    coins = []
+    for k in range(STEPS):
+        update = bool(torch.rand((), generator=gen).item() < P_UPDATE)
+        coins.append(update)
+        if not update:
+            continue
+        if cls == "UVd" and not (feat == "on" and k == INF_STEP):
+            torch.rand((), generator=gen), torch.rand((), generator=gen)
+        if cls == "Kron" and hvp != "whitening":
+            for s in SHAPES:
+                torch.randn(s, dtype=dtype, generator=gen)
+    return coins
+
+
+def raw(t):
+    return t.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes()
+
+
+def state_tensors(opt):
+    if isinstance(opt, psgd.Kron):
+        return [q for pair in opt.factors for q in pair]
+    return [opt._U, opt._V, opt._d]
+
+
+def run(cls, tail, hvp, dt, feat, dev):
+    dtype, rounding = DTYPES[dt]
+    torch.manual_seed(1234)                       # the global device generator: UVd's initial U, V and its probe vectors
+    init = torch.Generator().manual_seed(5)
+    params = [torch.randn(s, generator=init).to(dev, dtype).requires_grad_(True) for s in SHAPES]
+    hess = [torch.rand(s, generator=init).add_(0.5).to(dev) for s in SHAPES]
+    step_no = [0]
+
+    def closure():
+        loss = sum(0.5 * torch.sum(h * p.float() * p.float()) for p, h in zip(params, hess)) + 0.1 * params[0].float().sum() ** 2
+        if feat == "on" and step_no[0] == INF_STEP:
+            loss = loss + params[1].float().sum() * float("inf")
+        return loss
+    kw = dict(lr_params=0.05, lr_preconditioner=0.1, grad_clip_max_norm=1.0, preconditioner_update_probability=P_UPDATE,
+              exact_hessian_vector_product=hvp != "fd", step_tail=tail, generator=torch.Generator().manual_seed(SEED),
+              param_rounding=rounding, **(FEATURES_ON if feat == "on" else {}))
+    if cls == "UVd":
+        opt = psgd.UVd(params, rank_of_modification=3, **kw)
+    else:
+        opt = psgd.Kron(params, any_rank=True, preconditioner_fit="whitening" if hvp == "whitening" else "hessian", **kw)
+    coins = ""
+    for k in range(STEPS):
+        step_no[0] = k
+        before = [raw(t) for t in state_tensors(opt)]
+        opt.step(closure)
+        coins += "s" if opt.last_step_skipped else "01"[before != [raw(t) for t in state_tensors(opt)]]
+    h = hashlib.sha256()
+    moms = opt._m if isinstance(opt._m, list) else [] if opt._m is None else [opt._m]
+    for t in params + state_tensors(opt) + moms:
+        h.update(raw(t))
+    h.update(repr((opt.skipped_steps, opt.loss_scale.value, opt._param_round_step, getattr(opt, "probe_step", None))).encode())
+    return h.hexdigest(), coins
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    replay = {}
+    for c in configurations():
+        coins = replay[c] = replayed_coins(c[0], c[2], c[3], c[4])
+        if len({u for k, u in enumerate(coins) if k != INF_STEP}) != 2:           # (the step that may be skipped does not count)
+            raise SystemExit("%s: the coins %r hold one outcome only; choose another SEED" % ("-".join(c), coins))
+    dev = torch.device("cuda:0")
+    lines = []
+    for c in configurations():
+        digest, coins = run(*c, dev)
+        want = "".join("s" if c[4] == "on" and k == INF_STEP else "01"[u] for k, u in enumerate(replay[c]))
+        lines.append("%-32s %s coins %s%s" % ("-".join(c), digest, coins, "" if coins == want else " (replayed: %s)" % want))
+        print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
