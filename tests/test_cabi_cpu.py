@@ -114,6 +114,46 @@ def test_kron_route_flags_anchor_the_route_table(lib):
     assert R(1024, 4096) & inv
 
 
+# Exported symbols that compute nothing on caller memory: version / error text, size and layout queries, host-only route and key
+# functions, tuning setters, the profiling hooks, and the read-back of the bf16 hand-off counter.  Everything else is a compute
+# entry point and must have an extent test.
+NOT_COMPUTE = {
+    "psgd_abi_version", "psgd_error_string", "psgd_set_tuning", "psgd_kron_set_tuning", "psgd_kron_bf16_set_tuning",
+    "psgd_prof_enable", "psgd_prof_collect",
+    "psgd_uvd_workspace_bytes", "psgd_uvd_ws_region", "psgd_uvd_gram_wide_scratch_bytes", "psgd_uvd_wide_scratch_bytes",
+    "psgd_uvd_wide_update_scratch_bytes", "psgd_uvd_wide_update_apply_scratch_bytes", "psgd_uvd_bf16_workspace_bytes",
+    "psgd_uvd_bf16_ws_region", "psgd_uvd_bf16_rounding_key", "psgd_splu_workspace_bytes", "psgd_splu_ws_region",
+    "psgd_splu_bf16_workspace_bytes", "psgd_kron_dd_workspace_bytes", "psgd_kron_dd_workspace_bytes_batched",
+    "psgd_kron_sparse_workspace_bytes", "psgd_kron_dd_workspace_bytes_bf16", "psgd_kron_dd_update_workspace_bytes_bf16",
+    "psgd_kron_dd_apply_direct_distinct", "psgd_kron_dd_route_flags", "psgd_kron_bf16_handoff_counter_offset",
+    "psgd_kron_bf16_handoff_timeouts", "psgd_dense_workspace_bytes",
+}
+
+
+def test_every_compute_entry_point_has_an_extent_test():
+    """A kernel cannot arrive without a guard-band test: every exported symbol is exempt by name (NOT_COMPUTE), in the case table of
+    tests/test_extents_gpu.py (and really called there), or in its covered-elsewhere list (the list kernels) with a GPU test file that runs it by name."""
+    from tests import test_extents_gpu as ext
+    declared = set(_declared_symbols())
+    table = {n for names in ext.ENTRY_POINTS.values() for n in names}
+    elsewhere = set(ext.COVERED_ELSEWHERE)
+    assert NOT_COMPUTE <= declared and table <= declared and elsewhere <= declared, "a list names a symbol the header does not declare"
+    assert not (table & elsewhere) and not (NOT_COMPUTE & (table | elsewhere))
+    # covered elsewhere = the list kernels, by name pattern, all of them and nothing else: no other entry point can hide there
+    is_list = lambda n: n.startswith(ext.COVERED_ELSEWHERE_PATTERNS)
+    assert elsewhere == {n for n in declared if is_list(n)}, sorted(elsewhere ^ {n for n in declared if is_list(n)})
+    missing = declared - NOT_COMPUTE - table - elsewhere
+    assert not missing, "compute entry points without an extent test: %s" % sorted(missing)
+    src = open(ext.__file__).read()
+    for name in sorted(table):
+        fmt = name.replace("_ds_", "_%s_").replace("_nd_", "_%s_").replace("_ns_", "_%s_")
+        called = any(form % n in src for form in ('call("%s"', 'exchange("%s"') for n in (name, fmt))
+        assert called, name + " is in the case table but no case calls it"
+    for name, path in ext.COVERED_ELSEWHERE.items():
+        text = open(os.path.join(ROOT, path)).read()
+        assert os.path.basename(path).endswith("_gpu.py") and (name in text or name[len("psgd_"):] in text), (name, path)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))
