@@ -264,32 +264,8 @@ def _encode_features(sd, momentum, weight_decay, buffers=None, momentum_step=0, 
     return _psgd._guard_encode(sd, guard, skipped_steps, loss_scale, good_steps)
 
 
-_PRECONDITIONER_FITS = ("hessian", "whitening")
-
-
-def _preconditioner_fit(preconditioner_fit):
-    """the preconditioner_fit argument of the constructor, judged before anything touches a device: True for "whitening" """
-    if preconditioner_fit not in _PRECONDITIONER_FITS:
-        raise ValueError("Kron: preconditioner_fit must be 'hessian' or 'whitening', got %r" % (preconditioner_fit,))
-    return preconditioner_fit == "whitening"
-
-
-def _probe_encode(sd, whitening, seed0, step):
-    """the checkpoint keys of the probe stream, added to sd when the optimizer fits by gradient whitening; returns sd"""
-    if whitening:
-        sd["probe_seed0"], sd["probe_step"] = int(seed0), int(step)
-    return sd
-
-
-def _probe_decode(sd, whitening, seed0):
-    """(seed0, step) after loading sd into an optimizer whose own probe seed is seed0: the dict's pair where it has one; the
-    optimizer's seed with the counter at 0 where it has none (a dict of a hessian-fit optimizer); a hessian-fit optimizer ignores
-    the keys and gets (seed0, 0)"""
-    if not whitening or "probe_seed0" not in sd:
-        return seed0, 0
-    if "probe_step" not in sd:
-        raise ValueError("Kron.load_state_dict: the state dict has 'probe_seed0' but no 'probe_step'")
-    return int(sd["probe_seed0"]), int(sd["probe_step"])
+# the checkpoint keys of the probe stream: one implementation for both classes (_StepFeatures of the UVd module)
+_probe_encode, _probe_decode = _psgd._probe_encode, _psgd._probe_decode
 
 
 def _decode_features(sd, shapes):
@@ -417,9 +393,8 @@ class Kron(_psgd._StepFeatures):
                  param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None):
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
-        self._whiten = _preconditioner_fit(preconditioner_fit)
-        self.preconditioner_fit = preconditioner_fit
-        self._probe_seed0, self._probe_step, self._probe, self._probe_plan = None, 0, None, None
+        self._init_fit(preconditioner_fit)
+        self._probe, self._probe_plan = None, None
         self._operands, self._operand_min_dim = _operands_dtype(operands), _operand_min_dim(operand_min_dim)
         if vector_route not in ("list", "layer"):
             raise ValueError("Kron: vector_route must be 'list' or 'layer', got %r" % (vector_route,))
@@ -528,16 +503,6 @@ class Kron(_psgd._StepFeatures):
         """the indices (parameter order) of the layers that run on the bf16-operand kernels: kron_operand_layers of this optimizer"""
         return list(self._ops)
 
-    @property
-    def probe_seed0(self):
-        """the construction seed of the probe stream (None with preconditioner_fit="hessian")"""
-        return self._probe_seed0
-
-    @property
-    def probe_step(self):
-        """the number of steps that drew a probe so far: the k of uvd_step_rounding_seed(probe_seed0, k) of the next draw"""
-        return self._probe_step
-
     def state_dict(self):
         """Everything a bit-faithful resume needs except the parameters (the caller's): the factors (CPU clones), the formats and
         parameter shapes, the five hyper-parameters, and get_state() of the generator behind the coin and the perturbations
@@ -570,7 +535,7 @@ class Kron(_psgd._StepFeatures):
         factors, hyper, rng = _decode_state(sd, self._formats, self._shapes, self._layer_shapes)
         bufs, m_step = _decode_features(sd, self._shapes)
         sr_state = _psgd._param_rounding_decode("Kron.load_state_dict", sd, self._param_sr, self._param_round_seed0)
-        probe_state = _probe_decode(sd, self._whiten, self._probe_seed0)
+        probe_state = _probe_decode(sd, self._whiten, self._probe_seed0, "Kron.load_state_dict")
         try:
             self._coin_generator().set_state(rng)
         except (RuntimeError, TypeError) as e:
@@ -908,8 +873,7 @@ class Kron(_psgd._StepFeatures):
             return closure_returns
         if route == "whitening":
             with torch.no_grad():
-                multi_randn(self._probe, _psgd.uvd_step_rounding_seed(self._probe_seed0, self._probe_step), plan=self._probe_plan)
-            self._probe_step += 1
+                multi_randn(self._probe, self._next_probe_seed(), plan=self._probe_plan)
             dXs, dGs = self._probe, list(grads)
         elif route == "exact":
             dXs, dGs = vs, second

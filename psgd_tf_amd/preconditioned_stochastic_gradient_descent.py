@@ -328,6 +328,27 @@ def counter_randn(seed, index0, n, scale=1.0):
     return np.float32(scale) * z
 
 
+_PRECONDITIONER_FITS = ("hessian", "whitening")
+
+
+def _probe_encode(sd, whitening, seed0, step):
+    """the checkpoint keys of the probe stream, added to sd when the optimizer fits by gradient whitening (both classes); returns sd"""
+    if whitening:
+        sd["probe_seed0"], sd["probe_step"] = int(seed0), int(step)
+    return sd
+
+
+def _probe_decode(sd, whitening, seed0, name="load_state_dict"):
+    """(seed0, step) after loading sd into an optimizer whose own probe seed is seed0: the dict's pair where it has one; the
+    optimizer's seed with the counter at 0 where it has none (a dict of a hessian-fit optimizer); a hessian-fit optimizer ignores
+    the keys and gets (seed0, 0)"""
+    if not whitening or "probe_seed0" not in sd:
+        return seed0, 0
+    if "probe_step" not in sd:
+        raise ValueError("%s: the state dict has 'probe_seed0' but no 'probe_step'" % name)
+    return int(sd["probe_seed0"]), int(sd["probe_step"])
+
+
 _UVD_TENSOR_IDS = {"U": 0, "V": 1, "d": 2}           # the tensor ids of psgd_uvd_bf16_rounding_key
 _NARROW_STAGING_BYTES = 64 << 20                     # UVd.load_state_dict: the fp32 staging buffer of an fp32 -> native bf16 load
 
@@ -1089,7 +1110,8 @@ class _Hyper:
 
 class _StepFeatures:
     """The switches that class UVd and class Kron share, written once: momentum, weight decay, nonfinite="skip", the loss scale,
-    the seeds drawn at construction, the stream of param_rounding="stochastic" and the guard's checkpoint keys.  The class that
+    the seeds drawn at construction, the stream of param_rounding="stochastic", the preconditioner_fit switch with the state of
+    its probe stream (probe_seed0 / probe_step) and the guard's checkpoint keys.  The class that
     inherits this provides self._params (the parameters, in order), self._generator and, where param_rounding is on,
     _param_round_seed0 / _param_round_step.  Messages carry the name of that class.  The schedules (uvd_loss_scale_next,
     uvd_momentum_coefficients, uvd_step_rounding_seed) are looked up in this module at the call."""
@@ -1184,6 +1206,32 @@ class _StepFeatures:
         gen = self._coin_generator()
         return int(torch.randint(0, 2 ** 62, (), generator=gen, device=gen.device).item())
 
+    def _init_fit(self, preconditioner_fit):
+        """the preconditioner_fit argument of a constructor, judged before anything touches a device: sets preconditioner_fit,
+        _whiten (True for "whitening") and the probe stream's state -- no seed yet (the constructor draws it with _draw_seed, after
+        every seed it drew before this switch existed) and the counter at 0"""
+        if preconditioner_fit not in _PRECONDITIONER_FITS:
+            raise ValueError("%s: preconditioner_fit must be 'hessian' or 'whitening', got %r" % (type(self).__name__, preconditioner_fit))
+        self.preconditioner_fit = preconditioner_fit
+        self._whiten = preconditioner_fit == "whitening"
+        self._probe_seed0, self._probe_step = None, 0
+
+    @property
+    def probe_seed0(self):
+        """the construction seed of the probe stream (None with preconditioner_fit="hessian")"""
+        return self._probe_seed0
+
+    @property
+    def probe_step(self):
+        """the number of steps that drew a probe so far: the k of uvd_step_rounding_seed(probe_seed0, k) of the next draw"""
+        return self._probe_step
+
+    def _next_probe_seed(self):
+        """the seed of the probe of an updating whitening step; advances probe_step"""
+        seed = uvd_step_rounding_seed(self._probe_seed0, self._probe_step)
+        self._probe_step += 1
+        return seed
+
     def _next_param_round_seed(self):
         """the seed of the rounding stream of a step that writes the parameters (param_rounding="stochastic"); advances the counter"""
         seed = uvd_step_rounding_seed(self._param_round_seed0, self._param_round_step)
@@ -1274,7 +1322,28 @@ class UVd(_StepFeatures):
     uvd_step_rounding_seed(seed0, k) and the element's global flat index (psgd_uvd_param_update_multi_sr on the fused tail,
     param_update_stochastic_ on the torch tail: the same bits).  seed0: param_rounding_seed, or a draw from the generator behind
     the coins; k counts the steps that wrote the parameters.  The perturbation of :723 and its undo stay round-to-nearest.
-    state_dict() carries param_round_seed0 / param_round_step; param_rounding itself is a constructor choice, like step_tail."""
+    state_dict() carries param_round_seed0 / param_round_step; param_rounding itself is a constructor choice, like step_tail.
+
+    preconditioner_fit="whitening" (extension, keyword-only; "hessian" by default: nothing changes, no new function is called, no
+    new number is drawn; any other value is a ValueError before a device is touched) fits the preconditioner to the GRADIENTS
+    instead of to Hessian-vector products: the update of :732-733 is fed the pair (v, h) = (probe, g), v ~ N(0, I) drawn fresh on
+    every updating step and g the raw flat float32 gradient of this step (1 / loss_scale folded into its pack; never the momentum
+    buffer).  The criterion E[h' P h + v' P^-1 v] is then minimised by P = Q'Q = (E[g g'])^(-1/2) within the UVd form: the
+    preconditioner whitens the gradient (the gradient-whitening fit of the PSGD papers).  A step needs ONE ordinary
+    backward pass: no create_graph, no second closure call, no perturbation of the parameters -- so closures whose backward cannot
+    be differentiated again (fused attention kernels, custom Functions marked once_differentiable) train, and the step no longer
+    pays the second backward.  exact_hessian_vector_product is ignored on this route (nothing is rejected).  The probe is this
+    rank's flat float32 vector -- the arena's v region on a placed state, else a buffer made once -- filled by ONE multi_randn
+    launch over one segment on BOTH step tails (there is no torch.randn on this route, no per-tensor probe, and v is never
+    packed): the stream of updating step k is keyed by uvd_step_rounding_seed(probe_seed0, k) and the element's GLOBAL flat index
+    (index0 = this rank's first row), whatever `generator` is, so a row-sharded run draws the rows of the one-process probe;
+    probe_seed0 = probe_seed, or a draw from the generator behind the coins (after the draws of the native state's and the
+    parameters' seeds where those happen; row-sharded, from the synchronised generator: the same on every rank); k = probe_step
+    counts the steps that drew a probe.  Without momentum, on a state that is not placed, h and g are one buffer, packed once (the
+    kernels only read them); with momentum or a placed state each has its own.  The probe is finite by construction and is not
+    judged by the guard; a skipped step returns before it is drawn and leaves probe_step alone.  state_dict() carries probe_seed0
+    / probe_step; preconditioner_fit itself is a constructor choice, like step_tail.  The whitened gradient has roughly unit scale
+    per element, as Adam's update has: lr_params and grad_clip_max_norm tuned for the Hessian fit do NOT carry over."""
 
     def __init__(self, params_with_grad, rank_of_modification: int = 10, preconditioner_init_scale=1.0,
                  lr_params=0.01, lr_preconditioner=0.01,
@@ -1282,7 +1351,7 @@ class UVd(_StepFeatures):
                  exact_hessian_vector_product: bool = True, generator=None, state_dtype=None, group=None,
                  stage_backend=None, placement="auto", state_route="widen", state_rounding=None, step_tail="torch",
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
-                 *, param_rounding="nearest", param_rounding_seed=None):
+                 *, param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None):
         # group (extension): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
         # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the
         # concatenation of the ranks' vectors in rank order, and U, V, d hold this rank's rows only.  A step then costs three
@@ -1307,6 +1376,9 @@ class UVd(_StepFeatures):
         # skipped step stay round-to-nearest.  Judged here, before anything touches a device.
         self._param_sr = _param_rounding("UVd", param_rounding, self._dtype)
         self._param_round_seed0, self._param_round_step = None, 0
+        # preconditioner_fit (extension, keyword-only; "hessian" = nothing changes; see the class docstring): judged here too
+        self._init_fit(preconditioner_fit)
+        self._probe, self._probe_plan = None, None
         # psgd.py:657-658 allows half-precision parameters.  The preconditioner state U, V, d and all of its arithmetic
         # stay fp32 here (mixed precision: the HIP kernels compute in fp32; v, Hv and the gradient are widened on the
         # way in, the preconditioned gradient is narrowed on the way out).  _tiny and the finite-difference scale follow
@@ -1361,11 +1433,14 @@ class UVd(_StepFeatures):
             from . import sharded as _sharded
             self._sharded = _sharded
             self._coins = _sharded.branch_rng_for(generator, group, self._device)
-        # the construction seeds, from the generator behind the coins: the native state's first, then the parameters'
+        # the construction seeds, from the generator behind the coins: the native state's first, then the parameters', then the
+        # probe's (row-sharded: that generator is the synchronised one, so every rank holds the same probe_seed0)
         if self._native:
             self._round_seed0, self._round_step = self._draw_seed(None), 0
         if self._param_sr:
             self._param_round_seed0 = self._draw_seed(param_rounding_seed)
+        if self._whiten:
+            self._probe_seed0 = self._draw_seed(probe_seed)
         self.lr_params = _Hyper(lr_params)                                                   # :673
         self.lr_preconditioner = _Hyper(lr_preconditioner)                                   # :674
         self.grad_clip_max_norm = _Hyper(math.inf if grad_clip_max_norm is None else grad_clip_max_norm)  # :675-678
@@ -1547,6 +1622,36 @@ class UVd(_StepFeatures):
             return None
         return self._grad_flat(grads, mom, inv, flat)
 
+    # ------------------------------------------------------------------------------------- preconditioner_fit="whitening"
+    def _whitening_inputs(self, grads, mom, inv):
+        """(h, g) of an updating whitening step, or (None, None) where the guard skips it: h the raw flat fp32 gradient of this
+        step (1 / loss_scale folded into the pack; never the momentum buffer), g what _grad_flat returns.  Without momentum on a
+        state that is not placed the two hold the same bits: ONE pack, ONE buffer passed for both -- every form of the fused
+        call (fp32, bf16 state, ranks above 32, the staged sharded ones) takes v, h and g as const pointers and only reads them.
+        With momentum, or on a placed state (its layout was measured with distinct streams), h gets its own region.  Guarded: the
+        packs judge what they write (h in slot 1, g in slot 2 of the plan's flags); with momentum uvd_check judges the gradients
+        before the blend, as on every guarded step.  The decision is _guarded_grad's: the one host read of the step."""
+        guard = self._guard
+        if mom == 0.0 and self._arena is None:
+            g = self._guarded_grad(grads, mom, inv, ()) if guard else self._grad_flat(grads, mom)
+            return g, g
+        h = self._flat(grads, "h", inv=inv, slot=1 if guard and self._tail is not None else None)
+        g = self._guarded_grad(grads, mom, inv, (h,)) if guard else self._grad_flat(grads, mom)
+        return (None, None) if g is None else (h, g)
+
+    def _draw_probe(self):
+        """v ~ N(0, I) of an updating whitening step, drawn straight into this rank's flat fp32 vector -- the arena's v region on a
+        placed state, else a buffer made once -- by ONE multi_randn launch over one segment, on either step tail: seed
+        uvd_step_rounding_seed(probe_seed0, probe_step), index0 = this rank's first global row, scale 1.  Advances probe_step."""
+        if self._probe_plan is None:
+            from .multi_tail import MultiTailPlan
+            n = self._param_cumsizes[-1]
+            self._probe_plan = MultiTailPlan([n], self._device)
+            self._probe = self._arena.v.view(-1) if self._arena is not None else \
+                torch.empty(n, dtype=torch.float32, device=self._device)
+        multi_randn([self._probe], self._next_probe_seed(), self._row0(), plan=self._probe_plan)
+        return self._probe
+
     # ------------------------------------------------------------------------------------------------- checkpoint / resume
     _HYPER_KEYS = ("lr_params", "lr_preconditioner", "grad_clip_max_norm", "preconditioner_update_probability",
                    "exact_hessian_vector_product")
@@ -1570,6 +1675,8 @@ class UVd(_StepFeatures):
             round_seed0, round_step  native route only: together they fix every stored code of every later step
             param_round_seed0, param_round_step    param_rounding="stochastic" only: the seed and the step counter of the
                                      parameters' rounding stream (param_rounding itself is a constructor choice and is not saved)
+            probe_seed0, probe_step  preconditioner_fit="whitening" only: the seed and the step counter of the probe stream, the
+                                     same on every rank (preconditioner_fit itself is a constructor choice and is not saved)
             hyper                    lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability (floats),
                                      exact_hessian_vector_product (bool)
                                      and, optional when loading, momentum and weight_decay (floats)
@@ -1602,6 +1709,7 @@ class UVd(_StepFeatures):
         if self._native:
             sd["round_seed0"], sd["round_step"] = int(self._round_seed0), int(self._round_step)
         _param_rounding_encode(sd, self._param_sr, self._param_round_seed0, self._param_round_step)
+        _probe_encode(sd, self._whiten, self._probe_seed0, self._probe_step)
         return _guard_encode(sd, self._guard, self.skipped_steps, self.loss_scale.value, self._good_steps)
 
     def load_state_dict(self, sd, *, strict=True, narrow_rounding=None, narrow_seed=None):
@@ -1612,7 +1720,9 @@ class UVd(_StepFeatures):
         saved state (row-sharded: every rank loads the same bytes into the
         synchronised generator; nothing is broadcast again) and, on the native route, so do round_seed0 / round_step.  With
         param_rounding="stochastic", param_round_seed0 / param_round_step are restored where the dict has them; a dict without
-        them leaves this object's seed and sets the counter to 0; a nearest optimizer ignores them.  A guarded
+        them leaves this object's seed and sets the counter to 0; a nearest optimizer ignores them.  With
+        preconditioner_fit="whitening", probe_seed0 / probe_step likewise: restored where the dict has them, this object's seed
+        and a counter of 0 where it has not (a dict of a hessian-fit optimizer); a hessian-fit optimizer ignores them.  A guarded
         optimizer (nonfinite="skip") restores skipped_steps, loss_scale_good_steps and, when both sides scale the loss, loss_scale
         where the dict has them and starts them fresh where it has not (a dict of an unguarded optimizer); an unguarded one
         ignores them.
@@ -1701,6 +1811,7 @@ class UVd(_StepFeatures):
         if self._native and "round_seed0" in sd:
             self._round_seed0, self._round_step = int(sd["round_seed0"]), int(need("round_step"))
         self._param_round_seed0, self._param_round_step = _param_rounding_decode(name, sd, self._param_sr, self._param_round_seed0)
+        self._probe_seed0, self._probe_step = _probe_decode(sd, self._whiten, self._probe_seed0, name)
         self._guard_decode(sd)
         with torch.no_grad():
             if how == "copy":
@@ -1776,7 +1887,14 @@ class UVd(_StepFeatures):
         "dynamic": S starts at 2^16, halves on a skipped step and doubles after loss_scale_growth_interval good steps in a row
         (uvd_loss_scale_next).
         Out of scope: a non-finite value that the state itself produces from finite inputs propagates as before, and the
-        functional preconditioner calls (update_precond_UVd_math_ and the others) are unchanged."""
+        functional preconditioner calls (update_precond_UVd_math_ and the others) are unchanged.
+
+        preconditioner_fit="whitening" (nothing of this runs with "hessian"): a step whose coin says update calls the closure ONCE,
+        takes grads = autograd.grad(scaled(loss), params) and forms h and g from them (_whitening_inputs); the guard, where on,
+        sees the gradients only and a skipped step returns before the probe is drawn: probe_step, U, V, d, the parameters, the
+        momentum buffer and every counter keep their bits.  Then ONE multi_randn launch fills the flat probe (_draw_probe),
+        probe_step advances, and :732-733, :748 run on (v, h, g) = (probe, raw gradient, gradient or momentum buffer).  Nothing is
+        undone in the tail: the parameters were never perturbed.  A step whose coin says no update is the path it always was."""
         params = self._params_with_grad
         if self._group is None:
             update_Q = _draw_branch(float(self.preconditioner_update_probability), self._generator)   # :703
@@ -1788,7 +1906,18 @@ class UVd(_StepFeatures):
         if guard:
             self._stamp = self._stamp % (2 ** 31 - 1) + 1       # 1 .. 2^31 - 1, then 1 again: the flags are never zeroed
         vs = None
-        if update_Q:
+        undo = update_Q and not exact and not self._whiten          # the step carries the perturbation of :723 and takes it back
+        if update_Q and self._whiten:                               # ONE ordinary backward; (v, h) = (counter-based probe, gradient)
+            with torch.enable_grad():
+                closure_returns = closure()
+                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
+            h, grad = self._whitening_inputs(grads, mom, inv)
+            if guard:
+                self._guard_outcome(grad is None)
+                if grad is None:                                    # before the probe is drawn: probe_step does not move
+                    return closure_returns
+            pre_grad = self._precondition(self._draw_probe(), h, grad)
+        elif update_Q:
             if exact:                                                                         # :706-714
                 with torch.enable_grad():
                     closure_returns = closure()
@@ -1843,7 +1972,7 @@ class UVd(_StepFeatures):
             sr_index0 = int(self._row0()) if self._group is not None else 0
         if fused:                                                                             # :750-762 in the step-tail kernels
             sr_kw = dict(rounding="stochastic", rounding_seed=sr_seed, index0=sr_index0) if sr else {}
-            uvd_step_tail(params, pre_grad, float(self.lr_params), max_norm, self._tiny, vs if (not exact) and update_Q else None,
+            uvd_step_tail(params, pre_grad, float(self.lr_params), max_norm, self._tiny, vs if undo else None,
                           self._group, plan=self._tail, weight_decay=wd, **sr_kw)
             return closure_returns
         decay = None
@@ -1867,7 +1996,6 @@ class UVd(_StepFeatures):
                 grad_norm = self._sharded.global_norm(pre_grad, self._group) + self._tiny
             lr = float(self.lr_params) * torch.clamp(max_norm / grad_norm, max=1.0)
         with torch.no_grad():                                                                 # :757-762
-            undo = (not exact) and update_Q
             for k, (p, i, j) in enumerate(zip(params, self._param_sizes, self._param_cumsizes)):
                 _torch_param_update_(p, torch.reshape(pre_grad[j - i:j], p.shape), vs[k] if undo else None, lr, decay, sr_seed,
                                      sr_index0 + j - i)

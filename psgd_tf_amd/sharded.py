@@ -250,7 +250,8 @@ def reshard_uvd_state(state_dicts, new_row_counts):
     """The W state dicts of ONE row-sharded checkpoint (UVd.state_dict() of every rank, in any order) as W' dicts whose row
     counts are new_row_counts: offline, on the CPU, no process group.  The inputs must tile [0, num_params_global) without gap
     or overlap and agree on format, rank, dtypes, route, rounding, hyper, round_seed0 / round_step, param_round_seed0 /
-    param_round_step (the parameters' rounding stream of param_rounding="stochastic": carried through), momentum_step, the keys of a guarded
+    param_round_step (the parameters' rounding stream of param_rounding="stochastic": carried through), probe_seed0 / probe_step
+    (the probe stream of preconditioner_fit="whitening": global, not per-rank, carried through unchanged), momentum_step, the keys of a guarded
     optimizer (nonfinite, skipped_steps, loss_scale, loss_scale_good_steps: carried through as they are) and branch_rng
     (ValueError naming what does not).  momentum_buffer is split by rows as d is when every input dict has one (dropped otherwise).  new_row_counts must sum to num_params_global, and every entry but the last must be a multiple of 64
     (shards start at multiples of 64 rows, see shard_rows).  Output k holds rows [row0', row0' + n') with its own num_params
@@ -266,7 +267,7 @@ def reshard_uvd_state(state_dicts, new_row_counts):
     if first.get("format") != 1:
         raise ValueError("%s: 'format' is %r; this version reads format 1" % (name, first.get("format")))
     for key in ("format", "rank", "num_params_global", "state_dtype", "state_route", "state_rounding", "hyper", "round_seed0",
-                "round_step", "param_round_seed0", "param_round_step", "momentum_step", "nonfinite", "skipped_steps", "loss_scale",
+                "round_step", "param_round_seed0", "param_round_step", "probe_seed0", "probe_step", "momentum_step", "nonfinite", "skipped_steps", "loss_scale",
                 "loss_scale_good_steps"):
         for s in sds[1:]:
             if s.get(key) != first.get(key):

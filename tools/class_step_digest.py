@@ -10,7 +10,7 @@ behind the coin and preconditioner_update_probability=0.5.  The configurations a
     dtype      float32, bfloat16 with param_rounding="nearest", bfloat16 with param_rounding="stochastic"
     features   off, or momentum 0.9 + weight decay + nonfinite="skip" + loss_scale="dynamic" with an Inf gradient in step 3
 
-and class Kron(preconditioner_fit="whitening") on every tail, dtype and feature setting.  The digest covers the parameters, the
+and preconditioner_fit="whitening" of both classes on every tail, dtype and feature setting.  The digest covers the parameters, the
 preconditioner state (U, V, d or the factors), the momentum buffers, skipped_steps, the current loss scale and the counters of
 the rounding and probe streams.  Before anything runs on the device the coins of every configuration are replayed on the CPU
 from the generator alone, and a configuration whose coins (the step with the Inf gradient left out) do not hold both outcomes is
@@ -39,8 +39,8 @@ DTYPES = {"fp32": (torch.float32, "nearest"), "bf16": (torch.bfloat16, "nearest"
 def configurations():
     for cls, tail, hvp, dt, feat in itertools.product(("UVd", "Kron"), ("torch", "fused"), ("exact", "fd"), DTYPES, ("off", "on")):
         yield cls, tail, hvp, dt, feat
-    for tail, dt, feat in itertools.product(("torch", "fused"), DTYPES, ("off", "on")):
-        yield "Kron", tail, "whitening", dt, feat
+    for cls, tail, dt, feat in itertools.product(("Kron", "UVd"), ("torch", "fused"), DTYPES, ("off", "on")):
+        yield cls, tail, "whitening", dt, feat
 
 
 def replayed_coins(cls, hvp, dt, feat):
@@ -91,8 +91,8 @@ def run(cls, tail, hvp, dt, feat, dev):
     kw = dict(lr_params=0.05, lr_preconditioner=0.1, grad_clip_max_norm=1.0, preconditioner_update_probability=P_UPDATE,
               exact_hessian_vector_product=hvp != "fd", step_tail=tail, generator=torch.Generator().manual_seed(SEED),
               param_rounding=rounding, **(FEATURES_ON if feat == "on" else {}))
-    if cls == "UVd":
-        opt = psgd.UVd(params, rank_of_modification=3, **kw)
+    if cls == "UVd":                              # (its Hessian-fit lines are built without the keyword, as before it existed)
+        opt = psgd.UVd(params, rank_of_modification=3, **dict(kw, **({"preconditioner_fit": "whitening"} if hvp == "whitening" else {})))
     else:
         opt = psgd.Kron(params, any_rank=True, preconditioner_fit="whitening" if hvp == "whitening" else "hessian", **kw)
     coins = ""
@@ -105,7 +105,9 @@ def run(cls, tail, hvp, dt, feat, dev):
     moms = opt._m if isinstance(opt._m, list) else [] if opt._m is None else [opt._m]
     for t in params + state_tensors(opt) + moms:
         h.update(raw(t))
-    h.update(repr((opt.skipped_steps, opt.loss_scale.value, opt._param_round_step, getattr(opt, "probe_step", None))).encode())
+    # (a Hessian-fit UVd hashes None for the probe counter, as it did when the class had none: its lines stay comparable)
+    probe_step = None if cls == "UVd" and hvp != "whitening" else opt.probe_step
+    h.update(repr((opt.skipped_steps, opt.loss_scale.value, opt._param_round_step, probe_step)).encode())
     return h.hexdigest(), coins
 
 

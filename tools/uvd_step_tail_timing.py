@@ -22,6 +22,11 @@ Peak memory: torch.cuda.max_memory_allocated over three further steps minus what
                                                               # the 16-byte host read), with a loss scale, and both with momentum=0.9
                                                               # (one more read of the gradients); the legs alternate, --rounds times
     python tools/uvd_step_tail_timing.py --guard --legs plain --root OTHER      # the plain leg of a checkout without the arguments
+    python tools/uvd_step_tail_timing.py --whitening          # the same shapes: preconditioner_fit="whitening" against the exact and
+                                                              # the finite-difference Hessian steps, legs alternating, --rounds times
+    python tools/uvd_step_tail_timing.py --whitening --parent-module FILE       # ... and the default (exact) step of the parent
+                                                              # commit's module (its preconditioned_stochastic_gradient_descent.py,
+                                                              # loaded next to this one on the same library) as the leg "parent"
 """
 import argparse
 import os
@@ -146,6 +151,48 @@ def guard_table(a):
             print(row, flush=True)
 
 
+WHITENING_LEGS = {"whitening": {"preconditioner_fit": "whitening"}, "exact": {}, "fd": {"exact_hessian_vector_product": False},
+                  "parent": {}}
+
+
+def _parent_module(path):
+    """the parent commit's UVd module, loaded as a sibling inside the package (its relative imports resolve to this checkout)"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("psgd_tf_amd._parent_psgd", path)
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules[spec.name] = mod
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def whitening_table(a):
+    """the fused step with the whitening fit (one backward, one multi_randn launch) against the two Hessian steps (a double
+    backward; a second closure call on perturbed parameters), in one job with the legs alternating.  The closure of this tool
+    costs next to nothing, so the difference is the floor of what the second backward costs; "parent": the default step of the
+    parent commit's module, which must equal "exact" to within the spread"""
+    global psgd
+    legs = a.legs.split(",")
+    mine, parent = psgd, _parent_module(a.parent_module) if a.parent_module else None
+    if parent is None:
+        legs = [leg for leg in legs if leg != "parent"]
+    print("# fused tail, fp32, r = 20, 256 tensors, clip on | leg: median step [min .. max] us   (root: %s)" % _root)
+    for N in ([4_000_000] if a.quick else [4_000_000, 100_000_000]):
+        steps = a.steps if N <= 4_000_000 else max(5, a.steps // 4)
+        for rnd in range(a.rounds):
+            row = "N=%d r=20 k=256 float32 round %d |" % (N, rnd)
+            for leg in legs:
+                psgd = parent if leg == "parent" else mine
+                try:
+                    params, opt, closure = build(N, 20, 256, torch.float32, True, "fused", **WHITENING_LEGS[leg])
+                finally:
+                    psgd = mine
+                med, lo, hi = timed(lambda: opt.step(closure), steps, a.chunks, a.warm_seconds)
+                row += " %s: %.1f [%.1f .. %.1f] us |" % (leg, med * 1e6, lo * 1e6, hi * 1e6)
+                del params, opt, closure
+                torch.cuda.empty_cache()
+            print(row, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tail", choices=["torch", "fused", "both"], default="both")
@@ -156,13 +203,18 @@ def main():
     ap.add_argument("--trace", nargs=3, metavar=("N", "K", "TAIL"))
     ap.add_argument("--momentum", action="store_true", help="the momentum / weight-decay table instead of the tail table")
     ap.add_argument("--guard", action="store_true", help="the guarded-step table instead of the tail table")
-    ap.add_argument("--rounds", type=int, default=2, help="with --guard: passes over the legs")
+    ap.add_argument("--whitening", action="store_true", help="the whitening-fit table instead of the tail table")
+    ap.add_argument("--parent-module", default=None, help="with --whitening: the parent commit's UVd module file (leg 'parent')")
+    ap.add_argument("--rounds", type=int, default=2, help="with --guard / --whitening: passes over the legs")
     ap.add_argument("--legs", default=None, help="with --momentum / --guard: which legs (comma-separated; default: all)")
     ap.add_argument("--root", default=None, help="import the package from this checkout instead of the tool's own")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "this tool measures on the GPU"
     if a.legs is None:
-        a.legs = ",".join(GUARD_LEGS if a.guard else MOMENTUM_LEGS)
+        a.legs = ",".join(WHITENING_LEGS if a.whitening else GUARD_LEGS if a.guard else MOMENTUM_LEGS)
+    if a.whitening:
+        assert a.chunks >= 7 and all(leg in WHITENING_LEGS for leg in a.legs.split(","))
+        return whitening_table(a)
     if a.guard:
         assert a.chunks >= 7 and all(leg in GUARD_LEGS for leg in a.legs.split(","))
         return guard_table(a)
