@@ -1,17 +1,15 @@
 // psgd_multi_tail.hip -- the tail of a step on LISTS of fp32 tensors (class Kron: mnist_with_lenet5.py:54-56 and the finite-difference
-// route of psgd.py:716-727, :734-736, :761) on gfx950, whatever the number of tensors.
+// route of psgd.py:716-727, :734-736) on gfx950, whatever the number of tensors; the parameter update itself (psgd_multi_param_update_*)
+// is psgd_param_update.hip.
 //
 //   psgd_multi_sumsq_f32         sum of fl32(x x) over every element of every tensor -> one device double       (the clip norm's square)
-//   psgd_multi_param_update_f32  p <- p - fl32(lr_eff g),  with vs: p <- p - fl32(fl32(lr_eff g) + v);  without g: p <- p + v
 //   psgd_multi_diff_scale_f32    h <- fl32(fl32(a - b) s),  and x <- fl32(v s) when given
 //   psgd_multi_blend_f32         m <- fl32(fl32(beta m) + fl32(omb g));  beta == 0 does not read m                (momentum of class Kron)
 //   psgd_multi_scale_check_f32   one to three lists: x <- fl32(x s_j) where s_j != 1, and a stamp stored to a flag word when a
 //                                product is not finite                                                              (guarded step)
-//   psgd_multi_param_update_wd_f32  the update with decoupled weight decay: delta <- fl32(delta + fl32(fl32(lr_eff wd) p))
 // and, for parameters of type T = bf16 / fp16 (everything else of the step stays fp32):
 //   psgd_multi_widen_check       one to three lists of T tensors -> as many lists of fp32 tensors, dst <- fl32(float(src) s_j), with the
 //                                flag of psgd_multi_scale_check_f32 on the written values
-//   psgd_multi_param_update_t    the update on T parameters and vs, fp32 gradients: the rounding chain of psgd_uvd_param_update_multi_wd
 // and, for the VECTOR LAYERS of class Kron (a rank-1 parameter of length n is the [1, n] layer of the (dense, scaling) format:
 // Ql is 1 x 1, qr is [1, n]; psgd.py:276-322), all k of them in one launch each:
 //   psgd_multi_vec_update_f32    the factor update of psgd.py:276-307 on every (ql, qr), in place
@@ -19,15 +17,10 @@
 // and, for the layers of class Kron(operands="bfloat16") that run on the bf16-operand Kron kernels (psgd_kron_bf16.hip):
 //   psgd_multi_narrow_bf16       one to three lists of fp32 tensors -> as many lists of bf16 tensors, round to nearest even
 //   psgd_multi_sumsq_mixed       psgd_multi_sumsq_f32 on a list whose tensors are fp32 or bf16, tensor by tensor
-//   psgd_multi_param_update_mixed  psgd_multi_param_update_t (for fp32 parameters: _wd_f32) with such a list as the gradients
-// and, for bf16 parameters written with STOCHASTIC rounding (param_rounding="stochastic" of class Kron; these two read `start` of
-// the parameter table):
-//   psgd_multi_param_update_sr        the update formed once in fp32 and narrowed once, fp32 gradients
-//   psgd_multi_param_update_mixed_sr  the same with a mixed list as the gradients
-// and, for the probe vectors of class Kron(preconditioner_fit="whitening") (this one reads `start` of its table too):
+// and, for the probe vectors of class Kron(preconditioner_fit="whitening") (this one reads `start` of its table):
 //   psgd_multi_randn_f32         out <- fl32(scale z), z standard normal, a counter-based draw keyed by (seed, flat element index)
 //
-// The tables are those of psgd_uvd_tail.hip: a SEGMENT is one tensor {pointer, start, count}, a CHUNK one piece of at most
+// The tables are those of tail_common.h: a SEGMENT is one tensor {pointer, start, count}, a CHUNK one piece of at most
 // PSGD_UVD_TAIL_CHUNK consecutive elements of one segment {segment index, offset}.  Here EVERY operand is a list: each has its own
 // segment table, all tables of a call describe tensors of the same sizes, one chunk table serves them all, and `start` is not read.
 // A chunk never runs past the shortest of its segments, whatever the tables say.
@@ -44,7 +37,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "psgd_hip.h"
-#include "tail_types.h"
+#include "tail_common.h"
 #include "bf16_state.h"
 #include "nanmax.h"
 
@@ -53,33 +46,11 @@
 
 namespace psgdm {
 
-constexpr int kT = 256;                    // threads per workgroup
-constexpr int kChunk = PSGD_UVD_TAIL_CHUNK;
-constexpr int kMaxGrid = 2048;             // 8 workgroups per CU; the rest is grid-stride
-constexpr int kSumsqBlocks = 1024;         // partials of the sum of squares: PSGD_MULTI_SUMSQ_WS_BYTES / 8
-static_assert(kSumsqBlocks * 8 == PSGD_MULTI_SUMSQ_WS_BYTES, "workspace constant of the header");
-
-struct Seg {
-  uint64_t ptr;
-  int64_t start, count;
-};
-struct Chunk {
-  int64_t seg, off;
-};
-
-// the vector types, and F32 / BF16 / F16 (the PSGD_DTYPE_* codes) with their conversions and 16-byte accesses: tail_types.h
+// the tables, the launch shape, F32 / BF16 / F16 (the PSGD_DTYPE_* codes) with their conversions and 16-byte accesses: tail_common.h
 using namespace psgdtt;
 
-// elements in front of the first 16-byte boundary at or after p, at most n
-__device__ __forceinline__ int head_of(const void* p, int n) {
-  const int h = (int)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) / 4;
-  return h < n ? h : n;
-}
-// ... for elements of 2 bytes
-__device__ __forceinline__ int head_of_16bit(const void* p, int n) {
-  const int h = (int)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) / 2;
-  return h < n ? h : n;
-}
+constexpr int kSumsqBlocks = 1024;         // partials of the sum of squares: PSGD_MULTI_SUMSQ_WS_BYTES / 8
+static_assert(kSumsqBlocks * 8 == PSGD_MULTI_SUMSQ_WS_BYTES, "workspace constant of the header");
 
 // One chunk of a call: its element count (0: nothing to do) and the element pointers of up to five operands.
 template <int kOps>
@@ -110,17 +81,6 @@ __device__ __forceinline__ Piece<kOps> piece_of(const Seg* const (&tabs)[kOps], 
 }
 
 // ------------------------------------------------------------------------------------------------------------- sum of squares
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) lds[w] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < kT / 64; ++k) s += lds[k];
-  return s;
-}
-
 __global__ __launch_bounds__(kT) void k_multi_sumsq_partial(const Seg* __restrict__ segs, const Chunk* __restrict__ chunks,
                                                             int64_t nchunks, int k, double* __restrict__ partial) {
   __shared__ double lds[kT / 64];
@@ -131,87 +91,10 @@ __global__ __launch_bounds__(kT) void k_multi_sumsq_partial(const Seg* __restric
     const Piece<1> pc = piece_of<1>(tabs, chunks[c], k);
     const int n = pc.n;
     if (n <= 0) continue;
-    const float* x = pc.p[0];
-    const int head = head_of(x, n);
-    const int nvec = (n - head) / 4;
-    if (t < head) acc += (double)(x[t] * x[t]);
-#pragma unroll 2
-    for (int g = t; g < nvec; g += kT) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(x + head + 4 * g);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc += (double)(v[e] * v[e]);
-    }
-    const int i = head + nvec * 4 + t;
-    if (i < n) acc += (double)(x[i] * x[i]);
+    acc = sumsq_piece_f32(acc, pc.p[0], n, t);
   }
   const double s = block_sum(acc, lds);
   if (t == 0) partial[blockIdx.x] = s;
-}
-
-__global__ __launch_bounds__(kT) void k_multi_sumsq_fold(const double* __restrict__ partial, int n, double* __restrict__ out) {
-  __shared__ double lds[kT / 64];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < n; i += kT) acc += partial[i];
-  const double s = block_sum(acc, lds);
-  if (threadIdx.x == 0) out[0] = s;
-}
-
-// ------------------------------------------------------------------------------------------------------------ parameter update
-// kPre: delta = fl32(lr_eff g); kVs: delta = fl32(delta + v); kWd: delta = fl32(delta + fl32(c p)), c = fl32(lr_eff wd);
-// p = fl32(p - delta).  !kPre (kVs): p = fl32(p + v).  Every product, sum and difference is rounded on its own.
-template <bool kPre, bool kVs, bool kWd>
-__device__ __forceinline__ float update_one(float p, float g, float v, float lr_eff, float c) {
-  if constexpr (!kPre) {
-    return p + v;
-  } else {
-    float delta = lr_eff * g;
-    if constexpr (kVs) delta = delta + v;
-    if constexpr (kWd) {
-      const float decay = c * p;
-      delta = delta + decay;
-    }
-    return p - delta;
-  }
-}
-
-template <bool kPre, bool kVs, bool kWd = false>
-__global__ __launch_bounds__(kT) void k_multi_param_update(const Seg* __restrict__ psegs, const Seg* __restrict__ gsegs,
-                                                           const Seg* __restrict__ vsegs, const Chunk* __restrict__ chunks,
-                                                           int64_t nchunks, int k, float lr, const double* __restrict__ sumsq,
-                                                           float max_norm, float tiny, float wd) {
-  const int t = threadIdx.x;
-  float lr_eff = lr;
-  if (kPre && sumsq) {        // lr_eff = fl32(lr * min(max_norm / (sqrt(sumsq) + tiny), 1)) in fp64, one rounding
-    // the minimum propagates NaN as torch.minimum does: a NaN norm makes lr_eff, and with it every parameter, NaN
-    const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
-    lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
-  }
-  const float decay_c = kWd ? lr_eff * wd : 0.f;         // c = fl32(lr_eff wd)
-  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    const Seg* const tabs[3] = {psegs, kPre ? gsegs : nullptr, kVs ? vsegs : nullptr};
-    const Piece<3> pc = piece_of<3>(tabs, chunks[c], k);
-    const int n = pc.n;
-    if (n <= 0) continue;
-    float* p = pc.p[0];
-    const float* g = pc.p[1];
-    const float* v = pc.p[2];
-    const int head = head_of(p, n);
-    const int nvec = (n - head) / 4;
-    if (t < head) p[t] = update_one<kPre, kVs, kWd>(p[t], kPre ? g[t] : 0.f, kVs ? v[t] : 0.f, lr_eff, decay_c);
-#pragma unroll 2
-    for (int q = t; q < nvec; q += kT) {
-      const int i = head + q * 4;
-      f32x4 x = *reinterpret_cast<const f32x4*>(p + i);
-      f32x4 gg = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (kPre) gg = *reinterpret_cast<const f32x4_u*>(g + i);
-      if constexpr (kVs) vv = *reinterpret_cast<const f32x4_u*>(v + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) x[e] = update_one<kPre, kVs, kWd>(x[e], gg[e], vv[e], lr_eff, decay_c);
-      *reinterpret_cast<f32x4*>(p + i) = x;
-    }
-    const int i = head + nvec * 4 + t;
-    if (i < n) p[i] = update_one<kPre, kVs, kWd>(p[i], kPre ? g[i] : 0.f, kVs ? v[i] : 0.f, lr_eff, decay_c);
-  }
 }
 
 // ------------------------------------------------------------------------------------------------------- difference and scale
@@ -232,7 +115,7 @@ __global__ __launch_bounds__(kT) void k_multi_diff_scale(const Seg* __restrict__
     float* h = pc.p[2];
     const float* v = pc.p[3];
     float* x = pc.p[4];
-    const int head = head_of(h, n);
+    const int head = head_of<4>(h, n);
     const int nvec = (n - head) / 4;
     if (t < head) {
       const float d = a[t] - b[t];
@@ -292,7 +175,7 @@ __global__ __launch_bounds__(kT) void k_multi_blend(const Seg* __restrict__ mseg
     if (n <= 0) continue;
     float* m = pc.p[0];
     const float* g = pc.p[1];
-    const int head = head_of(m, n);
+    const int head = head_of<4>(m, n);
     const int nvec = (n - head) / 4;
     if (t < head) m[t] = blend_one<kRead>(kRead ? m[t] : 0.f, g[t], beta, omb);
 #pragma unroll 2
@@ -311,15 +194,12 @@ __global__ __launch_bounds__(kT) void k_multi_blend(const Seg* __restrict__ mseg
 }
 
 // ------------------------------------------------------------------------------------------------------------- scale and check
-// The non-finite predicate of the guarded step, on a value as it is formed: exponent all ones (+-Inf, NaN).
-__device__ __forceinline__ bool not_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) == 0x7F800000u; }
-
 // one list inside one chunk: y = fl32(x s), stored in place where s != 1 (a list with s == 1 is only read); returns whether a y of
 // this lane is not finite.  Every list is its own stored operand: head, body and tail are laid on its own 16-byte boundaries.
 __device__ __forceinline__ bool scale_check_list(float* x, int n, float s, int t) {
   const bool store = s != 1.f;
   bool bad = false;
-  const int head = head_of(x, n);
+  const int head = head_of<4>(x, n);
   const int nvec = (n - head) / 4;
   if (t < head) {
     const float y = x[t] * s;
@@ -374,7 +254,7 @@ __global__ __launch_bounds__(kT) void k_multi_scale_check(const Seg* __restrict_
 template <class T>
 __device__ __forceinline__ bool widen_list(const uint16_t* src, float* dst, int n, float s, int t) {
   bool bad = false;
-  const int head = head_of(dst, n);
+  const int head = head_of<4>(dst, n);
   const int nvec = (n - head) / 4;
   if (t < head) {
     const float y = T::widen(src[t]) * s;
@@ -438,96 +318,6 @@ __global__ __launch_bounds__(kT) void k_multi_widen_check(const Seg* __restrict_
       if (srcs[j]) bad |= widen_list<T>(sp[j], dp[j], n, scales[j], t);
   }
   if (flag != nullptr && bad) *reinterpret_cast<volatile int32_t*>(flag) = stamp;
-}
-
-// --------------------------------------------------------------------------------- half-precision parameters: the typed update
-// The rounding chain of psgd_uvd_param_update_multi_wd (k_uvd_param_update) with the gradients in a list of fp32 tensors:
-// delta = T(fl32(lr_eff g)); kVs: delta = T(delta + v); kWd: delta = T(delta + T(fl32(c p))), c = fl32(lr_eff wd); the caller
-// narrows p - delta.  !kPre: p + v.  kOpaque (the scalar head and tail): the products reach the narrowing as rounded fp32 values
-// in a register -- left to itself hipcc selects v_fma_mixlo_f16 x, y, 0 for the float16 narrow(x * y), and the +0 addend turns a -0
-// product into +0 (see psgd_uvd_tail.hip, where the same chain is tested for it).
-template <class T, bool kPre, bool kVs, bool kWd, bool kOpaque = false>
-__device__ __forceinline__ float update_one_t(float p, float g, float v, float lr_eff, float c) {
-  if constexpr (!kPre) {
-    return p + v;
-  } else {
-    float prod = lr_eff * g;
-    if constexpr (kOpaque) asm("" : "+v"(prod));
-    float delta = T::widen(T::narrow(prod));
-    if constexpr (kVs) delta = T::widen(T::narrow(delta + v));
-    if constexpr (kWd) {
-      float dec = c * p;
-      if constexpr (kOpaque) asm("" : "+v"(dec));
-      delta = T::widen(T::narrow(delta + T::widen(T::narrow(dec))));
-    }
-    return p - delta;
-  }
-}
-
-// parameters and vs of type T (bf16 / fp16), gradients fp32.  The stored side is p: a scalar head to its 16-byte boundary, a body of
-// 8 elements (16 bytes) per lane and access, a scalar tail; g (two 16-byte reads) and v go through the element-aligned types.
-template <class T, bool kPre, bool kVs, bool kWd>
-__global__ __launch_bounds__(kT) void k_multi_param_update_t(const Seg* __restrict__ psegs, const Seg* __restrict__ gsegs,
-                                                             const Seg* __restrict__ vsegs, const Chunk* __restrict__ chunks,
-                                                             int64_t nchunks, int k, float lr, const double* __restrict__ sumsq,
-                                                             float max_norm, float tiny, float wd) {
-  static_assert(T::E == 8, "bf16 / fp16 only: the fp32 lists keep k_multi_param_update");
-  const int t = threadIdx.x;
-  float lr_eff = lr;
-  if (kPre && sumsq) {        // as k_multi_param_update: fp64, one rounding, a NaN norm propagates
-    const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
-    lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
-  }
-  const float dc = kWd ? lr_eff * wd : 0.f;         // c = fl32(lr_eff wd)
-  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    const Chunk ch = chunks[c];
-    if ((uint64_t)ch.seg >= (uint64_t)k || ch.off < 0) continue;
-    const Seg ps = psegs[ch.seg];
-    int64_t left = ps.count - ch.off;
-    left = left < kChunk ? left : kChunk;
-    uint16_t* p = reinterpret_cast<uint16_t*>(ps.ptr) + ch.off;
-    const float* g = nullptr;
-    const uint16_t* v = nullptr;
-    if constexpr (kPre) {
-      const Seg gs = gsegs[ch.seg];
-      const int64_t l = gs.count - ch.off;
-      left = l < left ? l : left;
-      g = reinterpret_cast<const float*>(gs.ptr) + ch.off;
-    }
-    if constexpr (kVs) {
-      const Seg vsg = vsegs[ch.seg];
-      const int64_t l = vsg.count - ch.off;
-      left = l < left ? l : left;
-      v = reinterpret_cast<const uint16_t*>(vsg.ptr) + ch.off;
-    }
-    if (left <= 0) continue;
-    const int n = (int)left;
-    const int head = head_of_16bit(p, n);
-    const int nvec = (n - head) / 8;
-    if (t < head)
-      p[t] = T::narrow(update_one_t<T, kPre, kVs, kWd, true>(T::widen(p[t]), kPre ? g[t] : 0.f, kVs ? T::widen(v[t]) : 0.f, lr_eff, dc));
-#pragma unroll 2
-    for (int q = t; q < nvec; q += kT) {
-      const int i = head + q * 8;
-      float x[8], gg[8], vv[8];
-      load_16<T>(p + i, x);
-      if constexpr (kPre) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          const f32x4_u w = *reinterpret_cast<const f32x4_u*>(g + i + 4 * b);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) gg[4 * b + e] = w[e];
-        }
-      }
-      if constexpr (kVs) load_any<T>(v + i, vv);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = update_one_t<T, kPre, kVs, kWd>(x[e], kPre ? gg[e] : 0.f, kVs ? vv[e] : 0.f, lr_eff, dc);
-      store_16<T>(p + i, x);
-    }
-    const int i = head + nvec * 8 + t;
-    if (i < n)
-      p[i] = T::narrow(update_one_t<T, kPre, kVs, kWd, true>(T::widen(p[i]), kPre ? g[i] : 0.f, kVs ? T::widen(v[i]) : 0.f, lr_eff, dc));
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- vector layers
@@ -703,7 +493,7 @@ __global__ __launch_bounds__(kT) void k_multi_vec_apply(const Seg* __restrict__ 
     float* out = reinterpret_cast<float*>(so.ptr);
     const float ql = reinterpret_cast<const float*>(sl.ptr)[0];
     const float ql2 = ql * ql;
-    vec_sweep(n, head_of(out, n), t,
+    vec_sweep(n, head_of<4>(out, n), t,
               [&](int i) {
                 const float r = qr[i];
                 out[i] = (ql2 * g[i]) * (r * r);
@@ -724,7 +514,7 @@ __global__ __launch_bounds__(kT) void k_multi_vec_apply(const Seg* __restrict__ 
 // range -> +-Inf).  The stored side is dst: a scalar head to its 16-byte boundary, a body of 8 elements per lane and access (two
 // 16-byte reads of src through the element-aligned type, one 16-byte store), a scalar tail.
 __device__ __forceinline__ void narrow_list(const float* src, uint16_t* dst, int n, int t) {
-  const int head = head_of_16bit(dst, n);
+  const int head = head_of<2>(dst, n);
   const int nvec = (n - head) / 8;
   if (t < head) dst[t] = BF16::narrow(src[t]);
 #pragma unroll 2
@@ -777,7 +567,7 @@ __global__ __launch_bounds__(kT) void k_multi_narrow_bf16(const Seg* __restrict_
 
 // The MIXED lists: every segment of the gradient list is fp32 or bf16, and its `start` field -- which no list kernel reads --
 // holds its PSGD_DTYPE_* code.  A segment with any other code moves nothing: the tables live on the device and the host cannot
-// judge them.
+// judge them.  (The update that takes such a list: GradMixed of psgd_param_update.hip.)
 
 // k_multi_sumsq_partial on a mixed list.  An fp32 segment is summed exactly as there (the same lanes take the same elements in the
 // same order: the same bits).  A bf16 segment is summed as that kernel sums a 16-BYTE ALIGNED fp32 tensor of the widened values --
@@ -797,18 +587,7 @@ __global__ __launch_bounds__(kT) void k_multi_sumsq_partial_mixed(const Seg* __r
     if (left <= 0) continue;
     const int n = (int)left;
     if (s.start == PSGD_DTYPE_F32) {
-      const float* x = reinterpret_cast<const float*>(s.ptr) + ch.off;
-      const int head = head_of(x, n);
-      const int nvec = (n - head) / 4;
-      if (t < head) acc += (double)(x[t] * x[t]);
-#pragma unroll 2
-      for (int g = t; g < nvec; g += kT) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + head + 4 * g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc += (double)(v[e] * v[e]);
-      }
-      const int i = head + nvec * 4 + t;
-      if (i < n) acc += (double)(x[i] * x[i]);
+      acc = sumsq_piece_f32(acc, reinterpret_cast<const float*>(s.ptr) + ch.off, n, t);
     } else if (s.start == PSGD_DTYPE_BF16) {
       const uint16_t* x = reinterpret_cast<const uint16_t*>(s.ptr) + ch.off;
       const int nvec = n / 4;
@@ -830,182 +609,6 @@ __global__ __launch_bounds__(kT) void k_multi_sumsq_partial_mixed(const Seg* __r
   }
   const double s = block_sum(acc, lds);
   if (t == 0) partial[blockIdx.x] = s;
-}
-
-// elements in front of the first 16-byte boundary at or after p for elements of type T, at most n
-template <class T>
-__device__ __forceinline__ int head_of_t(const void* p, int n) {
-  const int h = (int)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) / (int)sizeof(typename T::raw);
-  return h < n ? h : n;
-}
-
-// one gradient element, and E consecutive ones from an address aligned to the element only, of a mixed segment as floats
-__device__ __forceinline__ float grad_at(const void* g, bool bf, int i) {
-  return bf ? BF16::widen(reinterpret_cast<const uint16_t*>(g)[i]) : reinterpret_cast<const float*>(g)[i];
-}
-template <int E>
-__device__ __forceinline__ void load_grad(const void* g, bool bf, int i, float (&gg)[E]) {
-  if (!bf) {
-#pragma unroll
-    for (int b = 0; b < E / 4; ++b) {
-      const f32x4_u w = *reinterpret_cast<const f32x4_u*>(reinterpret_cast<const float*>(g) + i + 4 * b);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) gg[4 * b + e] = w[e];
-    }
-  } else if constexpr (E == 8) {
-    load_any<BF16>(reinterpret_cast<const uint16_t*>(g) + i, gg);
-  } else {
-    const u16x4_u w = *reinterpret_cast<const u16x4_u*>(reinterpret_cast<const uint16_t*>(g) + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) gg[e] = BF16::widen(w[e]);
-  }
-}
-
-// k_multi_param_update (T = F32) and k_multi_param_update_t (T = BF16 / F16) with a mixed gradient list: the rounding chain of
-// update_one_t on float(g), which for T = F32 (widen and narrow are the identity) is that of update_one.  Every product reaches its
-// rounding as an fp32 value in a register (kOpaque, head, body and tail alike).  Parameters and vs of type T; the stored side is p.
-template <class T, bool kVs, bool kWd>
-__global__ __launch_bounds__(kT) void k_multi_param_update_mixed(const Seg* __restrict__ psegs, const Seg* __restrict__ gsegs,
-                                                                 const Seg* __restrict__ vsegs, const Chunk* __restrict__ chunks,
-                                                                 int64_t nchunks, int k, float lr, const double* __restrict__ sumsq,
-                                                                 float max_norm, float tiny, float wd) {
-  using raw = typename T::raw;
-  constexpr int E = T::E;
-  const int t = threadIdx.x;
-  float lr_eff = lr;
-  if (sumsq) {                // as k_multi_param_update: fp64, one rounding, a NaN norm propagates
-    const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
-    lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
-  }
-  const float dc = kWd ? lr_eff * wd : 0.f;         // c = fl32(lr_eff wd)
-  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    const Chunk ch = chunks[c];
-    if ((uint64_t)ch.seg >= (uint64_t)k || ch.off < 0) continue;
-    const Seg ps = psegs[ch.seg];
-    const Seg gs = gsegs[ch.seg];
-    if (gs.start != PSGD_DTYPE_F32 && gs.start != PSGD_DTYPE_BF16) continue;
-    const bool bf = gs.start == PSGD_DTYPE_BF16;
-    int64_t left = ps.count - ch.off;
-    left = left < kChunk ? left : kChunk;
-    {
-      const int64_t l = gs.count - ch.off;
-      left = l < left ? l : left;
-    }
-    raw* p = reinterpret_cast<raw*>(ps.ptr) + ch.off;
-    const void* g = reinterpret_cast<const char*>(gs.ptr) + ch.off * (bf ? 2 : 4);
-    const raw* v = nullptr;
-    if constexpr (kVs) {
-      const Seg vsg = vsegs[ch.seg];
-      const int64_t l = vsg.count - ch.off;
-      left = l < left ? l : left;
-      v = reinterpret_cast<const raw*>(vsg.ptr) + ch.off;
-    }
-    if (left <= 0) continue;
-    const int n = (int)left;
-    const int head = head_of_t<T>(p, n);
-    const int nvec = (n - head) / E;
-    if (t < head)
-      p[t] = T::narrow(update_one_t<T, true, kVs, kWd, true>(T::widen(p[t]), grad_at(g, bf, t), kVs ? T::widen(v[t]) : 0.f, lr_eff, dc));
-#pragma unroll 2
-    for (int q = t; q < nvec; q += kT) {
-      const int i = head + q * E;
-      float x[E], gg[E], vv[E];
-      load_16<T>(p + i, x);
-      load_grad<E>(g, bf, i, gg);
-      if constexpr (kVs) load_any<T>(v + i, vv);
-#pragma unroll
-      for (int e = 0; e < E; ++e) x[e] = update_one_t<T, true, kVs, kWd, true>(x[e], gg[e], kVs ? vv[e] : 0.f, lr_eff, dc);
-      store_16<T>(p + i, x);
-    }
-    const int i = head + nvec * E + t;
-    if (i < n)
-      p[i] = T::narrow(update_one_t<T, true, kVs, kWd, true>(T::widen(p[i]), grad_at(g, bf, i), kVs ? T::widen(v[i]) : 0.f, lr_eff, dc));
-  }
-}
-
-// ------------------------------------------------------------------------- bf16 parameters: the update with stochastic rounding
-// psgd_multi_param_update_sr (kMixed false: gradients fp32) and psgd_multi_param_update_mixed_sr (kMixed true: every gradient
-// segment fp32 or bf16 as its `start` says) in ONE kernel, so that the tables are handled in one place.  The update is formed ONCE
-// in fp32 and narrowed ONCE: with w = float(p),  d = fl32(lr_eff * float(g));  kVs: d = fl32(d + float(v));
-// kWd: d = fl32(d + fl32(c * w)), c = fl32(lr_eff * wd);  x = fl32(w - d);  p = narrow_param(x, key, idx)  (bf16_state.h).
-// idx = index0 + the PARAMETER segment's start + the offset inside it -- these kernels, unlike every other list kernel, read
-// `start` of the parameter table: the element's place in the optimizer's flat parameter order.  The launch shape, the chunk loop
-// and the accesses are those of k_multi_param_update_t<BF16> / k_multi_param_update_mixed<BF16>; one hash per element.
-template <bool kVs, bool kWd>
-__device__ __forceinline__ float update_one_sr(float w, float g, float v, float lr_eff, float c) {
-  float d = lr_eff * g;
-  if constexpr (kVs) d = d + v;
-  if constexpr (kWd) {
-    const float dec = c * w;
-    d = d + dec;
-  }
-  return w - d;
-}
-
-template <bool kMixed, bool kVs, bool kWd>
-__global__ __launch_bounds__(kT) void k_multi_param_update_sr(const Seg* __restrict__ psegs, const Seg* __restrict__ gsegs,
-                                                              const Seg* __restrict__ vsegs, const Chunk* __restrict__ chunks,
-                                                              int64_t nchunks, int k, float lr, const double* __restrict__ sumsq,
-                                                              float max_norm, float tiny, float wd, psgd::bf16s::SrKey key,
-                                                              unsigned long long index0) {
-  using T = BF16;
-  constexpr int E = 8;
-  const int t = threadIdx.x;
-  float lr_eff = lr;
-  if (sumsq) {                // as k_multi_param_update: fp64, one rounding, a NaN norm propagates
-    const double ratio = (double)max_norm / (sqrt(sumsq[0]) + (double)tiny);
-    lr_eff = (float)((double)lr * (ratio != ratio ? ratio : (ratio < 1.0 ? ratio : 1.0)));
-  }
-  const float dc = kWd ? lr_eff * wd : 0.f;         // c = fl32(lr_eff wd)
-  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    const Chunk ch = chunks[c];
-    if ((uint64_t)ch.seg >= (uint64_t)k || ch.off < 0) continue;
-    const Seg ps = psegs[ch.seg];
-    const Seg gs = gsegs[ch.seg];
-    if (kMixed && gs.start != PSGD_DTYPE_F32 && gs.start != PSGD_DTYPE_BF16) continue;
-    const bool bf = kMixed && gs.start == PSGD_DTYPE_BF16;
-    int64_t left = ps.count - ch.off;
-    left = left < kChunk ? left : kChunk;
-    {
-      const int64_t l = gs.count - ch.off;
-      left = l < left ? l : left;
-    }
-    uint16_t* p = reinterpret_cast<uint16_t*>(ps.ptr) + ch.off;
-    const void* g = reinterpret_cast<const char*>(gs.ptr) + ch.off * (bf ? 2 : 4);
-    const uint16_t* v = nullptr;
-    if constexpr (kVs) {
-      const Seg vsg = vsegs[ch.seg];
-      const int64_t l = vsg.count - ch.off;
-      left = l < left ? l : left;
-      v = reinterpret_cast<const uint16_t*>(vsg.ptr) + ch.off;
-    }
-    if (left <= 0) continue;
-    const int n = (int)left;
-    const unsigned long long idx0 = index0 + (unsigned long long)(ps.start + ch.off);
-    const int head = head_of_16bit(p, n);
-    const int nvec = (n - head) / E;
-    if (t < head)
-      p[t] = (uint16_t)psgd::bf16s::narrow_param(
-          update_one_sr<kVs, kWd>(T::widen(p[t]), grad_at(g, bf, t), kVs ? T::widen(v[t]) : 0.f, lr_eff, dc), key, idx0 + t);
-#pragma unroll 2
-    for (int q = t; q < nvec; q += kT) {
-      const int i = head + q * E;
-      float x[E], gg[E], vv[E];
-      load_16<T>(p + i, x);
-      load_grad<E>(g, bf, i, gg);
-      if constexpr (kVs) load_any<T>(v + i, vv);
-      u16x8 y;
-#pragma unroll
-      for (int e = 0; e < E; ++e)
-        y[e] = (uint16_t)psgd::bf16s::narrow_param(update_one_sr<kVs, kWd>(x[e], gg[e], kVs ? vv[e] : 0.f, lr_eff, dc), key,
-                                                   idx0 + (unsigned)(i + e));
-      *reinterpret_cast<u16x8*>(p + i) = y;
-    }
-    const int i = head + nvec * E + t;
-    if (i < n)
-      p[i] = (uint16_t)psgd::bf16s::narrow_param(
-          update_one_sr<kVs, kWd>(T::widen(p[i]), grad_at(g, bf, i), kVs ? T::widen(v[i]) : 0.f, lr_eff, dc), key, idx0 + (unsigned)i);
-  }
 }
 
 // ------------------------------------------------------------------------------------------- probe vectors: counter-based normals
@@ -1060,7 +663,7 @@ __global__ __launch_bounds__(kT) void k_multi_randn(const Seg* __restrict__ segs
     const int n = (int)left;
     float* out = reinterpret_cast<float*>(sg.ptr) + ch.off;
     const uint64_t i0 = index0 + (uint64_t)(sg.start + ch.off);
-    const int head = head_of(out, n);
+    const int head = head_of<4>(out, n);
     const int nvec = (n - head) / 4;
     if (t < head) out[t] = randn_one(K, i0 + (unsigned)t, scale);
     const bool odd = ((i0 + (unsigned)head) & 1ull) != 0;              // the same for every group of four of this piece
@@ -1088,81 +691,6 @@ __global__ __launch_bounds__(kT) void k_multi_randn(const Seg* __restrict__ segs
   }
 }
 
-static int grid_for(int64_t nchunks) { return (int)(nchunks < kMaxGrid ? nchunks : kMaxGrid); }
-
-// the two stochastic entry points: argument checks of psgd_multi_param_update_mixed (a gradient list is required: the perturbation
-// p + v and its undo round to nearest), bf16 parameters only, index0 >= 0
-template <bool kMixed>
-static int update_sr_entry(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
-                           int64_t nchunks, int dtype, float lr, const double* sumsq, float max_norm, float tiny, float wd,
-                           uint64_t seed, int64_t index0, void* stream) {
-  if (dtype != PSGD_DTYPE_BF16 || index0 < 0) return PSGD_ERR_BAD_ARG;
-  if (!param_segs || !grad_segs || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
-  if (nchunks == 0) return PSGD_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for(nchunks);
-  const Seg* ps = (const Seg*)param_segs;
-  const Seg* gs = (const Seg*)grad_segs;
-  const Seg* vsg = (const Seg*)vs_segs;
-  const Chunk* ch = (const Chunk*)chunks;
-  const psgd::bf16s::SrKey key = psgd::bf16s::make_key(seed, 16u);          // tensor id 16: the parameters (bf16_state.h)
-  const unsigned long long i0 = (unsigned long long)index0;
-#define PSGD_MULTI_UPDATE_SR(VS, WD)                                                                                             \
-  hipLaunchKernelGGL((k_multi_param_update_sr<kMixed, VS, WD>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, \
-                     sumsq, max_norm, tiny, wd, key, i0)
-  if (wd != 0.f) {                           // (a NaN wd decays too: it propagates)
-    if (vsg)
-      PSGD_MULTI_UPDATE_SR(true, true);
-    else
-      PSGD_MULTI_UPDATE_SR(false, true);
-  } else if (vsg)
-    PSGD_MULTI_UPDATE_SR(true, false);
-  else
-    PSGD_MULTI_UPDATE_SR(false, false);
-#undef PSGD_MULTI_UPDATE_SR
-  return hipGetLastError() == hipSuccess ? PSGD_OK : PSGD_ERR_LAUNCH;
-}
-
-template <class T>
-static void launch_update_mixed(int grid, hipStream_t st, const Seg* ps, const Seg* gs, const Seg* vsg, const Chunk* ch,
-                                int64_t nchunks, int k, float lr, const double* sumsq, float max_norm, float tiny, float wd) {
-#define PSGD_MULTI_UPDATE_MIXED(VS, WD)                                                                                         \
-  hipLaunchKernelGGL((k_multi_param_update_mixed<T, VS, WD>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, \
-                     sumsq, max_norm, tiny, wd)
-  if (wd != 0.f) {                           // (a NaN wd decays too: it propagates)
-    if (vsg)
-      PSGD_MULTI_UPDATE_MIXED(true, true);
-    else
-      PSGD_MULTI_UPDATE_MIXED(false, true);
-  } else if (vsg)
-    PSGD_MULTI_UPDATE_MIXED(true, false);
-  else
-    PSGD_MULTI_UPDATE_MIXED(false, false);
-#undef PSGD_MULTI_UPDATE_MIXED
-}
-
-template <class T>
-static void launch_update_t(int grid, hipStream_t st, const Seg* ps, const Seg* gs, const Seg* vsg, const Chunk* ch, int64_t nchunks,
-                            int k, float lr, const double* sumsq, float max_norm, float tiny, float wd) {
-#define PSGD_MULTI_UPDATE_T(PRE, VS, WD)                                                                                         \
-  hipLaunchKernelGGL((k_multi_param_update_t<T, PRE, VS, WD>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, \
-                     sumsq, max_norm, tiny, wd)
-  if (!gs)
-    PSGD_MULTI_UPDATE_T(false, true, false);
-  else if (wd != 0.f) {                      // (a NaN wd decays too: it propagates)
-    if (vsg)
-      PSGD_MULTI_UPDATE_T(true, true, true);
-    else
-      PSGD_MULTI_UPDATE_T(true, false, true);
-  } else if (vsg)
-    PSGD_MULTI_UPDATE_T(true, true, false);
-  else
-    PSGD_MULTI_UPDATE_T(true, false, false);
-#undef PSGD_MULTI_UPDATE_T
-}
-
-static int launched() { return hipGetLastError() == hipSuccess ? PSGD_OK : PSGD_ERR_LAUNCH; }
-
 }  // namespace psgdm
 
 using namespace psgdm;
@@ -1178,44 +706,8 @@ int psgd_multi_sumsq_f32(const void* segs, int k, const void* chunks, int64_t nc
   const int nb = (int)(nchunks < kSumsqBlocks ? nchunks : kSumsqBlocks);      // a function of nchunks alone: the partition never changes
   hipLaunchKernelGGL(k_multi_sumsq_partial, dim3(nb), dim3(kT), 0, st, (const Seg*)segs, (const Chunk*)chunks, nchunks, k,
                      (double*)ws);
-  hipLaunchKernelGGL(k_multi_sumsq_fold, dim3(1), dim3(kT), 0, st, (const double*)ws, nb, out);
+  hipLaunchKernelGGL(k_sumsq_fold, dim3(1), dim3(kT), 0, st, (const double*)ws, nb, out);
   return launched();
-}
-
-int psgd_multi_param_update_wd_f32(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
-                                   int64_t nchunks, float lr, const double* sumsq, float max_norm, float tiny, float wd,
-                                   void* stream) {
-  if (!param_segs || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
-  if (!grad_segs && (!vs_segs || sumsq)) return PSGD_ERR_BAD_ARG;            // nothing to do, or a clip norm without a gradient
-  if (!grad_segs && wd != 0.f) return PSGD_ERR_BAD_ARG;                      // the perturbation p + v takes no decay
-  if (nchunks == 0) return PSGD_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const Seg* ps = (const Seg*)param_segs;
-  const Seg* gs = (const Seg*)grad_segs;
-  const Seg* vsg = (const Seg*)vs_segs;
-  const Chunk* ch = (const Chunk*)chunks;
-  const int grid = grid_for(nchunks);
-#define PSGD_MULTI_UPDATE(PRE, VS, WD)                                                                                          \
-  hipLaunchKernelGGL((k_multi_param_update<PRE, VS, WD>), dim3(grid), dim3(kT), 0, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq, \
-                     max_norm, tiny, wd)
-  if (!gs)
-    PSGD_MULTI_UPDATE(false, true, false);
-  else if (wd != 0.f) {                      // (a NaN wd decays too: it propagates)
-    if (vsg)
-      PSGD_MULTI_UPDATE(true, true, true);
-    else
-      PSGD_MULTI_UPDATE(true, false, true);
-  } else if (vsg)
-    PSGD_MULTI_UPDATE(true, true, false);
-  else
-    PSGD_MULTI_UPDATE(true, false, false);
-#undef PSGD_MULTI_UPDATE
-  return launched();
-}
-
-int psgd_multi_param_update_f32(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
-                                int64_t nchunks, float lr, const double* sumsq, float max_norm, float tiny, void* stream) {
-  return psgd_multi_param_update_wd_f32(param_segs, grad_segs, vs_segs, k, chunks, nchunks, lr, sumsq, max_norm, tiny, 0.f, stream);
 }
 
 int psgd_multi_blend_f32(const void* m_segs, const void* g_segs, int k, const void* chunks, int64_t nchunks, float beta, float omb,
@@ -1286,27 +778,6 @@ int psgd_multi_widen_check(const void* src0, const void* src1, const void* src2,
   return launched();
 }
 
-int psgd_multi_param_update_t(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
-                              int64_t nchunks, int dtype, float lr, const double* sumsq, float max_norm, float tiny, float wd,
-                              void* stream) {
-  if (dtype < PSGD_DTYPE_F32 || dtype > PSGD_DTYPE_F16) return PSGD_ERR_BAD_ARG;
-  if (dtype == PSGD_DTYPE_F32)                // every operand fp32: the same kernels, the same bits
-    return psgd_multi_param_update_wd_f32(param_segs, grad_segs, vs_segs, k, chunks, nchunks, lr, sumsq, max_norm, tiny, wd, stream);
-  if (!param_segs || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;
-  if (!grad_segs && (!vs_segs || sumsq)) return PSGD_ERR_BAD_ARG;            // nothing to do, or a clip norm without a gradient
-  if (!grad_segs && wd != 0.f) return PSGD_ERR_BAD_ARG;                      // the perturbation p + v takes no decay
-  if (nchunks == 0) return PSGD_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for(nchunks);
-  if (dtype == PSGD_DTYPE_BF16)
-    launch_update_t<BF16>(grid, st, (const Seg*)param_segs, (const Seg*)grad_segs, (const Seg*)vs_segs, (const Chunk*)chunks, nchunks,
-                          k, lr, sumsq, max_norm, tiny, wd);
-  else
-    launch_update_t<F16>(grid, st, (const Seg*)param_segs, (const Seg*)grad_segs, (const Seg*)vs_segs, (const Chunk*)chunks, nchunks,
-                         k, lr, sumsq, max_norm, tiny, wd);
-  return launched();
-}
-
 int psgd_multi_vec_update_f32(const void* ql_segs, const void* qr_segs, const void* dx_segs, const void* dg_segs, int k,
                               int64_t min_count, float step, float tiny, void* stream) {
   if (!ql_segs || !qr_segs || !dx_segs || !dg_segs || k < 1 || min_count < 2) return PSGD_ERR_BAD_ARG;
@@ -1343,43 +814,8 @@ int psgd_multi_sumsq_mixed(const void* segs, int k, const void* chunks, int64_t 
   const int nb = (int)(nchunks < kSumsqBlocks ? nchunks : kSumsqBlocks);      // the partition of psgd_multi_sumsq_f32
   hipLaunchKernelGGL(k_multi_sumsq_partial_mixed, dim3(nb), dim3(kT), 0, st, (const Seg*)segs, (const Chunk*)chunks, nchunks, k,
                      (double*)ws);
-  hipLaunchKernelGGL(k_multi_sumsq_fold, dim3(1), dim3(kT), 0, st, (const double*)ws, nb, out);
+  hipLaunchKernelGGL(k_sumsq_fold, dim3(1), dim3(kT), 0, st, (const double*)ws, nb, out);
   return launched();
-}
-
-int psgd_multi_param_update_mixed(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
-                                  int64_t nchunks, int dtype, float lr, const double* sumsq, float max_norm, float tiny, float wd,
-                                  void* stream) {
-  if (dtype < PSGD_DTYPE_F32 || dtype > PSGD_DTYPE_F16) return PSGD_ERR_BAD_ARG;
-  if (!param_segs || !grad_segs || !chunks || k < 0 || nchunks < 0) return PSGD_ERR_BAD_ARG;   // (p + v keeps its entry points)
-  if (nchunks == 0) return PSGD_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for(nchunks);
-  const Seg* ps = (const Seg*)param_segs;
-  const Seg* gs = (const Seg*)grad_segs;
-  const Seg* vsg = (const Seg*)vs_segs;
-  const Chunk* ch = (const Chunk*)chunks;
-  if (dtype == PSGD_DTYPE_F32)
-    launch_update_mixed<F32>(grid, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq, max_norm, tiny, wd);
-  else if (dtype == PSGD_DTYPE_BF16)
-    launch_update_mixed<BF16>(grid, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq, max_norm, tiny, wd);
-  else
-    launch_update_mixed<F16>(grid, st, ps, gs, vsg, ch, nchunks, k, lr, sumsq, max_norm, tiny, wd);
-  return launched();
-}
-
-int psgd_multi_param_update_sr(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
-                               int64_t nchunks, int dtype, float lr, const double* sumsq, float max_norm, float tiny, float wd,
-                               uint64_t seed, int64_t index0, void* stream) {
-  return update_sr_entry<false>(param_segs, grad_segs, vs_segs, k, chunks, nchunks, dtype, lr, sumsq, max_norm, tiny, wd, seed, index0,
-                                stream);
-}
-
-int psgd_multi_param_update_mixed_sr(const void* param_segs, const void* grad_segs, const void* vs_segs, int k, const void* chunks,
-                                     int64_t nchunks, int dtype, float lr, const double* sumsq, float max_norm, float tiny, float wd,
-                                     uint64_t seed, int64_t index0, void* stream) {
-  return update_sr_entry<true>(param_segs, grad_segs, vs_segs, k, chunks, nchunks, dtype, lr, sumsq, max_norm, tiny, wd, seed, index0,
-                               stream);
 }
 
 int psgd_multi_randn_f32(const void* out_segs, int k, const void* chunks, int64_t nchunks, uint64_t seed, int64_t index0, float scale,

@@ -1,7 +1,7 @@
-// tail_types.h -- the element types of the step-tail kernels (psgd_uvd_tail.hip, psgd_multi_tail.hip): fp32 / bf16 / fp16 as the
+// tail_types.h -- the element types of the step-tail kernels (psgd_uvd_tail.hip, psgd_multi_tail.hip, psgd_param_update.hip): fp32 / bf16 / fp16 as the
 // PSGD_DTYPE_* codes of the C ABI name them, their conversions to and from float, and 16-byte vector accesses on them.  The
 // conversions are the ones the tests of psgd_uvd_tail.hip pin bit for bit against torch (fp16 subnormals, NaN -> quiet NaN);
-// both files take them from here so that there is one copy.
+// every unit takes them from here so that there is one copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,12 +17,14 @@ typedef uint16_t u16x4_u __attribute__((ext_vector_type(4), aligned(2)));    // 
 // dtype codes of the C ABI
 struct F32 {
   using raw = float;
+  using vec = f32x4;               // 16 bytes of raw
   static constexpr int E = 4;
   static __device__ __forceinline__ float widen(float x) { return x; }
   static __device__ __forceinline__ float narrow(float x) { return x; }
 };
 struct BF16 {
   using raw = uint16_t;
+  using vec = u16x8;
   static constexpr int E = 8;
   static __device__ __forceinline__ float widen(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
   static __device__ __forceinline__ uint16_t narrow(float x) {          // round to nearest even, NaN -> quiet NaN
@@ -33,6 +35,7 @@ struct BF16 {
 };
 struct F16 {
   using raw = uint16_t;
+  using vec = u16x8;
   static constexpr int E = 8;
   static __device__ __forceinline__ float widen(uint16_t b) {
     union { uint16_t u; _Float16 h; } c;
