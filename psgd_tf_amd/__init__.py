@@ -6,6 +6,7 @@ Contents (only what the hot path needs):
   preconditioned_stochastic_gradient_descent.py    host-side mirror of the reference module
   kron.py                                          Kronecker dispatch + formats
   kron_optimizer.py                                class Kron
+  splu_optimizer.py                                class SPLU
   multi_tail.py                                    the multi-tensor (list) kernels of its step tail as functions
   sharded.py                                       row-sharded multi-GPU UVd (torch.distributed / RCCL)
 """

@@ -16,6 +16,7 @@ hello_psgd.py:5) carry over with torch tensors in place of tf tensors:
     precond_grad_UVd_math(U, V, d, g) -> Tensor                        psgd.py:619
     class UVd(...).step(closure)                                       psgd.py:630
     class Kron(...).step(closure)                                      (extension: the train_step of mnist_with_lenet5.py:43-57)
+    class SPLU(...).step(closure)                                      (extension: demo_usage_of_all_preconditioners.py:43-64)
 
 The UVd, sparse-LU and Kron arithmetic runs in hand-written HIP kernels behind the
 C ABI of include/psgd_hip.h (bound in _lib.py).  Tensors must be fp32 and resident on a ROCm
@@ -1528,6 +1529,14 @@ class UVd(_StepFeatures):
             self._V.copy_(V)
             self._d.copy_(d)
 
+    # Shared with class SPLU (splu_optimizer.py), which takes step, _pack_scale, _momentum_buffer, _grad_flat, _grad_cat,
+    # _guarded_grad and _whitening_inputs from this class as they are.  What those seven read on `self`, and so what SPLU provides
+    # too: _params_with_grad, _param_sizes, _param_cumsizes, _device, _generator, _group (None there: no branch on it is entered, so
+    # _sharded and _coins are never touched), _arena (None there, likewise), _tail (a UVdTailPlan or None; its .flags), _stamp,
+    # _fd_inv_scale, _delta_param_scale, _tiny, _m / _m_step, _param_sr, the five _Hyper objects of the constructor, and the methods
+    # _flat(tensors, name, fd_scaled, inv, slot), _draw_probe(), _precondition(v, h, grad) and _row0().  A change to one of the seven
+    # that reads anything else on `self` outside a `_group is not None` / `_arena is not None` branch must give it to SPLU as well;
+    # tests/test_splu_class_cpu.py::test_the_borrowed_step_reads_only_what_splu_provides holds the list.
     def _pack_scale(self, fd_scaled, inv):
         """the scale of a pack: 1 / delta_param_scale (:734-736) where fd_scaled, times inv = 1 / loss_scale, rounded once to fp32"""
         base = self._fd_inv_scale if fd_scaled else 1.0
@@ -2010,3 +2019,7 @@ from .kron_optimizer import multi_blend, multi_scale_check, multi_widen_check  #
 from .kron_optimizer import multi_vec_precond_update, multi_vec_precond_grad, kron_layers  # noqa: E402,F401
 from .kron_optimizer import multi_narrow, kron_operand_layers  # noqa: E402,F401
 from .kron_optimizer import multi_randn  # noqa: E402,F401
+
+# --------------------------------------------------------------------------- sparse-LU optimizer (splu_optimizer.py)
+# (after class UVd, whose step it takes, and after multi_randn)
+from .splu_optimizer import SPLU, splu_initial_factors  # noqa: E402,F401
