@@ -34,6 +34,7 @@ import ctypes
 import os
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1308,269 +1309,128 @@ def _flatten_params(params_with_grad):
     return out
 
 
-class UVd(_StepFeatures):
-    """Low-rank modification (UVd) preconditioner as an optimizer, psgd.py:630-764.
+class _FlatStep(_StepFeatures):
+    """An optimizer that preconditions ONE flat float32 vector (psgd.py:692-764): everything of class UVd and class SPLU but the
+    preconditioner itself -- step(), the flat-vector plumbing behind it, the stages of the constructor and the checkpoint pair.
+    A row-sharded flat vector (group=) is part of this class: its branches read _group, _coins and _sharded.
 
-    Same constructor arguments and defaults as the reference (psgd.py:663-666).  Parameters are
-    torch tensors with requires_grad=True on a ROCm device (the reference's `.trainable` filter,
-    :670, maps to requires_grad).  `step(closure)` returns whatever closure returns (:764).
+    A subclass's __init__ calls _init_params, _init_hypers, _init_tail and _draw_seeds in this order, its own checks between
+    them and every check before _init_tail (the first stage that touches a device), sets _rank, _store_dtype and _state_rounding,
+    and provides
 
-    param_rounding="stochastic" (extension, keyword-only; "nearest" by default: nothing changes; bfloat16 parameters only, anything
-    else is a ValueError before a device is touched).  There is no float32 master copy: the parameter is the bfloat16 tensor, and
-    under round to nearest a weight ignores every update below half its spacing.  With "stochastic" the update of :757-762 is
-    formed once in float32 and narrowed once with the stochastic rounding of the bf16-stored states -- w = float(p),
-    d = fl32(lr_eff g), d = fl32(d + float(v)), d = fl32(d + fl32(c w)), p <- SR(fl32(w - d)) -- on a stream keyed by
-    uvd_step_rounding_seed(seed0, k) and the element's global flat index (psgd_uvd_param_update_multi_sr on the fused tail,
-    param_update_stochastic_ on the torch tail: the same bits).  seed0: param_rounding_seed, or a draw from the generator behind
-    the coins; k counts the steps that wrote the parameters.  The perturbation of :723 and its undo stay round-to-nearest.
-    state_dict() carries param_round_seed0 / param_round_step; param_rounding itself is a constructor choice, like step_tail.
+        _precondition(v, h, grad)      the flat preconditioned gradient; v and h are None on a step that leaves the state alone
+        _flat_region(name, narrow)     where the flat vector `name` lives: "v", "h", "g" of psgd.py:729-730 / :747, "m" the
+                                       momentum buffer, "probe" the probe of the whitening fit.  None: it has no home there -- a
+                                       step vector is then a fresh tensor, "m" and "probe" are made once by this class (_m, _probe).
+                                       narrow: the torch tail asks, for parts that are not float32 yet.  Never None for a step
+                                       vector on the fused tail.  Asked at every call, never cached.
+        _state_encode(sd, host)        state_dict(): adds the subclass's keys to sd
+        _state_judge(sd, name, need, same, **how)    load_state_dict(): judges those keys against this object, changes nothing,
+                                       returns what _state_commit takes
+        _state_commit(judged)          writes the state; it cannot refuse any more"""
 
-    preconditioner_fit="whitening" (extension, keyword-only; "hessian" by default: nothing changes, no new function is called, no
-    new number is drawn; any other value is a ValueError before a device is touched) fits the preconditioner to the GRADIENTS
-    instead of to Hessian-vector products: the update of :732-733 is fed the pair (v, h) = (probe, g), v ~ N(0, I) drawn fresh on
-    every updating step and g the raw flat float32 gradient of this step (1 / loss_scale folded into its pack; never the momentum
-    buffer).  The criterion E[h' P h + v' P^-1 v] is then minimised by P = Q'Q = (E[g g'])^(-1/2) within the UVd form: the
-    preconditioner whitens the gradient (the gradient-whitening fit of the PSGD papers, PAPERS.md).  A step needs ONE ordinary
-    backward pass: no create_graph, no second closure call, no perturbation of the parameters -- so closures whose backward cannot
-    be differentiated again (fused attention kernels, custom Functions marked once_differentiable) train, and the step no longer
-    pays the second backward.  exact_hessian_vector_product is ignored on this route (nothing is rejected).  The probe is this
-    rank's flat float32 vector -- the arena's v region on a placed state, else a buffer made once -- filled by ONE multi_randn
-    launch over one segment on BOTH step tails (there is no torch.randn on this route, no per-tensor probe, and v is never
-    packed): the stream of updating step k is keyed by uvd_step_rounding_seed(probe_seed0, k) and the element's GLOBAL flat index
-    (index0 = this rank's first row), whatever `generator` is, so a row-sharded run draws the rows of the one-process probe;
-    probe_seed0 = probe_seed, or a draw from the generator behind the coins (after the draws of the native state's and the
-    parameters' seeds where those happen; row-sharded, from the synchronised generator: the same on every rank); k = probe_step
-    counts the steps that drew a probe.  Without momentum, on a state that is not placed, h and g are one buffer, packed once (the
-    kernels only read them); with momentum or a placed state each has its own.  The probe is finite by construction and is not
-    judged by the guard; a skipped step returns before it is drawn and leaves probe_step alone.  state_dict() carries probe_seed0
-    / probe_step; preconditioner_fit itself is a constructor choice, like step_tail.  The whitened gradient has roughly unit scale
-    per element, as Adam's update has: lr_params and grad_clip_max_norm tuned for the Hessian fit do NOT carry over."""
+    _HYPER_KEYS = ("lr_params", "lr_preconditioner", "grad_clip_max_norm", "preconditioner_update_probability",
+                   "exact_hessian_vector_product")
 
-    def __init__(self, params_with_grad, rank_of_modification: int = 10, preconditioner_init_scale=1.0,
-                 lr_params=0.01, lr_preconditioner=0.01,
-                 grad_clip_max_norm=None, preconditioner_update_probability=1.0,
-                 exact_hessian_vector_product: bool = True, generator=None, state_dtype=None, group=None,
-                 stage_backend=None, placement="auto", state_route="widen", state_rounding=None, step_tail="torch",
-                 momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
-                 *, param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None):
-        # group (extension, SURVEY 8e): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
-        # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the
-        # concatenation of the ranks' vectors in rank order, and U, V, d hold this rank's rows only.  A step then costs three
-        # collectives: the two exchanges of sharded.update_precond_UVd_math_and_precond_grad (r-dimensional sums, never N-sized
-        # data) and one scalar all-reduce for the clip norm of :753 (none without clipping); the coins of :703, :562, :588 come
-        # from one generator whose state rank 0 broadcasts once.  The closure returns this rank's loss; its gradient and
-        # Hessian-vector product with respect to this rank's parameters are what a model-parallel closure computes.
-        params = _flatten_params(params_with_grad)
-        self._params = self._params_with_grad = [p for p in params if p.requires_grad]       # :670 (one list under both names)
-        p0 = self._params_with_grad[0]
-        self._dtype = p0.dtype                                                               # :671
+    # ------------------------------------------------------------------------------------------- the stages of a constructor
+    def _init_params(self, params_with_grad, generator, param_rounding, preconditioner_fit):
+        """psgd.py:668-671, :684-686 and the two keyword-only switches, judged in this order: the parameters with requires_grad
+        (the reference's .trainable) in tf.nest.flatten order, their dtype and device, their index, param_rounding,
+        preconditioner_fit.  Returns the number of elements."""
+        name = type(self).__name__
+        self._params = self._params_with_grad = [p for p in _flatten_params(params_with_grad) if p.requires_grad]   # one list, two names
+        self._dtype, self._device, self._generator = self._params[0].dtype, self._params[0].device, generator
         if self._dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError("UVd: parameters must be float32, float16 or bfloat16, got %s" % self._dtype)
-        # param_rounding (extension, keyword-only; "nearest" = nothing changes).  The parameters are the only copy of the weights:
-        # there is no fp32 master.  Under round to nearest a bfloat16 weight ignores every update below half its spacing (2^-9 for
-        # a weight near 1), so late in training most updates are lost without a sign of it.  "stochastic" (bfloat16 parameters
-        # only) forms the update of :757-762 once in float32 and narrows it once with the stochastic rounding of the bf16-stored
-        # states (uvd_step_tail(rounding="stochastic"); param_update_stochastic_ on the torch tail, the same bits): unbiased, so
-        # small updates accumulate in expectation.  The stream of step k is keyed by uvd_step_rounding_seed(seed0, k) and the
-        # element's GLOBAL flat index, seed0 = param_rounding_seed or a draw from the generator behind the coins; k counts the steps
-        # that wrote the parameters (a skipped step does not advance it).  The finite-difference perturbation and its undo on a
-        # skipped step stay round-to-nearest.  Judged here, before anything touches a device.
-        self._param_sr = _param_rounding("UVd", param_rounding, self._dtype)
+            raise TypeError("%s: parameters must be float32, float16 or bfloat16, got %s" % (name, self._dtype))
+        self._param_sr = _param_rounding(name, param_rounding, self._dtype)
         self._param_round_seed0, self._param_round_step = None, 0
-        # preconditioner_fit (extension, keyword-only; "hessian" = nothing changes; see the class docstring): judged here too
+        self._round_seed0, self._round_step = None, None        # the stream of a state the kernels round (_draw_seeds)
         self._init_fit(preconditioner_fit)
         self._probe, self._probe_plan = None, None
-        # psgd.py:657-658 allows half-precision parameters.  The preconditioner state U, V, d and all of its arithmetic
-        # stay fp32 here (mixed precision: the HIP kernels compute in fp32; v, Hv and the gradient are widened on the
-        # way in, the preconditioned gradient is narrowed on the way out).  _tiny and the finite-difference scale follow
-        # the parameter dtype as in the reference (:682-683).
-        # state_dtype (extension; default None = fp32): "param" or a torch dtype STORES U, V, d in that type, as the reference does
-        # for half-precision parameters (psgd.py:688-690) -- every step widens them, runs the fp32 kernels and rounds the updated
-        # state back, so the memory held between steps and the rounding of the state once per step are the reference's; its
-        # arithmetic (every TF op in the parameters' type) is not reproduced.
-        self._state_dtype = torch.float32
-        if state_dtype is None:
-            self._store_dtype = torch.float32
-        else:
-            self._store_dtype = self._dtype if state_dtype == "param" else state_dtype
-            if self._store_dtype not in (torch.float32, torch.float16, torch.bfloat16):
-                raise TypeError("UVd: state_dtype must be None, 'param', float32, float16 or bfloat16, got %r" % (state_dtype,))
-        self._device = p0.device
-        r = int(rank_of_modification)
-        if r < 1:
-            raise ValueError("UVd: rank_of_modification must be >= 1, got %d" % r)
-        # state_route (extension): "widen" (default) = the behaviour above for a narrow state_dtype; "native" = a bfloat16 state is
-        # read and written by the bf16-state kernels themselves (psgd_uvd_bf16.hip): no fp32 copies of U, V, d exist at any time.
-        # state_rounding: how those kernels narrow what they write, "stochastic" (default of the native route: under round to
-        # nearest a bf16 d practically stops learning, its increments are below half a spacing) or "nearest".  The seed of step k
-        # is a hash of one seed fixed here (drawn from `generator` when given, the module's branch generator otherwise) and k
-        # (uvd_step_rounding_seed).
-        if state_route not in ("widen", "native"):
-            raise ValueError("UVd: state_route must be 'widen' or 'native', got %r" % (state_route,))
-        self._native = state_route == "native"
-        if self._native:
-            if self._store_dtype != torch.bfloat16:
-                raise ValueError("UVd: state_route='native' needs a bfloat16 state (state_dtype=torch.bfloat16, or 'param' with "
-                                 "bfloat16 parameters), got %s" % (self._store_dtype,))
-            if r > _lib.UVD_MAX_RANK:
-                raise ValueError("UVd: state_route='native' supports ranks up to %d, got %d" % (_lib.UVD_MAX_RANK, r))
-            # row-sharded (group=): this rank's rows in bf16, the staged bf16 kernels of sharded.py -- 4 exchanges per step.  The
-            # bf16 stages exist in the HIP backend only, and the group must be a real process group.
-            if stage_backend is not None:
-                raise ValueError("UVd: state_route='native' runs the HIP stages of its group= only (stage_backend= is not supported)")
-            if group is not None:
-                import torch.distributed as _dist
-                if not (_dist.is_available() and isinstance(group, _dist.ProcessGroup)):
-                    raise ValueError("UVd: state_route='native' needs group= to be a torch.distributed process group, got %r"
-                                     % (type(group),))
-            state_rounding = "stochastic" if state_rounding is None else state_rounding
-            if state_rounding not in _ROUNDINGS:
-                raise ValueError("UVd: state_rounding must be 'stochastic' or 'nearest', got %r" % (state_rounding,))
-        elif state_rounding is not None:
-            raise ValueError("UVd: state_rounding applies to state_route='native' only")
-        self._state_rounding = state_rounding
-        self._group, self._generator = group, generator
-        if group is not None:       # the generator whose state rank 0 broadcasts, once, here: the coins and one seed for all ranks
-            from . import sharded as _sharded
-            self._sharded = _sharded
-            self._coins = _sharded.branch_rng_for(generator, group, self._device)
-        # the construction seeds, from the generator behind the coins: the native state's first, then the parameters', then the
-        # probe's (row-sharded: that generator is the synchronised one, so every rank holds the same probe_seed0)
-        if self._native:
-            self._round_seed0, self._round_step = self._draw_seed(None), 0
-        if self._param_sr:
-            self._param_round_seed0 = self._draw_seed(param_rounding_seed)
-        if self._whiten:
-            self._probe_seed0 = self._draw_seed(probe_seed)
+        self._param_sizes, self._param_cumsizes = uvd_param_index(self._params)
+        return self._param_cumsizes[-1]
+
+    def _init_hypers(self, lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability,
+                     exact_hessian_vector_product, *features):
+        """psgd.py:673-683: the five _Hyper objects; momentum, weight_decay, nonfinite, loss_scale and
+        loss_scale_growth_interval (_init_features, which checks them); the tiny of the clip and the finite-difference scale,
+        which follow the parameters' dtype"""
         self.lr_params = _Hyper(lr_params)                                                   # :673
         self.lr_preconditioner = _Hyper(lr_preconditioner)                                   # :674
         self.grad_clip_max_norm = _Hyper(math.inf if grad_clip_max_norm is None else grad_clip_max_norm)  # :675-678
         self.preconditioner_update_probability = _Hyper(preconditioner_update_probability)  # :679
         self.exact_hessian_vector_product = _Hyper(bool(exact_hessian_vector_product))       # :680
-        # momentum, weight_decay (extensions, off by default; _Hyper objects like the others).  momentum: the flat gradient of :747
-        # is blended into a buffer m that this object keeps, m <- beta_k m + (1 - beta_k) g with beta_k = min(k / (k + 1), momentum)
-        # (the warm-up of the PyTorch PSGD optimizers; k counts the steps blended so far, and a step taken with momentum == 0 sets
-        # it back to 0), and m takes the place of g in :748 -- v, h, the finite-difference undo and the clip norm (now of P m) are
-        # as before.  m is this rank's flat fp32 vector: the arena's g region when the state is placed, one tensor otherwise; with
-        # the fused tail the blend rides on the pack of g (uvd_pack_blend: no flat g exists).  weight_decay (decoupled): the update
-        # of :757-762 gains delta <- T(delta + T(fl32(fl32(lr_eff wd) p))).  Both tails round alike (every operation on its own);
-        # with either one on, the torch tail forms the clipped lr as the kernel does (fp64 from the fp32 squares, one rounding).
-        # nonfinite, loss_scale, loss_scale_growth_interval (extensions, off by default; see step()): "skip" = a step whose v, h or
-        # g holds a non-finite value changes nothing.  All five are checked and stored by _init_features.
-        self._init_features(momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval)
+        self._init_features(*features)
         self._stamp = 0
         self._tiny = torch.finfo(self._dtype).tiny                                           # :682
         self._delta_param_scale = torch.finfo(self._dtype).eps ** 0.5                        # :683
-        self._param_sizes, self._param_cumsizes = uvd_param_index(self._params_with_grad)    # :684-685
-        num_params = self._param_cumsizes[-1]                                                # :686
-        # step_tail (extension): "torch" (default) = the tail of step() as torch expressions, a handful of launches per parameter tensor;
-        # "fused" = the step-tail kernels (uvd_pack, uvd_step_tail): the lists of :729-730, :747 packed into flat vectors that this
-        # object owns (the arena's when the state is placed), the clip norm of :753 and the update of :757-762 in a number of launches
-        # that does not depend on the number of tensors -- the same roundings, so without clipping the same bits.  Parameters that
-        # are not contiguous, or not of one dtype, keep the torch tail for the life of the object (one warning).
+        self._fd_inv_scale = float(np.float32(1.0) / np.float32(self._delta_param_scale))    # what torch's `/ scale` multiplies by
+
+    def _init_tail(self, step_tail):
+        """step_tail: "torch" = the tail of step() as torch expressions, a handful of launches per parameter tensor; "fused" =
+        the step-tail kernels (uvd_pack, uvd_step_tail) on flat vectors, in a number of launches that does not depend on the
+        number of tensors -- the same roundings, so without clipping the same bits.  Parameters that are not contiguous, or not
+        of one dtype, keep the torch tail for the life of the object (one warning).  The plan is the first thing a constructor
+        puts on the device."""
         if step_tail not in ("torch", "fused"):
-            raise ValueError("UVd: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
-        self._tail, self._flat_bufs = None, {}
+            raise ValueError("%s: step_tail must be 'torch' or 'fused', got %r" % (type(self).__name__, step_tail))
+        self._tail = None
         if step_tail == "fused":
-            if all(p.is_contiguous() and p.dtype == self._dtype for p in self._params_with_grad):
+            if all(p.is_contiguous() and p.dtype == self._dtype for p in self._params):
                 self._tail = UVdTailPlan(self._param_sizes, self._dtype, self._device)
-                import numpy as np
-                self._fd_inv_scale = float(np.float32(1.0) / np.float32(self._delta_param_scale))   # what torch's `/ scale` multiplies by
             else:
                 import warnings
-                warnings.warn("UVd: step_tail='fused' needs contiguous parameters of one dtype; this optimizer keeps the torch tail")
-        self._stage_backend, self._num_params_global = stage_backend, num_params
-        if group is not None:
-            self._num_params_global = self._sharded.global_rows(num_params, self._device, group)  # :686 over all ranks (set-up time)
-        uv_scale = (1.0 / (self._num_params_global * r)) ** 0.5                              # :687 (the GLOBAL N)
-        sd = self._state_dtype
-        # placement (extension): "probe" / "packed" carve U, V, d, the workspace, the output and the flat v / h / g vectors of :729-730,
-        # :747 out of allocations owned by this object (placement.UVdArena; "probe" times candidate layouts once and keeps the
-        # fastest: where the WRITTEN streams sit relative to the read ones is worth 5 %); None = plain allocations; "auto" (default)
-        # = "probe" when a factor is at least 1 GiB (the search costs ~0.6 s and allocates up to ~100 GiB while it runs; smaller
-        # states are close to cache-resident and gain little), None below
-        self._arena = None
-        if placement not in (None, "auto", "probe", "packed"):
-            raise ValueError("UVd: placement must be None, 'auto', 'probe' or 'packed', got %r" % (placement,))
-        if placement == "auto":
-            placement = "probe" if 4 * num_params * r >= (1 << 30) else None
-        if placement is not None and self._device.type == "cuda" and self._store_dtype == torch.float32 \
-                and r <= _lib.UVD_MAX_RANK and stage_backend is None:
-            from . import placement as _placement
-            self._arena = (_placement.UVdArena.probe if placement == "probe" else _placement.UVdArena.packed)(
-                num_params, r, self._device)
-        # the keywords of the two calls of step() (_precondition) that never change
-        out = None if self._arena is None else self._arena.out
-        self._apply_kw = dict(group=group, backend=stage_backend) if group is not None else dict(out=out)
-        self._update_kw = dict(self._apply_kw, out=out, generator=generator, rounding=state_rounding or "nearest")
-        if self._arena is not None:
-            self._arena.install_workspace()
-            self._U, self._V, self._d = self._arena.U, self._arena.V, self._arena.d
-            self._U.normal_().mul_(uv_scale)                                                 # :688
-            self._V.normal_().mul_(uv_scale)                                                 # :689
-            self._d.fill_(float(preconditioner_init_scale))                                  # :690
-            return
-        self._U = torch.randn(num_params, r, dtype=sd, device=self._device) * uv_scale       # :688
-        self._V = torch.randn(num_params, r, dtype=sd, device=self._device) * uv_scale       # :689
-        self._d = torch.ones(num_params, 1, dtype=sd, device=self._device) * preconditioner_init_scale  # :690
-        if self._store_dtype != sd:
-            self._U, self._V, self._d = (x.to(self._store_dtype) for x in (self._U, self._V, self._d))
+                warnings.warn("%s: step_tail='fused' needs contiguous parameters of one dtype; this optimizer keeps the torch tail"
+                              % type(self).__name__)
 
-    def _state_fp32(self):
-        """the state the kernels work on: the stored tensors themselves (fp32, or bf16 on the native route), or fp32 copies of a
-        half-precision state"""
-        if self._store_dtype == torch.float32 or self._native:
-            return self._U, self._V, self._d
-        return self._U.float(), self._V.float(), self._d.float()
+    def _draw_seeds(self, rounded_state, param_rounding_seed, probe_seed):
+        """the construction seeds, from the generator behind the coins, in the order of the checkpoint contract: the state's
+        (rounded_state: the kernels round what they store), the parameters', the probe's.  Row-sharded, that generator is the
+        synchronised one (_coins is set before this): every rank holds the same seeds."""
+        if rounded_state:
+            self._round_seed0, self._round_step = self._draw_seed(None), 0
+        if self._param_sr:
+            self._param_round_seed0 = self._draw_seed(param_rounding_seed)
+        if self._whiten:
+            self._probe_seed0 = self._draw_seed(probe_seed)
 
-    def _state_store(self, U, V, d):
-        if self._store_dtype != torch.float32 and not self._native:
-            self._U.copy_(U)
-            self._V.copy_(V)
-            self._d.copy_(d)
+    # ------------------------------------------------------------------------------------------------ the flat vectors of a step
 
-    # Shared with class SPLU (splu_optimizer.py), which takes step, _pack_scale, _momentum_buffer, _grad_flat, _grad_cat,
-    # _guarded_grad and _whitening_inputs from this class as they are.  What those seven read on `self`, and so what SPLU provides
-    # too: _params_with_grad, _param_sizes, _param_cumsizes, _device, _generator, _group (None there: no branch on it is entered, so
-    # _sharded and _coins are never touched), _arena (None there, likewise), _tail (a UVdTailPlan or None; its .flags), _stamp,
-    # _fd_inv_scale, _delta_param_scale, _tiny, _m / _m_step, _param_sr, the five _Hyper objects of the constructor, and the methods
-    # _flat(tensors, name, fd_scaled, inv, slot), _draw_probe(), _precondition(v, h, grad) and _row0().  A change to one of the seven
-    # that reads anything else on `self` outside a `_group is not None` / `_arena is not None` branch must give it to SPLU as well;
-    # tests/test_splu_class_cpu.py::test_the_borrowed_step_reads_only_what_splu_provides holds the list.
     def _pack_scale(self, fd_scaled, inv):
         """the scale of a pack: 1 / delta_param_scale (:734-736) where fd_scaled, times inv = 1 / loss_scale, rounded once to fp32"""
         base = self._fd_inv_scale if fd_scaled else 1.0
         if inv == 1.0:
             return base
-        import numpy as np
         return float(np.float32(base) * np.float32(inv))
 
     def _flat(self, tensors, name, fd_scaled=False, inv=1.0, slot=None):
-        """psgd.py:729-730, :747: the per-parameter tensors as one flat vector in the state's type -- concatenated straight into
-        the arena's region for it when the state is placed (no second copy, and the vector sits where the sweeps read it).
-        fd_scaled (fused tail only): the division of :734-736 rides on the pack.  inv: 1 / loss_scale, a power of two, folded into
-        the pack (torch tail: one exact multiplication).  slot (guarded step, fused tail): the pack checks what it writes and
-        stamps that word of the plan's flags."""
+        """psgd.py:729-730, :747: the per-parameter tensors as one flat float32 vector, written where _flat_region says it lives
+        (no second copy, and the vector sits where the sweeps read it) -- by one uvd_pack launch on the fused tail, by one
+        torch.cat on the torch tail, which makes a fresh tensor where the vector has no home.  fd_scaled (fused tail only): the
+        division of :734-736 rides on the pack.  inv: 1 / loss_scale, a power of two, folded into the pack (torch tail: one exact
+        multiplication).  slot (guarded step, fused tail): the pack checks what it writes and stamps that word of the plan's
+        flags."""
         if self._tail is not None:
-            out = getattr(self._arena, name).view(-1) if self._arena is not None else self._flat_bufs.get(name)
-            if out is None:
-                out = self._flat_bufs[name] = torch.empty(self._tail.total, dtype=torch.float32, device=self._device)
-            if slot is not None:
-                return uvd_pack([_c(x) for x in tensors], out, self._pack_scale(fd_scaled, inv), plan=self._tail, role=name,
-                                flag=self._tail.flags[slot:slot + 1], stamp=self._stamp)
-            return uvd_pack([_c(x) for x in tensors], out, self._pack_scale(fd_scaled, inv), plan=self._tail, role=name)
+            kw = {} if slot is None else dict(flag=self._tail.flags[slot:slot + 1], stamp=self._stamp)
+            return uvd_pack([_c(x) for x in tensors], self._flat_region(name), self._pack_scale(fd_scaled, inv), plan=self._tail,
+                            role=name, **kw)
         parts = [torch.reshape(x, [-1]) for x in tensors]
-        if self._arena is not None and all(x.dtype == self._state_dtype for x in parts):
-            flat = torch.cat(parts, 0, out=getattr(self._arena, name).view(-1))
+        narrow = not all(x.dtype == torch.float32 for x in parts)
+        out = self._flat_region(name, narrow)
+        if out is None:
+            flat = torch.cat(parts, 0).to(torch.float32)
+        elif narrow:
+            flat = out.copy_(torch.cat(parts, 0))
         else:
-            flat = torch.cat(parts, 0).to(self._state_dtype)
+            flat = torch.cat(parts, 0, out=out)
         return flat if inv == 1.0 else flat.mul_(inv)
 
     def _momentum_buffer(self):
-        """this rank's flat fp32 momentum vector: the arena's g region when the state is placed, else one zero-initialised tensor
-        created on first use"""
-        if self._arena is not None:
-            return self._arena.g.view(-1)
+        """this rank's flat fp32 momentum vector: where _flat_region places it, else one zero-initialised tensor created on
+        first use"""
+        m = self._flat_region("m")
+        if m is not None:
+            return m
         if self._m is None:
             self._m = torch.zeros(self._param_cumsizes[-1], dtype=torch.float32, device=self._device)
         return self._m
@@ -1634,14 +1494,14 @@ class UVd(_StepFeatures):
     # ------------------------------------------------------------------------------------- preconditioner_fit="whitening"
     def _whitening_inputs(self, grads, mom, inv):
         """(h, g) of an updating whitening step, or (None, None) where the guard skips it: h the raw flat fp32 gradient of this
-        step (1 / loss_scale folded into the pack; never the momentum buffer), g what _grad_flat returns.  Without momentum on a
-        state that is not placed the two hold the same bits: ONE pack, ONE buffer passed for both -- every form of the fused
-        call (fp32, bf16 state, ranks above 32, the staged sharded ones) takes v, h and g as const pointers and only reads them.
-        With momentum, or on a placed state (its layout was measured with distinct streams), h gets its own region.  Guarded: the
-        packs judge what they write (h in slot 1, g in slot 2 of the plan's flags); with momentum uvd_check judges the gradients
-        before the blend, as on every guarded step.  The decision is _guarded_grad's: the one host read of the step."""
+        step (1 / loss_scale folded into the pack; never the momentum buffer), g what _grad_flat returns.  Without momentum,
+        where _flat_region gives the momentum buffer no place, the two hold the same bits: ONE pack, ONE buffer passed for both
+        -- every preconditioner call takes v, h and g as const pointers and only reads them.  With momentum, or where the
+        momentum buffer has its place (a placed state: its layout was measured with distinct streams), h gets its own region.
+        Guarded: the packs judge what they write (h in slot 1, g in slot 2 of the plan's flags); with momentum uvd_check judges
+        the gradients before the blend, as on every guarded step.  The decision is _guarded_grad's: the one host read of the step."""
         guard = self._guard
-        if mom == 0.0 and self._arena is None:
+        if mom == 0.0 and self._flat_region("m") is None:
             g = self._guarded_grad(grads, mom, inv, ()) if guard else self._grad_flat(grads, mom)
             return g, g
         h = self._flat(grads, "h", inv=inv, slot=1 if guard and self._tail is not None else None)
@@ -1649,227 +1509,26 @@ class UVd(_StepFeatures):
         return (None, None) if g is None else (h, g)
 
     def _draw_probe(self):
-        """v ~ N(0, I) of an updating whitening step, drawn straight into this rank's flat fp32 vector -- the arena's v region on a
-        placed state, else a buffer made once -- by ONE multi_randn launch over one segment, on either step tail: seed
-        uvd_step_rounding_seed(probe_seed0, probe_step), index0 = this rank's first global row, scale 1.  Advances probe_step."""
+        """v ~ N(0, I) of an updating whitening step, drawn straight into this rank's flat fp32 vector -- where _flat_region places
+        it, else a buffer made once; _probe is the vector of the latest draw -- by ONE multi_randn launch over one segment, on
+        either step tail: seed uvd_step_rounding_seed(probe_seed0, probe_step), index0 = this rank's first global row, scale 1.
+        Advances probe_step."""
+        n = self._param_cumsizes[-1]
         if self._probe_plan is None:
             from .multi_tail import MultiTailPlan
-            n = self._param_cumsizes[-1]
             self._probe_plan = MultiTailPlan([n], self._device)
-            self._probe = self._arena.v.view(-1) if self._arena is not None else \
-                torch.empty(n, dtype=torch.float32, device=self._device)
-        multi_randn([self._probe], self._next_probe_seed(), self._row0(), plan=self._probe_plan)
-        return self._probe
-
-    # ------------------------------------------------------------------------------------------------- checkpoint / resume
-    _HYPER_KEYS = ("lr_params", "lr_preconditioner", "grad_clip_max_norm", "preconditioner_update_probability",
-                   "exact_hessian_vector_product")
+        v = self._flat_region("probe")
+        if v is None:
+            v = self._probe if self._probe is not None else torch.empty(n, dtype=torch.float32, device=self._device)
+        self._probe = v
+        multi_randn([v], self._next_probe_seed(), self._row0(), plan=self._probe_plan)
+        return v
 
     def _row0(self):
+        """the global index of this rank's first row (row-sharded: one set-up collective the first time)"""
         if self._group is None:
             return 0
-        return self._sharded.global_row0(self._U.shape[0], self._device, self._group)
-
-    def state_dict(self):
-        """Everything a bit-faithful resume of this optimizer needs, as a flat dict of CPU tensors and plain Python values (safe
-        for torch.save / torch.load(weights_only=True)):
-
-            format                   1
-            U, V, d                  this rank's rows in the STORED dtype (clones on the CPU, never views of an arena)
-            rank                     the rank of the modification r
-            num_params, row0         this rank's row count and the global index of its first row (unsharded: row0 = 0)
-            num_params_global        rows of the global vector (unsharded: num_params)
-            param_sizes              the element counts of this rank's parameter tensors
-            state_dtype, state_route, state_rounding    strings ("torch.bfloat16", "native" / "widen", "stochastic" / "nearest" / "none")
-            round_seed0, round_step  native route only: together they fix every stored code of every later step
-            param_round_seed0, param_round_step    param_rounding="stochastic" only: the seed and the step counter of the
-                                     parameters' rounding stream (param_rounding itself is a constructor choice and is not saved)
-            probe_seed0, probe_step  preconditioner_fit="whitening" only: the seed and the step counter of the probe stream, the
-                                     same on every rank (preconditioner_fit itself is a constructor choice and is not saved)
-            hyper                    lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability (floats),
-                                     exact_hessian_vector_product (bool)
-                                     and, optional when loading, momentum and weight_decay (floats)
-            momentum_buffer, momentum_step    only when momentum > 0: this rank's rows of the momentum buffer (fp32) and the number of
-                                     steps blended into it
-            nonfinite, skipped_steps, loss_scale, loss_scale_good_steps    only when nonfinite="skip": "skip", the number of
-                                     skipped steps, the current loss scale (None without loss scaling) and the good steps
-                                     counted towards the next growth of a dynamic scale
-            branch_rng               get_state() of the generator behind the coin flips: the generator= argument, else the
-                                     module's branch generator; row-sharded, the synchronised generator all ranks draw from
-
-        NOT saved: the parameters (they are the caller's), and the global CUDA generator that draws the probe vectors of
-        :713 / :721 -- it belongs to the caller; save torch.cuda.get_rng_state() next to this dict and restore it with
-        torch.cuda.set_rng_state() where the resumed run must draw the same vectors.
-
-        Row-sharded: every rank calls it (row0 is one set-up collective the first time, sharded.global_row0) and saves its own dict."""
-        def host(t):
-            return t.detach().to("cpu", copy=True).contiguous()
-        n = int(self._U.shape[0])
-        sd = {"format": 1, "U": host(self._U), "V": host(self._V), "d": host(self._d),
-              "rank": int(self._U.shape[1]), "num_params": n, "num_params_global": int(self._num_params_global),
-              "row0": int(self._row0()), "param_sizes": [int(s) for s in self._param_sizes],
-              "state_dtype": str(self._store_dtype), "state_route": "native" if self._native else "widen",
-              "state_rounding": self._state_rounding if self._state_rounding is not None else "none",
-              "hyper": {k: (bool if k == "exact_hessian_vector_product" else float)(getattr(self, k)) for k in self._HYPER_KEYS},
-              "branch_rng": self._coin_generator().get_state().clone()}
-        sd["hyper"]["momentum"], sd["hyper"]["weight_decay"] = float(self.momentum), float(self.weight_decay)
-        if float(self.momentum) > 0.0:
-            sd["momentum_buffer"], sd["momentum_step"] = host(self._momentum_buffer()), int(self._m_step)
-        if self._native:
-            sd["round_seed0"], sd["round_step"] = int(self._round_seed0), int(self._round_step)
-        _param_rounding_encode(sd, self._param_sr, self._param_round_seed0, self._param_round_step)
-        _probe_encode(sd, self._whiten, self._probe_seed0, self._probe_step)
-        return _guard_encode(sd, self._guard, self.skipped_steps, self.loss_scale.value, self._good_steps)
-
-    def load_state_dict(self, sd, *, strict=True, narrow_rounding=None, narrow_seed=None):
-        """Restore what state_dict() saved, IN PLACE: U, V, d are written into the tensors this object already holds (a placed
-        state stays in its arena; every pointer the tail plan and the workspaces cache stays valid), the hyper-parameters are
-        assigned (momentum and weight_decay when the dict has them; momentum_buffer / momentum_step are restored, and a dict
-        without them zeroes the buffer of a momentum optimizer and restarts its warm-up), the generator behind the coins gets the
-        saved state (row-sharded: every rank loads the same bytes into the
-        synchronised generator; nothing is broadcast again) and, on the native route, so do round_seed0 / round_step.  With
-        param_rounding="stochastic", param_round_seed0 / param_round_step are restored where the dict has them; a dict without
-        them leaves this object's seed and sets the counter to 0; a nearest optimizer ignores them.  With
-        preconditioner_fit="whitening", probe_seed0 / probe_step likewise: restored where the dict has them, this object's seed
-        and a counter of 0 where it has not (a dict of a hessian-fit optimizer); a hessian-fit optimizer ignores them.  A guarded
-        optimizer (nonfinite="skip") restores skipped_steps, loss_scale_good_steps and, when both sides scale the loss, loss_scale
-        where the dict has them and starts them fresh where it has not (a dict of an unguarded optimizer); an unguarded one
-        ignores them.
-
-        Checked against this object (ValueError naming the key): format, rank, num_params, param_sizes (skipped when the dict
-        holds None, as a resharded one does); with strict=True also num_params_global and row0.  strict=False is for loading a
-        slice of a global state into an object that does not know where its rows sit (rows of a resharded checkpoint).
-
-        Dtypes: the same stored dtype is a bitwise copy; a bfloat16 checkpoint into a float32 state widens exactly; a float32
-        checkpoint into a NATIVE bfloat16 state is streamed -- host -> pinned staging -> device staging (64 MiB at most, the only
-        fp32 image of the state that ever exists on the device) -> psgd_uvd_bf16_narrow_f32 -- with narrow_rounding (default: this
-        object's state_rounding) and narrow_seed (default: uvd_step_rounding_seed(round_seed0, 2**40 + round_step), a stream
-        disjoint from every step's); the rounding index is the GLOBAL element index (from the dict's row0), so the codes depend
-        on neither the chunking nor the row split.  Such a checkpoint carries no round_seed0 / round_step: the object keeps
-        its own.  Any other pair of dtypes raises TypeError.  The parameters and the global CUDA generator are the caller's."""
-        name = "UVd.load_state_dict"
-
-        def need(key):
-            if key not in sd:
-                raise ValueError("%s: the state dict has no %r" % (name, key))
-            return sd[key]
-
-        def same(key, mine):
-            got = need(key)
-            if got != mine:
-                raise ValueError("%s: %r is %r in the state dict, %r in this optimizer" % (name, key, got, mine))
-        if need("format") != 1:
-            raise ValueError("%s: 'format' is %r; this version reads format 1" % (name, sd["format"]))
-        if narrow_rounding is not None and narrow_rounding not in _ROUNDINGS:
-            raise ValueError("%s: narrow_rounding must be 'stochastic' or 'nearest', got %r" % (name, narrow_rounding))
-        n, r = int(self._U.shape[0]), int(self._U.shape[1])
-        same("rank", r)
-        same("num_params", n)
-        if need("param_sizes") is not None and [int(s) for s in sd["param_sizes"]] != [int(s) for s in self._param_sizes]:
-            raise ValueError("%s: 'param_sizes' is %r in the state dict, %r in this optimizer"
-                             % (name, list(sd["param_sizes"]), list(self._param_sizes)))
-        if strict:
-            same("num_params_global", int(self._num_params_global))
-            same("row0", int(self._row0()))
-        row0 = int(need("row0"))
-        src = {k: need(k) for k in ("U", "V", "d")}
-        for k, mine in (("U", self._U), ("V", self._V), ("d", self._d)):
-            if not isinstance(src[k], torch.Tensor) or tuple(src[k].shape) != tuple(mine.shape):
-                raise ValueError("%s: %r must be a tensor of shape %s" % (name, k, tuple(mine.shape)))
-        have = {src[k].dtype for k in src}
-        if len(have) != 1:
-            raise TypeError("%s: U, V and d of the state dict have different dtypes %s" % (name, sorted(str(x) for x in have)))
-        have = have.pop()
-        if have == self._store_dtype:
-            how = "copy"
-        elif have == torch.bfloat16 and self._store_dtype == torch.float32:
-            how = "copy"                                   # exact: every bfloat16 value is a float32 value
-        elif have == torch.float32 and self._native:
-            how = "narrow"
-        else:
-            raise TypeError("%s: a %s checkpoint cannot be loaded into a %s state (state_route=%r): the same dtype, bfloat16 into "
-                            "float32 and float32 into a native bfloat16 state are supported"
-                            % (name, have, self._store_dtype, "native" if self._native else "widen"))
-        hyper = need("hyper")
-        for k in self._HYPER_KEYS:
-            if k not in hyper:
-                raise ValueError("%s: 'hyper' has no %r" % (name, k))
-        mbuf = sd.get("momentum_buffer")
-        if mbuf is not None and (not isinstance(mbuf, torch.Tensor) or mbuf.dtype != torch.float32 or mbuf.numel() != n):
-            raise ValueError("%s: 'momentum_buffer' must be a float32 tensor of %d elements" % (name, n))
-        if mbuf is not None:
-            need("momentum_step")
-        rng_state = need("branch_rng")
-        try:
-            self._coin_generator().set_state(rng_state)
-        except (RuntimeError, TypeError) as e:
-            raise ValueError("%s: 'branch_rng' does not fit this optimizer's generator: %s" % (name, e))
-        for k in self._HYPER_KEYS:
-            getattr(self, k).assign(hyper[k])
-        for k in ("momentum", "weight_decay"):               # optional: a checkpoint from before them leaves this object's values
-            if k in hyper:
-                getattr(self, k).assign(hyper[k])
-        with torch.no_grad():
-            if mbuf is not None:
-                self._momentum_buffer().copy_(mbuf.reshape(-1))
-                self._m_step = int(sd["momentum_step"])
-            else:                                            # no buffer saved: a momentum optimizer starts its warm-up again
-                self._m_step = 0
-                if float(self.momentum) > 0.0:
-                    self._momentum_buffer().zero_()
-        if self._native and "round_seed0" in sd:
-            self._round_seed0, self._round_step = int(sd["round_seed0"]), int(need("round_step"))
-        self._param_round_seed0, self._param_round_step = _param_rounding_decode(name, sd, self._param_sr, self._param_round_seed0)
-        self._probe_seed0, self._probe_step = _probe_decode(sd, self._whiten, self._probe_seed0, name)
-        self._guard_decode(sd)
-        with torch.no_grad():
-            if how == "copy":
-                for k, mine in (("U", self._U), ("V", self._V), ("d", self._d)):
-                    mine.copy_(src[k])
-                return
-            rounding = narrow_rounding if narrow_rounding is not None else self._state_rounding
-            seed = uvd_step_rounding_seed(self._round_seed0, 2 ** 40 + self._round_step) if narrow_seed is None else int(narrow_seed)
-            self._load_narrowed(src, row0, r, rounding, seed)
-
-    def _load_narrowed(self, src, row0, r, rounding, seed):
-        """fp32 host tensors -> this object's native bf16 state, through ONE pinned and ONE device staging buffer of at most
-        _NARROW_STAGING_BYTES (reused chunk after chunk: the stream is drained before a buffer is refilled)"""
-        chunk = max(1, int(_NARROW_STAGING_BYTES) // 4)
-        cap = min(chunk, max(int(t.numel()) for t in src.values()))
-        pinned = torch.empty(cap, dtype=torch.float32, pin_memory=True)
-        staged = torch.empty(cap, dtype=torch.float32, device=self._device)
-        stream = torch.cuda.current_stream(self._device)
-        for k, mine, index0 in (("U", self._U, row0 * r), ("V", self._V, row0 * r), ("d", self._d, row0)):
-            if not mine.is_contiguous():
-                raise ValueError("UVd.load_state_dict: the native state must be contiguous")
-            flat, host = mine.view(-1), src[k].detach().contiguous().view(-1)
-            for lo in range(0, int(host.numel()), chunk):
-                m = min(chunk, int(host.numel()) - lo)
-                pinned[:m].copy_(host[lo:lo + m])
-                staged[:m].copy_(pinned[:m], non_blocking=True)
-                uvd_bf16_narrow_(flat[lo:lo + m], staged[:m], tensor=k, index0=index0 + lo, rounding=rounding, rounding_seed=seed)
-                stream.synchronize()
-
-    def _precondition(self, v, h, grad):
-        """psgd.py:748 on the flat gradient; with v and h (None on a step that leaves the preconditioner alone) after :732-733,
-        as one fused call: the same results in three sweeps instead of six.  Row-sharded: this rank's rows, 2 exchanges (4 for
-        a native bf16 state), :562 and :588 from the synchronised generator.  A native state gets the rounding seed of this step."""
-        U, V, d = self._state_fp32()
-        g = grad[:, None].contiguous()
-        if self._group is not None:          # (looked up at the call, as a global is: a spy on the module attribute sees the call)
-            apply, fused = self._sharded.precond_grad_UVd_math, self._sharded.update_precond_UVd_math_and_precond_grad
-        else:
-            apply, fused = precond_grad_UVd_math, update_precond_UVd_math_and_precond_grad
-        if v is None:
-            return apply(U, V, d, g, **self._apply_kw)
-        seed = None
-        if self._native:
-            seed = uvd_step_rounding_seed(self._round_seed0, self._round_step)
-            self._round_step += 1
-        pre_grad = fused(U, V, d, v[:, None].contiguous(), h[:, None].contiguous(), g, step=float(self.lr_preconditioner),
-                         tiny=self._tiny, rounding_seed=seed, **self._update_kw)
-        self._state_store(U, V, d)
-        return pre_grad
+        return self._sharded.global_row0(self._param_cumsizes[-1], self._device, self._group)
 
     def step(self, closure):
         """psgd.py:692-764.
@@ -2010,6 +1669,420 @@ class UVd(_StepFeatures):
                                      sr_index0 + j - i)
         return closure_returns                                                              # :764
 
+    # ------------------------------------------------------------------------------------------------- checkpoint / resume
+    def state_dict(self):
+        """Everything a bit-faithful resume needs, as a flat dict of CPU tensors and plain Python values (safe for torch.save /
+        torch.load(weights_only=True)); the subclass documents its own keys and adds them in _state_encode:
+
+            format                   1
+            rank, num_params         the rank r and this rank's row count
+            param_sizes              the element counts of this rank's parameter tensors
+            state_dtype, state_rounding    strings ("torch.bfloat16"; "stochastic" / "nearest" / "none")
+            round_seed0, round_step  a state the kernels round only: together they fix every stored code of every later step
+            param_round_seed0, param_round_step    param_rounding="stochastic" only: the seed and the step counter of the
+                                     parameters' rounding stream (param_rounding itself is a constructor choice and is not saved)
+            probe_seed0, probe_step  preconditioner_fit="whitening" only: the seed and the step counter of the probe stream, the
+                                     same on every rank (preconditioner_fit itself is a constructor choice and is not saved)
+            hyper                    lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability (floats),
+                                     exact_hessian_vector_product (bool)
+                                     and, optional when loading, momentum and weight_decay (floats)
+            momentum_buffer, momentum_step    only when momentum > 0: this rank's rows of the momentum buffer (fp32) and the number of
+                                     steps blended into it
+            nonfinite, skipped_steps, loss_scale, loss_scale_good_steps    only when nonfinite="skip": "skip", the number of
+                                     skipped steps, the current loss scale (None without loss scaling) and the good steps
+                                     counted towards the next growth of a dynamic scale
+            branch_rng               get_state() of the generator behind the coin flips: the generator= argument, else the
+                                     module's branch generator; row-sharded, the synchronised generator all ranks draw from
+
+        NOT saved: the parameters (they are the caller's), and the global CUDA generator that draws the probe vectors of
+        :713 / :721 -- it belongs to the caller; save torch.cuda.get_rng_state() next to this dict and restore it with
+        torch.cuda.set_rng_state() where the resumed run must draw the same vectors."""
+        def host(t):
+            return t.detach().to("cpu", copy=True).contiguous()
+        sd = {"format": 1, "rank": self._rank, "num_params": self._param_cumsizes[-1],
+              "param_sizes": [int(s) for s in self._param_sizes], "state_dtype": str(self._store_dtype),
+              "state_rounding": self._state_rounding if self._state_rounding is not None else "none",
+              "hyper": {k: (bool if k == "exact_hessian_vector_product" else float)(getattr(self, k)) for k in self._HYPER_KEYS},
+              "branch_rng": self._coin_generator().get_state().clone()}
+        self._state_encode(sd, host)
+        sd["hyper"]["momentum"], sd["hyper"]["weight_decay"] = float(self.momentum), float(self.weight_decay)
+        if float(self.momentum) > 0.0:
+            sd["momentum_buffer"], sd["momentum_step"] = host(self._momentum_buffer()), int(self._m_step)
+        if self._round_seed0 is not None:
+            sd["round_seed0"], sd["round_step"] = int(self._round_seed0), int(self._round_step)
+        _param_rounding_encode(sd, self._param_sr, self._param_round_seed0, self._param_round_step)
+        _probe_encode(sd, self._whiten, self._probe_seed0, self._probe_step)
+        return _guard_encode(sd, self._guard, self.skipped_steps, self.loss_scale.value, self._good_steps)
+
+    def load_state_dict(self, sd, **how):
+        """Restore what state_dict() saved, IN PLACE: the state is written into the tensors this object already holds, the
+        hyper-parameters are assigned (momentum and weight_decay when the dict has them; momentum_buffer / momentum_step are
+        restored, and a dict without them zeroes the buffer of a momentum optimizer and restarts its warm-up), the generator
+        behind the coins gets the saved state (row-sharded: every rank loads the same bytes into the synchronised generator;
+        nothing is broadcast again) and so do, where this object has the switch on and the dict has the keys, round_seed0 /
+        round_step, param_round_seed0 / param_round_step and probe_seed0 / probe_step; a dict without the keys of a switch this
+        object has on leaves its seed and starts the counter at 0, and an object with the switch off ignores them.  A guarded
+        optimizer (nonfinite="skip") restores skipped_steps, loss_scale_good_steps and, when both sides scale the loss,
+        loss_scale where the dict has them and starts them fresh where it has not; an unguarded one ignores them.
+
+        Checked against this object (ValueError naming the key): format, rank, num_params, param_sizes (skipped when the dict
+        holds None, as a resharded one does), then the subclass's keys (_state_judge; **how are its keywords).  Everything that can
+        refuse the dict is judged before anything of this object changes: a dict that is refused leaves this object as it was.
+        The parameters and the global CUDA generator are the caller's."""
+        name = type(self).__name__ + ".load_state_dict"
+
+        def need(key):
+            if key not in sd:
+                raise ValueError("%s: the state dict has no %r" % (name, key))
+            return sd[key]
+
+        def same(key, mine):
+            got = need(key)
+            if got != mine:
+                raise ValueError("%s: %r is %r in the state dict, %r in this optimizer" % (name, key, got, mine))
+        if need("format") != 1:
+            raise ValueError("%s: 'format' is %r; this version reads format 1" % (name, sd["format"]))
+        n = self._param_cumsizes[-1]
+        same("rank", self._rank)
+        same("num_params", n)
+        if need("param_sizes") is not None and [int(s) for s in sd["param_sizes"]] != [int(s) for s in self._param_sizes]:
+            raise ValueError("%s: 'param_sizes' is %r in the state dict, %r in this optimizer"
+                             % (name, list(sd["param_sizes"]), list(self._param_sizes)))
+        judged = self._state_judge(sd, name, need, same, **how)
+        hyper = need("hyper")
+        for k in self._HYPER_KEYS:
+            if k not in hyper:
+                raise ValueError("%s: 'hyper' has no %r" % (name, k))
+        mbuf = sd.get("momentum_buffer")
+        if mbuf is not None and (not isinstance(mbuf, torch.Tensor) or mbuf.dtype != torch.float32 or mbuf.numel() != n):
+            raise ValueError("%s: 'momentum_buffer' must be a float32 tensor of %d elements" % (name, n))
+        if mbuf is not None:
+            need("momentum_step")
+        gen = self._coin_generator()
+        try:                                                     # tried on a scratch generator: this object's is not touched yet
+            torch.Generator(device=gen.device).set_state(need("branch_rng"))
+        except (RuntimeError, TypeError) as e:
+            raise ValueError("%s: 'branch_rng' does not fit this optimizer's generator: %s" % (name, e))
+        rounded = self._round_seed0 is not None and "round_seed0" in sd
+        if rounded:
+            need("round_step")
+        param_round = _param_rounding_decode(name, sd, self._param_sr, self._param_round_seed0)
+        probe = _probe_decode(sd, self._whiten, self._probe_seed0, name)
+        if self._guard and sd.get("loss_scale") is not None and self.loss_scale.value is not None:
+            S = float(sd["loss_scale"])
+            if not (S > 0.0 and math.isfinite(S) and math.frexp(S)[0] == 0.5):
+                raise ValueError("%s: 'loss_scale' must be a power of two, got %r" % (name, sd["loss_scale"]))
+        # ---- nothing below refuses the dict
+        gen.set_state(sd["branch_rng"])
+        for k in self._HYPER_KEYS + tuple(k for k in ("momentum", "weight_decay") if k in hyper):   # (the two: optional in a dict)
+            getattr(self, k).assign(hyper[k])
+        with torch.no_grad():
+            if mbuf is not None:
+                self._momentum_buffer().copy_(mbuf.reshape(-1))
+                self._m_step = int(sd["momentum_step"])
+            else:                                                # no buffer saved: a momentum optimizer starts its warm-up again
+                self._m_step = 0
+                if float(self.momentum) > 0.0:
+                    self._momentum_buffer().zero_()
+        if rounded:
+            self._round_seed0, self._round_step = int(sd["round_seed0"]), int(sd["round_step"])
+        (self._param_round_seed0, self._param_round_step), (self._probe_seed0, self._probe_step) = param_round, probe
+        self._guard_decode(sd)
+        with torch.no_grad():
+            self._state_commit(judged)
+
+
+class UVd(_FlatStep):
+    """Low-rank modification (UVd) preconditioner as an optimizer, psgd.py:630-764: _FlatStep (step(), the flat vectors, the
+    checkpoint skeleton) with the state U, V, d -- plain tensors, a bfloat16 state the kernels read and write, regions of a
+    placement.UVdArena, or this rank's rows of a row-sharded state.
+
+    Same constructor arguments and defaults as the reference (psgd.py:663-666).  Parameters are
+    torch tensors with requires_grad=True on a ROCm device (the reference's `.trainable` filter,
+    :670, maps to requires_grad).  `step(closure)` returns whatever closure returns (:764).
+
+    param_rounding="stochastic" (extension, keyword-only; "nearest" by default: nothing changes; bfloat16 parameters only, anything
+    else is a ValueError before a device is touched).  There is no float32 master copy: the parameter is the bfloat16 tensor, and
+    under round to nearest a weight ignores every update below half its spacing.  With "stochastic" the update of :757-762 is
+    formed once in float32 and narrowed once with the stochastic rounding of the bf16-stored states -- w = float(p),
+    d = fl32(lr_eff g), d = fl32(d + float(v)), d = fl32(d + fl32(c w)), p <- SR(fl32(w - d)) -- on a stream keyed by
+    uvd_step_rounding_seed(seed0, k) and the element's global flat index (psgd_uvd_param_update_multi_sr on the fused tail,
+    param_update_stochastic_ on the torch tail: the same bits).  seed0: param_rounding_seed, or a draw from the generator behind
+    the coins; k counts the steps that wrote the parameters.  The perturbation of :723 and its undo stay round-to-nearest.
+    state_dict() carries param_round_seed0 / param_round_step; param_rounding itself is a constructor choice, like step_tail.
+
+    preconditioner_fit="whitening" (extension, keyword-only; "hessian" by default: nothing changes, no new function is called, no
+    new number is drawn; any other value is a ValueError before a device is touched) fits the preconditioner to the GRADIENTS
+    instead of to Hessian-vector products: the update of :732-733 is fed the pair (v, h) = (probe, g), v ~ N(0, I) drawn fresh on
+    every updating step and g the raw flat float32 gradient of this step (1 / loss_scale folded into its pack; never the momentum
+    buffer).  The criterion E[h' P h + v' P^-1 v] is then minimised by P = Q'Q = (E[g g'])^(-1/2) within the UVd form: the
+    preconditioner whitens the gradient (the gradient-whitening fit of the PSGD papers, PAPERS.md).  A step needs ONE ordinary
+    backward pass: no create_graph, no second closure call, no perturbation of the parameters -- so closures whose backward cannot
+    be differentiated again (fused attention kernels, custom Functions marked once_differentiable) train, and the step no longer
+    pays the second backward.  exact_hessian_vector_product is ignored on this route (nothing is rejected).  The probe is this
+    rank's flat float32 vector -- the arena's v region on a placed state, else a buffer made once -- filled by ONE multi_randn
+    launch over one segment on BOTH step tails (there is no torch.randn on this route, no per-tensor probe, and v is never
+    packed): the stream of updating step k is keyed by uvd_step_rounding_seed(probe_seed0, k) and the element's GLOBAL flat index
+    (index0 = this rank's first row), whatever `generator` is, so a row-sharded run draws the rows of the one-process probe;
+    probe_seed0 = probe_seed, or a draw from the generator behind the coins (after the draws of the native state's and the
+    parameters' seeds where those happen; row-sharded, from the synchronised generator: the same on every rank); k = probe_step
+    counts the steps that drew a probe.  Without momentum, on a state that is not placed, h and g are one buffer, packed once (the
+    kernels only read them); with momentum or a placed state each has its own.  The probe is finite by construction and is not
+    judged by the guard; a skipped step returns before it is drawn and leaves probe_step alone.  state_dict() carries probe_seed0
+    / probe_step; preconditioner_fit itself is a constructor choice, like step_tail.  The whitened gradient has roughly unit scale
+    per element, as Adam's update has: lr_params and grad_clip_max_norm tuned for the Hessian fit do NOT carry over."""
+
+    def __init__(self, params_with_grad, rank_of_modification: int = 10, preconditioner_init_scale=1.0,
+                 lr_params=0.01, lr_preconditioner=0.01,
+                 grad_clip_max_norm=None, preconditioner_update_probability=1.0,
+                 exact_hessian_vector_product: bool = True, generator=None, state_dtype=None, group=None,
+                 stage_backend=None, placement="auto", state_route="widen", state_rounding=None, step_tail="torch",
+                 momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
+                 *, param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None):
+        # group (extension, SURVEY 8e): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
+        # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the
+        # concatenation of the ranks' vectors in rank order, and U, V, d hold this rank's rows only.  A step then costs three
+        # collectives: the two exchanges of sharded.update_precond_UVd_math_and_precond_grad (r-dimensional sums, never N-sized
+        # data) and one scalar all-reduce for the clip norm of :753 (none without clipping); the coins of :703, :562, :588 come
+        # from one generator whose state rank 0 broadcasts once.  The closure returns this rank's loss; its gradient and
+        # Hessian-vector product with respect to this rank's parameters are what a model-parallel closure computes.
+        # Every check comes before anything is drawn from a generator or touches a device (_FlatStep._init_tail is the first that
+        # does).  param_rounding and preconditioner_fit: the class docstring.
+        num_params = self._init_params(params_with_grad, generator, param_rounding, preconditioner_fit)   # :668-671, :684-686
+        # psgd.py:657-658 allows half-precision parameters.  The preconditioner state U, V, d and all of its arithmetic
+        # stay fp32 here (mixed precision: the HIP kernels compute in fp32; v, Hv and the gradient are widened on the
+        # way in, the preconditioned gradient is narrowed on the way out).  _tiny and the finite-difference scale follow
+        # the parameter dtype as in the reference (:682-683).
+        # state_dtype (extension; default None = fp32): "param" or a torch dtype STORES U, V, d in that type, as the reference does
+        # for half-precision parameters (psgd.py:688-690) -- every step widens them, runs the fp32 kernels and rounds the updated
+        # state back, so the memory held between steps and the rounding of the state once per step are the reference's; its
+        # arithmetic (every TF op in the parameters' type) is not reproduced.
+        self._store_dtype = torch.float32 if state_dtype is None else self._dtype if state_dtype == "param" else state_dtype
+        if self._store_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError("UVd: state_dtype must be None, 'param', float32, float16 or bfloat16, got %r" % (state_dtype,))
+        r = self._rank = int(rank_of_modification)
+        if r < 1:
+            raise ValueError("UVd: rank_of_modification must be >= 1, got %d" % r)
+        # state_route (extension): "widen" (default) = the behaviour above for a narrow state_dtype; "native" = a bfloat16 state is
+        # read and written by the bf16-state kernels themselves (psgd_uvd_bf16.hip): no fp32 copies of U, V, d exist at any time.
+        # state_rounding: how those kernels narrow what they write, "stochastic" (default of the native route: under round to
+        # nearest a bf16 d practically stops learning, its increments are below half a spacing) or "nearest".  The seed of step k
+        # is a hash of one seed fixed here (drawn from `generator` when given, the module's branch generator otherwise) and k
+        # (uvd_step_rounding_seed).
+        if state_route not in ("widen", "native"):
+            raise ValueError("UVd: state_route must be 'widen' or 'native', got %r" % (state_route,))
+        self._native = state_route == "native"
+        if self._native:
+            if self._store_dtype != torch.bfloat16:
+                raise ValueError("UVd: state_route='native' needs a bfloat16 state (state_dtype=torch.bfloat16, or 'param' with "
+                                 "bfloat16 parameters), got %s" % (self._store_dtype,))
+            if r > _lib.UVD_MAX_RANK:
+                raise ValueError("UVd: state_route='native' supports ranks up to %d, got %d" % (_lib.UVD_MAX_RANK, r))
+            # row-sharded (group=): this rank's rows in bf16, the staged bf16 kernels of sharded.py -- 4 exchanges per step.  The
+            # bf16 stages exist in the HIP backend only, and the group must be a real process group.
+            if stage_backend is not None:
+                raise ValueError("UVd: state_route='native' runs the HIP stages of its group= only (stage_backend= is not supported)")
+            if group is not None:
+                import torch.distributed as _dist
+                if not (_dist.is_available() and isinstance(group, _dist.ProcessGroup)):
+                    raise ValueError("UVd: state_route='native' needs group= to be a torch.distributed process group, got %r"
+                                     % (type(group),))
+            state_rounding = "stochastic" if state_rounding is None else state_rounding
+            if state_rounding not in _ROUNDINGS:
+                raise ValueError("UVd: state_rounding must be 'stochastic' or 'nearest', got %r" % (state_rounding,))
+        elif state_rounding is not None:
+            raise ValueError("UVd: state_rounding applies to state_route='native' only")
+        self._state_rounding = state_rounding
+        # momentum, weight_decay (extensions, off by default; _Hyper objects like the others).  momentum: the flat gradient of :747
+        # is blended into a buffer m that this object keeps, m <- beta_k m + (1 - beta_k) g with beta_k = min(k / (k + 1), momentum)
+        # (the warm-up of the PyTorch PSGD optimizers; k counts the steps blended so far, and a step taken with momentum == 0 sets
+        # it back to 0), and m takes the place of g in :748 -- v, h, the finite-difference undo and the clip norm (now of P m) are
+        # as before.  m is this rank's flat fp32 vector: the arena's g region when the state is placed, one tensor otherwise; with
+        # the fused tail the blend rides on the pack of g (uvd_pack_blend: no flat g exists).  weight_decay (decoupled): the update
+        # of :757-762 gains delta <- T(delta + T(fl32(fl32(lr_eff wd) p))).  Both tails round alike (every operation on its own);
+        # with either one on, the torch tail forms the clipped lr as the kernel does (fp64 from the fp32 squares, one rounding).
+        # nonfinite, loss_scale, loss_scale_growth_interval (extensions, off by default; see step()): "skip" = a step whose v, h or
+        # g holds a non-finite value changes nothing.
+        self._init_hypers(lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability,
+                          exact_hessian_vector_product, momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval)
+        # placement (extension): "probe" / "packed" carve U, V, d, the workspace, the output and the flat v / h / g vectors of :729-730,
+        # :747 out of allocations owned by this object (placement.UVdArena; "probe" times candidate layouts once and keeps the
+        # fastest: where the WRITTEN streams sit relative to the read ones is worth 5 %); None = plain allocations; "auto" (default)
+        # = "probe" when a factor is at least 1 GiB (the search costs ~0.6 s and allocates up to ~100 GiB while it runs; smaller
+        # states are close to cache-resident and gain little), None below
+        if placement not in (None, "auto", "probe", "packed"):
+            raise ValueError("UVd: placement must be None, 'auto', 'probe' or 'packed', got %r" % (placement,))
+        if placement == "auto":
+            placement = "probe" if 4 * num_params * r >= (1 << 30) else None
+        self._init_tail(step_tail)                              # (on the fused tail the flat vectors are this object's, or the arena's)
+        # group (extension, SURVEY 8e): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
+        # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the
+        # concatenation of the ranks' vectors in rank order, and U, V, d hold this rank's rows only.  A step then costs three
+        # collectives: the two exchanges of sharded.update_precond_UVd_math_and_precond_grad (r-dimensional sums, never N-sized
+        # data) and one scalar all-reduce for the clip norm of :753 (none without clipping); the coins of :703, :562, :588 come
+        # from one generator whose state rank 0 broadcasts once.  The closure returns this rank's loss; its gradient and
+        # Hessian-vector product with respect to this rank's parameters are what a model-parallel closure computes.
+        self._group, self._stage_backend, self._num_params_global = group, stage_backend, num_params
+        if group is not None:       # the generator whose state rank 0 broadcasts, once, here: the coins and one seed for all ranks
+            from . import sharded as _sharded
+            self._sharded = _sharded
+            self._coins = _sharded.branch_rng_for(generator, group, self._device)
+            self._num_params_global = _sharded.global_rows(num_params, self._device, group)  # :686 over all ranks (set-up time)
+        self._draw_seeds(self._native, param_rounding_seed, probe_seed)
+        uv_scale = (1.0 / (self._num_params_global * r)) ** 0.5                              # :687 (the GLOBAL N)
+        self._arena, self._flat_bufs = None, {}
+        if placement is not None and self._device.type == "cuda" and self._store_dtype == torch.float32 \
+                and r <= _lib.UVD_MAX_RANK and stage_backend is None:
+            from . import placement as _placement
+            self._arena = (_placement.UVdArena.probe if placement == "probe" else _placement.UVdArena.packed)(
+                num_params, r, self._device)
+        # the keywords of the two calls of step() (_precondition) that never change
+        out = None if self._arena is None else self._arena.out
+        self._apply_kw = dict(group=group, backend=stage_backend) if group is not None else dict(out=out)
+        self._update_kw = dict(self._apply_kw, out=out, generator=generator, rounding=state_rounding or "nearest")
+        if self._arena is not None:
+            self._arena.install_workspace()
+            self._U, self._V, self._d = self._arena.U, self._arena.V, self._arena.d
+            self._U.normal_().mul_(uv_scale)                                                 # :688
+            self._V.normal_().mul_(uv_scale)                                                 # :689
+            self._d.fill_(float(preconditioner_init_scale))                                  # :690
+            return
+        self._U = torch.randn(num_params, r, dtype=torch.float32, device=self._device) * uv_scale       # :688
+        self._V = torch.randn(num_params, r, dtype=torch.float32, device=self._device) * uv_scale       # :689
+        self._d = torch.ones(num_params, 1, dtype=torch.float32, device=self._device) * preconditioner_init_scale  # :690
+        if self._store_dtype != torch.float32:
+            self._U, self._V, self._d = (x.to(self._store_dtype) for x in (self._U, self._V, self._d))
+
+    def _state_fp32(self):
+        """the state the kernels work on: the stored tensors themselves (fp32, or bf16 on the native route), or fp32 copies of a
+        half-precision state"""
+        if self._store_dtype == torch.float32 or self._native:
+            return self._U, self._V, self._d
+        return self._U.float(), self._V.float(), self._d.float()
+
+    def _state_store(self, U, V, d):
+        if self._store_dtype != torch.float32 and not self._native:
+            self._U.copy_(U)
+            self._V.copy_(V)
+            self._d.copy_(d)
+
+    def _flat_region(self, name, narrow=False):
+        """_FlatStep's question.  A placed state: the arena's region ("m" is its g region, "probe" its v region) -- on the torch
+        tail only for parts that are float32 already (narrow ones are concatenated and widened into a fresh tensor, as without an
+        arena).  No arena: on the fused tail a buffer for v, h or g made on first use; nothing on the torch tail, and nothing for
+        the momentum buffer and the probe, which _FlatStep then makes once."""
+        if self._arena is not None:
+            return None if narrow else getattr(self._arena, {"m": "g", "probe": "v"}.get(name, name)).view(-1)
+        if self._tail is None or name in ("m", "probe"):
+            return None
+        if name not in self._flat_bufs:
+            self._flat_bufs[name] = torch.empty(self._tail.total, dtype=torch.float32, device=self._device)
+        return self._flat_bufs[name]
+
+    # ------------------------------------------------------------------------------------------------- checkpoint / resume
+    def _state_encode(self, sd, host):
+        """state_dict() of _FlatStep with these keys besides:
+
+            U, V, d                  this rank's rows in the STORED dtype (clones on the CPU, never views of an arena)
+            row0, num_params_global  the global index of this rank's first row (unsharded: 0) and the rows of the global vector
+            state_route              "native" / "widen"
+
+        Row-sharded: every rank calls it (row0 is one set-up collective the first time, sharded.global_row0) and saves its own dict."""
+        sd.update(U=host(self._U), V=host(self._V), d=host(self._d), num_params_global=int(self._num_params_global),
+                  row0=int(self._row0()), state_route="native" if self._native else "widen")
+
+    def load_state_dict(self, sd, *, strict=True, narrow_rounding=None, narrow_seed=None):
+        """_FlatStep.load_state_dict: U, V, d are written into the tensors this object already holds (a placed state stays in
+        its arena; every pointer the tail plan and the workspaces cache stays valid), and a dict that is refused, on whatever
+        key, leaves this object as it was.
+
+        Checked besides the common keys: with strict=True num_params_global and row0.  strict=False is for loading a slice of a
+        global state into an object that does not know where its rows sit (rows of a resharded checkpoint).
+
+        Dtypes: the same stored dtype is a bitwise copy; a bfloat16 checkpoint into a float32 state widens exactly; a float32
+        checkpoint into a NATIVE bfloat16 state is streamed -- host -> pinned staging -> device staging (64 MiB at most, the only
+        fp32 image of the state that ever exists on the device) -> psgd_uvd_bf16_narrow_f32 -- with narrow_rounding (default: this
+        object's state_rounding) and narrow_seed (default: uvd_step_rounding_seed(round_seed0, 2**40 + round_step), a stream
+        disjoint from every step's); the rounding index is the GLOBAL element index (from the dict's row0), so the codes depend
+        on neither the chunking nor the row split.  Such a checkpoint carries no round_seed0 / round_step: the object keeps
+        its own.  Any other pair of dtypes raises TypeError."""
+        super().load_state_dict(sd, strict=strict, narrow_rounding=narrow_rounding, narrow_seed=narrow_seed)
+
+    def _state_judge(self, sd, name, need, same, strict, narrow_rounding, narrow_seed):
+        if narrow_rounding is not None and narrow_rounding not in _ROUNDINGS:
+            raise ValueError("%s: narrow_rounding must be 'stochastic' or 'nearest', got %r" % (name, narrow_rounding))
+        if strict:
+            same("num_params_global", int(self._num_params_global))
+            same("row0", int(self._row0()))
+        row0 = int(need("row0"))
+        src = {k: need(k) for k in ("U", "V", "d")}
+        for k, mine in (("U", self._U), ("V", self._V), ("d", self._d)):
+            if not isinstance(src[k], torch.Tensor) or tuple(src[k].shape) != tuple(mine.shape):
+                raise ValueError("%s: %r must be a tensor of shape %s" % (name, k, tuple(mine.shape)))
+        have = {src[k].dtype for k in src}
+        if len(have) != 1:
+            raise TypeError("%s: U, V and d of the state dict have different dtypes %s" % (name, sorted(str(x) for x in have)))
+        have = have.pop()
+        if have == self._store_dtype or (have == torch.bfloat16 and self._store_dtype == torch.float32):
+            return src, None                               # a copy (exact: every bfloat16 value is a float32 value)
+        if not (have == torch.float32 and self._native):
+            raise TypeError("%s: a %s checkpoint cannot be loaded into a %s state (state_route=%r): the same dtype, bfloat16 into "
+                            "float32 and float32 into a native bfloat16 state are supported"
+                            % (name, have, self._store_dtype, "native" if self._native else "widen"))
+        if not all(t.is_contiguous() for t in (self._U, self._V, self._d)):
+            raise ValueError("UVd.load_state_dict: the native state must be contiguous")
+        return src, (row0, narrow_rounding if narrow_rounding is not None else self._state_rounding,
+                     None if narrow_seed is None else int(narrow_seed))
+
+    def _state_commit(self, judged):
+        src, narrow = judged
+        if narrow is None:
+            for k, mine in (("U", self._U), ("V", self._V), ("d", self._d)):
+                mine.copy_(src[k])
+            return
+        row0, rounding, seed = narrow                      # (the default seed: from round_seed0 / round_step as just restored)
+        if seed is None:
+            seed = uvd_step_rounding_seed(self._round_seed0, 2 ** 40 + self._round_step)
+        self._load_narrowed(src, row0, self._rank, rounding, seed)
+
+    def _load_narrowed(self, src, row0, r, rounding, seed):
+        """fp32 host tensors -> this object's native bf16 state, through ONE pinned and ONE device staging buffer of at most
+        _NARROW_STAGING_BYTES (reused chunk after chunk: the stream is drained before a buffer is refilled)"""
+        chunk = max(1, int(_NARROW_STAGING_BYTES) // 4)
+        cap = min(chunk, max(int(t.numel()) for t in src.values()))
+        pinned = torch.empty(cap, dtype=torch.float32, pin_memory=True)
+        staged = torch.empty(cap, dtype=torch.float32, device=self._device)
+        stream = torch.cuda.current_stream(self._device)
+        for k, mine, index0 in (("U", self._U, row0 * r), ("V", self._V, row0 * r), ("d", self._d, row0)):
+            flat, host = mine.view(-1), src[k].detach().contiguous().view(-1)
+            for lo in range(0, int(host.numel()), chunk):
+                m = min(chunk, int(host.numel()) - lo)
+                pinned[:m].copy_(host[lo:lo + m])
+                staged[:m].copy_(pinned[:m], non_blocking=True)
+                uvd_bf16_narrow_(flat[lo:lo + m], staged[:m], tensor=k, index0=index0 + lo, rounding=rounding, rounding_seed=seed)
+                stream.synchronize()
+
+    def _precondition(self, v, h, grad):
+        """psgd.py:748 on the flat gradient; with v and h (None on a step that leaves the preconditioner alone) after :732-733,
+        as one fused call: the same results in three sweeps instead of six.  Row-sharded: this rank's rows, 2 exchanges (4 for
+        a native bf16 state), :562 and :588 from the synchronised generator.  A native state gets the rounding seed of this step."""
+        U, V, d = self._state_fp32()
+        g = grad[:, None].contiguous()
+        if self._group is not None:          # (looked up at the call, as a global is: a spy on the module attribute sees the call)
+            apply, fused = self._sharded.precond_grad_UVd_math, self._sharded.update_precond_UVd_math_and_precond_grad
+        else:
+            apply, fused = precond_grad_UVd_math, update_precond_UVd_math_and_precond_grad
+        if v is None:
+            return apply(U, V, d, g, **self._apply_kw)
+        seed = None
+        if self._native:
+            seed = uvd_step_rounding_seed(self._round_seed0, self._round_step)
+            self._round_step += 1
+        pre_grad = fused(U, V, d, v[:, None].contiguous(), h[:, None].contiguous(), g, step=float(self.lr_preconditioner),
+                         tiny=self._tiny, rounding_seed=seed, **self._update_kw)
+        self._state_store(U, V, d)
+        return pre_grad
+
 
 # --------------------------------------------------------------------------- Kron optimizer (kron_optimizer.py, multi_tail.py)
 # (imported last: those modules build on the step-tail plan, _Hyper, _StepFeatures and the Kron entry points above; the multi_*
@@ -2021,5 +2094,5 @@ from .kron_optimizer import multi_narrow, kron_operand_layers  # noqa: E402,F401
 from .kron_optimizer import multi_randn  # noqa: E402,F401
 
 # --------------------------------------------------------------------------- sparse-LU optimizer (splu_optimizer.py)
-# (after class UVd, whose step it takes, and after multi_randn)
+# (after _FlatStep, its base class)
 from .splu_optimizer import SPLU, splu_initial_factors  # noqa: E402,F401

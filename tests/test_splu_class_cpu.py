@@ -182,19 +182,39 @@ def test_state_dict_keys_and_refusals():
     assert torch.equal(wide._l3, bf["l3"].float())
 
 
-def test_the_borrowed_step_reads_only_what_splu_provides():
-    """class SPLU takes step and six helpers from class UVd as they are (the comment above UVd._pack_scale): every attribute those
-    seven name on `self` exists on an SPLU object, except the two that only UVd's row-sharded branches touch"""
+SHARED = ("step", "_pack_scale", "_flat", "_momentum_buffer", "_grad_flat", "_grad_cat", "_guarded_grad", "_whitening_inputs",
+          "_draw_probe")
+SUBCLASS_STATE = ("_arena", "_U", "_V", "_d", "_L12", "_l3", "_U12", "_u3", "_native", "_in_place", "_out")
+
+
+def test_the_flat_step_is_one_copy_under_both_classes():
+    """class UVd and class SPLU are subclasses of _FlatStep and override none of the shared members"""
+    base = impl._FlatStep
+    assert issubclass(psgd.UVd, base) and issubclass(psgd.SPLU, base) and issubclass(base, impl._StepFeatures)
+    for f in SHARED:
+        assert getattr(psgd.UVd, f) is getattr(psgd.SPLU, f) is getattr(base, f), f
+        assert f not in vars(psgd.UVd) and f not in vars(psgd.SPLU), f
+    assert psgd.UVd._HYPER_KEYS is psgd.SPLU._HYPER_KEYS is base._HYPER_KEYS
+
+
+FEATURES = dict(momentum=0.9, nonfinite="skip", loss_scale="dynamic", preconditioner_fit="whitening")
+
+
+def test_the_base_class_reads_only_what_both_subclasses_provide():
+    """every self.<name> in the source of _FlatStep exists on an object of each subclass built without a device, with the defaults
+    and with the features on, except the two that only the row-sharded branches touch; and the source names no subclass's state
+    or placement"""
     import re
-    borrowed = ("step", "_pack_scale", "_momentum_buffer", "_grad_flat", "_grad_cat", "_guarded_grad", "_whitening_inputs")
-    opt = psgd.SPLU(_params(), 4)
-    names = set()
-    for f in borrowed:
-        assert getattr(psgd.SPLU, f) is getattr(psgd.UVd, f), f
-        names |= set(re.findall(r"\bself\.(\w+)", inspect.getsource(getattr(psgd.UVd, f))))
-    missing = sorted(n for n in names if not hasattr(opt, n))
-    assert missing == ["_coins", "_sharded"], missing
-    assert opt._group is None and opt._arena is None
+    source = inspect.getsource(impl._FlatStep)
+    names = set(re.findall(r"\bself\.(\w+)", source))
+    assert {"_flat_region", "_precondition", "_state_encode", "_state_judge", "_state_commit", "_group"} <= names
+    for opt in [cls(_params(), 4, **kw) for kw in ({}, FEATURES) for cls in (psgd.UVd, psgd.SPLU)]:
+        missing = sorted(n for n in names if not hasattr(opt, n))
+        assert missing == ["_coins", "_sharded"], (type(opt).__name__, missing)
+        assert opt._group is None
+    named = sorted(a for a in SUBCLASS_STATE if re.search(r"(?<!\w)%s\b" % a, source))
+    assert named == [], named
+    assert not hasattr(psgd.SPLU(_params(), 4), "_arena")
 
 
 def test_a_refused_state_dict_leaves_the_optimizer_as_it_was():

@@ -6,6 +6,7 @@ import ctypes
 import pytest
 import torch
 
+import preconditioned_stochastic_gradient_descent as psgd
 from psgd_tf_amd import _lib, sharded
 
 
@@ -147,3 +148,93 @@ def test_state_dict_values_survive_weights_only_loading():
     assert got["hyper"] == sd["hyper"] and got["param_sizes"] is None
     assert got["U"].dtype == torch.bfloat16 and torch.equal(_bits(got["U"]), _bits(sd["U"]))
     assert got["branch_rng"].dtype == torch.uint8 and torch.equal(got["branch_rng"], sd["branch_rng"])
+
+
+# ------------------------------------------------------------------------------- class UVd: judge first, then commit or draw
+SHAPES = [(5, 7), (4, 3), (7,)]
+FEATURES = dict(momentum=0.9, nonfinite="skip", loss_scale=2 ** 4, preconditioner_fit="whitening")
+
+
+def _class_params(dtype=torch.float32):
+    g = torch.Generator().manual_seed(0)
+    return [torch.randn(s, generator=g).to(dtype).requires_grad_(True) for s in SHAPES]
+
+
+def _raw(t):
+    return t.detach().reshape(-1).view(torch.uint8).clone()
+
+
+def _uvd_pair(dtype=torch.float32, **kw):
+    """an optimizer and the state dict of a differently-seeded twin that differs from it in every value a load restores"""
+    g = torch.Generator().manual_seed(3)
+    opt = psgd.UVd(_class_params(dtype), 3, generator=g, **dict(FEATURES, **kw))
+    opt._momentum_buffer().copy_(torch.arange(54.0))
+    opt._m_step, opt._probe_step = 3, 2
+    twin = psgd.UVd(_class_params(dtype), 3, generator=torch.Generator().manual_seed(9), lr_params=0.5,
+                    **dict(FEATURES, momentum=0.8, loss_scale=2 ** 6, **kw))
+    twin._momentum_buffer().copy_(torch.arange(54.0).flip(0))
+    twin._m_step, twin._probe_step, twin._param_round_step = 5, 7, 11
+    twin._U.mul_(2)
+    return g, opt, twin.state_dict()
+
+
+def _held(g, opt):
+    return (_raw(g.get_state()), float(opt.lr_params), float(opt.momentum), float(opt.loss_scale), opt.probe_seed0, opt.probe_step,
+            _raw(opt._m), opt._m_step, _raw(opt._U), opt._param_round_seed0, opt._param_round_step)
+
+
+def _same(a, b):
+    return all(torch.equal(x, y) if isinstance(x, torch.Tensor) else x == y for x, y in zip(a, b))
+
+
+def test_a_refused_state_dict_leaves_the_optimizer_as_it_was():
+    g, opt, sd = _uvd_pair()
+    refused = [dict(sd, loss_scale=3.0), {k: v for k, v in sd.items() if k != "probe_step"},
+               dict(sd, branch_rng=torch.zeros(3, dtype=torch.uint8)), dict(sd, momentum_buffer=torch.zeros(53))]
+    gb, optb, sdb = _uvd_pair(torch.bfloat16, param_rounding="stochastic")
+    cases = [(g, opt, bad) for bad in refused] + [(gb, optb, {k: v for k, v in sdb.items() if k != "param_round_step"})]
+    for gen, o, bad in cases:
+        before = _held(gen, o)
+        with pytest.raises(ValueError):
+            o.load_state_dict(bad)
+        assert _same(_held(gen, o), before)
+    for gen, o, good in ((g, opt, sd), (gb, optb, sdb)):
+        before = _held(gen, o)
+        o.load_state_dict(good)
+        want = (_raw(good["branch_rng"]), good["hyper"]["lr_params"], good["hyper"]["momentum"], good["loss_scale"],
+                good["probe_seed0"], good["probe_step"], _raw(good["momentum_buffer"]), good["momentum_step"], _raw(good["U"]),
+                good.get("param_round_seed0"), good.get("param_round_step", 0))
+        assert _same(_held(gen, o), want) and not any(_same([x], [y]) for x, y in zip(before[:9], want[:9]))
+
+
+BAD_ARGUMENTS = [(dict(step_tail="x"), "step_tail"), (dict(placement="x"), "placement"), (dict(state_route="x"), "state_route"),
+                 (dict(state_dtype=torch.bfloat16, state_route="native", state_rounding="up"), "state_rounding must be"),
+                 (dict(state_rounding="nearest"), "state_rounding applies"), (dict(preconditioner_fit="x"), "preconditioner_fit"),
+                 (dict(param_rounding="x"), "param_rounding"), (dict(momentum=1.0), "momentum"), (dict(nonfinite="x"), "nonfinite"),
+                 (dict(loss_scale=2.0), "loss_scale needs"), (dict(nonfinite="skip", loss_scale=3.0), "loss_scale must be a power of two"),
+                 (dict(nonfinite="skip", loss_scale="x"), "loss_scale must be None"),
+                 (dict(loss_scale_growth_interval=0), "loss_scale_growth_interval"), (dict(rank_of_modification=0), "rank_of_modification")]
+
+
+@pytest.mark.parametrize("bad, match", BAD_ARGUMENTS, ids=[m.split()[0] + str(i) for i, (_, m) in enumerate(BAD_ARGUMENTS)])
+def test_a_bad_argument_is_refused_before_anything_is_drawn(bad, match):
+    """each call would draw all three construction seeds if it were accepted (a native bfloat16 state, stochastic parameter
+    rounding, the whitening fit): the generator behind them is left as it was"""
+    g = torch.Generator().manual_seed(7)
+    before = g.get_state().clone()
+    kw = dict(rank_of_modification=3, generator=g, state_dtype=torch.bfloat16, state_route="native", param_rounding="stochastic",
+              preconditioner_fit="whitening")
+    if "state_rounding" in bad and "state_route" not in bad:
+        kw.update(state_dtype=None, state_route="widen")
+    with pytest.raises(ValueError, match="UVd: " + match):
+        psgd.UVd(_class_params(torch.bfloat16), **dict(kw, **bad))
+    assert torch.equal(g.get_state(), before)
+
+
+def test_a_good_construction_draws_state_parameters_probe_in_this_order():
+    g = torch.Generator().manual_seed(7)
+    opt = psgd.UVd(_class_params(torch.bfloat16), 3, generator=g, state_dtype=torch.bfloat16, state_route="native",
+                   param_rounding="stochastic", preconditioner_fit="whitening")
+    twin = torch.Generator().manual_seed(7)
+    want = [int(torch.randint(0, 2 ** 62, (), generator=twin).item()) for _ in range(3)]
+    assert [opt._round_seed0, opt._param_round_seed0, opt.probe_seed0] == want and torch.equal(g.get_state(), twin.get_state())

@@ -574,3 +574,56 @@ def test_load_errors(psgd):
         psgd.uvd_bf16_narrow_(opt._U, opt._U.float(), tensor="Q")
     with pytest.raises(TypeError):
         psgd.uvd_bf16_narrow_(opt._U.float(), opt._U.float(), tensor="U")
+
+
+# ------------------------------------------------------------------------------------------------ 10. judge, then commit
+TINY = [(5, 7), (4, 3), (7,)]
+ROUTES = {"packed": dict(placement="packed"), "native": dict(state_dtype=torch.bfloat16, state_route="native", placement=None)}
+
+
+def _tiny(psgd, route, seed):
+    g = torch.Generator().manual_seed(0)
+    params = [torch.randn(s, generator=g).to(_dev()).requires_grad_(True) for s in TINY]
+    c = [torch.rand(s, generator=g).add(0.5).to(_dev()) for s in TINY]
+    torch.cuda.manual_seed(seed)
+    opt = psgd.UVd(params, 3, lr_params=0.05 * seed, lr_preconditioner=0.1, generator=torch.Generator().manual_seed(seed),
+                   momentum=0.9, preconditioner_fit="whitening", step_tail="fused", **ROUTES[route])
+    return opt, params, lambda: sum(0.5 * (ci * p * p).sum() for p, ci in zip(params, c))
+
+
+@pytest.mark.parametrize("route", list(ROUTES))
+def test_a_refused_load_changes_nothing_on_the_device_routes(psgd, route):
+    """the two routes of the state that cannot be built without a device: a refused dict leaves the tensors, the momentum buffer
+    and the rounding stream as they were, the accepted one gives the twin's next step bit for bit"""
+    twin, tparams, tclosure = _tiny(psgd, route, 9)
+    for _ in range(2):
+        twin.step(tclosure)
+    sd = _through_torch_save(twin.state_dict())
+    opt, params, closure = _tiny(psgd, route, 3)
+    opt.step(closure)
+
+    def held():
+        return [t.detach().clone() for t in (opt._U, opt._V, opt._d, opt._momentum_buffer())], (opt._round_seed0, opt._round_step)
+    tensors = (opt._U, opt._V, opt._d)
+    before = held()
+    with pytest.raises(ValueError, match="probe_step"):
+        opt.load_state_dict({k: v for k, v in sd.items() if k != "probe_step"})
+    after = held()
+    assert all(_same_bits(a, b) for a, b in zip(after[0], before[0])) and after[1] == before[1]
+    assert all(a is b for a, b in zip(tensors, (opt._U, opt._V, opt._d))) and float(opt.lr_params) == 0.05 * 3
+    if route == "packed":
+        assert opt._U is opt._arena.U and opt._V is opt._arena.V and opt._d is opt._arena.d and opt._m is None
+    else:
+        assert opt._arena is None and opt._round_seed0 is not None and before[1][1] == 1
+    assert not _same_bits(opt._U, twin._U) and opt.probe_step == 1 and twin.probe_step == 2
+    opt.load_state_dict(sd)
+    assert all(a is b for a, b in zip(tensors, (opt._U, opt._V, opt._d))) and (opt._round_seed0, opt._round_step) == \
+        (twin._round_seed0, twin._round_step)
+    with torch.no_grad():
+        for p, q in zip(params, tparams):
+            p.copy_(q)
+    twin.step(tclosure)
+    opt.step(closure)
+    got = [opt._U, opt._V, opt._d, opt._momentum_buffer()] + params
+    want = [twin._U, twin._V, twin._d, twin._momentum_buffer()] + tparams
+    assert all(_same_bits(a, b) for a, b in zip(got, want)) and opt.probe_step == twin.probe_step == 3

@@ -1,18 +1,20 @@
-"""One sha256 per configuration of class UVd and class Kron after 6 steps: a refactor of the classes' host layer must leave every
-digest that repeats from run to run as it was.
+"""One sha256 per configuration of class UVd, class Kron and class SPLU after 6 steps: a refactor of the classes' host layer must
+leave every digest that repeats from run to run as it was.
 
     python tools/class_step_digest.py [--out FILE]
 
-Three parameters of shapes (5, 7), (4, 3) and (7,) -- Kron(any_rank=True), UVd(rank_of_modification=3) -- a seeded CPU generator
-behind the coin and preconditioner_update_probability=0.5.  The configurations are the cross product of
+Three parameters of shapes (5, 7), (4, 3) and (7,) -- Kron(any_rank=True), UVd and SPLU(rank_of_modification=3) -- a seeded CPU
+generator behind the coin and preconditioner_update_probability=0.5.  The configurations are the cross product of
 
-    class      UVd, Kron                       tail     torch, fused             hvp     exact, fd (finite differences)
+    class      UVd, Kron, SPLU                 tail     torch, fused             hvp     exact, fd (finite differences)
     dtype      float32, bfloat16 with param_rounding="nearest", bfloat16 with param_rounding="stochastic"
     features   off, or momentum 0.9 + weight decay + nonfinite="skip" + loss_scale="dynamic" with an Inf gradient in step 3
 
-and preconditioner_fit="whitening" of both classes on every tail, dtype and feature setting.  The digest covers the parameters, the
-preconditioner state (U, V, d or the factors), the momentum buffers, skipped_steps, the current loss scale and the counters of
-the rounding and probe streams.  Before anything runs on the device the coins of every configuration are replayed on the CPU
+and preconditioner_fit="whitening" of the three classes on every tail, dtype and feature setting; then class UVd on the three
+routes of its state that the grid does not reach (EXTRA_UVD: a placed state, a bfloat16 state read and written natively, a
+bfloat16 state widened every step), each on the fused tail with the features on, exact and whitening.  The digest covers the
+parameters, the preconditioner state (U, V, d or the factors), the momentum buffers, skipped_steps, the current loss scale and
+the counters of the rounding and probe streams.  Before anything runs on the device the coins of every configuration are replayed on the CPU
 from the generator alone, and a configuration whose coins (the step with the Inf gradient left out) do not hold both outcomes is
 an error; after the run the replay is compared with what the steps did (a step updated the preconditioner when its state
 changed), and a line that disagrees says so.
@@ -33,6 +35,8 @@ import preconditioned_stochastic_gradient_descent as psgd  # noqa: E402
 SHAPES = [(5, 7), (4, 3), (7,)]
 STEPS, INF_STEP, P_UPDATE, SEED = 6, 2, 0.5, 1
 FEATURES_ON = dict(momentum=0.9, weight_decay=0.01, nonfinite="skip", loss_scale="dynamic")
+EXTRA_UVD = {"UVd:packed": dict(placement="packed"), "UVd:bf16native": dict(state_dtype=torch.bfloat16, state_route="native"),
+             "UVd:bf16widen": dict(state_dtype=torch.bfloat16)}
 DTYPES = {"fp32": (torch.float32, "nearest"), "bf16": (torch.bfloat16, "nearest"), "bf16sr": (torch.bfloat16, "stochastic")}
 
 
@@ -41,15 +45,20 @@ def configurations():
         yield cls, tail, hvp, dt, feat
     for cls, tail, dt, feat in itertools.product(("Kron", "UVd"), ("torch", "fused"), DTYPES, ("off", "on")):
         yield cls, tail, "whitening", dt, feat
+    for tail, hvp, dt, feat in itertools.product(("torch", "fused"), ("exact", "fd", "whitening"), DTYPES, ("off", "on")):
+        yield "SPLU", tail, hvp, dt, feat
+    for cls, hvp in itertools.product(EXTRA_UVD, ("exact", "whitening")):
+        yield cls, "fused", hvp, "fp32", "on"
 
 
 def replayed_coins(cls, hvp, dt, feat):
-    """the coins of the six steps, from the CPU generator alone: the draws of the constructor (the seed of the parameters'
-    rounding stream, then the probe seed), then per step the coin and what the class draws after it from the same generator --
-    class UVd the two branches of an update that runs, class Kron its probe vectors in the parameters' dtype"""
+    """the coins of the six steps, from the CPU generator alone: the draws of the constructor (the seed of a native bfloat16
+    state, the seed of the parameters' rounding stream, then the probe seed), then per step the coin and what the class draws
+    after it from the same generator -- class UVd the two branches of an update that runs, class Kron its probe vectors in the
+    parameters' dtype, class SPLU nothing"""
     gen = torch.Generator().manual_seed(SEED)
     dtype, rounding = DTYPES[dt]
-    for _ in range((rounding == "stochastic") + (hvp == "whitening")):
+    for _ in range((cls == "UVd:bf16native") + (rounding == "stochastic") + (hvp == "whitening")):
         torch.randint(0, 2 ** 62, (), generator=gen)
     coins = []
     for k in range(STEPS):
@@ -57,7 +66,7 @@ def replayed_coins(cls, hvp, dt, feat):
         coins.append(update)
         if not update:
             continue
-        if cls == "UVd" and not (feat == "on" and k == INF_STEP):
+        if cls.startswith("UVd") and not (feat == "on" and k == INF_STEP):
             torch.rand((), generator=gen), torch.rand((), generator=gen)
         if cls == "Kron" and hvp != "whitening":
             for s in SHAPES:
@@ -72,6 +81,8 @@ def raw(t):
 def state_tensors(opt):
     if isinstance(opt, psgd.Kron):
         return [q for pair in opt.factors for q in pair]
+    if isinstance(opt, psgd.SPLU):
+        return list(opt.factors)
     return [opt._U, opt._V, opt._d]
 
 
@@ -91,8 +102,11 @@ def run(cls, tail, hvp, dt, feat, dev):
     kw = dict(lr_params=0.05, lr_preconditioner=0.1, grad_clip_max_norm=1.0, preconditioner_update_probability=P_UPDATE,
               exact_hessian_vector_product=hvp != "fd", step_tail=tail, generator=torch.Generator().manual_seed(SEED),
               param_rounding=rounding, **(FEATURES_ON if feat == "on" else {}))
-    if cls == "UVd":                              # (its Hessian-fit lines are built without the keyword, as before it existed)
-        opt = psgd.UVd(params, rank_of_modification=3, **dict(kw, **({"preconditioner_fit": "whitening"} if hvp == "whitening" else {})))
+    if cls.startswith("UVd"):                     # (its Hessian-fit lines are built without the keyword, as before it existed)
+        kw.update(EXTRA_UVD.get(cls, {}), **({"preconditioner_fit": "whitening"} if hvp == "whitening" else {}))
+        opt = psgd.UVd(params, rank_of_modification=3, **kw)
+    elif cls == "SPLU":
+        opt = psgd.SPLU(params, rank_of_modification=3, preconditioner_fit="whitening" if hvp == "whitening" else "hessian", **kw)
     else:
         opt = psgd.Kron(params, any_rank=True, preconditioner_fit="whitening" if hvp == "whitening" else "hessian", **kw)
     coins = ""
@@ -102,11 +116,12 @@ def run(cls, tail, hvp, dt, feat, dev):
         opt.step(closure)
         coins += "s" if opt.last_step_skipped else "01"[before != [raw(t) for t in state_tensors(opt)]]
     h = hashlib.sha256()
-    moms = opt._m if isinstance(opt._m, list) else [] if opt._m is None else [opt._m]
+    # (a placed UVd keeps its momentum in the arena's g region and leaves _m at None: _momentum_buffer() is where it lives)
+    moms = opt._m if isinstance(opt._m, list) else [opt._momentum_buffer()] if cls == "UVd:packed" else [] if opt._m is None else [opt._m]
     for t in params + state_tensors(opt) + moms:
         h.update(raw(t))
     # (a Hessian-fit UVd hashes None for the probe counter, as it did when the class had none: its lines stay comparable)
-    probe_step = None if cls == "UVd" and hvp != "whitening" else opt.probe_step
+    probe_step = None if cls.startswith("UVd") and hvp != "whitening" else opt.probe_step
     h.update(repr((opt.skipped_steps, opt.loss_scale.value, opt._param_round_step, probe_step)).encode())
     return h.hexdigest(), coins
 
