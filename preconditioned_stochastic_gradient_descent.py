@@ -9,4 +9,4 @@ from psgd_tf_amd.preconditioned_stochastic_gradient_descent import (  # noqa: F4
     uvd_pack, uvd_step_tail, uvd_tail_chunks, UVdTailPlan, uvd_pack_blend, uvd_momentum_coefficients,
     uvd_check, uvd_loss_scale_next, Kron, multi_sumsq, multi_param_update, multi_diff_scale, kron_initial_factors,
     multi_blend, multi_scale_check, multi_widen_check, multi_vec_precond_update, multi_vec_precond_grad, kron_layers,
-    multi_narrow, kron_operand_layers, SPLU, splu_initial_factors)
+    multi_narrow, kron_operand_layers, SPLU, splu_initial_factors, Dense, dense_initial_factor)

@@ -17,6 +17,7 @@ hello_psgd.py:5) carry over with torch tensors in place of tf tensors:
     class UVd(...).step(closure)                                       psgd.py:630
     class Kron(...).step(closure)                                      (extension: the train_step of mnist_with_lenet5.py:43-57)
     class SPLU(...).step(closure)                                      (extension: demo_usage_of_all_preconditioners.py:43-64)
+    class Dense(...).step(closure)                                     (extension: demo_usage_of_all_preconditioners.py:26-41)
 
 The UVd, sparse-LU and Kron arithmetic runs in hand-written HIP kernels behind the
 C ABI of include/psgd_hip.h (bound in _lib.py).  Tensors must be fp32 and resident on a ROCm
@@ -1310,8 +1311,9 @@ def _flatten_params(params_with_grad):
 
 
 class _FlatStep(_StepFeatures):
-    """An optimizer that preconditions ONE flat float32 vector (psgd.py:692-764): everything of class UVd and class SPLU but the
-    preconditioner itself -- step(), the flat-vector plumbing behind it, the stages of the constructor and the checkpoint pair.
+    """An optimizer that preconditions ONE flat float32 vector (psgd.py:692-764): everything of its three subclasses -- class UVd,
+    class SPLU (splu_optimizer.py) and class Dense (dense_optimizer.py) -- but the preconditioner itself: step(), the flat-vector
+    plumbing behind it, the stages of the constructor and the checkpoint pair.
     A row-sharded flat vector (group=) is part of this class: its branches read _group, _coins and _sharded.
 
     A subclass's __init__ calls _init_params, _init_hypers, _init_tail and _draw_seeds in this order, its own checks between
@@ -2096,3 +2098,6 @@ from .kron_optimizer import multi_randn  # noqa: E402,F401
 # --------------------------------------------------------------------------- sparse-LU optimizer (splu_optimizer.py)
 # (after _FlatStep, its base class)
 from .splu_optimizer import SPLU, splu_initial_factors  # noqa: E402,F401
+
+# --------------------------------------------------------------------------- dense optimizer (dense_optimizer.py)
+from .dense_optimizer import Dense, dense_initial_factor  # noqa: E402,F401

@@ -1,19 +1,19 @@
-"""One sha256 per configuration of class UVd, class Kron and class SPLU after 6 steps: a refactor of the classes' host layer must
-leave every digest that repeats from run to run as it was.
+"""One sha256 per configuration of class UVd, class Kron, class SPLU and class Dense after 6 steps: a refactor of the classes'
+host layer must leave every digest that repeats from run to run as it was.
 
     python tools/class_step_digest.py [--out FILE]
 
-Three parameters of shapes (5, 7), (4, 3) and (7,) -- Kron(any_rank=True), UVd and SPLU(rank_of_modification=3) -- a seeded CPU
-generator behind the coin and preconditioner_update_probability=0.5.  The configurations are the cross product of
+Three parameters of shapes (5, 7), (4, 3) and (7,) -- Kron(any_rank=True), UVd and SPLU(rank_of_modification=3), Dense -- a
+seeded CPU generator behind the coin and preconditioner_update_probability=0.5.  The configurations are the cross product of
 
-    class      UVd, Kron, SPLU                 tail     torch, fused             hvp     exact, fd (finite differences)
+    class      UVd, Kron, SPLU, Dense          tail     torch, fused             hvp     exact, fd (finite differences)
     dtype      float32, bfloat16 with param_rounding="nearest", bfloat16 with param_rounding="stochastic"
     features   off, or momentum 0.9 + weight decay + nonfinite="skip" + loss_scale="dynamic" with an Inf gradient in step 3
 
-and preconditioner_fit="whitening" of the three classes on every tail, dtype and feature setting; then class UVd on the three
+and preconditioner_fit="whitening" of the four classes on every tail, dtype and feature setting; then class UVd on the three
 routes of its state that the grid does not reach (EXTRA_UVD: a placed state, a bfloat16 state read and written natively, a
 bfloat16 state widened every step), each on the fused tail with the features on, exact and whitening.  The digest covers the
-parameters, the preconditioner state (U, V, d or the factors), the momentum buffers, skipped_steps, the current loss scale and
+parameters, the preconditioner state (U, V, d, the factors or Q), the momentum buffers, skipped_steps, the current loss scale and
 the counters of the rounding and probe streams.  Before anything runs on the device the coins of every configuration are replayed on the CPU
 from the generator alone, and a configuration whose coins (the step with the Inf gradient left out) do not hold both outcomes is
 an error; after the run the replay is compared with what the steps did (a step updated the preconditioner when its state
@@ -49,13 +49,15 @@ def configurations():
         yield "SPLU", tail, hvp, dt, feat
     for cls, hvp in itertools.product(EXTRA_UVD, ("exact", "whitening")):
         yield cls, "fused", hvp, "fp32", "on"
+    for tail, hvp, dt, feat in itertools.product(("torch", "fused"), ("exact", "fd", "whitening"), DTYPES, ("off", "on")):
+        yield "Dense", tail, hvp, dt, feat            # (last: the lines before it keep their places)
 
 
 def replayed_coins(cls, hvp, dt, feat):
     """the coins of the six steps, from the CPU generator alone: the draws of the constructor (the seed of a native bfloat16
     state, the seed of the parameters' rounding stream, then the probe seed), then per step the coin and what the class draws
     after it from the same generator -- class UVd the two branches of an update that runs, class Kron its probe vectors in the
-    parameters' dtype, class SPLU nothing"""
+    parameters' dtype, class SPLU and class Dense nothing"""
     gen = torch.Generator().manual_seed(SEED)
     dtype, rounding = DTYPES[dt]
     for _ in range((cls == "UVd:bf16native") + (rounding == "stochastic") + (hvp == "whitening")):
@@ -83,6 +85,8 @@ def state_tensors(opt):
         return [q for pair in opt.factors for q in pair]
     if isinstance(opt, psgd.SPLU):
         return list(opt.factors)
+    if isinstance(opt, psgd.Dense):
+        return [opt.Q]
     return [opt._U, opt._V, opt._d]
 
 
@@ -107,6 +111,8 @@ def run(cls, tail, hvp, dt, feat, dev):
         opt = psgd.UVd(params, rank_of_modification=3, **kw)
     elif cls == "SPLU":
         opt = psgd.SPLU(params, rank_of_modification=3, preconditioner_fit="whitening" if hvp == "whitening" else "hessian", **kw)
+    elif cls == "Dense":
+        opt = psgd.Dense(params, preconditioner_fit="whitening" if hvp == "whitening" else "hessian", **kw)
     else:
         opt = psgd.Kron(params, any_rank=True, preconditioner_fit="whitening" if hvp == "whitening" else "hessian", **kw)
     coins = ""
