@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.multi_randn_cases import MOMENT_N, MOMENT_SEED, moment_figures
+from tests.multi_randn_cases import MOMENT_N, MOMENT_SEED, moment_figures, reference as _reference
 
 pytestmark = pytest.mark.gpu
 
@@ -62,17 +62,6 @@ def _carve(sizes, offsets):
 
 def _sentinels_kept(buf, outside):
     return bool((buf.view(torch.int32)[outside] == SENTINEL).all())
-
-
-_want = {}
-
-
-def _reference(psgd, seed, index0, n):
-    """counter_randn at scale 1, computed once per stream and shared"""
-    key = (seed, index0, n)
-    if key not in _want:
-        _want[key] = psgd.counter_randn(seed, index0, n)
-    return _want[key]
 
 
 def _tolerance(want, scale):
