@@ -71,7 +71,7 @@ class Dense(_psgd._FlatStep):
                  exact_hessian_vector_product: bool = True, generator=None,
                  step_tail="torch", momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None,
                  loss_scale_growth_interval=2000, *, param_rounding="nearest", param_rounding_seed=None,
-                 preconditioner_fit="hessian", probe_seed=None, max_num_params=32768):
+                 preconditioner_fit="hessian", probe_seed=None, param_groups=None, max_num_params=32768):
         # the stages of _FlatStep with this class's check between them; every check comes before anything touches a device
         N = self._init_params(params_with_grad, generator, param_rounding, preconditioner_fit)
         if N > int(max_num_params):
@@ -81,6 +81,7 @@ class Dense(_psgd._FlatStep):
         self._rank, self._store_dtype, self._state_rounding = 0, torch.float32, None
         self._init_hypers(lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability,
                           exact_hessian_vector_product, momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval)
+        self._init_groups(param_groups)          # (None: nothing changes; _StepFeatures._init_groups)
         self._init_tail(step_tail)
         self._draw_seeds(False, param_rounding_seed, probe_seed)
         # the two buffers of the factor: the update reads _Qs[_cur] and writes the other, which holds nothing until then

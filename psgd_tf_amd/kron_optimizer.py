@@ -390,7 +390,8 @@ class Kron(_psgd._StepFeatures):
                  exact_hessian_vector_product=True, *, layer_batch=True, step_tail="torch", generator=None,
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
                  any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM,
-                 param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None):
+                 param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None,
+                 param_groups=None):
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
         self._init_fit(preconditioner_fit)
@@ -422,6 +423,10 @@ class Kron(_psgd._StepFeatures):
         # param_rounding (see the class docstring): judged before the parameters' device is looked at
         self._param_sr = _psgd._param_rounding("Kron", param_rounding, params[0].dtype)
         self._param_round_seed0, self._param_round_step = None, 0
+        # param_groups (None by default: nothing changes): a learning-rate scale and a weight decay per group of parameter tensors,
+        # the switch of class UVd (_StepFeatures._init_groups); judged here, before the parameters' device is looked at
+        self._params = params
+        self._init_groups(param_groups)
         self._shapes = [tuple(int(s) for s in p.shape) for p in params]
         layers = kron_layers(self._shapes, preconditioner_formats, any_rank)
         self._formats = [f for _, _, f in layers]
@@ -434,7 +439,7 @@ class Kron(_psgd._StepFeatures):
             if not p.is_cuda or p.device != dev:
                 raise ValueError("Kron: parameter %d (shape %s) is on %s; all parameters must be on one HIP device (parameter 0 is on %s)"
                                  % (i, tuple(p.shape), p.device, dev))
-        self._params, self._device = params, dev
+        self._device = dev
         # T = the parameters' dtype.  Half precision: factors, momentum buffers and everything the preconditioner reads stay fp32;
         # delta, s and tiny follow T as in class UVd (psgd.py:682-683)
         self._dtype = params[0].dtype
@@ -473,6 +478,8 @@ class Kron(_psgd._StepFeatures):
         self._tail = None
         if step_tail == "fused":
             self._tail = MultiTailPlan([int(p.numel()) for p in params], dev)
+            for g in self.param_groups or ():                   # the groups' chunk tables: made here, once
+                self._tail.group_chunks(g.indices)
             # dG and dX of the finite-difference route: written whole by multi_diff_scale before anything reads them
             self._fd_h = [torch.empty_like(p, dtype=_f32, requires_grad=False) for p in params]
             self._fd_x = [torch.empty_like(p, dtype=_f32, requires_grad=False) for p in params]
@@ -519,7 +526,7 @@ class Kron(_psgd._StepFeatures):
         sd = _encode_features(sd, mom, float(self.weight_decay), self._momentum_buffers() if mom > 0.0 else None, self._m_step,
                               self._guard, self.skipped_steps, self.loss_scale.value, self._good_steps)
         sd = _psgd._param_rounding_encode(sd, self._param_sr, self._param_round_seed0, self._param_round_step)
-        return _probe_encode(sd, self._whiten, self._probe_seed0, self._probe_step)
+        return self._groups_encode(_probe_encode(sd, self._whiten, self._probe_seed0, self._probe_step))
 
     def load_state_dict(self, sd):
         """Restore what state_dict() saved.  The factors become NEW device tensors (as after an update), the hyper-parameters are
@@ -536,6 +543,7 @@ class Kron(_psgd._StepFeatures):
         bufs, m_step = _decode_features(sd, self._shapes)
         sr_state = _psgd._param_rounding_decode("Kron.load_state_dict", sd, self._param_sr, self._param_round_seed0)
         probe_state = _probe_decode(sd, self._whiten, self._probe_seed0, "Kron.load_state_dict")
+        group_values = self._groups_judge(sd, "Kron.load_state_dict")
         try:
             self._coin_generator().set_state(rng)
         except (RuntimeError, TypeError) as e:
@@ -549,6 +557,7 @@ class Kron(_psgd._StepFeatures):
         self._m_step = m_step
         self._param_round_seed0, self._param_round_step = sr_state
         self._probe_seed0, self._probe_step = probe_state
+        self._groups_commit(group_values)
         with torch.no_grad():
             if bufs is not None:
                 for m, b in zip(self._momentum_buffers(), bufs):
@@ -844,6 +853,7 @@ class Kron(_psgd._StepFeatures):
         exact = bool(self.exact_hessian_vector_product)
         fused = self._tail is not None
         mom, wd, S, inv, scaled = self._step_scales()
+        groups = self._step_groups(wd)                          # None without param_groups: nothing below changes
         # how this step feeds step 4: None leaves the factors alone.  The branches differ in what they hand to _screen and in
         # what becomes (dX, dG) after it; "whitening" and None take their gradients alike
         route = None if not update_Q else "whitening" if self._whiten else "exact" if exact else "fd"
@@ -900,8 +910,10 @@ class Kron(_psgd._StepFeatures):
                 pre_grads = [g.contiguous() for g in pre_grads]          # (the mirrored formats return transposed views)
                 sumsq = multi_sumsq(pre_grads, plan=self._tail) if clip else None
                 sr_kw = dict(rounding="stochastic", rounding_seed=sr_seed) if sr else {}
+                # with groups: the one sum of squares above, then one launch of the update per group
+                wd_kw = dict(weight_decay=wd) if groups is None else dict(tensor_groups=groups)
                 multi_param_update(params, pre_grads, undo, lr, sumsq, max_norm if clip else None, self._tiny, plan=self._tail,
-                                   weight_decay=wd, **sr_kw)
+                                   **wd_kw, **sr_kw)
                 return closure_returns
             if self._ops:                                   # float(pg) of the bf16 preconditioned gradients, exact
                 pre_grads = [g.float() if g.dtype != _f32 else g for g in pre_grads]
@@ -912,15 +924,25 @@ class Kron(_psgd._StepFeatures):
                     S = s if S is None else S + s
                 f64 = lambda x: torch.tensor(float(np.float32(x)), dtype=torch.float64, device=self._device)
                 ratio = torch.minimum(f64(max_norm) / (torch.sqrt(S) + f64(self._tiny)), f64(1.0))
-                lr = (f64(lr) * ratio).float()
-            else:
-                lr = float(np.float32(lr))
-            decay = None
-            if wd != 0.0:                                   # c = fl32(lr_eff * wd), as the kernel forms it
-                decay = lr * torch.tensor(wd, dtype=_f32, device=self._device) if clip else float(np.float32(lr) * np.float32(wd))
+
+            def coefficients(lr_j, wd_j):
+                """(lr_eff, c or None) of the kernel for a learning rate and a weight decay given as Python floats"""
+                lr_j = (f64(lr_j) * ratio).float() if clip else float(np.float32(lr_j))
+                if wd_j == 0.0:
+                    return lr_j, None                       # c = fl32(lr_eff * wd), as the kernel forms it
+                return lr_j, lr_j * torch.tensor(wd_j, dtype=_f32, device=self._device) if clip else \
+                    float(np.float32(lr_j) * np.float32(wd_j))
+            if groups is None:
+                coef = [coefficients(lr, wd)] * len(params)
+            else:                     # per tensor: fl32(lr * lr_scale_j), the product in double, and the group's decay, which is
+                coef = [None] * len(params)                 # absent where fl32(wd_j) == 0, as in the kernel
+                for indices, scale, wd_j in groups:
+                    pair = coefficients(lr * scale, float(np.float32(wd_j)))
+                    for i in indices:
+                        coef[i] = pair
             for k, (p, g) in enumerate(zip(params, pre_grads)):
                 if self._reshape:
                     g = g.reshape(p.shape)
-                _psgd._torch_param_update_(p, g, None if undo is None else undo[k], lr, decay, sr_seed,
+                _psgd._torch_param_update_(p, g, None if undo is None else undo[k], *coef[k], sr_seed,
                                            self._param_starts[k] if sr else 0)
         return closure_returns

@@ -171,7 +171,7 @@ def multi_sumsq(tensors, *, plan=None, out=None, ws=None):
 
 
 def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None, tiny=None, *, plan=None, weight_decay=0.0,
-                       rounding="nearest", rounding_seed=None, index0=0):
+                       rounding="nearest", rounding_seed=None, index0=0, tensor_groups=None):
     """For all parameters in ONE launch (psgd_multi_param_update_f32), every operation rounded to float32 on its own:
         p <- p - lr_eff * g                     vs None
         p <- p - (lr_eff * g + v)               vs given (the undo of the finite-difference perturbation, psgd.py:761)
@@ -194,7 +194,13 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
     d = fl32(lr_eff * float(g)), d = fl32(d + float(v)), d = fl32(d + fl32(c * w)), p <- SR(fl32(w - d)) -- with the stochastic
     narrowing of stochastic_narrow_bf16 under rounding_seed (None: drawn from the module's branch generator) on the flat index
     index0 + the element's place in the concatenation of params.  "nearest" (default): nothing changes, and rounding_seed / index0
-    must be left alone."""
+    must be left alone.
+    tensor_groups (None: nothing changes): a sequence of (indices, lr_scale, weight_decay) that partitions range(len(params));
+    weight_decay itself must then be left at 0.  The entry point the call would take anyway is launched once per group over the
+    group's chunks (plan.group_chunks: the plan's segment tables, uploaded once) with lr_j = fl32(float(lr) * lr_scale_j), the
+    product formed in double and rounded once, and the group's weight_decay, so lr_eff_j = fl32(double(lr_j) * the clip factor)
+    and c_j = fl32(lr_eff_j * fl32(wd_j)); a group whose weight_decay is 0 takes the form without the decay term.  sumsq is the
+    caller's, of all gradients and before any scale; the stochastic-rounding index of an element does not depend on the grouping."""
     what = "multi_param_update"
     wd = float(weight_decay)
     if not wd >= 0.0:
@@ -216,6 +222,7 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
     if mixed:
         dtypes["grads"] = _MIXED
     (params, grads, vs), plan = _lists(what, ("params", params), ("grads", grads), ("vs", vs), plan=plan, dtypes=dtypes)
+    groups = _psgd._tensor_groups(what, tensor_groups, len(params), wd, grads is not None)
     if grads is None and (vs is None or sumsq is not None or wd != 0.0):
         raise ValueError("%s: grads=None adds vs to the parameters; it needs vs and takes no sumsq and no weight_decay" % what)
     if (sumsq is None) != (max_norm is None):
@@ -227,43 +234,39 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
         raise ValueError("%s: rounding='stochastic' needs bfloat16 parameters on the HIP device, got %s" % (what, params[0].dtype))
     if not plan.nchunks:
         return
-    if sr:
-        if rounding_seed is None:
-            rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=_psgd._branch_rng).item())
-        name = "psgd_multi_param_update_mixed_sr" if mixed else "psgd_multi_param_update_sr"
-        rc = getattr(_lib.load(), name)(
-            plan.table("params", params, what, T),
-            plan.mixed_table("grads_mixed", grads, what) if mixed else plan.table("grads", grads, what),
-            None if vs is None else plan.table("vs", vs, what, T), len(params), plan.chunks.data_ptr(), plan.nchunks,
-            _psgd._TAIL_DTYPES[T], float(lr), None if sumsq is None else sumsq.data_ptr(),
-            0.0 if max_norm is None else float(max_norm), float(torch.finfo(T).tiny if tiny is None else tiny), wd,
-            int(rounding_seed) & (2 ** 64 - 1), int(index0), _psgd._stream_ptr(plan.device))
-        _lib.check(rc, name)
-        return
-    if mixed:
-        rc = _lib.load().psgd_multi_param_update_mixed(
-            plan.table("params", params, what, T), plan.mixed_table("grads_mixed", grads, what),
-            None if vs is None else plan.table("vs", vs, what, T), len(params), plan.chunks.data_ptr(), plan.nchunks,
-            _psgd._TAIL_DTYPES[T], float(lr), None if sumsq is None else sumsq.data_ptr(),
-            0.0 if max_norm is None else float(max_norm), float(torch.finfo(T).tiny if tiny is None else tiny), wd,
-            _psgd._stream_ptr(plan.device))
-        _lib.check(rc, "psgd_multi_param_update_mixed")
-        return
-    tabs = (plan.table("params", params, what, T), None if grads is None else plan.table("grads", grads, what),
-            None if vs is None else plan.table("vs", vs, what, T), len(params), plan.chunks.data_ptr(), plan.nchunks)
-    tail = (float(lr), None if sumsq is None else sumsq.data_ptr(), 0.0 if max_norm is None else float(max_norm),
+    if sr and rounding_seed is None:
+        rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=_psgd._branch_rng).item())
+    # the segment tables: made (and uploaded where a pointer moved) once, whatever the number of launches
+    ptab = plan.table("params", params, what, T)
+    gtab = None if grads is None else plan.mixed_table("grads_mixed", grads, what) if mixed else plan.table("grads", grads, what)
+    vtab = None if vs is None else plan.table("vs", vs, what, T)
+    clip = (None if sumsq is None else sumsq.data_ptr(), 0.0 if max_norm is None else float(max_norm),
             float(torch.finfo(T).tiny if tiny is None else tiny))
-    if T != _f32:
-        rc = _lib.load().psgd_multi_param_update_t(*tabs, _psgd._TAIL_DTYPES[T], *tail, wd, _psgd._stream_ptr(plan.device))
-        _lib.check(rc, "psgd_multi_param_update_t")
-        return
-    args = tabs + tail
-    if wd == 0.0:
-        rc = _lib.load().psgd_multi_param_update_f32(*args, _psgd._stream_ptr(plan.device))
-        _lib.check(rc, "psgd_multi_param_update_f32")
-    else:
-        rc = _lib.load().psgd_multi_param_update_wd_f32(*args, wd, _psgd._stream_ptr(plan.device))
-        _lib.check(rc, "psgd_multi_param_update_wd_f32")
+    # one launch over the plan's chunks, or one per group over the group's: the same tables, the same sum of squares
+    launches = [(plan.chunks, plan.nchunks, float(lr), wd)] if groups is None else \
+        [plan.group_chunks(indices) + (float(lr) * scale, wd_j) for indices, scale, wd_j in groups]
+    for chunks, nchunks, lr_j, wd_j in launches:
+        if not nchunks:
+            continue
+        tabs = (ptab, gtab, vtab, len(params), chunks.data_ptr(), nchunks)
+        if sr:
+            name = "psgd_multi_param_update_mixed_sr" if mixed else "psgd_multi_param_update_sr"
+            rc = getattr(_lib.load(), name)(*tabs, _psgd._TAIL_DTYPES[T], lr_j, *clip, wd_j, int(rounding_seed) & (2 ** 64 - 1),
+                                            int(index0), _psgd._stream_ptr(plan.device))
+        elif mixed:
+            name = "psgd_multi_param_update_mixed"
+            rc = _lib.load().psgd_multi_param_update_mixed(*tabs, _psgd._TAIL_DTYPES[T], lr_j, *clip, wd_j,
+                                                           _psgd._stream_ptr(plan.device))
+        elif T != _f32:
+            name = "psgd_multi_param_update_t"
+            rc = _lib.load().psgd_multi_param_update_t(*tabs, _psgd._TAIL_DTYPES[T], lr_j, *clip, wd_j, _psgd._stream_ptr(plan.device))
+        elif wd_j == 0.0:
+            name = "psgd_multi_param_update_f32"
+            rc = _lib.load().psgd_multi_param_update_f32(*tabs, lr_j, *clip, _psgd._stream_ptr(plan.device))
+        else:
+            name = "psgd_multi_param_update_wd_f32"
+            rc = _lib.load().psgd_multi_param_update_wd_f32(*tabs, lr_j, *clip, wd_j, _psgd._stream_ptr(plan.device))
+        _lib.check(rc, name)
 
 
 def multi_diff_scale(a, b, h, v=None, x=None, s=1.0, *, plan=None):

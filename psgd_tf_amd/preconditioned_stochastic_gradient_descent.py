@@ -868,9 +868,10 @@ class UVdTailPlan:
             self.starts.append(acc)
             acc += n
         self.total = acc
-        chunks = uvd_tail_chunks(self.sizes)
+        chunks = self._host_chunks = uvd_tail_chunks(self.sizes)
         self.nchunks = int(chunks.shape[0])
         self.chunks = torch.from_numpy(chunks).to(self.device) if self.nchunks else None
+        self._group_chunks = {}
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=self.device)
         self.ws = torch.empty(_lib.UVD_SUMSQ_WS_BYTES, dtype=torch.uint8, device=self.device)
         # the flag words of the guarded step (uvd_pack(flag=, stamp=), uvd_check): slots v, h, g and one spare.  Zero ONCE, here:
@@ -892,8 +893,57 @@ class UVdTailPlan:
             tab = self._tables[role] = _SegTable(self.starts, self.sizes, dev)
         return tab.refresh([t.data_ptr() for t in tensors])
 
+    def group_chunks(self, indices):
+        """(device chunk table, its row count) of the SUB-PLAN of the tensors at `indices` (a tuple, ascending): the rows of the
+        plan's chunk table whose segment is one of them, in the plan's order.  A launch over it walks these tensors only and reads
+        the plan's own segment tables, all k rows of them: a segment keeps its row, its pointer and its `start` (the offset in the
+        flat order that the flat gradient and the stochastic-rounding index are taken from), so nothing about an element depends
+        on the grouping, and a table whose pointers change from step to step (vs, a gradient list) is still uploaded once, not
+        once per group.  Made at the first call for these indices and kept: an upload of 16 bytes per chunk, nothing N-sized."""
+        got = self._group_chunks.get(indices)
+        if got is None:
+            rows = self._host_chunks[np.isin(self._host_chunks[:, 0], np.asarray(indices, dtype=np.int64))]
+            while len(self._group_chunks) >= 64:
+                self._group_chunks.pop(next(iter(self._group_chunks)))
+            got = self._group_chunks[indices] = (torch.from_numpy(np.ascontiguousarray(rows)).to(self.device) if len(rows) else None,
+                                                 int(rows.shape[0]))
+        return got
 
-_tail_plans = {}     # (device, dtype, sizes) -> UVdTailPlan of the calls that bring none (a model has one or two such keys)
+
+def _tensor_groups(what, tensor_groups, k, weight_decay, pre):
+    """The tensor_groups argument of a functional step tail, checked: a list of (indices, lr_scale, weight_decay) -- sorted index
+    tuples that partition range(k), lr_scale a finite float >= 0, weight_decay a float >= 0.  None stays None."""
+    if tensor_groups is None:
+        return None
+    if float(weight_decay) != 0.0:
+        raise ValueError("%s: with tensor_groups every group brings its own weight_decay; leave the weight_decay argument at 0" % what)
+    if not pre:
+        raise ValueError("%s: tensor_groups apply to the update; the perturbation p + v is one launch over all tensors" % what)
+    out, seen = [], set()
+    for j, group in enumerate(tensor_groups):
+        try:
+            indices, scale, wd = group
+            indices, scale, wd = tuple(sorted(int(i) for i in indices)), float(scale), float(wd)
+        except (TypeError, ValueError):
+            raise ValueError("%s: tensor_groups[%d] must be (indices, lr_scale, weight_decay), got %r" % (what, j, group))
+        if not indices:
+            raise ValueError("%s: tensor_groups[%d] has no indices" % (what, j))
+        if not (scale >= 0.0 and math.isfinite(scale)):
+            raise ValueError("%s: tensor_groups[%d]: lr_scale must be finite and >= 0, got %r" % (what, j, scale))
+        if not wd >= 0.0:
+            raise ValueError("%s: tensor_groups[%d]: weight_decay must be >= 0, got %r" % (what, j, wd))
+        for i in indices:
+            if not 0 <= i < k or i in seen:
+                raise ValueError("%s: tensor_groups must partition range(%d); index %d of tensor_groups[%d] is %s"
+                                 % (what, k, i, j, "listed twice" if i in seen else "out of range"))
+            seen.add(i)
+        out.append((indices, scale, wd))
+    if len(seen) != k:
+        raise ValueError("%s: tensor_groups must partition range(%d); %r are in no group" % (what, k, sorted(set(range(k)) - seen)))
+    return out
+
+
+_tail_plans = {}    # (device, dtype, sizes) -> UVdTailPlan of the calls that bring none (a model has one or two such keys)
 
 
 def _tail_plan(tensors, what):
@@ -1019,7 +1069,7 @@ def uvd_sumsq(x, *, plan):
 
 
 def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group=None, *, plan=None, weight_decay=0.0,
-                  rounding="nearest", rounding_seed=None, index0=0):
+                  rounding="nearest", rounding_seed=None, index0=0, tensor_groups=None):
     """psgd.py:750-762 on all parameters in place, in launches that do not depend on len(params):
         lr_eff = lr                                                         (max_norm None or inf, :750-751)
                  lr * min(max_norm / (||pre_grad|| + tiny), 1)              (:753-754; the norm never reaches the host)
@@ -1035,6 +1085,13 @@ def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group
     p <- SR(fl32(w - d)), SR the stochastic narrowing of stochastic_narrow_bf16 under rounding_seed (None: drawn from the module's
     branch generator) on the flat index index0 + the element's place in the concatenation of params (index0: this rank's first
     row on a row-sharded vector).  With "nearest" (default) nothing changes, and rounding_seed / index0 must be left alone.
+    tensor_groups (extension; None: nothing changes): a sequence of (indices, lr_scale, weight_decay) that partitions
+    range(len(params)); weight_decay itself must then be left at 0.  The sum of squares -- of the WHOLE pre_grad, before any scale
+    -- is taken once (and all-reduced once), then the update entry point is launched once per group over the group's chunks
+    (UVdTailPlan.group_chunks) with lr_j = fl32(float(lr) * lr_scale_j), the product formed in double and rounded once, and the
+    group's weight_decay: lr_eff_j = fl32(double(lr_j) * the clip factor), c_j = fl32(lr_eff_j * fl32(wd_j)), and a group whose
+    weight_decay is 0 takes the form without the decay term.  The stochastic-rounding index of an element does not depend on
+    the grouping.
     The parameters are written through their pointers: autograd's version counters do not move."""
     params = list(params)
     if rounding not in _PARAM_ROUNDINGS:
@@ -1055,6 +1112,7 @@ def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group
     wd = float(weight_decay)
     if not wd >= 0.0:
         raise ValueError("uvd_step_tail: weight_decay must be >= 0, got %r" % (weight_decay,))
+    groups = _tensor_groups("uvd_step_tail", tensor_groups, len(params), wd, pre_grad is not None)
     if pre_grad is None:
         if vsegs is None or clip or wd != 0.0:
             raise ValueError("uvd_step_tail: pre_grad=None adds vs to the parameters; it needs vs and takes no max_norm and no "
@@ -1068,21 +1126,29 @@ def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group
             if group is not None:
                 from . import sharded as _sharded
                 _sharded.all_reduce_sum_f64_(sumsq, group)
-    if plan.nchunks:
-        tiny = torch.finfo(plan.dtype).tiny if tiny is None else tiny
-        args = (psegs, vsegs, len(params), plan.chunks.data_ptr(), plan.nchunks, plan.code,
-                None if pre_grad is None else pre_grad.data_ptr(), float(lr), None if sumsq is None else sumsq.data_ptr(),
+    if not plan.nchunks:
+        return
+    tiny = torch.finfo(plan.dtype).tiny if tiny is None else tiny
+    if sr and rounding_seed is None:
+        rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=_branch_rng).item())
+    # one launch over the plan's chunks, or one per group over the group's: the same tables, the same sum of squares
+    launches = [(plan.chunks, plan.nchunks, float(lr), wd)] if groups is None else \
+        [plan.group_chunks(indices) + (float(lr) * scale, wd_j) for indices, scale, wd_j in groups]
+    for chunks, nchunks, lr_j, wd_j in launches:
+        if not nchunks:
+            continue
+        args = (psegs, vsegs, len(params), chunks.data_ptr(), nchunks, plan.code,
+                None if pre_grad is None else pre_grad.data_ptr(), lr_j, None if sumsq is None else sumsq.data_ptr(),
                 float(max_norm) if clip else 0.0, float(tiny))
         if sr:
-            if rounding_seed is None:
-                rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=_branch_rng).item())
-            rc = _lib.load().psgd_uvd_param_update_multi_sr(*args, wd, int(rounding_seed) & (2 ** 64 - 1), int(index0), _stream_ptr(dev))
+            rc = _lib.load().psgd_uvd_param_update_multi_sr(*args, wd_j, int(rounding_seed) & (2 ** 64 - 1), int(index0),
+                                                            _stream_ptr(dev))
             _lib.check(rc, "psgd_uvd_param_update_multi_sr")
-        elif wd == 0.0:
+        elif wd_j == 0.0:
             rc = _lib.load().psgd_uvd_param_update_multi(*args, _stream_ptr(dev))
             _lib.check(rc, "psgd_uvd_param_update_multi")
         else:
-            rc = _lib.load().psgd_uvd_param_update_multi_wd(*args, wd, _stream_ptr(dev))
+            rc = _lib.load().psgd_uvd_param_update_multi_wd(*args, wd_j, _stream_ptr(dev))
             _lib.check(rc, "psgd_uvd_param_update_multi_wd")
 
 
@@ -1111,8 +1177,37 @@ class _Hyper:
         return "_Hyper(%r)" % (self.value,)
 
 
+class _ParamGroup:
+    """One entry of opt.param_groups: indices, a tuple of positions in the optimizer's parameter order (ascending), and the two
+    _Hyper objects lr_scale and weight_decay (None: the group follows opt.weight_decay).  A schedule changes them with .assign();
+    every step reads and checks them again."""
+
+    def __init__(self, indices, lr_scale, weight_decay):
+        self.indices = tuple(int(i) for i in indices)
+        self.lr_scale, self.weight_decay = _Hyper(lr_scale), _Hyper(weight_decay)
+
+    def __repr__(self):
+        return "_ParamGroup(indices=%r, lr_scale=%r, weight_decay=%r)" % (self.indices, self.lr_scale.value, self.weight_decay.value)
+
+
+def _group_values(name, which, lr_scale, weight_decay):
+    """(lr_scale, weight_decay) of one parameter group as floats, checked: lr_scale finite and >= 0, weight_decay None or >= 0"""
+    try:
+        scale = float(lr_scale)
+        wd = None if weight_decay is None else float(weight_decay)
+    except (TypeError, ValueError):
+        raise ValueError("%s: %s: lr_scale must be a float and weight_decay a float or None, got %r and %r"
+                         % (name, which, lr_scale, weight_decay))
+    if not (scale >= 0.0 and math.isfinite(scale)):
+        raise ValueError("%s: %s: lr_scale must be finite and >= 0, got %r" % (name, which, lr_scale))
+    if wd is not None and not wd >= 0.0:
+        raise ValueError("%s: %s: weight_decay must be >= 0 (or None: the optimizer's), got %r" % (name, which, weight_decay))
+    return scale, wd
+
+
 class _StepFeatures:
     """The switches that class UVd and class Kron share, written once: momentum, weight decay, nonfinite="skip", the loss scale,
+    parameter groups (param_groups: a learning-rate scale and a weight decay per group of tensors; _init_groups, _step_groups),
     the seeds drawn at construction, the stream of param_rounding="stochastic", the preconditioner_fit switch with the state of
     its probe stream (probe_seed0 / probe_step) and the guard's checkpoint keys.  The class that
     inherits this provides self._params (the parameters, in order), self._generator and, where param_rounding is on,
@@ -1173,6 +1268,92 @@ class _StepFeatures:
         S = self._loss_scale_value() if self._guard else 1.0
         inv = 1.0 / S                                           # exact: S is a power of two
         return mom, wd, S, inv, (lambda loss: loss) if S == 1.0 else (lambda loss: loss * S)
+
+    # ------------------------------------------------------------------------------------------------- parameter groups
+    param_groups = None                  # _init_groups makes it a list of _ParamGroup where the constructor was given groups
+
+    def _init_groups(self, param_groups):
+        """the param_groups argument of a constructor, judged against self._params before anything touches a device: None, or a
+        sequence of dicts {"params": [tensors], "lr_scale": 1.0, "weight_decay": None}.  Tensors are matched by identity; the
+        parameters named in no group form an implicit last group (lr_scale 1.0, weight_decay None: it follows opt.weight_decay).
+        Sets self.param_groups (None without groups)."""
+        name = type(self).__name__
+        if param_groups is None:
+            return
+        place = {id(p): i for i, p in enumerate(self._params)}
+        groups, seen = [], set()
+        for j, g in enumerate(param_groups):
+            if not isinstance(g, dict):
+                raise ValueError("%s: param_groups[%d] must be a dict with 'params', got %r" % (name, j, type(g)))
+            unknown = sorted(set(g) - {"params", "lr_scale", "weight_decay"}, key=str)
+            if unknown:
+                raise ValueError("%s: param_groups[%d] has unknown key%s %s (a group holds 'params', 'lr_scale' and 'weight_decay')"
+                                 % (name, j, "" if len(unknown) == 1 else "s", ", ".join(repr(k) for k in unknown)))
+            tensors = g.get("params")
+            tensors = [tensors] if isinstance(tensors, torch.Tensor) else list(tensors if tensors is not None else ())
+            if not tensors:
+                raise ValueError("%s: param_groups[%d] has no 'params'" % (name, j))
+            indices = []
+            for t in tensors:
+                i = place.get(id(t))
+                if i is None:
+                    raise ValueError("%s: param_groups[%d] names a tensor%s that is not one of this optimizer's parameters (they are "
+                                     "matched by identity, and only those that require grad count)"
+                                     % (name, j, " of shape %s" % (tuple(t.shape),) if isinstance(t, torch.Tensor) else ""))
+                if i in seen:
+                    raise ValueError("%s: parameter %d (shape %s) is listed twice in param_groups (again in group %d)"
+                                     % (name, i, tuple(t.shape), j))
+                seen.add(i)
+                indices.append(i)
+            scale, wd = _group_values(name, "param_groups[%d]" % j, g.get("lr_scale", 1.0), g.get("weight_decay"))
+            groups.append(_ParamGroup(sorted(indices), scale, wd))
+        rest = [i for i in range(len(self._params)) if i not in seen]
+        if rest:
+            groups.append(_ParamGroup(rest, 1.0, None))
+        self.param_groups = groups
+
+    def _step_groups(self, wd):
+        """None without groups; else [(indices, lr_scale, weight_decay)] of this step, the values read from the groups' _Hyper
+        objects and checked again (a schedule may have assigned anything); a weight_decay of None follows wd, opt.weight_decay"""
+        if self.param_groups is None:
+            return None
+        name = type(self).__name__
+        out = []
+        for j, g in enumerate(self.param_groups):
+            scale, gwd = _group_values(name, "param_groups[%d]" % j, g.lr_scale.value, g.weight_decay.value)
+            out.append((g.indices, scale, wd if gwd is None else gwd))
+        return out
+
+    def _groups_encode(self, sd):
+        """the checkpoint key of the groups, added to sd when the constructor was given groups (all classes); returns sd"""
+        if self.param_groups is not None:
+            sd["param_groups"] = [{"indices": [int(i) for i in g.indices], "lr_scale": float(g.lr_scale.value),
+                                   "weight_decay": None if g.weight_decay.value is None else float(g.weight_decay.value)}
+                                  for g in self.param_groups]
+        return sd
+
+    def _groups_judge(self, sd, name):
+        """what _groups_commit takes, from a state dict: None where the dict has no 'param_groups' (this object keeps its values),
+        else the checked (lr_scale, weight_decay) of every group.  The dict's groups must be this object's, index for index and
+        in this order (ValueError; an object without groups refuses a dict that has them).  Changes nothing."""
+        if "param_groups" not in sd:
+            return None
+        theirs = sd["param_groups"]
+        try:
+            got = [tuple(int(i) for i in g["indices"]) for g in theirs]
+        except (TypeError, KeyError, ValueError):
+            raise ValueError("%s: 'param_groups' must be a list of dicts with 'indices', 'lr_scale' and 'weight_decay'" % name)
+        mine = None if self.param_groups is None else [g.indices for g in self.param_groups]
+        if got != mine:
+            raise ValueError("%s: 'param_groups' partitions the parameters as %r in the state dict, %r in this optimizer"
+                             % (name, got, mine))
+        return [_group_values(name, "'param_groups'[%d]" % j, g.get("lr_scale", 1.0), g.get("weight_decay"))
+                for j, g in enumerate(theirs)]
+
+    def _groups_commit(self, values):
+        for g, (scale, wd) in zip(self.param_groups or (), values or ()):
+            g.lr_scale.assign(scale)
+            g.weight_decay.assign(wd)
 
     def _guard_outcome(self, skipped, undo_vs=None):
         """book-keeping of a guarded step once its decision is known; a skipped finite-difference step takes the perturbation of
@@ -1380,6 +1561,8 @@ class _FlatStep(_StepFeatures):
         if step_tail == "fused":
             if all(p.is_contiguous() and p.dtype == self._dtype for p in self._params):
                 self._tail = UVdTailPlan(self._param_sizes, self._dtype, self._device)
+                for g in self.param_groups or ():               # the groups' chunk tables: made here, once
+                    self._tail.group_chunks(g.indices)
             else:
                 import warnings
                 warnings.warn("%s: step_tail='fused' needs contiguous parameters of one dtype; this optimizer keeps the torch tail"
@@ -1572,6 +1755,7 @@ class _FlatStep(_StepFeatures):
             update_Q = self._coins.draw(float(self.preconditioner_update_probability))       # the same coin on every rank
         exact = bool(self.exact_hessian_vector_product)
         mom, wd, S, inv, scaled = self._step_scales()
+        groups = self._step_groups(wd)                              # None without param_groups: nothing below changes
         guard, fused = self._guard, self._tail is not None
         if guard:
             self._stamp = self._stamp % (2 ** 31 - 1) + 1       # 1 .. 2^31 - 1, then 1 again: the flags are never zeroed
@@ -1642,21 +1826,37 @@ class _FlatStep(_StepFeatures):
             sr_index0 = int(self._row0()) if self._group is not None else 0
         if fused:                                                                             # :750-762 in the step-tail kernels
             sr_kw = dict(rounding="stochastic", rounding_seed=sr_seed, index0=sr_index0) if sr else {}
+            # with groups: one sum of squares, then one launch of the update per group, each with its own lr and weight decay
+            wd_kw = dict(weight_decay=wd) if groups is None else dict(tensor_groups=groups)
             uvd_step_tail(params, pre_grad, float(self.lr_params), max_norm, self._tiny, vs if undo else None,
-                          self._group, plan=self._tail, weight_decay=wd, **sr_kw)
+                          self._group, plan=self._tail, **wd_kw, **sr_kw)
             return closure_returns
         decay = None
-        if mom != 0.0 or wd != 0.0 or sr:      # the torch tail of the extensions: lr_eff as the step-tail kernel forms it, one op per rounding
-            lr = torch.tensor(float(self.lr_params), dtype=torch.float32, device=pre_grad.device)
+        if mom != 0.0 or wd != 0.0 or sr or groups is not None:      # the torch tail of the extensions: lr_eff as the step-tail kernel forms it, one op per rounding
+            f32t = lambda x: torch.tensor(x, dtype=torch.float32, device=pre_grad.device)
+            clip_factor = None
             if not math.isinf(max_norm):
                 sq = torch.sum((pre_grad * pre_grad).double()).reshape(1)
                 if self._group is not None:
                     self._sharded.all_reduce_sum_f64_(sq, self._group)
                 f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))          # the kernel takes max_norm and tiny as floats
                 ratio = f32(max_norm) / (torch.sqrt(sq[0]) + f32(self._tiny))
-                lr = (lr.double() * torch.clamp(ratio, max=1.0)).float()
-            if wd != 0.0:
-                decay = lr * torch.tensor(wd, dtype=torch.float32, device=pre_grad.device)
+                clip_factor = torch.clamp(ratio, max=1.0)
+
+            def coefficients(lr_j, wd_j):
+                """(lr_eff, c or None) of the kernel for a learning rate and a weight decay given as Python floats"""
+                lr_j = f32t(lr_j)
+                if clip_factor is not None:
+                    lr_j = (lr_j.double() * clip_factor).float()
+                return lr_j, lr_j * f32t(wd_j) if wd_j != 0.0 else None
+            if groups is None:
+                lr, decay = coefficients(float(self.lr_params), wd)
+            else:                                  # per tensor: fl32(lr * lr_scale_j), the product in double, and the group's decay,
+                lr, decay = [None] * len(params), [None] * len(params)      # which is absent where fl32(wd_j) == 0, as in the kernel
+                for indices, scale, wd_j in groups:
+                    pair = coefficients(float(self.lr_params) * scale, float(np.float32(wd_j)))
+                    for i in indices:
+                        lr[i], decay[i] = pair
         elif math.isinf(max_norm):                                                            # :750-751
             lr = float(self.lr_params)
         else:                                                                                 # :753-754
@@ -1667,7 +1867,8 @@ class _FlatStep(_StepFeatures):
             lr = float(self.lr_params) * torch.clamp(max_norm / grad_norm, max=1.0)
         with torch.no_grad():                                                                 # :757-762
             for k, (p, i, j) in enumerate(zip(params, self._param_sizes, self._param_cumsizes)):
-                _torch_param_update_(p, torch.reshape(pre_grad[j - i:j], p.shape), vs[k] if undo else None, lr, decay, sr_seed,
+                lr_k, decay_k = (lr, decay) if groups is None else (lr[k], decay[k])
+                _torch_param_update_(p, torch.reshape(pre_grad[j - i:j], p.shape), vs[k] if undo else None, lr_k, decay_k, sr_seed,
                                      sr_index0 + j - i)
         return closure_returns                                                              # :764
 
@@ -1695,6 +1896,8 @@ class _FlatStep(_StepFeatures):
                                      counted towards the next growth of a dynamic scale
             branch_rng               get_state() of the generator behind the coin flips: the generator= argument, else the
                                      module's branch generator; row-sharded, the synchronised generator all ranks draw from
+            param_groups             only when the constructor was given param_groups: [{"indices": [...], "lr_scale": float,
+                                     "weight_decay": float or None}, ...], the groups of opt.param_groups in order
 
         NOT saved: the parameters (they are the caller's), and the global CUDA generator that draws the probe vectors of
         :713 / :721 -- it belongs to the caller; save torch.cuda.get_rng_state() next to this dict and restore it with
@@ -1714,6 +1917,7 @@ class _FlatStep(_StepFeatures):
             sd["round_seed0"], sd["round_step"] = int(self._round_seed0), int(self._round_step)
         _param_rounding_encode(sd, self._param_sr, self._param_round_seed0, self._param_round_step)
         _probe_encode(sd, self._whiten, self._probe_seed0, self._probe_step)
+        self._groups_encode(sd)
         return _guard_encode(sd, self._guard, self.skipped_steps, self.loss_scale.value, self._good_steps)
 
     def load_state_dict(self, sd, **how):
@@ -1726,6 +1930,9 @@ class _FlatStep(_StepFeatures):
         object has on leaves its seed and starts the counter at 0, and an object with the switch off ignores them.  A guarded
         optimizer (nonfinite="skip") restores skipped_steps, loss_scale_good_steps and, when both sides scale the loss,
         loss_scale where the dict has them and starts them fresh where it has not; an unguarded one ignores them.
+        param_groups: a dict without the key leaves the groups' lr_scale and weight_decay as they are; with the key, the dict's
+        groups must be this object's index for index (ValueError otherwise, also for an object built without groups) and their
+        values are assigned.
 
         Checked against this object (ValueError naming the key): format, rank, num_params, param_sizes (skipped when the dict
         holds None, as a resharded one does), then the subclass's keys (_state_judge; **how are its keywords).  Everything that can
@@ -1774,8 +1981,10 @@ class _FlatStep(_StepFeatures):
             S = float(sd["loss_scale"])
             if not (S > 0.0 and math.isfinite(S) and math.frexp(S)[0] == 0.5):
                 raise ValueError("%s: 'loss_scale' must be a power of two, got %r" % (name, sd["loss_scale"]))
+        group_values = self._groups_judge(sd, name)
         # ---- nothing below refuses the dict
         gen.set_state(sd["branch_rng"])
+        self._groups_commit(group_values)
         for k in self._HYPER_KEYS + tuple(k for k in ("momentum", "weight_decay") if k in hyper):   # (the two: optional in a dict)
             getattr(self, k).assign(hyper[k])
         with torch.no_grad():
@@ -1840,7 +2049,8 @@ class UVd(_FlatStep):
                  exact_hessian_vector_product: bool = True, generator=None, state_dtype=None, group=None,
                  stage_backend=None, placement="auto", state_route="widen", state_rounding=None, step_tail="torch",
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
-                 *, param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None):
+                 *, param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None,
+                 param_groups=None):
         # group (extension): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
         # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the
         # concatenation of the ranks' vectors in rank order, and U, V, d hold this rank's rows only.  A step then costs three
@@ -1916,6 +2126,9 @@ class UVd(_FlatStep):
             raise ValueError("UVd: placement must be None, 'auto', 'probe' or 'packed', got %r" % (placement,))
         if placement == "auto":
             placement = "probe" if 4 * num_params * r >= (1 << 30) else None
+        # param_groups (extension, keyword-only; None by default: nothing changes): a learning-rate scale and a weight decay per
+        # group of parameter tensors (_StepFeatures._init_groups); row-sharded, of this rank's tensors
+        self._init_groups(param_groups)
         self._init_tail(step_tail)                              # (on the fused tail the flat vectors are this object's, or the arena's)
         # group (extension): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
         # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the

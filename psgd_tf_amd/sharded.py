@@ -253,7 +253,8 @@ def reshard_uvd_state(state_dicts, new_row_counts):
     param_round_step (the parameters' rounding stream of param_rounding="stochastic": carried through), probe_seed0 / probe_step
     (the probe stream of preconditioner_fit="whitening": global, not per-rank, carried through unchanged), momentum_step, the keys of a guarded
     optimizer (nonfinite, skipped_steps, loss_scale, loss_scale_good_steps: carried through as they are) and branch_rng
-    (ValueError naming what does not).  momentum_buffer is split by rows as d is when every input dict has one (dropped otherwise).  new_row_counts must sum to num_params_global, and every entry but the last must be a multiple of 64
+    (ValueError naming what does not).  A dict that carries 'param_groups' is refused (ValueError): groups name a rank's own
+    tensors, which a split by rows does not keep, and are rebuilt by the constructor.  momentum_buffer is split by rows as d is when every input dict has one (dropped otherwise).  new_row_counts must sum to num_params_global, and every entry but the last must be a multiple of 64
     (shards start at multiples of 64 rows, see shard_rows).  Output k holds rows [row0', row0' + n') with its own num_params
     and row0; its param_sizes is None (the new ranks' parameter lists are not known here), which UVd.load_state_dict skips.
 
@@ -263,6 +264,9 @@ def reshard_uvd_state(state_dicts, new_row_counts):
     sds = sorted(state_dicts, key=lambda s: int(s["row0"]))
     if not sds:
         raise ValueError("%s: no state dicts" % name)
+    if any("param_groups" in s for s in sds):
+        raise ValueError("%s: a state dict carries 'param_groups'; parameter groups are made of a rank's own tensors and cannot be "
+                         "resharded by rows: drop the key and pass param_groups= to the constructors of the new ranks" % name)
     first = sds[0]
     if first.get("format") != 1:
         raise ValueError("%s: 'format' is %r; this version reads format 1" % (name, first.get("format")))

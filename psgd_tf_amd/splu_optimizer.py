@@ -79,7 +79,7 @@ class SPLU(_psgd._FlatStep):
                  exact_hessian_vector_product: bool = True, generator=None, state_dtype=None, state_rounding=None,
                  step_tail="torch", momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None,
                  loss_scale_growth_interval=2000, *, param_rounding="nearest", param_rounding_seed=None,
-                 preconditioner_fit="hessian", probe_seed=None):
+                 preconditioner_fit="hessian", probe_seed=None, param_groups=None):
         # the stages of _FlatStep with this class's checks between them; every check comes before anything touches a device
         N = self._init_params(params_with_grad, generator, param_rounding, preconditioner_fit)
         store = torch.float32 if state_dtype is None else self._dtype if state_dtype == "param" else state_dtype
@@ -104,6 +104,7 @@ class SPLU(_psgd._FlatStep):
         self._state_rounding = state_rounding
         self._init_hypers(lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability,
                           exact_hessian_vector_product, momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval)
+        self._init_groups(param_groups)          # (None: nothing changes; _StepFeatures._init_groups)
         self._init_tail(step_tail)
         self._draw_seeds(self._bf16, param_rounding_seed, probe_seed)
         # the native kernels take a float32 state in place; anything else goes through the functions and gets fresh factors
