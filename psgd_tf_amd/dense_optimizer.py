@@ -63,6 +63,9 @@ class Dense(_psgd._FlatStep):
     hyper-parameters, the generator state and every counter and seed class UVd saves ("rank" is 0); a resumed run is
     bit-identical to the uninterrupted one.  A load writes into the current buffer.
 
+    mixed_dtypes=True (keyword-only, False by default: nothing changes): the switch of class UVd, with its meaning there -- one
+    optimizer over float32, bfloat16 and float16 tensors on both tails.
+
     Out of scope: group= (a row-sharded state), placement=, a narrow (bfloat16) state, any fused update -> apply, and any
     in-place update."""
 
@@ -71,9 +74,10 @@ class Dense(_psgd._FlatStep):
                  exact_hessian_vector_product: bool = True, generator=None,
                  step_tail="torch", momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None,
                  loss_scale_growth_interval=2000, *, param_rounding="nearest", param_rounding_seed=None,
-                 preconditioner_fit="hessian", probe_seed=None, param_groups=None, max_num_params=32768):
+                 preconditioner_fit="hessian", probe_seed=None, param_groups=None, mixed_dtypes=False,
+                 max_num_params=32768):
         # the stages of _FlatStep with this class's check between them; every check comes before anything touches a device
-        N = self._init_params(params_with_grad, generator, param_rounding, preconditioner_fit)
+        N = self._init_params(params_with_grad, generator, param_rounding, preconditioner_fit, mixed_dtypes)
         if N > int(max_num_params):
             raise ValueError("Dense: the parameters have %d elements and the state of the dense preconditioner would take 2 * 4 * N^2 "
                              "= %d bytes; max_num_params is %d.  psgd.SPLU and psgd.UVd hold a state that grows with N, not N^2"

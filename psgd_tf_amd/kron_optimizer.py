@@ -382,7 +382,19 @@ class Kron(_psgd._StepFeatures):
     preconditioner_fit itself is a constructor choice like step_tail.  The whitened gradient has roughly unit scale per element,
     as Adam's update has: lr_params and grad_clip_max_norm tuned for the Hessian fit do NOT carry over.
 
-    Out of scope: mixed dtypes, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale),
+    mixed_dtypes=True (keyword-only; False by default: nothing changes, a second dtype is the TypeError it was; anything but a
+    bool is a ValueError before a device is touched): every parameter is float32, bfloat16 or float16 on its own, on both tails;
+    a list of one dtype behaves bit for bit as with False.  The switch of class UVd: each tensor is
+    updated as in a one-dtype optimizer of its own dtype given the same float32 preconditioned gradient; delta and tiny are the
+    largest over the dtypes present; param_rounding="stochastic" rounds the bfloat16 tensors and leaves the float32 ones to
+    "nearest" (a float16 tensor, or no bfloat16 one, is a ValueError).  The widening pass widens the bfloat16 and the float16
+    tensors (multi_widen_check once per such dtype over its sub-plan); the float32 tensors SKIP it and are their own wide copies,
+    scaled and judged in place by one multi_scale_check launch over the float32 sub-plan on a guarded step, under the same stamp
+    and flag word: still one host read.  The perturbation and the update run once per dtype present, crossed with param_groups
+    once per (group, dtype) pair that has tensors; sums of squares, blend, randn, diff-scale and the narrowing of operands stay
+    single.  Operand layers are chosen by shape and format as always.  Not in state_dict(), which carries no dtype.
+
+    Out of scope: mixed dtypes with the switch off, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale),
     float16 stochastic rounding."""
 
     def __init__(self, params_with_grad, preconditioner_formats="dense", preconditioner_init_scale=1.0, lr_params=0.01,
@@ -391,7 +403,8 @@ class Kron(_psgd._StepFeatures):
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
                  any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM,
                  param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None,
-                 param_groups=None):
+                 param_groups=None, mixed_dtypes=False):
+        _psgd._mixed_dtypes_switch("Kron", mixed_dtypes)
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
         self._init_fit(preconditioner_fit)
@@ -412,7 +425,7 @@ class Kron(_psgd._StepFeatures):
             tag = "parameter %d (shape %s, %s)" % (i, tuple(p.shape), p.dtype)
             if p.dtype not in _DTYPE_NAMES:
                 raise TypeError("Kron: %s must be float32, bfloat16 or float16" % tag)
-            if p.dtype != params[0].dtype:
+            if p.dtype != params[0].dtype and not mixed_dtypes:
                 raise TypeError("Kron: %s must be %s like parameter 0" % (tag, params[0].dtype))     # one dtype per optimizer
             if p.dim() != 2 and not any_rank:
                 raise ValueError("Kron: %s must have rank 2; reshape it (the reference's demos fold a bias into its matrix)" % tag)
@@ -421,7 +434,10 @@ class Kron(_psgd._StepFeatures):
             if not p.is_contiguous():
                 raise ValueError("Kron: %s is not contiguous" % tag)
         # param_rounding (see the class docstring): judged before the parameters' device is looked at
-        self._param_sr = _psgd._param_rounding("Kron", param_rounding, params[0].dtype)
+        # mixed_dtypes (see the class docstring): _dtypes holds every tensor's own, _mixed says that more than one is present
+        self._dtypes = [p.dtype for p in params]
+        self._mixed = len(set(self._dtypes)) > 1
+        self._param_sr = _psgd._param_rounding("Kron", param_rounding, set(self._dtypes) if self._mixed else params[0].dtype)
         self._param_round_seed0, self._param_round_step = None, 0
         # param_groups (None by default: nothing changes): a learning-rate scale and a weight decay per group of parameter tensors,
         # the switch of class UVd (_StepFeatures._init_groups); judged here, before the parameters' device is looked at
@@ -443,8 +459,11 @@ class Kron(_psgd._StepFeatures):
         # T = the parameters' dtype.  Half precision: factors, momentum buffers and everything the preconditioner reads stay fp32;
         # delta, s and tiny follow T as in class UVd (psgd.py:682-683)
         self._dtype = params[0].dtype
-        self._half = self._dtype != _f32
+        self._half = self._dtype != _f32 or self._mixed
         self._delta, self._fd_inv, self._tiny = _dtype_constants(self._dtype)
+        if self._mixed:           # one perturbation scale and one floor for all tensors: the largest over the dtypes present
+            self._tiny, self._delta = _psgd.mixed_dtype_constants(self._dtypes)
+            self._fd_inv = float(np.float32(1.0) / np.float32(self._delta))
         self._Qs = [kron_initial_factors(s, f, preconditioner_init_scale, dev, "parameter %d" % i)
                     for i, (s, f) in enumerate(zip(self._layer_shapes, self._formats))]
         # the vector layers of the list route (none with any_rank off or vector_route="layer") and all other layers; the applies of
@@ -468,6 +487,7 @@ class Kron(_psgd._StepFeatures):
         self._layer_batch = bool(layer_batch)
         self._generator = generator
         # the construction seeds, from the generator behind the coin: the parameters' first, then the probe's
+        self._param_starts = None
         if self._param_sr:
             self._param_round_seed0 = self._draw_seed(param_rounding_seed)
             self._param_starts = [0]
@@ -477,16 +497,20 @@ class Kron(_psgd._StepFeatures):
             self._probe_seed0 = self._draw_seed(probe_seed)
         self._tail = None
         if step_tail == "fused":
-            self._tail = MultiTailPlan([int(p.numel()) for p in params], dev)
+            self._tail = MultiTailPlan([int(p.numel()) for p in params], dev, self._dtypes if self._mixed else None)
             for g in self.param_groups or ():                   # the groups' chunk tables: made here, once
                 self._tail.group_chunks(g.indices)
+                if self._mixed:                                 # ... and those of the (group, dtype) pairs
+                    self._tail.dtype_chunks(g.indices)
             # dG and dX of the finite-difference route: written whole by multi_diff_scale before anything reads them
             self._fd_h = [torch.empty_like(p, dtype=_f32, requires_grad=False) for p in params]
             self._fd_x = [torch.empty_like(p, dtype=_f32, requires_grad=False) for p in params]
             if self._half:
                 # the fp32 copies of the gradients, the second list and the probe vectors: written whole by the one
                 # multi_widen_check launch of a step before anything reads them
-                self._wide = [[torch.empty_like(p, dtype=_f32, requires_grad=False) for p in params] for _ in range(3)]
+                # (mixed: a float32 tensor skips the widening pass and has no copy)
+                self._wide = [[None if p.dtype == _f32 else torch.empty_like(p, dtype=_f32, requires_grad=False) for p in params]
+                              for _ in range(3)]
             if self._ops:
                 # the bf16 copies of the gradient, dX and dG of every operand layer, in the layer's shape (6 bytes per element of
                 # these layers): each is written whole by a multi_narrow launch before the preconditioner call that reads it
@@ -629,12 +653,23 @@ class Kron(_psgd._StepFeatures):
                 scales += [inv, 1.0]
             dsts = self._wide[:len(srcs)]
             plan, bad = self._tail, False
+            scale_f32 = self._mixed and (self._guard or inv != 1.0)
+            if self._mixed:
+                # the float32 tensors skip the widening pass: they are their own wide copies, scaled in place and judged by a
+                # multi_scale_check launch over the float32 sub-plan where there is a scale or a guard, else not touched at all
+                if scale_f32 and inv != 1.0:
+                    srcs = [self._owned(ts) for ts in srcs]
+                dsts = [[x if w is None else w for x, w in zip(ts, ws)] for ts, ws in zip(srcs, dsts)]
             if self._guard:
-                stamp = plan.next_stamp()
+                stamp = plan.next_stamp()                       # one stamp, one flag word for all launches of this pass
                 multi_widen_check(srcs, dsts, scales, flag=plan.flag, stamp=stamp, plan=plan)
+                if scale_f32:
+                    multi_scale_check(srcs, scales, flag=plan.flag, stamp=stamp, plan=plan)
                 bad = int(plan.flag.item()) == stamp                                            # the host read of a guarded step
             else:
                 multi_widen_check(srcs, dsts, scales, plan=plan)
+                if scale_f32:
+                    multi_scale_check(srcs, scales, plan=plan)
             wide = dsts + [None] * (3 - len(dsts))
             return wide[0], wide[1], wide[2], bad
         grads = [g.float() * inv for g in grads]
@@ -943,6 +978,6 @@ class Kron(_psgd._StepFeatures):
             for k, (p, g) in enumerate(zip(params, pre_grads)):
                 if self._reshape:
                     g = g.reshape(p.shape)
-                _psgd._torch_param_update_(p, g, None if undo is None else undo[k], *coef[k], sr_seed,
-                                           self._param_starts[k] if sr else 0)
+                _psgd._torch_param_update_(p, g, None if undo is None else undo[k], *coef[k],
+                                           sr_seed if p.dtype == torch.bfloat16 else None, self._param_starts[k] if sr else 0)
         return closure_returns

@@ -21,16 +21,21 @@ _TINY = float(np.finfo(np.float32).tiny)
 _HALF = (torch.bfloat16, torch.float16)
 _MIXED = (torch.float32, torch.bfloat16)            # the dtypes of a mixed list: a preconditioned gradient is one or the other
 _DTYPE_NAMES = {torch.float32: "float32", torch.bfloat16: "bfloat16", torch.float16: "float16"}
+_CODE_DTYPES = {code: dt for dt, code in _psgd._TAIL_DTYPES.items()}
 
 
 # --------------------------------------------------------------------------- list kernels
 class MultiTailPlan(_psgd.UVdTailPlan):
     """The chunk table, the segment tables (one per role), the device double of the clip norm and the workspace of its reduction for
     lists of tensors of fixed sizes.  The tables hold pointers and element counts only, so one plan serves the fp32 lists and
-    the bfloat16 / float16 lists of the typed entry points alike.  Calls that share a plan must run on one stream."""
+    the bfloat16 / float16 lists of the typed entry points alike.  Calls that share a plan must run on one stream.
+    dtypes (None: nothing changes): one dtype per PARAMETER tensor, float32, bfloat16 or float16 each.  With more than one present
+    the plan is MIXED (UVdTailPlan): the typed lists of a call (params, vs, the sources of a widening) are checked tensor by
+    tensor against these, and every typed launch runs once per dtype present over that dtype's sub-plan (dtype_chunks)."""
 
-    def __init__(self, sizes, device):
-        super().__init__(sizes, torch.float32, device)
+    def __init__(self, sizes, device, dtypes=None):
+        # (dtypes that are all one: the dtype-agnostic plan, whose typed calls take T from params[0] as they always did)
+        super().__init__(sizes, list(dtypes) if dtypes is not None and len(set(dtypes)) > 1 else torch.float32, device)
         self.ws = torch.empty(_lib.MULTI_SUMSQ_WS_BYTES, dtype=torch.uint8, device=self.device)
         # the flag word of the guarded step (multi_scale_check) and the stamp last stored to it.  The word is zeroed ONCE, here: the
         # kernel stores a stamp that this word has not seen before, so nothing ever clears it again
@@ -38,20 +43,9 @@ class MultiTailPlan(_psgd.UVdTailPlan):
         self.stamp = 0
 
     def table(self, role, tensors, what, dtype=_f32):
-        """device pointer of the segment table of `tensors` (contiguous tensors of `dtype` with the plan's sizes) in this role"""
-        if dtype == self.dtype:
-            return super().table(role, tensors, what)
-        if len(tensors) != len(self.sizes):
-            raise ValueError("%s: %d tensors, the plan has %d" % (what, len(tensors), len(self.sizes)))
-        for t, n in zip(tensors, self.sizes):
-            if t.dtype != dtype or t.device != self.device or t.numel() != n or not t.is_contiguous():
-                raise ValueError("%s: every tensor must be a contiguous %s tensor on %s with the plan's element count (%d), got %s %s "
-                                 "%s%s" % (what, dtype, self.device, n, t.dtype, t.device, tuple(t.shape),
-                                           "" if t.is_contiguous() else " strided"))
-        tab = self._tables.get(role)
-        if tab is None:
-            tab = self._tables[role] = _psgd._SegTable(self.starts, self.sizes, self.device)
-        return tab.refresh([t.data_ptr() for t in tensors])
+        """device pointer of the segment table of `tensors` (contiguous tensors of `dtype` -- one for all, or a list with one per
+        tensor -- with the plan's sizes) in this role"""
+        return super().table(role, tensors, what, dtype)
 
     def mixed_table(self, role, tensors, what):
         """device pointer of the segment table of a MIXED list in this role: contiguous tensors with the plan's sizes, each float32
@@ -90,9 +84,14 @@ def _check_list(what, name, tensors, sizes=None, device=None, dtype=_f32):
     tensors = list(tensors)
     if sizes is not None and len(tensors) != len(sizes):
         raise ValueError("%s: %s has %d tensors, the first list has %d" % (what, name, len(tensors), len(sizes)))
+    each = dtype if isinstance(dtype, list) else None           # (a list: one dtype per position, a mixed plan's)
+    if each is not None and len(each) != len(tensors):
+        raise ValueError("%s: %s has %d tensors, the plan has %d" % (what, name, len(tensors), len(each)))
     for i, t in enumerate(tensors):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s: %s[%d] is not a torch tensor (%r)" % (what, name, i, type(t)))
+        if each is not None:
+            dtype = each[i]
         if t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):          # (a tuple: a mixed list)
             raise TypeError("%s: %s[%d] must be %s, got %s" % (what, name, i, " or ".join(
                 _DTYPE_NAMES[d] for d in (dtype if isinstance(dtype, tuple) else (dtype,))), t.dtype))
@@ -186,6 +185,10 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
     float32, and the call goes to psgd_multi_param_update_t: delta = T(float32(lr_eff * g)), then T(delta + v), then
     T(delta + T(float32(c * float(p)))), p <- T(p - delta); p <- T(p + v) without grads.  tiny then defaults to finfo(T).tiny.
     (A half-precision tensor that is not on the device is refused as before: params must be float32.)
+    A plan built for a MIXED list (MultiTailPlan(sizes, device, dtypes)): params and vs have the plan's dtype at every position, and
+    the entry point a one-dtype list of that dtype would take is launched once per dtype present over that dtype's sub-plan
+    (crossed with tensor_groups: per (group, dtype) pair that has tensors); rounding="stochastic" applies to the bfloat16 tensors
+    and needs one and no float16 tensor; tiny defaults to the largest finfo(T).tiny present.
     MIXED gradients: when some tensors of grads are bfloat16 device tensors and the others float32 (the preconditioned gradients
     of bf16-operand layers), the call goes to psgd_multi_param_update_mixed, which reads every gradient as float(g) and rounds as
     above for the parameters' dtype, float32 included.  A list without a bfloat16 tensor calls the entry points of before.
@@ -214,7 +217,9 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
         raise ValueError("%s: rounding='stochastic' needs grads (the perturbation p + v rounds to nearest) and index0 >= 0" % what)
     params = list(params)
     T = _f32
-    if params and isinstance(params[0], torch.Tensor) and params[0].is_cuda and params[0].dtype in _HALF:
+    if plan is not None and plan.mixed:                         # a plan built for a mixed list: one dtype per position
+        T = list(plan.dtypes)
+    elif params and isinstance(params[0], torch.Tensor) and params[0].is_cuda and params[0].dtype in _HALF:
         T = params[0].dtype
     grads = None if grads is None else list(grads)
     mixed = grads is not None and _has_bf16(grads)
@@ -230,7 +235,9 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
     if sumsq is not None and (not isinstance(sumsq, torch.Tensor) or sumsq.dtype != torch.float64 or sumsq.device != plan.device
                               or sumsq.numel() < 1):
         raise ValueError("%s: sumsq must be a float64 tensor of at least one element on %s" % (what, plan.device))
-    if sr and T != torch.bfloat16:
+    if sr and isinstance(T, list):
+        _psgd._param_rounding(what, rounding, set(T))
+    elif sr and T != torch.bfloat16:
         raise ValueError("%s: rounding='stochastic' needs bfloat16 parameters on the HIP device, got %s" % (what, params[0].dtype))
     if not plan.nchunks:
         return
@@ -241,15 +248,21 @@ def multi_param_update(params, grads, vs=None, lr=0.0, sumsq=None, max_norm=None
     gtab = None if grads is None else plan.mixed_table("grads_mixed", grads, what) if mixed else plan.table("grads", grads, what)
     vtab = None if vs is None else plan.table("vs", vs, what, T)
     clip = (None if sumsq is None else sumsq.data_ptr(), 0.0 if max_norm is None else float(max_norm),
-            float(torch.finfo(T).tiny if tiny is None else tiny))
-    # one launch over the plan's chunks, or one per group over the group's: the same tables, the same sum of squares
-    launches = [(plan.chunks, plan.nchunks, float(lr), wd)] if groups is None else \
-        [plan.group_chunks(indices) + (float(lr) * scale, wd_j) for indices, scale, wd_j in groups]
-    for chunks, nchunks, lr_j, wd_j in launches:
+            float((plan.tiny if isinstance(T, list) else torch.finfo(T).tiny) if tiny is None else tiny))
+    # one launch over the plan's chunks, or one per group over the group's: the same tables, the same sum of squares.  A mixed
+    # plan: each of these once per dtype present, as the call of a one-dtype list of that dtype, over that dtype's rows
+    if isinstance(T, list):
+        launches = [(_CODE_DTYPES[code], chunks, n, float(lr) * scale, wd_j)
+                    for indices, scale, wd_j in (groups if groups is not None else [(None, 1.0, wd)])
+                    for code, chunks, n in plan.dtype_chunks(indices)]
+    else:
+        launches = [(T, plan.chunks, plan.nchunks, float(lr), wd)] if groups is None else \
+            [(T,) + plan.group_chunks(indices) + (float(lr) * scale, wd_j) for indices, scale, wd_j in groups]
+    for T, chunks, nchunks, lr_j, wd_j in launches:
         if not nchunks:
             continue
         tabs = (ptab, gtab, vtab, len(params), chunks.data_ptr(), nchunks)
-        if sr:
+        if sr and T == torch.bfloat16:                          # (the float32 tensors of a mixed list: as under "nearest")
             name = "psgd_multi_param_update_mixed_sr" if mixed else "psgd_multi_param_update_sr"
             rc = getattr(_lib.load(), name)(*tabs, _psgd._TAIL_DTYPES[T], lr_j, *clip, wd_j, int(rounding_seed) & (2 ** 64 - 1),
                                             int(index0), _psgd._stream_ptr(plan.device))
@@ -318,7 +331,10 @@ def multi_scale_check(lists, scales, *, flag=None, stamp=None, plan=None):
         raise ValueError("%s: flag and stamp go together (got flag=%s, stamp=%r)" % (what, "None" if flag is None else "given", stamp))
     if flag is None and all(s == 1.0 for s in scales):
         raise ValueError("%s: no flag and every scale is 1: nothing to do" % what)
-    lists, plan = _lists(what, *[("lists[%d]" % j, ts) for j, ts in enumerate(lists)], plan=plan)
+    # a mixed plan: only its float32 tensors are walked; the positions of the other dtypes hold tensors of those dtypes, untouched
+    own = list(plan.dtypes) if plan is not None and plan.mixed else None
+    lists, plan = _lists(what, *[("lists[%d]" % j, ts) for j, ts in enumerate(lists)], plan=plan,
+                         dtypes=None if own is None else {"lists[%d]" % j: own for j in range(len(lists))})
     if any(ts is None for ts in lists):
         raise ValueError("%s: a list is None" % what)
     word = None
@@ -328,11 +344,15 @@ def multi_scale_check(lists, scales, *, flag=None, stamp=None, plan=None):
             raise ValueError("%s: stamp must be in 1 .. 2^31 - 1, got %r" % (what, stamp))
     if not plan.nchunks:
         return
-    tabs = [plan.table("check%d" % j, ts, what) for j, ts in enumerate(lists)] + [None] * (3 - len(lists))
-    rc = _lib.load().psgd_multi_scale_check_f32(*tabs, *(scales + [1.0] * (3 - len(scales))), len(lists[0]), plan.chunks.data_ptr(),
-                                                plan.nchunks, word, 0 if stamp is None else int(stamp),
-                                                _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_scale_check_f32")
+    tabs = [plan.table("check%d" % j, ts, what, _f32 if own is None else own) for j, ts in enumerate(lists)] + \
+        [None] * (3 - len(lists))
+    for code, chunks, nchunks in plan.by_dtype:
+        if code != _lib.DTYPE_F32:
+            continue
+        rc = _lib.load().psgd_multi_scale_check_f32(*tabs, *(scales + [1.0] * (3 - len(scales))), len(lists[0]), chunks.data_ptr(),
+                                                    nchunks, word, 0 if stamp is None else int(stamp),
+                                                    _psgd._stream_ptr(plan.device))
+        _lib.check(rc, "psgd_multi_scale_check_f32")
 
 
 def multi_widen_check(srcs, dsts, scales, *, flag=None, stamp=None, plan=None):
@@ -341,7 +361,10 @@ def multi_widen_check(srcs, dsts, scales, *, flag=None, stamp=None, plan=None):
     srcs[0][0]; every destination is written whole.  With flag and stamp (both or neither) stamp is stored to flag[0], an int32
     device word, when any value written is +-Inf or NaN -- the flag of multi_scale_check: the caller passes a stamp it has not
     used on this word before (1 .. 2^31 - 1; plan.next_stamp() for plan.flag) and reads flag[0] == stamp after the launch;
-    nothing zeroes the word.  Without a flag the call only widens."""
+    nothing zeroes the word.  Without a flag the call only widens.
+    A plan built for a MIXED list: srcs have the plan's dtype at every position, one launch per half-precision dtype present over
+    its sub-plan, all under the one stamp and flag; the float32 positions are skipped (neither read nor written: their dsts may
+    be the sources themselves) and are left to multi_scale_check with the same plan, which walks the float32 sub-plan only."""
     what = "multi_widen_check"
     srcs, dsts, scales = list(srcs), list(dsts), [float(np.float32(s)) for s in scales]
     if not 1 <= len(srcs) <= 3 or len(dsts) != len(srcs) or len(scales) != len(srcs):
@@ -352,9 +375,10 @@ def multi_widen_check(srcs, dsts, scales, *, flag=None, stamp=None, plan=None):
     srcs = [None if ts is None else list(ts) for ts in srcs]
     if any(ts is None for ts in srcs) or any(ts is None for ts in dsts):
         raise ValueError("%s: a list is None" % what)
+    own = list(plan.dtypes) if plan is not None and plan.mixed else None
     first = srcs[0][0] if srcs[0] else None
-    T = first.dtype if isinstance(first, torch.Tensor) else None
-    if isinstance(first, torch.Tensor) and T not in _HALF:
+    T = own if own is not None else first.dtype if isinstance(first, torch.Tensor) else None
+    if own is None and isinstance(first, torch.Tensor) and T not in _HALF:
         raise TypeError("%s: srcs[0][0] must be bfloat16 or float16, got %s (float32 lists are scaled in place by multi_scale_check)"
                         % (what, T))
     names = ["srcs[%d]" % j for j in range(len(srcs))]
@@ -369,12 +393,14 @@ def multi_widen_check(srcs, dsts, scales, *, flag=None, stamp=None, plan=None):
     if not plan.nchunks:
         return
     pad = [None] * (3 - len(srcs))
-    rc = _lib.load().psgd_multi_widen_check(*([plan.table("widen_src%d" % j, ts, what, T) for j, ts in enumerate(srcs)] + pad),
-                                            *([plan.table("widen_dst%d" % j, ts, what) for j, ts in enumerate(dsts)] + pad),
-                                            *(scales + [1.0] * len(pad)), len(srcs[0]), plan.chunks.data_ptr(), plan.nchunks,
-                                            _psgd._TAIL_DTYPES[T], word, 0 if stamp is None else int(stamp),
-                                            _psgd._stream_ptr(plan.device))
-    _lib.check(rc, "psgd_multi_widen_check")
+    tabs = [plan.table("widen_src%d" % j, ts, what, T) for j, ts in enumerate(srcs)] + pad + \
+        [plan.table("widen_dst%d" % j, ts, what) for j, ts in enumerate(dsts)] + pad
+    for code, chunks, nchunks in plan.by_dtype if own is not None else [(_psgd._TAIL_DTYPES[T], plan.chunks, plan.nchunks)]:
+        if code == _lib.DTYPE_F32:                              # (a mixed plan: its float32 tensors skip the widening pass)
+            continue
+        rc = _lib.load().psgd_multi_widen_check(*tabs, *(scales + [1.0] * len(pad)), len(srcs[0]), chunks.data_ptr(), nchunks,
+                                                code, word, 0 if stamp is None else int(stamp), _psgd._stream_ptr(plan.device))
+        _lib.check(rc, "psgd_multi_widen_check")
 
 
 def multi_narrow(srcs, dsts, *, plan=None):

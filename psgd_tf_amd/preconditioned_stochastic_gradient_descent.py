@@ -268,10 +268,17 @@ def param_update_stochastic_(p, g, v, lr_eff, c, seed, index0):
 
 
 def _param_rounding(name, param_rounding, dtype):
-    """the param_rounding argument of a constructor, judged before anything touches a device: True for "stochastic" """
+    """the param_rounding argument of a constructor, judged before anything touches a device: True for "stochastic".  dtype: the
+    parameters' dtype, or (mixed_dtypes=True) the collection of the dtypes present: "stochastic" then rounds the bfloat16
+    tensors, and needs one of them and no float16 tensor"""
     if param_rounding not in _PARAM_ROUNDINGS:
         raise ValueError("%s: param_rounding must be 'nearest' or 'stochastic', got %r" % (name, param_rounding))
-    if param_rounding == "stochastic" and dtype != torch.bfloat16:
+    if param_rounding == "stochastic" and isinstance(dtype, (set, frozenset, list, tuple)):
+        if torch.float16 in dtype or torch.bfloat16 not in dtype:
+            raise ValueError("%s: param_rounding='stochastic' rounds the bfloat16 parameters of a mixed list: it needs at least one "
+                             "and no float16 parameter (float16 stochastic rounding is not supported), got %s"
+                             % (name, sorted(str(d) for d in set(dtype))))
+    elif param_rounding == "stochastic" and dtype != torch.bfloat16:
         raise ValueError("%s: param_rounding='stochastic' needs bfloat16 parameters, got %s (float32 parameters are not rounded; "
                          "float16 stochastic rounding is not supported)" % (name, dtype))
     return param_rounding == "stochastic"
@@ -856,13 +863,28 @@ class _SegTable:
 class UVdTailPlan:
     """Everything about a list of parameter tensors that the step-tail kernels need and that does not change from step to step:
     sizes, start offsets, the chunk table on the device, one segment table per role ("params", "vs", "v", "h", "g", ...), the
-    device double of the clip norm and the workspace of its reduction.  Calls that share a plan must run on one stream."""
+    device double of the clip norm and the workspace of its reduction.  Calls that share a plan must run on one stream.
+
+    dtype: one dtype for all tensors, or a list with one per tensor (a MIXED plan when more than one is present: mixed is True,
+    dtype and code are None).  The kernels take the element type per launch, so a mixed list is served by the typed entry points
+    launched once per dtype present over that dtype's rows of the chunk table (by_dtype, dtype_chunks); the segment tables are
+    the one-dtype ones -- a table holds nothing typed -- and a launch never follows the pointer of a tensor of another dtype,
+    because no chunk of its sub-plan names that segment.  tiny: the largest finfo(T).tiny over the dtypes present."""
 
     def __init__(self, sizes, dtype, device):
-        if dtype not in _TAIL_DTYPES:
-            raise TypeError("UVd step tail: tensors must be float32, bfloat16 or float16, got %s" % (dtype,))
         self.sizes = tuple(int(n) for n in sizes)
-        self.dtype, self.code, self.device = dtype, _TAIL_DTYPES[dtype], torch.device(device)
+        dtypes = tuple(dtype) if isinstance(dtype, (list, tuple)) else (dtype,) * len(self.sizes)
+        if len(dtypes) != len(self.sizes):
+            raise ValueError("UVd step tail: %d dtypes for %d tensors" % (len(dtypes), len(self.sizes)))
+        for dt in dtypes if dtypes else (dtype,):
+            if dt not in _TAIL_DTYPES:
+                raise TypeError("UVd step tail: tensors must be float32, bfloat16 or float16, got %s" % (dt,))
+        self.dtypes = dtypes
+        self.present = tuple(dt for dt in _TAIL_DTYPES if dt in set(dtypes)) or (dtype,)     # in the order float32, bfloat16, float16
+        self.mixed = len(self.present) > 1
+        self.dtype = None if self.mixed else self.present[0]
+        self.code, self.device = None if self.mixed else _TAIL_DTYPES[self.dtype], torch.device(device)
+        self.tiny = max(torch.finfo(dt).tiny for dt in self.present)
         self.starts, acc = [], 0
         for n in self.sizes:
             self.starts.append(acc)
@@ -871,7 +893,9 @@ class UVdTailPlan:
         chunks = self._host_chunks = uvd_tail_chunks(self.sizes)
         self.nchunks = int(chunks.shape[0])
         self.chunks = torch.from_numpy(chunks).to(self.device) if self.nchunks else None
-        self._group_chunks = {}
+        self._group_chunks, self._dtype_chunks = {}, {}
+        # what a typed launch over the whole list walks: (dtype code, device chunk table, rows), one entry per dtype present
+        self.by_dtype = self.dtype_chunks(None)
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=self.device)
         self.ws = torch.empty(_lib.UVD_SUMSQ_WS_BYTES, dtype=torch.uint8, device=self.device)
         # the flag words of the guarded step (uvd_pack(flag=, stamp=), uvd_check): slots v, h, g and one spare.  Zero ONCE, here:
@@ -879,12 +903,14 @@ class UVdTailPlan:
         self.flags = torch.zeros(4, dtype=torch.int32, device=self.device)
         self._tables = {}
 
-    def table(self, role, tensors, what):
-        """device pointer of the segment table of `tensors` in this role (uploaded when a pointer changed)"""
+    def table(self, role, tensors, what, dtype=None):
+        """device pointer of the segment table of `tensors` in this role (uploaded when a pointer changed).  Every tensor is
+        checked against its own dtype: the plan's for its position, or `dtype` (one for all, or a list with one per tensor)"""
         if len(tensors) != len(self.sizes):
             raise ValueError("%s: %d tensors, the plan has %d" % (what, len(tensors), len(self.sizes)))
-        dt, dev = self.dtype, self.device
-        for t, n in zip(tensors, self.sizes):
+        dev = self.device
+        dts = self.dtypes if dtype is None else dtype if isinstance(dtype, (list, tuple)) else (dtype,) * len(self.sizes)
+        for t, n, dt in zip(tensors, self.sizes, dts):
             if t.dtype != dt or t.device != dev or t.numel() != n or not t.is_contiguous():
                 raise ValueError("%s: every tensor must be a contiguous %s tensor on %s with the plan's element count (%d), got %s %s "
                                  "%s%s" % (what, dt, dev, n, t.dtype, t.device, tuple(t.shape), "" if t.is_contiguous() else " strided"))
@@ -908,6 +934,55 @@ class UVdTailPlan:
             got = self._group_chunks[indices] = (torch.from_numpy(np.ascontiguousarray(rows)).to(self.device) if len(rows) else None,
                                                  int(rows.shape[0]))
         return got
+
+    def dtype_chunks(self, indices=None):
+        """[(PSGD_DTYPE_* code, device chunk table, its row count)]: the SUB-PLAN per dtype present, in the order float32,
+        bfloat16, float16, of the whole list (indices None: what by_dtype holds, made at construction) or of the tensors at
+        `indices`, the (group, dtype) pairs of a group.  Each is group_chunks of the tensors of that dtype among them: the sub-plans
+        partition the chunk table (the group's rows of it), keep its order and leave every segment its row, pointer and `start`.
+        A pair without a chunk is left out: it is not launched.  A one-dtype plan answers with its own table (the group's) under
+        its one code.  Kept per `indices`, like group_chunks."""
+        got = self._dtype_chunks.get(indices)
+        if got is None:
+            if not self.mixed:
+                one = (self.chunks, self.nchunks) if indices is None else self.group_chunks(indices)
+                got = [(self.code,) + one] if one[1] else []
+            else:
+                among = range(len(self.sizes)) if indices is None else indices
+                got = []
+                for dt in self.present:
+                    chunks, nchunks = self.group_chunks(tuple(i for i in among if self.dtypes[i] == dt))
+                    if nchunks:
+                        got.append((_TAIL_DTYPES[dt], chunks, nchunks))
+            while len(self._dtype_chunks) >= 64:
+                self._dtype_chunks.pop(next(iter(self._dtype_chunks)))
+            self._dtype_chunks[indices] = got
+        return got
+
+
+def tail_launch_count(dtypes, sizes, groups=None, *, packs=1, sums=1):
+    """The launches of one fused step tail over tensors of these dtypes and element counts, counted on the host:
+        (packs x D) + sums + (number of (group, dtype) pairs that hold an element)
+    packs: the typed roles launched over the whole list (pack, pack-blend, pack-check, check, widen-check, the perturbation of
+    psgd.py:723), each once per dtype present that holds an element, D <= 3; sums: the float32-only launches, which stay single
+    (the sum of squares of class UVd is one, that of class Kron two); groups: a partition of range(len(sizes)) into index
+    tuples (None: one group), each launched once per dtype it holds elements of."""
+    dtypes, sizes = list(dtypes), [int(n) for n in sizes]
+    if len(dtypes) != len(sizes):
+        raise ValueError("tail_launch_count: %d dtypes for %d sizes" % (len(dtypes), len(sizes)))
+    groups = [tuple(range(len(sizes)))] if groups is None else [tuple(g) for g in groups]
+    D = len({dt for dt, n in zip(dtypes, sizes) if n})
+    pairs = sum(len({dtypes[i] for i in g if sizes[i]}) for g in groups)
+    return int(packs) * D + int(sums) + pairs
+
+
+def mixed_dtype_constants(dtypes):
+    """(tiny, delta_param_scale) that an optimizer with mixed_dtypes=True shares among tensors of these dtypes: the LARGEST
+    finfo(T).tiny (psgd.py:682, the floor of the clip norm) and the LARGEST finfo(T).eps ** 0.5 (:683; one perturbation scale for
+    the whole vector, since the finite difference of :716-727 perturbs all parameters jointly).  Neither depends on the order;
+    with one dtype both are that dtype's values."""
+    present = set(dtypes)
+    return max(torch.finfo(dt).tiny for dt in present), max(torch.finfo(dt).eps ** 0.5 for dt in present)
 
 
 def _tensor_groups(what, tensor_groups, k, weight_decay, pre):
@@ -972,8 +1047,8 @@ def _flag_word(what, flag, stamp, dev):
 
 def uvd_pack(tensors, out, scale=1.0, *, plan=None, role="pack", flag=None, stamp=None):
     """out[:n] = torch.cat([t.reshape(-1) for t in tensors]).float() * scale in ONE launch whatever len(tensors) (psgd.py:729-730, :747;
-    scale: the 1 / delta_param_scale of :734-736).  tensors: contiguous device tensors of one dtype (float32, bfloat16 or float16),
-    empty ones allowed; out: a contiguous fp32 device tensor of at least n elements.  Returns out's first n elements, flat.
+    scale: the 1 / delta_param_scale of :734-736).  tensors: contiguous device tensors of one dtype (float32, bfloat16 or float16;
+    with a plan built for a mixed list each of its own, one launch per dtype present, sharing the flag word), empty ones allowed; out: a contiguous fp32 device tensor of at least n elements.  Returns out's first n elements, flat.
     flag and stamp (both or neither): the same bits from psgd_uvd_pack_check_f32, which also stores stamp (1 .. 2^31 - 1, one the
     caller has not used on this word before) to flag[0], an int32 device word, when a value it writes is not finite; the caller
     reads flag[0] == stamp after the launch.  Nothing zeroes the word."""
@@ -986,14 +1061,15 @@ def uvd_pack(tensors, out, scale=1.0, *, plan=None, role="pack", flag=None, stam
         raise ValueError("uvd_pack: out has %d elements, the tensors have %d" % (out.numel(), plan.total))
     segs = plan.table(role, tensors, "uvd_pack")
     word = None if flag is None else _flag_word("uvd_pack", flag, stamp, plan.device)
-    if plan.nchunks and flag is not None:
-        rc = _lib.load().psgd_uvd_pack_check_f32(segs, len(tensors), plan.chunks.data_ptr(), plan.nchunks, plan.code, float(scale),
-                                                 out.data_ptr(), word, int(stamp), _stream_ptr(dev))
-        _lib.check(rc, "psgd_uvd_pack_check_f32")
-    elif plan.nchunks:
-        rc = _lib.load().psgd_uvd_pack_f32(segs, len(tensors), plan.chunks.data_ptr(), plan.nchunks, plan.code, float(scale),
-                                           out.data_ptr(), _stream_ptr(dev))
-        _lib.check(rc, "psgd_uvd_pack_f32")
+    for code, chunks, nchunks in plan.by_dtype:                  # one launch; a mixed plan: one per dtype present, one flag word
+        if flag is not None:
+            rc = _lib.load().psgd_uvd_pack_check_f32(segs, len(tensors), chunks.data_ptr(), nchunks, code, float(scale),
+                                                     out.data_ptr(), word, int(stamp), _stream_ptr(dev))
+            _lib.check(rc, "psgd_uvd_pack_check_f32")
+        else:
+            rc = _lib.load().psgd_uvd_pack_f32(segs, len(tensors), chunks.data_ptr(), nchunks, code, float(scale),
+                                               out.data_ptr(), _stream_ptr(dev))
+            _lib.check(rc, "psgd_uvd_pack_f32")
     return out.view(-1)[:plan.total]
 
 
@@ -1008,8 +1084,8 @@ def uvd_check(tensors, scale=1.0, *, plan=None, role="check", flag, stamp):
         raise _lib.PsgdHipError("uvd_check runs on the HIP device only; no CPU fallback")
     segs = plan.table(role, tensors, "uvd_check")
     word = _flag_word("uvd_check", flag, stamp, dev)
-    if plan.nchunks:
-        rc = _lib.load().psgd_uvd_check_multi(segs, len(tensors), plan.chunks.data_ptr(), plan.nchunks, plan.code, float(scale), word,
+    for code, chunks, nchunks in plan.by_dtype:
+        rc = _lib.load().psgd_uvd_check_multi(segs, len(tensors), chunks.data_ptr(), nchunks, code, float(scale), word,
                                               int(stamp), _stream_ptr(dev))
         _lib.check(rc, "psgd_uvd_check_multi")
 
@@ -1052,8 +1128,8 @@ def uvd_pack_blend(tensors, out, beta, scale=1.0, *, plan=None, role="pack"):
     if out.numel() < plan.total:
         raise ValueError("uvd_pack_blend: out has %d elements, the tensors have %d" % (out.numel(), plan.total))
     segs = plan.table(role, tensors, "uvd_pack_blend")
-    if plan.nchunks:
-        rc = _lib.load().psgd_uvd_pack_blend_f32(segs, len(tensors), plan.chunks.data_ptr(), plan.nchunks, plan.code, float(scale),
+    for code, chunks, nchunks in plan.by_dtype:
+        rc = _lib.load().psgd_uvd_pack_blend_f32(segs, len(tensors), chunks.data_ptr(), nchunks, code, float(scale),
                                                  beta, omb, out.data_ptr(), _stream_ptr(dev))
         _lib.check(rc, "psgd_uvd_pack_blend_f32")
     return out.view(-1)[:plan.total]
@@ -1076,7 +1152,10 @@ def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group
         p <- T(p - delta),  delta = T(fl32(lr_eff * pre_grad slice)),  with vs: delta = T(delta + v)        (:757-762)
     with T the parameters' dtype: the roundings of the torch expressions of class UVd.  params (and vs): contiguous device tensors
     of one dtype; pre_grad: the flat fp32 preconditioned gradient of their concatenation.  tiny defaults to the dtype's smallest
-    normal (:682).  group: pre_grad holds this rank's rows of a row-sharded vector -- the sum of squares is all-reduced (one fp64
+    normal (:682).  With a plan built for a MIXED list (UVdTailPlan(sizes, [one dtype per tensor], device)) every tensor has its
+    own T: each launch below runs once per dtype present over that dtype's sub-plan, rounding="stochastic" applies to the
+    bfloat16 tensors (the float32 ones: as under "nearest"; a float16 one is refused) and tiny defaults to the largest present.
+    group: pre_grad holds this rank's rows of a row-sharded vector -- the sum of squares is all-reduced (one fp64
     scalar, the collective sharded.global_norm uses).  pre_grad None (vs required): p <- T(p + v), the perturbation of :723.
     weight_decay (extension, decoupled): with c = fl32(lr_eff * weight_decay), delta = T(delta + T(fl32(c * p))) after the vs term;
     0 (default) adds no rounding step.
@@ -1102,7 +1181,9 @@ def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group
     if sr and (pre_grad is None or int(index0) < 0):
         raise ValueError("uvd_step_tail: rounding='stochastic' needs pre_grad (the perturbation p + v rounds to nearest) and index0 >= 0")
     plan = plan if plan is not None else _tail_plan(params, "uvd_step_tail")
-    if sr and plan.dtype != torch.bfloat16:
+    if sr and plan.mixed:
+        _param_rounding("uvd_step_tail", rounding, plan.present)
+    elif sr and plan.dtype != torch.bfloat16:
         raise ValueError("uvd_step_tail: rounding='stochastic' needs bfloat16 parameters, got %s" % (plan.dtype,))
     dev = plan.device
     psegs = plan.table("params", params, "uvd_step_tail")
@@ -1128,19 +1209,18 @@ def uvd_step_tail(params, pre_grad, lr, max_norm=None, tiny=None, vs=None, group
                 _sharded.all_reduce_sum_f64_(sumsq, group)
     if not plan.nchunks:
         return
-    tiny = torch.finfo(plan.dtype).tiny if tiny is None else tiny
+    tiny = plan.tiny if tiny is None else tiny
     if sr and rounding_seed is None:
         rounding_seed = int(torch.randint(0, 2 ** 62, (), generator=_branch_rng).item())
-    # one launch over the plan's chunks, or one per group over the group's: the same tables, the same sum of squares
-    launches = [(plan.chunks, plan.nchunks, float(lr), wd)] if groups is None else \
-        [plan.group_chunks(indices) + (float(lr) * scale, wd_j) for indices, scale, wd_j in groups]
-    for chunks, nchunks, lr_j, wd_j in launches:
-        if not nchunks:
-            continue
-        args = (psegs, vsegs, len(params), chunks.data_ptr(), nchunks, plan.code,
+    # one launch over the plan's chunks, or one per group over the group's: the same tables, the same sum of squares.  A mixed
+    # plan: each of these once per dtype present, with that dtype's code, over that dtype's rows
+    launches = [sub + (float(lr), wd) for sub in plan.by_dtype] if groups is None else \
+        [sub + (float(lr) * scale, wd_j) for indices, scale, wd_j in groups for sub in plan.dtype_chunks(indices)]
+    for code, chunks, nchunks, lr_j, wd_j in launches:
+        args = (psegs, vsegs, len(params), chunks.data_ptr(), nchunks, code,
                 None if pre_grad is None else pre_grad.data_ptr(), lr_j, None if sumsq is None else sumsq.data_ptr(),
                 float(max_norm) if clip else 0.0, float(tiny))
-        if sr:
+        if sr and code == _lib.DTYPE_BF16:                      # (the float32 tensors of a mixed list: as under "nearest")
             rc = _lib.load().psgd_uvd_param_update_multi_sr(*args, wd_j, int(rounding_seed) & (2 ** 64 - 1), int(index0),
                                                             _stream_ptr(dev))
             _lib.check(rc, "psgd_uvd_param_update_multi_sr")
@@ -1491,6 +1571,21 @@ def _flatten_params(params_with_grad):
     return out
 
 
+def _mixed_dtypes_switch(name, mixed_dtypes):
+    """the mixed_dtypes argument of a constructor, judged before anything else: a bool, nothing that merely converts to one"""
+    if not isinstance(mixed_dtypes, bool):
+        raise ValueError("%s: mixed_dtypes must be True or False, got %r" % (name, mixed_dtypes))
+    return mixed_dtypes
+
+
+def _state_dtype_param(name, mixed, dtype):
+    """what state_dtype="param" means: the parameters' dtype; with more than one dtype present it names none (ValueError)"""
+    if mixed:
+        raise ValueError("%s: state_dtype='param' is ambiguous with parameters of more than one dtype (mixed_dtypes=True); "
+                         "name the dtype of the state" % name)
+    return dtype
+
+
 class _FlatStep(_StepFeatures):
     """An optimizer that preconditions ONE flat float32 vector (psgd.py:692-764): everything of its three subclasses -- class UVd,
     class SPLU (splu_optimizer.py) and class Dense (dense_optimizer.py) -- but the preconditioner itself: step(), the flat-vector
@@ -1516,16 +1611,23 @@ class _FlatStep(_StepFeatures):
                    "exact_hessian_vector_product")
 
     # ------------------------------------------------------------------------------------------- the stages of a constructor
-    def _init_params(self, params_with_grad, generator, param_rounding, preconditioner_fit):
-        """psgd.py:668-671, :684-686 and the two keyword-only switches, judged in this order: the parameters with requires_grad
-        (the reference's .trainable) in tf.nest.flatten order, their dtype and device, their index, param_rounding,
-        preconditioner_fit.  Returns the number of elements."""
+    def _init_params(self, params_with_grad, generator, param_rounding, preconditioner_fit, mixed_dtypes=False):
+        """psgd.py:668-671, :684-686 and the keyword-only switches, judged in this order: mixed_dtypes, the parameters with
+        requires_grad (the reference's .trainable) in tf.nest.flatten order, their dtype and device, their index, param_rounding,
+        preconditioner_fit.  Returns the number of elements.
+        mixed_dtypes=False: params[0].dtype is THE dtype, as in the reference (:671).  True: every tensor is float32, bfloat16 or
+        float16 on its own (TypeError otherwise) and _dtypes holds them; _mixed says that more than one is present -- a list of
+        one dtype is the optimizer it is with the switch off."""
         name = type(self).__name__
+        _mixed_dtypes_switch(name, mixed_dtypes)
         self._params = self._params_with_grad = [p for p in _flatten_params(params_with_grad) if p.requires_grad]   # one list, two names
         self._dtype, self._device, self._generator = self._params[0].dtype, self._params[0].device, generator
-        if self._dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError("%s: parameters must be float32, float16 or bfloat16, got %s" % (name, self._dtype))
-        self._param_sr = _param_rounding(name, param_rounding, self._dtype)
+        self._dtypes = [p.dtype for p in self._params] if mixed_dtypes else [self._dtype] * len(self._params)
+        for dt in self._dtypes:
+            if dt not in (torch.float32, torch.float16, torch.bfloat16):
+                raise TypeError("%s: parameters must be float32, float16 or bfloat16, got %s" % (name, dt))
+        self._mixed = len(set(self._dtypes)) > 1
+        self._param_sr = _param_rounding(name, param_rounding, set(self._dtypes) if self._mixed else self._dtype)
         self._param_round_seed0, self._param_round_step = None, 0
         self._round_seed0, self._round_step = None, None        # the stream of a state the kernels round (_draw_seeds)
         self._init_fit(preconditioner_fit)
@@ -1547,6 +1649,8 @@ class _FlatStep(_StepFeatures):
         self._stamp = 0
         self._tiny = torch.finfo(self._dtype).tiny                                           # :682
         self._delta_param_scale = torch.finfo(self._dtype).eps ** 0.5                        # :683
+        if self._mixed:                                   # the largest of each over the dtypes present, whatever the order
+            self._tiny, self._delta_param_scale = mixed_dtype_constants(self._dtypes)
         self._fd_inv_scale = float(np.float32(1.0) / np.float32(self._delta_param_scale))    # what torch's `/ scale` multiplies by
 
     def _init_tail(self, step_tail):
@@ -1559,10 +1663,12 @@ class _FlatStep(_StepFeatures):
             raise ValueError("%s: step_tail must be 'torch' or 'fused', got %r" % (type(self).__name__, step_tail))
         self._tail = None
         if step_tail == "fused":
-            if all(p.is_contiguous() and p.dtype == self._dtype for p in self._params):
-                self._tail = UVdTailPlan(self._param_sizes, self._dtype, self._device)
+            if all(p.is_contiguous() and p.dtype == dt for p, dt in zip(self._params, self._dtypes)):
+                self._tail = UVdTailPlan(self._param_sizes, self._dtypes if self._mixed else self._dtype, self._device)
                 for g in self.param_groups or ():               # the groups' chunk tables: made here, once
                     self._tail.group_chunks(g.indices)
+                    if self._mixed:                             # ... and those of the (group, dtype) pairs
+                        self._tail.dtype_chunks(g.indices)
             else:
                 import warnings
                 warnings.warn("%s: step_tail='fused' needs contiguous parameters of one dtype; this optimizer keeps the torch tail"
@@ -1832,7 +1938,7 @@ class _FlatStep(_StepFeatures):
                           self._group, plan=self._tail, **wd_kw, **sr_kw)
             return closure_returns
         decay = None
-        if mom != 0.0 or wd != 0.0 or sr or groups is not None:      # the torch tail of the extensions: lr_eff as the step-tail kernel forms it, one op per rounding
+        if mom != 0.0 or wd != 0.0 or sr or groups is not None or self._mixed:      # the torch tail of the extensions: lr_eff as the step-tail kernel forms it, one op per rounding
             f32t = lambda x: torch.tensor(x, dtype=torch.float32, device=pre_grad.device)
             clip_factor = None
             if not math.isinf(max_norm):
@@ -1868,8 +1974,8 @@ class _FlatStep(_StepFeatures):
         with torch.no_grad():                                                                 # :757-762
             for k, (p, i, j) in enumerate(zip(params, self._param_sizes, self._param_cumsizes)):
                 lr_k, decay_k = (lr, decay) if groups is None else (lr[k], decay[k])
-                _torch_param_update_(p, torch.reshape(pre_grad[j - i:j], p.shape), vs[k] if undo else None, lr_k, decay_k, sr_seed,
-                                     sr_index0 + j - i)
+                _torch_param_update_(p, torch.reshape(pre_grad[j - i:j], p.shape), vs[k] if undo else None, lr_k, decay_k,
+                                     sr_seed if p.dtype == torch.bfloat16 else None, sr_index0 + j - i)
         return closure_returns                                                              # :764
 
     # ------------------------------------------------------------------------------------------------- checkpoint / resume
@@ -2041,7 +2147,21 @@ class UVd(_FlatStep):
     kernels only read them); with momentum or a placed state each has its own.  The probe is finite by construction and is not
     judged by the guard; a skipped step returns before it is drawn and leaves probe_step alone.  state_dict() carries probe_seed0
     / probe_step; preconditioner_fit itself is a constructor choice, like step_tail.  The whitened gradient has roughly unit scale
-    per element, as Adam's update has: lr_params and grad_clip_max_norm tuned for the Hessian fit do NOT carry over."""
+    per element, as Adam's update has: lr_params and grad_clip_max_norm tuned for the Hessian fit do NOT carry over.
+
+    mixed_dtypes=True (extension, keyword-only; False by default: nothing changes, params[0].dtype is THE dtype; anything but a
+    bool is a ValueError before a device is touched) takes parameter tensors that are float32, bfloat16 or float16 each, on both
+    step tails; a list of one dtype behaves bit for bit as with False.  Each tensor is treated exactly as in a one-dtype optimizer
+    of its own dtype given the same float32 preconditioned gradient: the packs widen it from its own dtype, its update is rounded
+    once in its dtype, the undo of a skipped finite-difference step too.  tiny (:682) and delta_param_scale (:683) are the LARGEST
+    finfo(T).tiny and finfo(T).eps ** 0.5 over the dtypes present (mixed_dtype_constants; one perturbation scale, since :716-727
+    perturbs all parameters jointly), whatever the order of the list.  param_rounding="stochastic" rounds the bfloat16 tensors,
+    on the stream keyed by the index in the FULL flat order, and updates the float32 ones as under "nearest"; a float16 tensor or
+    no bfloat16 tensor is a ValueError.  state_dtype="param" is then ambiguous: ValueError.  Fused tail: every typed launch runs
+    once per dtype present over that dtype's sub-plan of the chunk table (UVdTailPlan.dtype_chunks), crossed with param_groups
+    once per (group, dtype) pair that has tensors -- (typed roles x D) + sums + pairs launches, D <= 3 (tail_launch_count) --
+    with the one-dtype segment tables and uploads; the guard's flag word is shared by the launches of a role.  A constructor
+    choice like step_tail: not in state_dict(), which carries no parameter dtype."""
 
     def __init__(self, params_with_grad, rank_of_modification: int = 10, preconditioner_init_scale=1.0,
                  lr_params=0.01, lr_preconditioner=0.01,
@@ -2050,7 +2170,7 @@ class UVd(_FlatStep):
                  stage_backend=None, placement="auto", state_route="widen", state_rounding=None, step_tail="torch",
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
                  *, param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None,
-                 param_groups=None):
+                 param_groups=None, mixed_dtypes=False):
         # group (extension): a torch.distributed process group (dist.group.WORLD for the default one) makes this a
         # ROW-SHARDED optimizer: `params_with_grad` are THIS rank's parameters, the global flat vector of psgd.py:729-730 is the
         # concatenation of the ranks' vectors in rank order, and U, V, d hold this rank's rows only.  A step then costs three
@@ -2060,7 +2180,7 @@ class UVd(_FlatStep):
         # Hessian-vector product with respect to this rank's parameters are what a model-parallel closure computes.
         # Every check comes before anything is drawn from a generator or touches a device (_FlatStep._init_tail is the first that
         # does).  param_rounding and preconditioner_fit: the class docstring.
-        num_params = self._init_params(params_with_grad, generator, param_rounding, preconditioner_fit)   # :668-671, :684-686
+        num_params = self._init_params(params_with_grad, generator, param_rounding, preconditioner_fit, mixed_dtypes)  # :668-671, :684-686
         # psgd.py:657-658 allows half-precision parameters.  The preconditioner state U, V, d and all of its arithmetic
         # stay fp32 here (mixed precision: the HIP kernels compute in fp32; v, Hv and the gradient are widened on the
         # way in, the preconditioned gradient is narrowed on the way out).  _tiny and the finite-difference scale follow
@@ -2069,7 +2189,8 @@ class UVd(_FlatStep):
         # for half-precision parameters (psgd.py:688-690) -- every step widens them, runs the fp32 kernels and rounds the updated
         # state back, so the memory held between steps and the rounding of the state once per step are the reference's; its
         # arithmetic (every TF op in the parameters' type) is not reproduced.
-        self._store_dtype = torch.float32 if state_dtype is None else self._dtype if state_dtype == "param" else state_dtype
+        self._store_dtype = torch.float32 if state_dtype is None else \
+            _state_dtype_param("UVd", self._mixed, self._dtype) if state_dtype == "param" else state_dtype
         if self._store_dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise TypeError("UVd: state_dtype must be None, 'param', float32, float16 or bfloat16, got %r" % (state_dtype,))
         r = self._rank = int(rank_of_modification)

@@ -70,6 +70,9 @@ class SPLU(_psgd._FlatStep):
     state_dict() / load_state_dict() carry the four factors in their stored dtype, the hyper-parameters, the generator state
     and every counter and seed class UVd saves; a resumed run is bit-identical to the uninterrupted one.
 
+    mixed_dtypes=True (keyword-only, False by default: nothing changes): the switch of class UVd, with its meaning there -- one
+    optimizer over float32, bfloat16 and float16 tensors on both tails; state_dtype="param" is then a ValueError.
+
     Out of scope: group= (a row-sharded state; the staged entry points exist, the class does not drive them), placement=, a
     float32 checkpoint continued on a bfloat16 state, and any fused update -> apply."""
 
@@ -79,10 +82,11 @@ class SPLU(_psgd._FlatStep):
                  exact_hessian_vector_product: bool = True, generator=None, state_dtype=None, state_rounding=None,
                  step_tail="torch", momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None,
                  loss_scale_growth_interval=2000, *, param_rounding="nearest", param_rounding_seed=None,
-                 preconditioner_fit="hessian", probe_seed=None, param_groups=None):
+                 preconditioner_fit="hessian", probe_seed=None, param_groups=None, mixed_dtypes=False):
         # the stages of _FlatStep with this class's checks between them; every check comes before anything touches a device
-        N = self._init_params(params_with_grad, generator, param_rounding, preconditioner_fit)
-        store = torch.float32 if state_dtype is None else self._dtype if state_dtype == "param" else state_dtype
+        N = self._init_params(params_with_grad, generator, param_rounding, preconditioner_fit, mixed_dtypes)
+        store = torch.float32 if state_dtype is None else \
+            _psgd._state_dtype_param("SPLU", self._mixed, self._dtype) if state_dtype == "param" else state_dtype
         if store == torch.float16:
             raise TypeError("SPLU: a float16 state is not supported (the native narrow state is bfloat16 only)")
         if store not in (torch.float32, torch.bfloat16):
