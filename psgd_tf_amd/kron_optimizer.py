@@ -204,8 +204,7 @@ def kron_operand_layers(layer_shapes, formats, operands=None, operand_min_dim=OP
 
 
 # --------------------------------------------------------------------------- checkpoint, host part
-_HYPER_KEYS = ("lr_params", "lr_preconditioner", "grad_clip_max_norm", "preconditioner_update_probability",
-               "exact_hessian_vector_product")
+_HYPER_KEYS = _psgd._StepFeatures._HYPER_KEYS
 
 
 def _encode_state(factors, formats, shapes, hyper, rng_state):
@@ -295,7 +294,9 @@ def _flatten(params_with_grad):
 
 class Kron(_psgd._StepFeatures):
     """Kronecker-product preconditioned SGD, one factor pair per rank-2 parameter: the train_step of mnist_with_lenet5.py:43-57 behind
-    the interface of class UVd.
+    the interface of class UVd.  Shared with the flat classes through _StepFeatures, not written here: the switches and
+    _init_step_hypers, _step_route, _closure_gradients, _tail_coefficients, _fused_tail_kwargs.  This class's own: _screen, _judge,
+    _widen, _blend, _update_factors, _precondition.
 
     params_with_grad: contiguous rank-2 tensors of one dtype (float32, bfloat16 or float16) with requires_grad=True on one HIP
     device (nested lists / dicts are flattened as class UVd does).  preconditioner_formats: "dense", a (left, right) pair of "dense" / "norm" / "scale", or one of either per
@@ -479,11 +480,8 @@ class Kron(_psgd._StepFeatures):
         if self._vec:
             self._vec_plan = MultiTailPlan([self._layer_shapes[i][1] for i in self._vec], dev)
             self._vec_out = [torch.empty(self._layer_shapes[i], dtype=_f32, device=dev) for i in self._vec]
-        self.lr_params = _psgd._Hyper(lr_params)
-        self.lr_preconditioner = _psgd._Hyper(lr_preconditioner)
-        self.grad_clip_max_norm = _psgd._Hyper(math.inf if grad_clip_max_norm is None else grad_clip_max_norm)
-        self.preconditioner_update_probability = _psgd._Hyper(preconditioner_update_probability)
-        self.exact_hessian_vector_product = _psgd._Hyper(bool(exact_hessian_vector_product))
+        self._init_step_hypers(lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability,
+                               exact_hessian_vector_product)
         self._layer_batch = bool(layer_batch)
         self._generator = generator
         # the construction seeds, from the generator behind the coin: the parameters' first, then the probe's
@@ -814,17 +812,18 @@ class Kron(_psgd._StepFeatures):
     def step(self, closure):
         """One step; returns what closure() returns (the loss is its first element when it is an iterable).
 
-        1. the coin of psgd.py:703: update the factors this step?
-        2. exact product: vs = randn per parameter, gradients with create_graph, Hvs from a second autograd.grad; dX = v, dG = Hv.
-        3. finite differences (psgd.py:716-727, :734-736): vs = randn * delta, delta = sqrt(eps_fp32); p += v; the closure runs a
-           second time; dG = (g' - g) * s, dX = v * s with s = float32(1) / float32(delta); the perturbation is undone in step 7.
+        1. the coin of psgd.py:703: update the factors this step?  (_step_route names what follows; the closure calls, the
+           backward passes and the draws of steps 2 and 3 are _StepFeatures._closure_gradients's, whose docstring fixes their order.)
+        2. exact product: dX = v, dG = Hv, the probe vectors drawn from `generator` (_randn).
+        3. finite differences (psgd.py:716-727, :734-736): delta = sqrt(eps_fp32); dG = (g' - g) * s, dX = v * s with
+           s = float32(1) / float32(delta); the perturbation p += v is undone in step 7.
         4. one update_precond_kron per layer (inside one kron.layer_batch() block); the factor references are rebound to the returned
            tensors, nothing is copied.
         5. one precond_grad_kron per layer (a second block).  any_rank: dX, dG and the gradients are taken in the shapes of the
            layers (views), and with vector_route="list" the vector layers leave steps 4 and 5 for one multi_vec_precond_update launch
            (in place: these factor tensors are not rebound) and one multi_vec_precond_grad launch.
-        6. with clipping, lr_eff = float32(lr_params * min(max_norm / (sqrt(S) + tiny), 1)) evaluated in fp64, S = the fp64 sum of
-           the float32 squares of all preconditioned gradients.  tiny = finfo(float32).tiny follows psgd.py:753 (class UVd), not
+        6. lr_eff and the decay coefficient c per tensor: the rule of _StepFeatures._tail_coefficients, S = the fp64 sum of the
+           float32 squares of all preconditioned gradients.  tiny = finfo(float32).tiny follows psgd.py:753 (class UVd), not
            mnist_with_lenet5.py:54-55, which divides by the bare norm: a zero gradient gives a zero step, not NaN.
         7. p <- p - float32(lr_eff * pg); after step 3, p <- p - float32(float32(lr_eff * pg) + v) (psgd.py:761).
 
@@ -872,9 +871,8 @@ class Kron(_psgd._StepFeatures):
         pg.float() per tensor, the definition the kernels match.  Inside layer_batch blocks the operand layers run at once, as
         outside a block; the class issues them before the block so that the queue of the small layers stays whole.
 
-        preconditioner_fit="whitening" (nothing of this runs with "hessian").  Steps 2 and 3 are replaced: the closure runs ONCE,
-        grads = autograd.grad(scaled(loss), params) without create_graph, and the parameters are not perturbed (nothing to undo in
-        step 7); exact_hessian_vector_product is not read.  The widening / scale / guard pass is that of a step that leaves the
+        preconditioner_fit="whitening" (nothing of this runs with "hessian").  Steps 2 and 3 give way to the "whitening" route: ONE
+        closure call, ONE ordinary backward, no perturbation (nothing to undo in step 7).  The widening / scale / guard pass is that of a step that leaves the
         factors alone: it sees the gradients only (inv is applied once), the probe is not judged because it is finite by
         construction, and a skipped step returns before the probe is drawn: probe_step, factors, parameters, momentum buffers
         and the warm-up counter keep their bits, and the next step draws the stream the skipped one would have drawn.  When the
@@ -885,34 +883,16 @@ class Kron(_psgd._StepFeatures):
         step 5, the clip, weight decay and param_rounding.  Nothing on this route differs between the tails before step 6."""
         params = self._params
         update_Q = self._coin()
-        exact = bool(self.exact_hessian_vector_product)
         fused = self._tail is not None
         mom, wd, S, inv, scaled = self._step_scales()
         groups = self._step_groups(wd)                          # None without param_groups: nothing below changes
-        # how this step feeds step 4: None leaves the factors alone.  The branches differ in what they hand to _screen and in
-        # what becomes (dX, dG) after it; "whitening" and None take their gradients alike
-        route = None if not update_Q else "whitening" if self._whiten else "exact" if exact else "fd"
-        undo = second = vs = None
-        with torch.enable_grad():
-            closure_returns = closure()
-            if route == "exact":
-                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params, create_graph=True)
-                vs = [self._randn(p) for p in params]
-                second = [h.detach() for h in torch.autograd.grad(grads, params, vs)]                    # the Hvs
-                grads = [g.detach() for g in grads]
-            else:
-                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
-        if route == "fd":
-            undo = vs = [self._randn(p) * self._delta for p in params]          # in the parameters' dtype: T(randn_T * delta)
-            with torch.no_grad():
-                if fused:
-                    multi_param_update(params, None, vs, plan=self._tail)
-                else:
-                    for p, v in zip(params, vs):
-                        p.add_(v)
-            with torch.enable_grad():
-                second = torch.autograd.grad(scaled(self._loss_of(closure())), params)                   # the perturbed gradients
-        # (after a half-precision widening undo stays the perturbation in T; the fp32 copy in vs feeds dX)
+        # the routes differ in what they hand to _screen and in what becomes (dX, dG) after it.  vs of "fd", T(randn_T * delta),
+        # stays the perturbation to undo after a half-precision widening, whose fp32 copy feeds dX
+        route = self._step_route(update_Q)
+        closure_returns, grads, second, vs = self._closure_gradients(
+            closure, route, scaled, self._randn, self._delta,
+            (lambda vs: multi_param_update(params, None, vs, plan=self._tail)) if fused else None)
+        undo = vs if route == "fd" else None
         grads, second, vs, bad = self._screen(grads, second, vs, inv, undo)
         if bad:                                                 # before a probe is drawn: probe_step does not move
             return closure_returns
@@ -944,37 +924,14 @@ class Kron(_psgd._StepFeatures):
             if fused:
                 pre_grads = [g.contiguous() for g in pre_grads]          # (the mirrored formats return transposed views)
                 sumsq = multi_sumsq(pre_grads, plan=self._tail) if clip else None
-                sr_kw = dict(rounding="stochastic", rounding_seed=sr_seed) if sr else {}
-                # with groups: the one sum of squares above, then one launch of the update per group
-                wd_kw = dict(weight_decay=wd) if groups is None else dict(tensor_groups=groups)
                 multi_param_update(params, pre_grads, undo, lr, sumsq, max_norm if clip else None, self._tiny, plan=self._tail,
-                                   **wd_kw, **sr_kw)
+                                   **self._fused_tail_kwargs(groups, wd, sr, sr_seed))
                 return closure_returns
             if self._ops:                                   # float(pg) of the bf16 preconditioned gradients, exact
                 pre_grads = [g.float() if g.dtype != _f32 else g for g in pre_grads]
-            if clip:
-                S = None
-                for g in pre_grads:
-                    s = torch.sum((g * g).double())
-                    S = s if S is None else S + s
-                f64 = lambda x: torch.tensor(float(np.float32(x)), dtype=torch.float64, device=self._device)
-                ratio = torch.minimum(f64(max_norm) / (torch.sqrt(S) + f64(self._tiny)), f64(1.0))
-
-            def coefficients(lr_j, wd_j):
-                """(lr_eff, c or None) of the kernel for a learning rate and a weight decay given as Python floats"""
-                lr_j = (f64(lr_j) * ratio).float() if clip else float(np.float32(lr_j))
-                if wd_j == 0.0:
-                    return lr_j, None                       # c = fl32(lr_eff * wd), as the kernel forms it
-                return lr_j, lr_j * torch.tensor(wd_j, dtype=_f32, device=self._device) if clip else \
-                    float(np.float32(lr_j) * np.float32(wd_j))
-            if groups is None:
-                coef = [coefficients(lr, wd)] * len(params)
-            else:                     # per tensor: fl32(lr * lr_scale_j), the product in double, and the group's decay, which is
-                coef = [None] * len(params)                 # absent where fl32(wd_j) == 0, as in the kernel
-                for indices, scale, wd_j in groups:
-                    pair = coefficients(lr * scale, float(np.float32(wd_j)))
-                    for i in indices:
-                        coef[i] = pair
+            sq = [torch.sum((g * g).double()) for g in pre_grads] if clip else None
+            sumsq = sum(sq[1:], sq[0]) if clip else None    # left to right, in fp64
+            coef = self._tail_coefficients(lr, wd, groups, max_norm, sumsq, self._tiny, len(params))
             for k, (p, g) in enumerate(zip(params, pre_grads)):
                 if self._reshape:
                     g = g.reshape(p.shape)

@@ -1286,13 +1286,105 @@ def _group_values(name, which, lr_scale, weight_decay):
 
 
 class _StepFeatures:
-    """The switches that class UVd and class Kron share, written once: momentum, weight decay, nonfinite="skip", the loss scale,
-    parameter groups (param_groups: a learning-rate scale and a weight decay per group of tensors; _init_groups, _step_groups),
-    the seeds drawn at construction, the stream of param_rounding="stochastic", the preconditioner_fit switch with the state of
-    its probe stream (probe_seed0 / probe_step) and the guard's checkpoint keys.  The class that
-    inherits this provides self._params (the parameters, in order), self._generator and, where param_rounding is on,
-    _param_round_seed0 / _param_round_step.  Messages carry the name of that class.  The schedules (uvd_loss_scale_next,
+    """What the flat classes (_FlatStep: UVd, SPLU, Dense) and class Kron share, written once.  The switches: momentum, weight
+    decay, nonfinite="skip", the loss scale, parameter groups (param_groups: a learning-rate scale and a weight decay per group of
+    tensors; _init_groups, _step_groups), the seeds drawn at construction, the stream of param_rounding="stochastic", the
+    preconditioner_fit switch with the state of its probe stream (probe_seed0 / probe_step) and the guard's checkpoint keys.  The
+    parts of a step that no preconditioner shapes: the reference's five hyper-parameters (_HYPER_KEYS, _init_step_hypers), the
+    route and the closure front (_step_route; _closure_gradients, the one place that calls the closure), the coefficients of the
+    torch tail (_tail_coefficients) and the keywords of the fused one (_fused_tail_kwargs).
+    The class that inherits this provides self._params (the parameters, in order), self._generator and, where param_rounding is
+    on, _param_round_seed0 / _param_round_step.  Messages carry the name of that class.  The schedules (uvd_loss_scale_next,
     uvd_momentum_coefficients, uvd_step_rounding_seed) are looked up in this module at the call."""
+
+    _HYPER_KEYS = ("lr_params", "lr_preconditioner", "grad_clip_max_norm", "preconditioner_update_probability",
+                   "exact_hessian_vector_product")
+
+    def _init_step_hypers(self, lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability,
+                          exact_hessian_vector_product):
+        """psgd.py:673-680: the five _Hyper objects of _HYPER_KEYS; grad_clip_max_norm=None means no clipping (inf)"""
+        self.lr_params = _Hyper(lr_params)                                                   # :673
+        self.lr_preconditioner = _Hyper(lr_preconditioner)                                   # :674
+        self.grad_clip_max_norm = _Hyper(math.inf if grad_clip_max_norm is None else grad_clip_max_norm)  # :675-678
+        self.preconditioner_update_probability = _Hyper(preconditioner_update_probability)  # :679
+        self.exact_hessian_vector_product = _Hyper(bool(exact_hessian_vector_product))       # :680
+
+    # ------------------------------------------------------------------------------------------------- the front of a step
+    def _step_route(self, update_Q):
+        """how this step feeds the preconditioner update, from its coin: None leaves the preconditioner alone; "whitening" (that
+        fit, whatever exact_hessian_vector_product says), "exact" (Hessian-vector products) or "fd" (finite differences)"""
+        if not update_Q:
+            return None
+        return "whitening" if self._whiten else "exact" if bool(self.exact_hessian_vector_product) else "fd"
+
+    def _closure_gradients(self, closure, route, scaled, randn, delta, perturb=None):
+        """The closure front of a step (psgd.py:706-727, :737-744): (closure_returns, grads, second, vs).  The ORDER is a contract:
+        it fixes which draws a step consumes, and tools/class_step_digest.py replays it on the CPU.
+        1. closure() under enable_grad; what it returns is passed through untouched (the loss is _loss_of it).
+        2. grads = autograd.grad(scaled(loss), params), create_graph=True only for "exact"; they come back without a graph.
+        3. "exact" and "fd": vs = one randn(p) per parameter, in parameter order; "fd": times delta (a Python float), in p's dtype.
+        4. "exact": second = the Hessian-vector products autograd.grad(grads, params, vs), which carry no graph.
+        5. "fd": the perturbation of :723 under no_grad -- perturb(vs), the class's list kernel, or with perturb=None (the torch
+           tail) p.add_(v) per tensor; the caller takes it back -- then closure() again: second = the perturbed gradients.
+        6. "whitening" and None: no draw, second = vs = None.
+        scaled: _step_scales's.  randn and perturb are hooks: there the classes differ (_randn_like; Kron's generator=)."""
+        params = self._params
+        second = vs = None
+        with torch.enable_grad():
+            closure_returns = closure()
+            grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params, create_graph=route == "exact")
+            if route == "exact":
+                vs = [randn(p) for p in params]
+                second = list(torch.autograd.grad(grads, params, vs))
+                grads = [g.detach() for g in grads]
+        if route == "fd":
+            vs = [randn(p) * delta for p in params]
+            with torch.no_grad():
+                if perturb is not None:
+                    perturb(vs)
+                else:
+                    for p, v in zip(params, vs):
+                        p.add_(v)
+            with torch.enable_grad():
+                second = torch.autograd.grad(scaled(self._loss_of(closure())), params)
+        return closure_returns, grads, second, vs
+
+    # ------------------------------------------------------------------------------------------------- the tail of a step
+    @staticmethod
+    def _tail_coefficients(lr, wd, groups, max_norm, sumsq, tiny, k):
+        """[(lr_eff, c or None)] * k of the torch tail, one pair per parameter tensor for _torch_param_update_: the rule the
+        step-tail kernels implement (fl32: rounded to float32; lr_scale_j = 1 and wd_j = wd without groups):
+            lr_j = fl32(lr lr_scale_j), the product in double
+            lr_eff_j = lr_j without a clip, else fl32(double(lr_j) min(fl32(max_norm) / (sqrt(sumsq) + fl32(tiny)), 1)) in double
+            c_j = fl32(lr_eff_j fl32(wd_j)); None where fl32(wd_j) == 0: no decay term is formed
+        groups: _step_groups's.  sumsq: None for no clip, else the caller's fp64 0-dim device tensor, the sum of squares of the whole
+        preconditioned gradient.  No host read: with a clip 0-dim float32 device tensors (NaN from a NaN sumsq), else Python floats."""
+        f32 = lambda x: float(np.float32(x))
+        ratio = None
+        if sumsq is not None:
+            ratio = torch.clamp(torch.full_like(sumsq, f32(max_norm)) / (torch.sqrt(sumsq) + f32(tiny)), max=1.0)
+
+        def pair(lr_j, wd_j):
+            lr_j, wd_j = f32(lr_j), f32(wd_j)
+            if ratio is None:
+                return lr_j, None if wd_j == 0.0 else float(np.float32(lr_j) * np.float32(wd_j))
+            lr_j = (lr_j * ratio).float()
+            return lr_j, None if wd_j == 0.0 else lr_j * wd_j
+        if groups is None:
+            return [pair(lr, wd)] * k
+        out = [None] * k
+        for indices, scale, wd_j in groups:
+            out_j = pair(lr * scale, wd_j)
+            for i in indices:
+                out[i] = out_j
+        return out
+
+    @staticmethod
+    def _fused_tail_kwargs(groups, wd, sr, sr_seed, index0=0):
+        """what weight decay, the groups (in its place: one launch of the update per group) and param_rounding (sr: this step's
+        seed and the GLOBAL flat index of the first element) add to the call of uvd_step_tail / multi_param_update"""
+        kw = dict(weight_decay=wd) if groups is None else dict(tensor_groups=groups)
+        return dict(kw, rounding="stochastic", rounding_seed=sr_seed, index0=index0) if sr else kw
 
     def _init_features(self, momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval):
         """momentum, weight_decay (off by default; _Hyper objects like the others), nonfinite, loss_scale,
@@ -1528,8 +1620,7 @@ def _torch_param_update_(p, g, v, lr, decay, sr_seed, index0):
     """One parameter tensor of the torch tail of either class, in place, one torch op per rounding: delta = T(lr g); v given (the
     undo of the finite-difference perturbation): delta = T(delta + v); decay given (c = fl32(lr_eff wd)): delta = T(delta +
     T(c float(p))); p <- T(p - delta).  For float32 .to(T) and .float() do nothing.  g: float32, in p's shape; lr and decay:
-    Python floats that hold float32 values, or 0-dim float32 tensors.  The products are written scalar first; class Kron wrote
-    them tensor first, and since a floating-point product does not depend on the order of its operands these are the same bits.
+    a pair of _StepFeatures._tail_coefficients (Python floats that hold float32 values, or 0-dim float32 tensors).
     sr_seed not None (param_rounding="stochastic"): param_update_stochastic_ on the flat indices index0, index0 + 1, ..."""
     if sr_seed is not None:                                     # formed once in fp32, narrowed once
         param_update_stochastic_(p, g, v, lr, decay, sr_seed, index0)
@@ -1591,6 +1682,8 @@ class _FlatStep(_StepFeatures):
     class SPLU (splu_optimizer.py) and class Dense (dense_optimizer.py) -- but the preconditioner itself: step(), the flat-vector
     plumbing behind it, the stages of the constructor and the checkpoint pair.
     A row-sharded flat vector (group=) is part of this class: its branches read _group, _coins and _sharded.
+    step() stands on what class Kron uses too (_StepFeatures: _step_route, _closure_gradients, _tail_coefficients,
+    _fused_tail_kwargs; _init_step_hypers in the constructor); its own are the flat vectors and the guard sequence (_step_grad).
 
     A subclass's __init__ calls _init_params, _init_hypers, _init_tail and _draw_seeds in this order, its own checks between
     them and every check before _init_tail (the first stage that touches a device), sets _rank, _store_dtype and _state_rounding,
@@ -1606,9 +1699,6 @@ class _FlatStep(_StepFeatures):
         _state_judge(sd, name, need, same, **how)    load_state_dict(): judges those keys against this object, changes nothing,
                                        returns what _state_commit takes
         _state_commit(judged)          writes the state; it cannot refuse any more"""
-
-    _HYPER_KEYS = ("lr_params", "lr_preconditioner", "grad_clip_max_norm", "preconditioner_update_probability",
-                   "exact_hessian_vector_product")
 
     # ------------------------------------------------------------------------------------------- the stages of a constructor
     def _init_params(self, params_with_grad, generator, param_rounding, preconditioner_fit, mixed_dtypes=False):
@@ -1637,14 +1727,11 @@ class _FlatStep(_StepFeatures):
 
     def _init_hypers(self, lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability,
                      exact_hessian_vector_product, *features):
-        """psgd.py:673-683: the five _Hyper objects; momentum, weight_decay, nonfinite, loss_scale and
+        """psgd.py:673-683: the five _Hyper objects (_init_step_hypers); momentum, weight_decay, nonfinite, loss_scale and
         loss_scale_growth_interval (_init_features, which checks them); the tiny of the clip and the finite-difference scale,
         which follow the parameters' dtype"""
-        self.lr_params = _Hyper(lr_params)                                                   # :673
-        self.lr_preconditioner = _Hyper(lr_preconditioner)                                   # :674
-        self.grad_clip_max_norm = _Hyper(math.inf if grad_clip_max_norm is None else grad_clip_max_norm)  # :675-678
-        self.preconditioner_update_probability = _Hyper(preconditioner_update_probability)  # :679
-        self.exact_hessian_vector_product = _Hyper(bool(exact_hessian_vector_product))       # :680
+        self._init_step_hypers(lr_params, lr_preconditioner, grad_clip_max_norm, preconditioner_update_probability,
+                               exact_hessian_vector_product)
         self._init_features(*features)
         self._stamp = 0
         self._tiny = torch.finfo(self._dtype).tiny                                           # :682
@@ -1782,6 +1869,15 @@ class _FlatStep(_StepFeatures):
             return None
         return self._grad_flat(grads, mom, inv, flat)
 
+    def _step_grad(self, grads, mom, inv, others=(), undo_vs=None):
+        """The flat gradient of a step on every route: _grad_flat; guarded, _guarded_grad and the book-keeping of its decision --
+        None: the step is skipped (the perturbation undo_vs of a finite-difference step taken back) and the caller returns."""
+        if not self._guard:
+            return self._grad_flat(grads, mom)                                                # :747
+        grad = self._guarded_grad(grads, mom, inv, others)
+        self._guard_outcome(grad is None, undo_vs if grad is None else None)
+        return grad
+
     # ------------------------------------------------------------------------------------- preconditioner_fit="whitening"
     def _whitening_inputs(self, grads, mom, inv):
         """(h, g) of an updating whitening step, or (None, None) where the guard skips it: h the raw flat fp32 gradient of this
@@ -1790,13 +1886,13 @@ class _FlatStep(_StepFeatures):
         -- every preconditioner call takes v, h and g as const pointers and only reads them.  With momentum, or where the
         momentum buffer has its place (a placed state: its layout was measured with distinct streams), h gets its own region.
         Guarded: the packs judge what they write (h in slot 1, g in slot 2 of the plan's flags); with momentum uvd_check judges
-        the gradients before the blend, as on every guarded step.  The decision is _guarded_grad's: the one host read of the step."""
-        guard = self._guard
+        the gradients before the blend, as on every guarded step.  The decision and its book-keeping are _step_grad's: the one
+        host read of the step."""
         if mom == 0.0 and self._flat_region("m") is None:
-            g = self._guarded_grad(grads, mom, inv, ()) if guard else self._grad_flat(grads, mom)
+            g = self._step_grad(grads, mom, inv)
             return g, g
-        h = self._flat(grads, "h", inv=inv, slot=1 if guard and self._tail is not None else None)
-        g = self._guarded_grad(grads, mom, inv, (h,)) if guard else self._grad_flat(grads, mom)
+        h = self._flat(grads, "h", inv=inv, slot=1 if self._guard and self._tail is not None else None)
+        g = self._step_grad(grads, mom, inv, (h,))
         return (None, None) if g is None else (h, g)
 
     def _draw_probe(self):
@@ -1848,133 +1944,77 @@ class _FlatStep(_StepFeatures):
         Out of scope: a non-finite value that the state itself produces from finite inputs propagates as before, and the
         functional preconditioner calls (update_precond_UVd_math_ and the others) are unchanged.
 
-        preconditioner_fit="whitening" (nothing of this runs with "hessian"): a step whose coin says update calls the closure ONCE,
-        takes grads = autograd.grad(scaled(loss), params) and forms h and g from them (_whitening_inputs); the guard, where on,
+        preconditioner_fit="whitening" (nothing of this runs with "hessian"): an updating step takes the "whitening" route -- ONE
+        closure call and ONE ordinary backward -- and forms h and g from the gradients (_whitening_inputs); the guard, where on,
         sees the gradients only and a skipped step returns before the probe is drawn: probe_step, U, V, d, the parameters, the
         momentum buffer and every counter keep their bits.  Then ONE multi_randn launch fills the flat probe (_draw_probe),
         probe_step advances, and :732-733, :748 run on (v, h, g) = (probe, raw gradient, gradient or momentum buffer).  Nothing is
-        undone in the tail: the parameters were never perturbed.  A step whose coin says no update is the path it always was."""
+        undone in the tail: the parameters were never perturbed.  A step whose coin says no update is the path it always was.
+        The order of closure calls, backward passes and draws on every route is written down in _StepFeatures._closure_gradients,
+        the coefficients (lr_eff, c) of the torch tail with an extension on in _StepFeatures._tail_coefficients."""
         params = self._params_with_grad
         if self._group is None:
             update_Q = _draw_branch(float(self.preconditioner_update_probability), self._generator)   # :703
         else:
             update_Q = self._coins.draw(float(self.preconditioner_update_probability))       # the same coin on every rank
-        exact = bool(self.exact_hessian_vector_product)
         mom, wd, S, inv, scaled = self._step_scales()
         groups = self._step_groups(wd)                              # None without param_groups: nothing below changes
         guard, fused = self._guard, self._tail is not None
         if guard:
             self._stamp = self._stamp % (2 ** 31 - 1) + 1       # 1 .. 2^31 - 1, then 1 again: the flags are never zeroed
-        vs = None
-        undo = update_Q and not exact and not self._whiten          # the step carries the perturbation of :723 and takes it back
-        if update_Q and self._whiten:                               # ONE ordinary backward; (v, h) = (counter-based probe, gradient)
-            with torch.enable_grad():
-                closure_returns = closure()
-                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
-            h, grad = self._whitening_inputs(grads, mom, inv)
-            if guard:
-                self._guard_outcome(grad is None)
-                if grad is None:                                    # before the probe is drawn: probe_step does not move
-                    return closure_returns
-            pre_grad = self._precondition(self._draw_probe(), h, grad)
-        elif update_Q:
-            if exact:                                                                         # :706-714
-                with torch.enable_grad():
-                    closure_returns = closure()
-                    loss = scaled(self._loss_of(closure_returns))
-                    grads = torch.autograd.grad(loss, params, create_graph=True)
-                    vs = [_randn_like(p) for p in params]
-                    Hvs = torch.autograd.grad(grads, params, vs)
-                grads = [g.detach() for g in grads]
-            else:                                                                             # :715-727
-                with torch.enable_grad():
-                    closure_returns = closure()
-                    grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
-                vs = [_randn_like(p) * self._delta_param_scale for p in params]
-                with torch.no_grad():
-                    if self._tail is not None:
-                        uvd_step_tail(params, None, 0.0, vs=vs, plan=self._tail)
-                    else:
-                        for p, v in zip(params, vs):
-                            p.add_(v)
-                with torch.enable_grad():
-                    perturbed_grads = torch.autograd.grad(scaled(self._loss_of(closure())), params)
-                Hvs = [pg - g for pg, g in zip(perturbed_grads, grads)]
-            v = self._flat(vs, "v", not exact, slot=0 if guard and fused and not exact else None)        # :729
-            h = self._flat(Hvs, "h", not exact, inv, slot=1 if guard and fused else None)                 # :730
-            if not exact and not fused:                                                       # :734-736
+        route = self._step_route(update_Q)
+        fd = route == "fd"                                          # the step carries the perturbation of :723 and takes it back
+        closure_returns, grads, second, vs = self._closure_gradients(       # :706-727, :737-744; _randn_like: looked up at the call
+            closure, route, scaled, lambda p: _randn_like(p), self._delta_param_scale,
+            (lambda vs: uvd_step_tail(params, None, 0.0, vs=vs, plan=self._tail)) if fused else None)
+        # per route (v, h) and the flat gradient; grad None: the guard skips the step (_step_grad has done the book-keeping)
+        if route == "whitening":                                    # (v, h) = (counter-based probe, gradient)
+            (h, grad), v = self._whitening_inputs(grads, mom, inv), None        # v: drawn after the decision, below
+        elif route is None:                                                                   # :737-744
+            v, h, grad = None, None, self._step_grad(grads, mom, inv)
+        else:
+            Hvs = [pg - g for pg, g in zip(second, grads)] if fd else second                  # :726, in the parameters' dtype
+            v = self._flat(vs, "v", fd, slot=0 if guard and fused and fd else None)           # :729
+            h = self._flat(Hvs, "h", fd, inv, slot=1 if guard and fused else None)            # :730
+            if fd and not fused:                                                              # :734-736
                 v = v / self._delta_param_scale
                 h = h / self._delta_param_scale
-            if guard:
-                grad = self._guarded_grad(grads, mom, inv, (v, h))
-                self._guard_outcome(grad is None, vs if grad is None and not exact else None)
-                if grad is None:
-                    return closure_returns
-            else:
-                grad = self._grad_flat(grads, mom)                                            # :747
-            pre_grad = self._precondition(v, h, grad)                                         # :732-733, :748
-        else:                                                                                 # :737-744
-            with torch.enable_grad():
-                closure_returns = closure()
-                grads = torch.autograd.grad(scaled(self._loss_of(closure_returns)), params)
-            if guard:
-                grad = self._guarded_grad(grads, mom, inv, ())
-                self._guard_outcome(grad is None)
-                if grad is None:
-                    return closure_returns
-            else:
-                grad = self._grad_flat(grads, mom)
-            pre_grad = self._precondition(None, None, grad)                                   # :747-748
+            grad = self._step_grad(grads, mom, inv, (v, h), vs if fd else None)
+        if grad is None:
+            return closure_returns
+        pre_grad = self._precondition(self._draw_probe() if route == "whitening" else v, h, grad)      # :732-733, :747-748
         max_norm = float(self.grad_clip_max_norm)
         sr, sr_seed, sr_index0 = self._param_sr, None, 0
         if sr:                           # this step writes the parameters: the seed of its rounding stream, the GLOBAL first index
             sr_seed = self._next_param_round_seed()
             sr_index0 = int(self._row0()) if self._group is not None else 0
         if fused:                                                                             # :750-762 in the step-tail kernels
-            sr_kw = dict(rounding="stochastic", rounding_seed=sr_seed, index0=sr_index0) if sr else {}
-            # with groups: one sum of squares, then one launch of the update per group, each with its own lr and weight decay
-            wd_kw = dict(weight_decay=wd) if groups is None else dict(tensor_groups=groups)
-            uvd_step_tail(params, pre_grad, float(self.lr_params), max_norm, self._tiny, vs if undo else None,
-                          self._group, plan=self._tail, **wd_kw, **sr_kw)
+            uvd_step_tail(params, pre_grad, float(self.lr_params), max_norm, self._tiny, vs if fd else None,
+                          self._group, plan=self._tail, **self._fused_tail_kwargs(groups, wd, sr, sr_seed, sr_index0))
             return closure_returns
-        decay = None
-        if mom != 0.0 or wd != 0.0 or sr or groups is not None or self._mixed:      # the torch tail of the extensions: lr_eff as the step-tail kernel forms it, one op per rounding
-            f32t = lambda x: torch.tensor(x, dtype=torch.float32, device=pre_grad.device)
-            clip_factor = None
+        if mom != 0.0 or wd != 0.0 or sr or groups is not None or self._mixed:      # the torch tail of the extensions: the kernels' rule
+            sumsq = None
             if not math.isinf(max_norm):
                 sq = torch.sum((pre_grad * pre_grad).double()).reshape(1)
                 if self._group is not None:
                     self._sharded.all_reduce_sum_f64_(sq, self._group)
-                f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))          # the kernel takes max_norm and tiny as floats
-                ratio = f32(max_norm) / (torch.sqrt(sq[0]) + f32(self._tiny))
-                clip_factor = torch.clamp(ratio, max=1.0)
-
-            def coefficients(lr_j, wd_j):
-                """(lr_eff, c or None) of the kernel for a learning rate and a weight decay given as Python floats"""
-                lr_j = f32t(lr_j)
-                if clip_factor is not None:
-                    lr_j = (lr_j.double() * clip_factor).float()
-                return lr_j, lr_j * f32t(wd_j) if wd_j != 0.0 else None
-            if groups is None:
-                lr, decay = coefficients(float(self.lr_params), wd)
-            else:                                  # per tensor: fl32(lr * lr_scale_j), the product in double, and the group's decay,
-                lr, decay = [None] * len(params), [None] * len(params)      # which is absent where fl32(wd_j) == 0, as in the kernel
-                for indices, scale, wd_j in groups:
-                    pair = coefficients(float(self.lr_params) * scale, float(np.float32(wd_j)))
-                    for i in indices:
-                        lr[i], decay[i] = pair
-        elif math.isinf(max_norm):                                                            # :750-751
-            lr = float(self.lr_params)
-        else:                                                                                 # :753-754
-            if self._group is None:
-                grad_norm = torch.sqrt(torch.sum(pre_grad * pre_grad)) + self._tiny
-            else:                                  # the norm of the GLOBAL vector: one scalar all-reduce, no host read
-                grad_norm = self._sharded.global_norm(pre_grad, self._group) + self._tiny
-            lr = float(self.lr_params) * torch.clamp(max_norm / grad_norm, max=1.0)
+                sumsq = sq[0]
+            coef = self._tail_coefficients(float(self.lr_params), wd, groups, max_norm, sumsq, self._tiny, len(params))
+        else:
+            # every extension off: the reference's own expressions, NOT _tail_coefficients -- psgd.py:750-754 forms the norm and the
+            # learning rate in float32, which gives other bits than the kernels' rule (fp64 sum, one rounding), by design
+            if math.isinf(max_norm):                                                          # :750-751
+                lr = float(self.lr_params)
+            else:                                                                             # :753-754
+                if self._group is None:
+                    grad_norm = torch.sqrt(torch.sum(pre_grad * pre_grad)) + self._tiny
+                else:                              # the norm of the GLOBAL vector: one scalar all-reduce, no host read
+                    grad_norm = self._sharded.global_norm(pre_grad, self._group) + self._tiny
+                lr = float(self.lr_params) * torch.clamp(max_norm / grad_norm, max=1.0)
+            coef = [(lr, None)] * len(params)
         with torch.no_grad():                                                                 # :757-762
             for k, (p, i, j) in enumerate(zip(params, self._param_sizes, self._param_cumsizes)):
-                lr_k, decay_k = (lr, decay) if groups is None else (lr[k], decay[k])
-                _torch_param_update_(p, torch.reshape(pre_grad[j - i:j], p.shape), vs[k] if undo else None, lr_k, decay_k,
+                _torch_param_update_(p, torch.reshape(pre_grad[j - i:j], p.shape), vs[k] if fd else None, *coef[k],
                                      sr_seed if p.dtype == torch.bfloat16 else None, sr_index0 + j - i)
         return closure_returns                                                              # :764
 

@@ -225,7 +225,10 @@ def test_a_refused_state_dict_leaves_the_optimizer_as_it_was():
 
 
 SHARED = ("step", "_pack_scale", "_flat", "_momentum_buffer", "_grad_flat", "_grad_cat", "_guarded_grad", "_whitening_inputs",
-          "_draw_probe", "_row0", "_init_params", "_init_hypers", "_init_tail", "_draw_seeds", "state_dict", "load_state_dict")
+          "_draw_probe", "_row0", "_init_params", "_init_hypers", "_init_tail", "_draw_seeds", "state_dict", "load_state_dict",
+          "_step_grad")
+# the members of a step that class Kron shares too: they live on _StepFeatures, and no class below it has a copy
+STEP_LAYER = ("_HYPER_KEYS", "_init_step_hypers", "_step_route", "_closure_gradients", "_tail_coefficients", "_fused_tail_kwargs")
 SUBCLASS_STATE = ("_Qs", "_cur", "_flat_bufs", "_out")
 
 
@@ -235,6 +238,9 @@ def test_the_flat_step_is_one_copy_under_the_three_classes():
     for f in SHARED:
         assert getattr(psgd.Dense, f) is getattr(base, f), f
         assert f not in vars(psgd.Dense), f
+    for f in STEP_LAYER:
+        assert getattr(psgd.Dense, f) is getattr(impl._StepFeatures, f), f
+        assert f not in vars(psgd.Dense) and f not in vars(base), f
     assert psgd.Dense._HYPER_KEYS is psgd.SPLU._HYPER_KEYS is base._HYPER_KEYS
     own = {k for k in vars(psgd.Dense) if not k.startswith("__")}
     assert own == {"Q", "_flat_region", "_precondition", "_state_encode", "_state_judge", "_state_commit"}, own

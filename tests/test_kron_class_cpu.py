@@ -37,6 +37,17 @@ def test_exported_from_the_package_module_and_the_shim():
     assert shim.multi_diff_scale is ko.multi_diff_scale
 
 
+def test_the_step_layer_is_the_one_copy_under_the_flat_classes():
+    """what class Kron shares with class UVd, class SPLU and class Dense in step() and __init__ lives on _StepFeatures alone"""
+    from psgd_tf_amd import psgd
+    base = psgd._StepFeatures
+    assert issubclass(ko.Kron, base) and not issubclass(ko.Kron, psgd._FlatStep)
+    for f in ("_HYPER_KEYS", "_init_step_hypers", "_step_route", "_closure_gradients", "_tail_coefficients", "_fused_tail_kwargs"):
+        assert getattr(ko.Kron, f) is getattr(base, f), f
+        assert f not in vars(ko.Kron), f
+    assert ko.Kron._HYPER_KEYS is psgd.UVd._HYPER_KEYS is ko._HYPER_KEYS
+
+
 @pytest.mark.parametrize("make, exc, match", [
     (lambda: ko.Kron([_param(3, 4), np.zeros((3, 4))]), TypeError, "parameter 1 is not a torch tensor"),
     (lambda: ko.Kron([_param(3, 4), _param(3, 4, dtype=torch.bfloat16)]), TypeError, r"parameter 1 \(shape \(3, 4\).*float32"),

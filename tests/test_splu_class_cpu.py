@@ -183,7 +183,9 @@ def test_state_dict_keys_and_refusals():
 
 
 SHARED = ("step", "_pack_scale", "_flat", "_momentum_buffer", "_grad_flat", "_grad_cat", "_guarded_grad", "_whitening_inputs",
-          "_draw_probe")
+          "_draw_probe", "_step_grad")
+# the members of a step that class Kron shares too: they live on _StepFeatures, and no class below it has a copy
+STEP_LAYER = ("_HYPER_KEYS", "_init_step_hypers", "_step_route", "_closure_gradients", "_tail_coefficients", "_fused_tail_kwargs")
 SUBCLASS_STATE = ("_arena", "_U", "_V", "_d", "_L12", "_l3", "_U12", "_u3", "_native", "_in_place", "_out")
 
 
@@ -194,6 +196,9 @@ def test_the_flat_step_is_one_copy_under_both_classes():
     for f in SHARED:
         assert getattr(psgd.UVd, f) is getattr(psgd.SPLU, f) is getattr(base, f), f
         assert f not in vars(psgd.UVd) and f not in vars(psgd.SPLU), f
+    for f in STEP_LAYER:
+        assert getattr(psgd.UVd, f) is getattr(psgd.SPLU, f) is getattr(impl._StepFeatures, f), f
+        assert f not in vars(psgd.UVd) and f not in vars(psgd.SPLU) and f not in vars(base), f
     assert psgd.UVd._HYPER_KEYS is psgd.SPLU._HYPER_KEYS is base._HYPER_KEYS
 
 

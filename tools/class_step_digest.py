@@ -12,7 +12,10 @@ seeded CPU generator behind the coin and preconditioner_update_probability=0.5. 
 
 and preconditioner_fit="whitening" of the four classes on every tail, dtype and feature setting; then class UVd on the three
 routes of its state that the grid does not reach (EXTRA_UVD: a placed state, a bfloat16 state read and written natively, a
-bfloat16 state widened every step), each on the fused tail with the features on, exact and whitening.  The digest covers the
+bfloat16 state widened every step), each on the fused tail with the features on, exact and whitening; then the two switches the
+grid predates, on the four classes, both tails, exact and fd, with the features on (SWITCHES: "groups" = float32 with two
+param_groups, lr_scale 0.5 with weight decay 0 over tensors 0 and 2, lr_scale 2.0 over tensor 1; "mixed" = mixed_dtypes=True over
+float32, bfloat16, float32).  The digest covers the
 parameters, the preconditioner state (U, V, d, the factors or Q), the momentum buffers, skipped_steps, the current loss scale and
 the counters of the rounding and probe streams.  Before anything runs on the device the coins of every configuration are replayed on the CPU
 from the generator alone, and a configuration whose coins (the step with the Inf gradient left out) do not hold both outcomes is
@@ -38,6 +41,14 @@ FEATURES_ON = dict(momentum=0.9, weight_decay=0.01, nonfinite="skip", loss_scale
 EXTRA_UVD = {"UVd:packed": dict(placement="packed"), "UVd:bf16native": dict(state_dtype=torch.bfloat16, state_route="native"),
              "UVd:bf16widen": dict(state_dtype=torch.bfloat16)}
 DTYPES = {"fp32": (torch.float32, "nearest"), "bf16": (torch.bfloat16, "nearest"), "bf16sr": (torch.bfloat16, "stochastic")}
+SWITCHES = {"groups": [torch.float32] * 3, "mixed": [torch.float32, torch.bfloat16, torch.float32]}    # in the place of a dtype
+
+
+def dtypes_of(dt):
+    """(the dtype of each of the three parameters, param_rounding) of a line's dtype field"""
+    if dt in SWITCHES:
+        return SWITCHES[dt], "nearest"
+    return [DTYPES[dt][0]] * len(SHAPES), DTYPES[dt][1]
 
 
 def configurations():
@@ -50,7 +61,9 @@ def configurations():
     for cls, hvp in itertools.product(EXTRA_UVD, ("exact", "whitening")):
         yield cls, "fused", hvp, "fp32", "on"
     for tail, hvp, dt, feat in itertools.product(("torch", "fused"), ("exact", "fd", "whitening"), DTYPES, ("off", "on")):
-        yield "Dense", tail, hvp, dt, feat            # (last: the lines before it keep their places)
+        yield "Dense", tail, hvp, dt, feat            # (the lines before it keep their places)
+    for cls, tail, hvp, dt in itertools.product(("UVd", "Kron", "SPLU", "Dense"), ("torch", "fused"), ("exact", "fd"), SWITCHES):
+        yield cls, tail, hvp, dt, "on"                # (last: a new line is added here, at the end)
 
 
 def replayed_coins(cls, hvp, dt, feat):
@@ -59,7 +72,7 @@ def replayed_coins(cls, hvp, dt, feat):
     after it from the same generator -- class UVd the two branches of an update that runs, class Kron its probe vectors in the
     parameters' dtype, class SPLU and class Dense nothing"""
     gen = torch.Generator().manual_seed(SEED)
-    dtype, rounding = DTYPES[dt]
+    dtypes, rounding = dtypes_of(dt)
     for _ in range((cls == "UVd:bf16native") + (rounding == "stochastic") + (hvp == "whitening")):
         torch.randint(0, 2 ** 62, (), generator=gen)
     coins = []
@@ -71,7 +84,7 @@ def replayed_coins(cls, hvp, dt, feat):
         if cls.startswith("UVd") and not (feat == "on" and k == INF_STEP):
             torch.rand((), generator=gen), torch.rand((), generator=gen)
         if cls == "Kron" and hvp != "whitening":
-            for s in SHAPES:
+            for s, dtype in zip(SHAPES, dtypes):
                 torch.randn(s, dtype=dtype, generator=gen)
     return coins
 
@@ -91,10 +104,10 @@ def state_tensors(opt):
 
 
 def run(cls, tail, hvp, dt, feat, dev):
-    dtype, rounding = DTYPES[dt]
+    dtypes, rounding = dtypes_of(dt)
     torch.manual_seed(1234)                       # the global device generator: UVd's initial U, V and its probe vectors
     init = torch.Generator().manual_seed(5)
-    params = [torch.randn(s, generator=init).to(dev, dtype).requires_grad_(True) for s in SHAPES]
+    params = [torch.randn(s, generator=init).to(dev, dtype).requires_grad_(True) for s, dtype in zip(SHAPES, dtypes)]
     hess = [torch.rand(s, generator=init).add_(0.5).to(dev) for s in SHAPES]
     step_no = [0]
 
@@ -106,6 +119,10 @@ def run(cls, tail, hvp, dt, feat, dev):
     kw = dict(lr_params=0.05, lr_preconditioner=0.1, grad_clip_max_norm=1.0, preconditioner_update_probability=P_UPDATE,
               exact_hessian_vector_product=hvp != "fd", step_tail=tail, generator=torch.Generator().manual_seed(SEED),
               param_rounding=rounding, **(FEATURES_ON if feat == "on" else {}))
+    if dt == "groups":
+        kw["param_groups"] = [dict(params=[params[0], params[2]], lr_scale=0.5, weight_decay=0.0), dict(params=[params[1]], lr_scale=2.0)]
+    if dt == "mixed":
+        kw["mixed_dtypes"] = True
     if cls.startswith("UVd"):                     # (its Hessian-fit lines are built without the keyword, as before it existed)
         kw.update(EXTRA_UVD.get(cls, {}), **({"preconditioner_fit": "whitening"} if hvp == "whitening" else {}))
         opt = psgd.UVd(params, rank_of_modification=3, **kw)

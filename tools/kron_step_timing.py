@@ -12,6 +12,11 @@ resolved, and the summary line says so.
 
     python tools/kron_step_timing.py [--chunks 9] [--steps 50] [--out profiles/kron_class.txt]
 
+With --parent-module FILE (the kron_optimizer.py of another commit, loaded beside this tree's; it runs on this tree's library and
+on this tree's _StepFeatures) the hand leg gives way to that commit's class on each tail, TWICE ("parent-torch", "parent-torch-2",
+...): whether the host layer of a step moved.  The bar is the parent in the same job, the margin the difference between the
+medians of its own two legs.
+
 --features times the switches of class Kron instead, same shapes and protocol, legs:
 
     off       class Kron, step_tail="fused", momentum / weight decay / guard at their defaults
@@ -328,6 +333,13 @@ def main():
             legs["on-torch"] = class_leg("torch", **FEATURES_ON)(shapes, dev)
             legs["on-fused"] = class_leg("fused", **FEATURES_ON)(shapes, dev)
             pairs = ([("parent", "off")] if a.parent_module else []) + [("on-torch", "on-fused"), ("on-fused", "off")]
+        elif a.parent_module:
+            parent = parent_class(a.parent_module)
+            legs, pairs = {}, []
+            for tail in ("torch", "fused"):
+                legs.update({tail: class_leg(tail)(shapes, dev), "parent-" + tail: class_leg(tail, parent)(shapes, dev),
+                             "parent-%s-2" % tail: class_leg(tail, parent)(shapes, dev)})
+                pairs += [(tail, "parent-" + tail), ("parent-%s-2" % tail, "parent-" + tail)]
         else:
             legs = {"hand": hand_leg(shapes, dev), "torch": class_leg("torch")(shapes, dev), "fused": class_leg("fused")(shapes, dev)}
             pairs = [("hand", "torch"), ("hand", "fused"), ("torch", "fused")]
@@ -341,7 +353,7 @@ def main():
                 times[k].append(timed(step, a.steps))
         med = {k: statistics.median(v) for k, v in times.items()}
         for k, v in times.items():
-            lines.append("%-10s %-8s %9.1f  [%9.1f .. %9.1f]" % (name, k, med[k], min(v), max(v)))
+            lines.append("%-10s %-14s %9.1f  [%9.1f .. %9.1f]" % (name, k, med[k], min(v), max(v)))
         spread = max(max(v) - min(v) for v in times.values())
         for x, y in pairs:
             d = med[x] - med[y]

@@ -16,6 +16,10 @@ over the chunks with [min .. max].  A difference between two legs counts as reso
     python tools/splu_step_timing.py --sizes 4000000          # one size
     python tools/splu_step_timing.py --trace 4000000          # 5 fused steps and nothing else, for
                                                               # rocprofv3 --kernel-trace --stats -- python tools/splu_step_timing.py --trace 4000000
+    python tools/splu_step_timing.py --sizes 4000000 --parent-module FILE --out FILE
+        # whether the host layer of a step moved: FILE is the psgd_tf_amd/__init__.py of another commit's built tree, loaded as a
+        # second package; its class SPLU runs on each tail TWICE ("parent-torch", "parent-torch-2", ...) in the place of the
+        # functional leg.  The bar is the parent in the same job, the margin the difference between the medians of its two legs.
 """
 import argparse
 import os
@@ -63,9 +67,19 @@ def functional_leg(N):
     return step
 
 
-def class_leg(N, tail):
+def parent_class(path):
+    """class SPLU of the package whose __init__.py is at `path`, loaded whole as a second package beside this tree's"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("psgd_tf_amd_parent", path, submodule_search_locations=[os.path.dirname(path)])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules[spec.name] = mod
+    spec.loader.exec_module(mod)
+    return mod.psgd.SPLU
+
+
+def class_leg(N, tail, cls=None):
     params = _params(N)
-    opt = psgd.SPLU(params, R, lr_params=LR, lr_preconditioner=LR_Q, step_tail=tail)
+    opt = (cls or psgd.SPLU)(params, R, lr_params=LR, lr_preconditioner=LR_Q, step_tail=tail)
     closure = _closure(params)
     return lambda: opt.step(closure)
 
@@ -79,8 +93,15 @@ def peak_delta(fn):
     return torch.cuda.max_memory_allocated() - before
 
 
-def table(N, steps, chunks, out):
+def table(N, steps, chunks, out, parent=None):
     legs = {"functional": functional_leg(N), "torch": class_leg(N, "torch"), "fused": class_leg(N, "fused")}
+    pairs = [("torch", "functional"), ("fused", "functional")]
+    if parent is not None:
+        del legs["functional"]
+        pairs = []
+        for tail in ("torch", "fused"):
+            legs.update({"parent-" + tail: class_leg(N, tail, parent), "parent-%s-2" % tail: class_leg(N, tail, parent)})
+            pairs += [(tail, "parent-" + tail), ("parent-%s-2" % tail, "parent-" + tail)]
     for fn in legs.values():                                  # warm-up: every leg has run every launch and holds its buffers
         for _ in range(5):
             fn()
@@ -96,12 +117,12 @@ def table(N, steps, chunks, out):
     med = {k: statistics.median(v) for k, v in times.items()}
     spread = {k: max(v) - min(v) for k, v in times.items()}
     for k in legs:
-        out("N=%d r=%d k=%d float32 | %-10s: %9.1f [%9.1f .. %9.1f] us per step, peak over a step +%d B"
+        out("N=%d r=%d k=%d float32 | %-14s: %9.1f [%9.1f .. %9.1f] us per step, peak over a step +%d B"
             % (N, R, K, k, med[k] * 1e6, min(times[k]) * 1e6, max(times[k]) * 1e6, peak_delta(legs[k])))
-    for k in ("torch", "fused"):
-        d, s = med[k] - med["functional"], max(spread[k], spread["functional"])
-        out("N=%d | %s - functional: %+.1f us (%+.1f %%), spread %.1f us: %s"
-            % (N, k, d * 1e6, 100.0 * d / med["functional"], s * 1e6, "resolved" if abs(d) > s else "NOT resolved"))
+    for k, base in pairs:
+        d, s = med[k] - med[base], max(spread[k], spread[base])
+        out("N=%d | %s - %s: %+.1f us (%+.1f %%), spread %.1f us: %s"
+            % (N, k, base, d * 1e6, 100.0 * d / med[base], s * 1e6, "resolved" if abs(d) > s else "NOT resolved"))
 
 
 def main():
@@ -111,6 +132,7 @@ def main():
     ap.add_argument("--chunks", type=int, default=9)
     ap.add_argument("--out", default=os.path.join(_root, "profiles", "splu_class.txt"))
     ap.add_argument("--trace", type=int, default=None, metavar="N")
+    ap.add_argument("--parent-module", default=None, metavar="FILE")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "this tool measures on the GPU"
     if a.trace is not None:
@@ -127,8 +149,9 @@ def main():
         lines.append(s)
     out("# one sparse-LU step, exact Hessian-vector products, no clipping | leg: median [min .. max] over %d chunks of %d steps, legs "
         "alternating" % (a.chunks, a.steps))
+    parent = parent_class(a.parent_module) if a.parent_module else None
     for N in (int(x) for x in a.sizes.split(",")):
-        table(N, a.steps, a.chunks, out)
+        table(N, a.steps, a.chunks, out, parent)
         torch.cuda.empty_cache()
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")
