@@ -7,6 +7,8 @@ Contents (only what the hot path needs):
   kron.py                                          Kronecker dispatch + formats
   kron_optimizer.py                                class Kron
   splu_optimizer.py                                class SPLU
+  dense_optimizer.py                               class Dense
+  xmat.py                                          the X-shaped / diagonal preconditioner (psgd_xmat.hip) and class XMat
   multi_tail.py                                    the multi-tensor (list) kernels of its step tail as functions
   sharded.py                                       row-sharded multi-GPU UVd (torch.distributed / RCCL)
 """

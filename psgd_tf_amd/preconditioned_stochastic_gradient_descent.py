@@ -2475,3 +2475,7 @@ from .splu_optimizer import SPLU, splu_initial_factors  # noqa: E402,F401
 
 # --------------------------------------------------------------------------- dense optimizer (dense_optimizer.py)
 from .dense_optimizer import Dense, dense_initial_factor  # noqa: E402,F401
+
+# --------------------------------------------------------------------------- X-shaped / diagonal preconditioner (xmat.py)
+from .xmat import XMat, xmat_initial_state, update_precond_Xmat_math_, precond_grad_Xmat_math  # noqa: E402,F401
+from .xmat import update_precond_grad_Xmat_math_  # noqa: E402,F401
