@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import kron as _kron
+from . import kron_quad as _quad
 from . import preconditioned_stochastic_gradient_descent as _psgd
 from .multi_tail import MultiTailPlan, _lists, _f32, _TINY, _HALF, _MIXED, _DTYPE_NAMES  # noqa: F401
 from .multi_tail import multi_sumsq, multi_param_update, multi_diff_scale, multi_blend, multi_scale_check  # noqa: F401
@@ -395,6 +396,18 @@ class Kron(_psgd._StepFeatures):
     once per (group, dtype) pair that has tensors; sums of squares, blend, randn, diff-scale and the narrowing of operands stay
     single.  Operand layers are chosen by shape and format as always.  Not in state_dict(), which carries no dtype.
 
+    preconditioner_update="quad" (keyword-only; "triangular" by default: not a launch, a bit or a checkpoint byte changes; any
+    other value, "quad" without preconditioner_fit="whitening", and "quad" with operands="bfloat16" are ValueErrors before a device
+    is touched): every (dense, dense) MATRIX layer (rank >= 3 views under any_rank included; opt.quad_layers) runs steps 4 and 5
+    through update_precond_kron_quad_ and precond_grad_kron_quad of kron_quad.py -- the inverse-free quadratic-form update on
+    SYMMETRIC factors, no solve, no inverse, no probe (include/psgd_kron_quad_hip.h).  Step 4 is fed the raw widened gradient and
+    rewrites Ql, Qr and the layer's pair of Lipschitz estimates L (opt.quad_L) in place; step 5 is fed the gradient (the momentum
+    buffer after the blend).  The factors start at scale I / I as always.  Every other layer -- the sparse formats, vector layers
+    on either vector_route, [1, 1] scalar layers -- keeps the triangular whitening update and its probe, and the probe launch still
+    draws for every parameter: the random stream does not depend on the switch.  Quad layers are issued outside the layer_batch
+    blocks, as operand layers are.  A skipped step leaves Ql, Qr and L bit for bit.  state_dict() gains 'preconditioner_update' and
+    'quad_L' (one tensor per quad layer, parameter order) only when the switch is on; a resumed run is bit-identical.
+
     Out of scope: mixed dtypes with the switch off, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale),
     float16 stochastic rounding."""
 
@@ -404,13 +417,20 @@ class Kron(_psgd._StepFeatures):
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
                  any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM,
                  param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None,
-                 param_groups=None, mixed_dtypes=False):
+                 param_groups=None, mixed_dtypes=False, preconditioner_update="triangular"):
         _psgd._mixed_dtypes_switch("Kron", mixed_dtypes)
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
         self._init_fit(preconditioner_fit)
         self._probe, self._probe_plan = None, None
         self._operands, self._operand_min_dim = _operands_dtype(operands), _operand_min_dim(operand_min_dim)
+        if preconditioner_update not in ("triangular", "quad"):
+            raise ValueError("Kron: preconditioner_update must be 'triangular' or 'quad', got %r" % (preconditioner_update,))
+        if preconditioner_update == "quad" and not self._whiten:
+            raise ValueError("Kron: preconditioner_update='quad' fits the factors to the gradients: it needs preconditioner_fit='whitening'")
+        if preconditioner_update == "quad" and self._operands is not None:
+            raise ValueError("Kron: preconditioner_update='quad' runs on float32 operands; operands='bfloat16' is not supported with it")
+        self.preconditioner_update = preconditioner_update
         if vector_route not in ("list", "layer"):
             raise ValueError("Kron: vector_route must be 'list' or 'layer', got %r" % (vector_route,))
         any_rank = bool(any_rank)
@@ -475,6 +495,12 @@ class Kron(_psgd._StepFeatures):
         # of self._mat that keep the fp32 calls
         self._ops = kron_operand_layers(self._layer_shapes, self._formats, self._operands, self._operand_min_dim)
         self._f32 = [i for i in self._mat if i not in set(self._ops)]
+        # the quad layers (none with preconditioner_update="triangular"): the (dense, dense) matrix layers; each keeps its pair of
+        # Lipschitz estimates L, and leaves self._f32 for update_precond_kron_quad_ / precond_grad_kron_quad
+        self._quad = [i for i in self._mat if preconditioner_update == "quad" and layers[i][0] == "matrix"
+                      and self._formats[i] == ("dense", "dense")]
+        self._quad_L = {i: torch.zeros(2, dtype=_f32, device=dev) for i in self._quad}
+        self._f32 = [i for i in self._f32 if i not in set(self._quad)]
         self._op_plan, self._op_bufs = None, None
         self._vec_plan, self._vec_out = None, None
         if self._vec:
@@ -528,6 +554,16 @@ class Kron(_psgd._StepFeatures):
         return self._Qs
 
     @property
+    def quad_layers(self):
+        """the indices (parameter order) of the layers that run the QUAD update (none on the triangular route)"""
+        return list(self._quad)
+
+    @property
+    def quad_L(self):
+        """{layer index: L}, L = [Ll, Lr] the float32 Lipschitz estimates of a quad layer, updated in place"""
+        return self._quad_L
+
+    @property
     def operand_layers(self):
         """the indices (parameter order) of the layers that run on the bf16-operand kernels: kron_operand_layers of this optimizer"""
         return list(self._ops)
@@ -548,6 +584,9 @@ class Kron(_psgd._StepFeatures):
         sd = _encode_features(sd, mom, float(self.weight_decay), self._momentum_buffers() if mom > 0.0 else None, self._m_step,
                               self._guard, self.skipped_steps, self.loss_scale.value, self._good_steps)
         sd = _psgd._param_rounding_encode(sd, self._param_sr, self._param_round_seed0, self._param_round_step)
+        if self._quad:
+            sd["preconditioner_update"] = "quad"
+            sd["quad_L"] = [self._quad_L[i].detach().to("cpu", copy=True) for i in self._quad]
         return self._groups_encode(_probe_encode(sd, self._whiten, self._probe_seed0, self._probe_step))
 
     def load_state_dict(self, sd):
@@ -566,6 +605,11 @@ class Kron(_psgd._StepFeatures):
         sr_state = _psgd._param_rounding_decode("Kron.load_state_dict", sd, self._param_sr, self._param_round_seed0)
         probe_state = _probe_decode(sd, self._whiten, self._probe_seed0, "Kron.load_state_dict")
         group_values = self._groups_judge(sd, "Kron.load_state_dict")
+        quad_L = sd.get("quad_L") if self._quad else None
+        if self._quad and (sd.get("preconditioner_update") != "quad" or not isinstance(quad_L, (list, tuple)) or len(quad_L) != len(self._quad)
+                           or any(not isinstance(t, torch.Tensor) or t.dtype != _f32 or tuple(t.shape) != (2,) for t in quad_L)):
+            raise ValueError("Kron.load_state_dict: this optimizer runs preconditioner_update='quad': the state dict must carry "
+                             "'preconditioner_update' == 'quad' and 'quad_L', one float32 tensor of shape (2,) per quad layer")
         try:
             self._coin_generator().set_state(rng)
         except (RuntimeError, TypeError) as e:
@@ -580,6 +624,8 @@ class Kron(_psgd._StepFeatures):
         self._param_round_seed0, self._param_round_step = sr_state
         self._probe_seed0, self._probe_step = probe_state
         self._groups_commit(group_values)
+        for i, t in zip(self._quad, quad_L or ()):
+            self._quad_L[i].copy_(t)
         with torch.no_grad():
             if bufs is not None:
                 for m, b in zip(self._momentum_buffers(), bufs):
@@ -748,7 +794,7 @@ class Kron(_psgd._StepFeatures):
         vector layers of the list route in ONE multi_vec_precond_update launch, in place"""
         dXs, dGs = self._as_layers(dXs), self._as_layers(dGs)
         Qs = self._Qs
-        if not self._vec and not self._ops:
+        if not self._vec and not self._ops and not self._quad:
             with self._block():
                 new = [_psgd.update_precond_kron(q[0], q[1], dX, dG, lr_q) for q, dX, dG in zip(Qs, dXs, dGs)]
             self._Qs = [[a, b] for a, b in new]
@@ -762,6 +808,8 @@ class Kron(_psgd._StepFeatures):
             bX, bG = self._narrow([[dXs[i] for i in ops], [dGs[i] for i in ops]], self._op_bufs and self._op_bufs[1:])
             for i, x, g in zip(ops, bX, bG):
                 Qs[i] = list(_psgd.update_precond_kron(Qs[i][0], Qs[i][1], x, g, lr_q))
+        for i in self._quad:                                # in place, outside the block; dG is the raw gradient, the probe unused
+            _quad.update_precond_kron_quad_(Qs[i][0], Qs[i][1], self._quad_L[i], dGs[i], lr_q)
         if self._f32:
             with self._block():
                 new = [_psgd.update_precond_kron(Qs[i][0], Qs[i][1], dXs[i], dGs[i], lr_q) for i in self._f32]
@@ -786,7 +834,7 @@ class Kron(_psgd._StepFeatures):
         multi_vec_precond_grad launch.  Returns the preconditioned gradients in the layers' shapes."""
         grads = self._as_layers(grads)
         Qs = self._Qs
-        if not self._vec and not self._ops:
+        if not self._vec and not self._ops and not self._quad:
             with self._block():
                 return [_psgd.precond_grad_kron(q[0], q[1], g) for q, g in zip(Qs, grads)]
         pre = [None] * len(grads)
@@ -796,6 +844,8 @@ class Kron(_psgd._StepFeatures):
             (bg,) = self._narrow([[grads[i] for i in ops]], self._op_bufs and self._op_bufs[:1])
             for i, g in zip(ops, bg):
                 pre[i] = _psgd.precond_grad_kron(Qs[i][0], Qs[i][1], g)
+        for i in self._quad:
+            pre[i] = _quad.precond_grad_kron_quad(Qs[i][0], Qs[i][1], grads[i])
         if self._f32:
             with self._block():
                 out = [_psgd.precond_grad_kron(Qs[i][0], Qs[i][1], grads[i]) for i in self._f32]

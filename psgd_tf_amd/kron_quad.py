@@ -1,0 +1,102 @@
+"""The inverse-free Kronecker whitening update (QUAD) on full symmetric factors, on psgd_kron_quad.hip.
+
+The reference has no code for this update; the PyTorch line of PSGD, which its README names as the place for updates, uses it in
+its Kron whitening optimizer.  include/psgd_kron_quad_hip.h states the definition in full: symmetric positive-definite factors
+Ql (M x M), Qr (N x N) with P = (Ql Ql) (x) (Qr Qr), no solve, no inverse, no probe, and a step bounded by the running
+Lipschitz estimates L = [Ll, Lr].
+
+    kron_quad_initial_state(M, N, scale, device)               (Ql, Qr, L) = (scale I, I, zeros(2))
+    update_precond_kron_quad_(Ql, Qr, L, G, step, decay)       the update, in place on Ql, Qr and L
+    precond_grad_kron_quad(Ql, Qr, G, out=None)                out = Ql (Ql G Qr) Qr
+
+The three C entry points are bound here, in a signature table of this module's own, on the library _lib.load() returns.  fp32 on
+the HIP device only; no fallback.  class Kron(preconditioner_fit="whitening", preconditioner_update="quad") runs its
+(dense, dense) matrix layers through these two functions.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from . import preconditioned_stochastic_gradient_descent as _psgd
+
+KRON_QUAD_TILE = 64          # PSGD_KRON_QUAD_TILE: edge of the output tile one workgroup owns
+
+_p, _i64, _int, _flt = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
+SIGNATURES = {
+    "psgd_kron_quad_workspace_bytes": (_i64, [_int, _int]),
+    "psgd_kron_quad_apply_f32": (_int, [_p, _p, _p, _p, _int, _int, _p, _i64, _p]),
+    "psgd_kron_quad_update_f32": (_int, [_p, _p, _p, _p, _int, _int, _flt, _flt, _p, _i64, _p]),
+}
+_bound = None
+
+
+def load():
+    """_lib.load() with this module's entry points bound (once per loaded library)"""
+    global _bound
+    lib = _lib.load()
+    if _bound is not lib:
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _bound = lib
+    return lib
+
+
+def _operands(name, Ql, Qr, G, **more):
+    """Ql [M, M], Qr [N, N] and G [M, N] float32 and contiguous on one HIP device, like every further named operand (its value a
+    (tensor, shape) pair).  Returns (device, M, N)."""
+    named = dict(Ql=Ql, Qr=Qr, G=G, **{k: v[0] for k, v in more.items()})
+    for k, t in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch tensor, got %r" % (name, k, type(t)))
+        if t.dtype != torch.float32:
+            raise TypeError("%s: %s must be float32, got %s" % (name, k, t.dtype))
+    if G.dim() != 2 or G.shape[0] < 1 or G.shape[1] < 1:
+        raise ValueError("%s: G must be a matrix [M, N] with M, N >= 1, got %s" % (name, tuple(G.shape)))
+    M, N = (int(s) for s in G.shape)
+    for k, (t, want) in dict(Ql=(Ql, (M, M)), Qr=(Qr, (N, N)), **more).items():
+        if tuple(t.shape) != want:
+            raise ValueError("%s: %s must have shape %s for G of shape %s, got %s" % (name, k, want, (M, N), tuple(t.shape)))
+    for k, t in named.items():
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (name, k))
+    return _psgd._require_hip(name, *named.values()), M, N
+
+
+def _workspace(device, M, N):
+    load()
+    return _psgd._workspace(("kron_quad",), device, "psgd_kron_quad_workspace_bytes", M, N)
+
+
+def kron_quad_initial_state(M, N, scale=1.0, device=None):
+    """(Ql, Qr, L) = (scale I [M, M], I [N, N], zeros(2)), float32"""
+    M, N = int(M), int(N)
+    if M < 1 or N < 1:
+        raise ValueError("kron_quad_initial_state: M and N must be >= 1, got %d and %d" % (M, N))
+    return (torch.eye(M, dtype=torch.float32, device=device) * float(scale), torch.eye(N, dtype=torch.float32, device=device),
+            torch.zeros(2, dtype=torch.float32, device=device))
+
+
+def precond_grad_kron_quad(Ql, Qr, G, out=None):
+    """out = Ql (Ql G Qr) Qr, four chained products.  out (made when None) must not be G, Ql or Qr."""
+    G = _psgd._c(G)
+    more = {} if out is None else {"out": (out, tuple(G.shape) if isinstance(G, torch.Tensor) else ())}
+    dev, M, N = _operands("precond_grad_kron_quad", Ql, Qr, G, **more)
+    if out is None:
+        out = torch.empty_like(G)
+    ws = _workspace(dev, M, N)
+    rc = load().psgd_kron_quad_apply_f32(Ql.data_ptr(), Qr.data_ptr(), G.data_ptr(), out.data_ptr(), M, N, ws.data_ptr(), ws.numel(),
+                                         _psgd._stream_ptr(dev))
+    _lib.check(rc, "psgd_kron_quad_apply_f32")
+    return out
+
+
+def update_precond_kron_quad_(Ql, Qr, L, G, step, decay=0.95):
+    """Ql, Qr, L <- the QUAD step on the gradient G, in place, six launches; the host reads nothing.  Returns None."""
+    G = _psgd._c(G)
+    dev, M, N = _operands("update_precond_kron_quad_", Ql, Qr, G, L=(L, (2,)))
+    ws = _workspace(dev, M, N)
+    rc = load().psgd_kron_quad_update_f32(Ql.data_ptr(), Qr.data_ptr(), L.data_ptr(), G.data_ptr(), M, N, float(step), float(decay),
+                                          ws.data_ptr(), ws.numel(), _psgd._stream_ptr(dev))
+    _lib.check(rc, "psgd_kron_quad_update_f32")

@@ -2479,3 +2479,6 @@ from .dense_optimizer import Dense, dense_initial_factor  # noqa: E402,F401
 # --------------------------------------------------------------------------- X-shaped / diagonal preconditioner (xmat.py)
 from .xmat import XMat, xmat_initial_state, update_precond_Xmat_math_, precond_grad_Xmat_math  # noqa: E402,F401
 from .xmat import update_precond_grad_Xmat_math_  # noqa: E402,F401
+
+# --------------------------------------------------------------------------- inverse-free Kron whitening update (kron_quad.py)
+from .kron_quad import kron_quad_initial_state, update_precond_kron_quad_, precond_grad_kron_quad  # noqa: E402,F401
