@@ -14,27 +14,47 @@ def _state(p):
     return [p[k].to(DEV).clone() for k in ("Ql", "Qr", "L")]
 
 
-def _increment_err(new, old, ref_new):
-    return qc.err(new.double().cpu() - old.double(), ref_new - old.double())
+def _increment_err(new, old, ref_new, err=qc.err):
+    return err(new.double().cpu() - old.double(), ref_new - old.double())
+
+
+def _apply_update_apply(p, M, N):
+    """every error norm-wise over the matrix and over each T x T tile, against the same bar"""
+    G = p["G"].to(DEV)
+    Ql, Qr, L = _state(p)
+    out = psgd.precond_grad_kron_quad(Ql, Qr, G)
+    e, et = qc.err(out, p["out"]), qc.tile_err(out, p["out"])
+    print("out", M, N, "apply %.2e tile-wise %.2e" % (e, et))
+    assert e < qc.APPLY_BAR and et < qc.APPLY_BAR
+    assert psgd.update_precond_kron_quad_(Ql, Qr, L, G, qc.STEP, qc.DECAY) is None
+    for k, new in (("Ql", Ql), ("Qr", Qr)):
+        e, ei = qc.err(new, p["new_" + k]), _increment_err(new, p[k], p["new_" + k])
+        et, eit = qc.tile_err(new, p["new_" + k]), _increment_err(new, p[k], p["new_" + k], qc.tile_err)
+        print(k, M, N, "state %.2e increment %.2e tile-wise %.2e %.2e" % (e, ei, et, eit))
+        assert e < qc.STATE_BAR and ei < qc.INCREMENT_BAR
+        assert et < qc.STATE_BAR and eit < qc.INCREMENT_BAR
+        assert torch.equal(new, new.T)
+    e = qc.err(L, p["new_L"])
+    print("L", M, N, "%.2e" % e)
+    assert e < qc.L_BAR
+    out = psgd.precond_grad_kron_quad(Ql, Qr, G)
+    e, et = qc.err(out, p["out_new"]), qc.tile_err(out, p["out_new"])
+    print("out_new", M, N, "apply %.2e tile-wise %.2e" % (e, et))
+    assert e < qc.APPLY_BAR and et < qc.APPLY_BAR
+    again = _state(p)                                   # the same call from the same start: the same bits
+    psgd.update_precond_kron_quad_(*again, G, qc.STEP, qc.DECAY)
+    assert all(torch.equal(a, b) for a, b in zip(again, (Ql, Qr, L)))
 
 
 @pytest.mark.parametrize("M, N, seed", qc.CASES)
 def test_apply_update_apply(M, N, seed):
-    p = qc.problem(M, N, seed)
-    G = p["G"].to(DEV)
-    Ql, Qr, L = _state(p)
-    assert qc.err(psgd.precond_grad_kron_quad(Ql, Qr, G), p["out"]) < qc.APPLY_BAR
-    assert psgd.update_precond_kron_quad_(Ql, Qr, L, G, qc.STEP, qc.DECAY) is None
-    for k, new in (("Ql", Ql), ("Qr", Qr)):
-        e, ei = qc.err(new, p["new_" + k]), _increment_err(new, p[k], p["new_" + k])
-        print(k, M, N, "state %.2e increment %.2e" % (e, ei))
-        assert e < qc.STATE_BAR and ei < qc.INCREMENT_BAR
-        assert torch.equal(new, new.T)
-    assert qc.err(L, p["new_L"]) < qc.L_BAR
-    assert qc.err(psgd.precond_grad_kron_quad(Ql, Qr, G), p["out_new"]) < qc.APPLY_BAR
-    again = _state(p)                                   # the same call from the same start: the same bits
-    psgd.update_precond_kron_quad_(*again, G, qc.STEP, qc.DECAY)
-    assert all(torch.equal(a, b) for a, b in zip(again, (Ql, Qr, L)))
+    _apply_update_apply(qc.problem(M, N, seed), M, N)
+
+
+def test_lipschitz_kernel_past_its_1024_threads():
+    """N > kLipT with the right side's j in the second trip of the strided loops (tests/test_kron_quad_cpu.py asserts j >= 1024)"""
+    M, N, seed, col = qc.LIP_CASE
+    _apply_update_apply(qc.problem(M, N, seed, col), M, N)
 
 
 @pytest.mark.parametrize("M, N, seed", [qc.CASES[3], qc.CASES[6]])
@@ -50,6 +70,21 @@ def test_nan_masks_are_the_restatements(M, N, seed, where):
     psgd.update_precond_kron_quad_(Ql, Qr, L, G.to(DEV), qc.STEP)
     for got, want in zip((out, Ql, Qr, L), ref):
         assert torch.equal(torch.isnan(got).cpu(), torch.isnan(want))
+
+
+@pytest.mark.parametrize("M, N, seed", [qc.CASES[3], qc.CASES[6]])
+@pytest.mark.parametrize("where", ["first", "middle", "last", "edge"])
+@pytest.mark.parametrize("value", ["inf", "-inf"])
+def test_inf_anywhere_in_g_makes_the_whole_state_nan(M, N, seed, where, value):
+    """the Inf half of the header's sentence, asserted itself and not as the restatement's mask (the NaN half is the test above);
+    edge: the last element of the partial tile at the top right"""
+    p = qc.problem(M, N, seed)
+    G = p["G"].clone()
+    at = {"first": 0, "middle": G.numel() // 2, "last": G.numel() - 1, "edge": (min(M, qc.T) - 1) * N + N - 1}[where]
+    G.view(-1)[at] = float(value)
+    Ql, Qr, L = _state(p)
+    psgd.update_precond_kron_quad_(Ql, Qr, L, G.to(DEV), qc.STEP)
+    assert bool(torch.isnan(Ql).all()) and bool(torch.isnan(Qr).all()) and bool(torch.isnan(L).all())
 
 
 def test_zero_gradient_grows_the_factors():
