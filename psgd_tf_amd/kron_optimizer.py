@@ -408,6 +408,14 @@ class Kron(_psgd._StepFeatures):
     blocks, as operand layers are.  A skipped step leaves Ql, Qr and L bit for bit.  state_dict() gains 'preconditioner_update' and
     'quad_L' (one tensor per quad layer, parameter order) only when the switch is on; a resumed run is bit-identical.
 
+    quad_diagonal=True (keyword-only; False by default: not a launch, a bit or a checkpoint byte changes; True without
+    preconditioner_update="quad" is a ValueError before a device is touched): the MATRIX layers in ("dense", "scale") and
+    ("scale", "dense") join opt.quad_layers and opt.quad_L and run steps 4 and 5 through the same two functions, which take a
+    scale factor [1, n] as diag(q) (kron_quad_diag.py, include/psgd_kron_quad_diag_hip.h): the format of an embedding table or
+    an LM head, whose long side cannot hold a dense factor.  Vector layers on either vector_route, [1, 1] layers and the formats
+    with a normalisation side stay on the triangular update.  state_dict() carries 'quad_diagonal' only when it is on, and
+    load_state_dict refuses a dict whose 'quad_diagonal' differs from this optimizer's.
+
     Out of scope: mixed dtypes with the switch off, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale),
     float16 stochastic rounding."""
 
@@ -417,7 +425,7 @@ class Kron(_psgd._StepFeatures):
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
                  any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM,
                  param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None,
-                 param_groups=None, mixed_dtypes=False, preconditioner_update="triangular"):
+                 param_groups=None, mixed_dtypes=False, preconditioner_update="triangular", quad_diagonal=False):
         _psgd._mixed_dtypes_switch("Kron", mixed_dtypes)
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
@@ -430,7 +438,10 @@ class Kron(_psgd._StepFeatures):
             raise ValueError("Kron: preconditioner_update='quad' fits the factors to the gradients: it needs preconditioner_fit='whitening'")
         if preconditioner_update == "quad" and self._operands is not None:
             raise ValueError("Kron: preconditioner_update='quad' runs on float32 operands; operands='bfloat16' is not supported with it")
-        self.preconditioner_update = preconditioner_update
+        if quad_diagonal and preconditioner_update != "quad":
+            raise ValueError("Kron: quad_diagonal=True extends preconditioner_update='quad' to layers with a scale side: it needs "
+                             "preconditioner_update='quad', got %r" % (preconditioner_update,))
+        self.preconditioner_update, self._quad_diagonal = preconditioner_update, bool(quad_diagonal)
         if vector_route not in ("list", "layer"):
             raise ValueError("Kron: vector_route must be 'list' or 'layer', got %r" % (vector_route,))
         any_rank = bool(any_rank)
@@ -495,10 +506,12 @@ class Kron(_psgd._StepFeatures):
         # of self._mat that keep the fp32 calls
         self._ops = kron_operand_layers(self._layer_shapes, self._formats, self._operands, self._operand_min_dim)
         self._f32 = [i for i in self._mat if i not in set(self._ops)]
-        # the quad layers (none with preconditioner_update="triangular"): the (dense, dense) matrix layers; each keeps its pair of
-        # Lipschitz estimates L, and leaves self._f32 for update_precond_kron_quad_ / precond_grad_kron_quad
+        # the quad layers (none with preconditioner_update="triangular"): the (dense, dense) matrix layers and, with quad_diagonal,
+        # those with one scale side; each keeps its pair of Lipschitz estimates L, and leaves self._f32 for
+        # update_precond_kron_quad_ / precond_grad_kron_quad
+        quad_formats = (("dense", "dense"),) + ((("dense", "scale"), ("scale", "dense")) if self._quad_diagonal else ())
         self._quad = [i for i in self._mat if preconditioner_update == "quad" and layers[i][0] == "matrix"
-                      and self._formats[i] == ("dense", "dense")]
+                      and self._formats[i] in quad_formats]
         self._quad_L = {i: torch.zeros(2, dtype=_f32, device=dev) for i in self._quad}
         self._f32 = [i for i in self._f32 if i not in set(self._quad)]
         self._op_plan, self._op_bufs = None, None
@@ -587,6 +600,8 @@ class Kron(_psgd._StepFeatures):
         if self._quad:
             sd["preconditioner_update"] = "quad"
             sd["quad_L"] = [self._quad_L[i].detach().to("cpu", copy=True) for i in self._quad]
+        if self._quad_diagonal:
+            sd["quad_diagonal"] = True
         return self._groups_encode(_probe_encode(sd, self._whiten, self._probe_seed0, self._probe_step))
 
     def load_state_dict(self, sd):
@@ -605,6 +620,9 @@ class Kron(_psgd._StepFeatures):
         sr_state = _psgd._param_rounding_decode("Kron.load_state_dict", sd, self._param_sr, self._param_round_seed0)
         probe_state = _probe_decode(sd, self._whiten, self._probe_seed0, "Kron.load_state_dict")
         group_values = self._groups_judge(sd, "Kron.load_state_dict")
+        if bool(sd.get("quad_diagonal", False)) != self._quad_diagonal:
+            raise ValueError("Kron.load_state_dict: 'quad_diagonal' of the state dict is %r, this optimizer's is %r"
+                             % (sd.get("quad_diagonal", False), self._quad_diagonal))
         quad_L = sd.get("quad_L") if self._quad else None
         if self._quad and (sd.get("preconditioner_update") != "quad" or not isinstance(quad_L, (list, tuple)) or len(quad_L) != len(self._quad)
                            or any(not isinstance(t, torch.Tensor) or t.dtype != _f32 or tuple(t.shape) != (2,) for t in quad_L)):

@@ -12,12 +12,17 @@ Lipschitz estimates L = [Ll, Lr].
 The three C entry points are bound here, in a signature table of this module's own, on the library _lib.load() returns.  fp32 on
 the HIP device only; no fallback.  class Kron(preconditioner_fit="whitening", preconditioner_update="quad") runs its
 (dense, dense) matrix layers through these two functions.
+
+One factor may be diagonal instead: a scale factor of shape [1, n], n >= 2, facing a square one sends both functions to
+kron_quad_diag.py (psgd_kron_qdiag.hip, include/psgd_kron_quad_diag_hip.h); kron_quad_initial_state(formats=("scale", "dense"))
+makes such a state.  Two scale factors are a ValueError.
 """
 import ctypes
 
 import torch
 
 from . import _lib
+from . import kron_quad_diag as _diag
 from . import preconditioned_stochastic_gradient_descent as _psgd
 
 KRON_QUAD_TILE = 64          # PSGD_KRON_QUAD_TILE: edge of the output tile one workgroup owns
@@ -69,18 +74,30 @@ def _workspace(device, M, N):
     return _psgd._workspace(("kron_quad",), device, "psgd_kron_quad_workspace_bytes", M, N)
 
 
-def kron_quad_initial_state(M, N, scale=1.0, device=None):
-    """(Ql, Qr, L) = (scale I [M, M], I [N, N], zeros(2)), float32"""
+def kron_quad_initial_state(M, N, scale=1.0, device=None, formats=("dense", "dense")):
+    """(Ql, Qr, L), float32: a "dense" side starts at I, a "scale" side at ones(1, n); the left factor is multiplied by scale;
+    L = zeros(2).  formats: ("dense", "dense"), ("scale", "dense") or ("dense", "scale")."""
     M, N = int(M), int(N)
     if M < 1 or N < 1:
         raise ValueError("kron_quad_initial_state: M and N must be >= 1, got %d and %d" % (M, N))
-    return (torch.eye(M, dtype=torch.float32, device=device) * float(scale), torch.eye(N, dtype=torch.float32, device=device),
-            torch.zeros(2, dtype=torch.float32, device=device))
+    formats = tuple(formats)
+    if formats not in (("dense", "dense"), ("scale", "dense"), ("dense", "scale")):
+        raise ValueError("kron_quad_initial_state: formats must be ('dense', 'dense'), ('scale', 'dense') or ('dense', 'scale'), got %r"
+                         % (formats,))
+    if "scale" in formats and (M, N)[formats.index("scale")] < 2:
+        raise ValueError("kron_quad_initial_state: a scale side has length >= 2 (a [1, 1] factor is a dense one), got %s" % ((M, N),))
+    make = lambda side, n: (torch.eye(n, dtype=torch.float32, device=device) if side == "dense"
+                            else torch.ones(1, n, dtype=torch.float32, device=device))
+    return make(formats[0], M) * float(scale), make(formats[1], N), torch.zeros(2, dtype=torch.float32, device=device)
 
 
 def precond_grad_kron_quad(Ql, Qr, G, out=None):
-    """out = Ql (Ql G Qr) Qr, four chained products.  out (made when None) must not be G, Ql or Qr."""
+    """out = Ql (Ql G Qr) Qr, four chained products.  out (made when None) must not be G, Ql or Qr.  With one scale factor
+    [1, n]: out = diag(ql o ql) ((G Qr) Qr) or its mirror, two launches (kron_quad_diag.py)."""
     G = _psgd._c(G)
+    side = _diag.diag_side("precond_grad_kron_quad", Ql, Qr)
+    if side is not None:
+        return _diag.apply(side, Ql, Qr, G, out)
     more = {} if out is None else {"out": (out, tuple(G.shape) if isinstance(G, torch.Tensor) else ())}
     dev, M, N = _operands("precond_grad_kron_quad", Ql, Qr, G, **more)
     if out is None:
@@ -93,8 +110,12 @@ def precond_grad_kron_quad(Ql, Qr, G, out=None):
 
 
 def update_precond_kron_quad_(Ql, Qr, L, G, step, decay=0.95):
-    """Ql, Qr, L <- the QUAD step on the gradient G, in place, six launches; the host reads nothing.  Returns None."""
+    """Ql, Qr, L <- the QUAD step on the gradient G, in place, six launches; the host reads nothing.  Returns None.  With one
+    scale factor [1, n] that side takes the diagonal rule (kron_quad_diag.py)."""
     G = _psgd._c(G)
+    side = _diag.diag_side("update_precond_kron_quad_", Ql, Qr)
+    if side is not None:
+        return _diag.update(side, Ql, Qr, L, G, step, decay)
     dev, M, N = _operands("update_precond_kron_quad_", Ql, Qr, G, L=(L, (2,)))
     ws = _workspace(dev, M, N)
     rc = load().psgd_kron_quad_update_f32(Ql.data_ptr(), Qr.data_ptr(), L.data_ptr(), G.data_ptr(), M, N, float(step), float(decay),
