@@ -19,6 +19,7 @@ import torch
 
 from . import kron as _kron
 from . import kron_quad as _quad
+from . import kron_quad_list as _qlist
 from . import preconditioned_stochastic_gradient_descent as _psgd
 from .multi_tail import MultiTailPlan, _lists, _f32, _TINY, _HALF, _MIXED, _DTYPE_NAMES  # noqa: F401
 from .multi_tail import multi_sumsq, multi_param_update, multi_diff_scale, multi_blend, multi_scale_check  # noqa: F401
@@ -416,6 +417,14 @@ class Kron(_psgd._StepFeatures):
     with a normalisation side stay on the triangular update.  state_dict() carries 'quad_diagonal' only when it is on, and
     load_state_dict refuses a dict whose 'quad_diagonal' differs from this optimizer's.
 
+    quad_route="layer" (keyword-only, the default: not a launch, a bit or a checkpoint byte changes) or "list" (a ValueError
+    without preconditioner_update="quad", like any other value, before a device is touched): with "list" all (dense, dense) quad
+    layers go through ONE KronQuadListPlan made at construction -- one update_precond_kron_quad_list_ call in step 4 and one
+    precond_grad_kron_quad_list call in step 5, six and four launches per group of layers instead of per layer
+    (kron_quad_list.py, include/psgd_kron_quad_list_hip.h).  The layers quad_diagonal=True brings in keep the per-layer calls.
+    Every layer's factors, L and preconditioned gradient have the bits of the "layer" route.  The route is not part of
+    state_dict(): a state saved under one route resumes under the other, bit-identically.
+
     Out of scope: mixed dtypes with the switch off, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale),
     float16 stochastic rounding."""
 
@@ -425,7 +434,7 @@ class Kron(_psgd._StepFeatures):
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
                  any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM,
                  param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None,
-                 param_groups=None, mixed_dtypes=False, preconditioner_update="triangular", quad_diagonal=False):
+                 param_groups=None, mixed_dtypes=False, preconditioner_update="triangular", quad_diagonal=False, quad_route="layer"):
         _psgd._mixed_dtypes_switch("Kron", mixed_dtypes)
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
@@ -442,6 +451,11 @@ class Kron(_psgd._StepFeatures):
             raise ValueError("Kron: quad_diagonal=True extends preconditioner_update='quad' to layers with a scale side: it needs "
                              "preconditioner_update='quad', got %r" % (preconditioner_update,))
         self.preconditioner_update, self._quad_diagonal = preconditioner_update, bool(quad_diagonal)
+        if quad_route not in ("layer", "list"):
+            raise ValueError("Kron: quad_route must be 'layer' or 'list', got %r" % (quad_route,))
+        if quad_route == "list" and preconditioner_update != "quad":
+            raise ValueError("Kron: quad_route='list' groups the launches of preconditioner_update='quad': it needs "
+                             "preconditioner_update='quad', got %r" % (preconditioner_update,))
         if vector_route not in ("list", "layer"):
             raise ValueError("Kron: vector_route must be 'list' or 'layer', got %r" % (vector_route,))
         any_rank = bool(any_rank)
@@ -514,6 +528,15 @@ class Kron(_psgd._StepFeatures):
                       and self._formats[i] in quad_formats]
         self._quad_L = {i: torch.zeros(2, dtype=_f32, device=dev) for i in self._quad}
         self._f32 = [i for i in self._f32 if i not in set(self._quad)]
+        # quad_route="list": the (dense, dense) quad layers share ONE plan (kron_quad_list.py), made here from their shapes, and the
+        # buffers their grouped apply writes, made once so that the pointers of its table never move; the quad layers with a scale
+        # side (quad_diagonal) stay in self._quad_layer, on the per-layer calls, like all of them with quad_route="layer"
+        self._quad_listed = [i for i in self._quad if quad_route == "list" and self._formats[i] == ("dense", "dense")]
+        self._quad_layer = [i for i in self._quad if i not in set(self._quad_listed)]
+        self._quad_plan, self._quad_out = None, None
+        if self._quad_listed:
+            self._quad_plan = _qlist.KronQuadListPlan([self._layer_shapes[i] for i in self._quad_listed], dev)
+            self._quad_out = [torch.empty(self._layer_shapes[i], dtype=_f32, device=dev) for i in self._quad_listed]
         self._op_plan, self._op_bufs = None, None
         self._vec_plan, self._vec_out = None, None
         if self._vec:
@@ -826,8 +849,12 @@ class Kron(_psgd._StepFeatures):
             bX, bG = self._narrow([[dXs[i] for i in ops], [dGs[i] for i in ops]], self._op_bufs and self._op_bufs[1:])
             for i, x, g in zip(ops, bX, bG):
                 Qs[i] = list(_psgd.update_precond_kron(Qs[i][0], Qs[i][1], x, g, lr_q))
-        for i in self._quad:                                # in place, outside the block; dG is the raw gradient, the probe unused
+        for i in self._quad_layer:                          # in place, outside the block; dG is the raw gradient, the probe unused
             _quad.update_precond_kron_quad_(Qs[i][0], Qs[i][1], self._quad_L[i], dGs[i], lr_q)
+        ql = self._quad_listed
+        if ql:                                              # quad_route="list": six launches per group of the plan, in place
+            _qlist.update_precond_kron_quad_list_([Qs[i][0] for i in ql], [Qs[i][1] for i in ql], [self._quad_L[i] for i in ql],
+                                                  [dGs[i].contiguous() for i in ql], lr_q, plan=self._quad_plan)
         if self._f32:
             with self._block():
                 new = [_psgd.update_precond_kron(Qs[i][0], Qs[i][1], dXs[i], dGs[i], lr_q) for i in self._f32]
@@ -862,8 +889,14 @@ class Kron(_psgd._StepFeatures):
             (bg,) = self._narrow([[grads[i] for i in ops]], self._op_bufs and self._op_bufs[:1])
             for i, g in zip(ops, bg):
                 pre[i] = _psgd.precond_grad_kron(Qs[i][0], Qs[i][1], g)
-        for i in self._quad:
+        for i in self._quad_layer:
             pre[i] = _quad.precond_grad_kron_quad(Qs[i][0], Qs[i][1], grads[i])
+        ql = self._quad_listed
+        if ql:
+            _qlist.precond_grad_kron_quad_list([Qs[i][0] for i in ql], [Qs[i][1] for i in ql], [grads[i].contiguous() for i in ql],
+                                               self._quad_out, plan=self._quad_plan)
+            for i, g in zip(ql, self._quad_out):
+                pre[i] = g
         if self._f32:
             with self._block():
                 out = [_psgd.precond_grad_kron(Qs[i][0], Qs[i][1], grads[i]) for i in self._f32]
