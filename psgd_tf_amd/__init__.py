@@ -10,6 +10,7 @@ Contents (only what the hot path needs):
   dense_optimizer.py                               class Dense
   xmat.py                                          the X-shaped / diagonal preconditioner (psgd_xmat.hip) and class XMat
   kron_quad.py                                     the inverse-free Kron whitening update on symmetric factors (psgd_kron_quad.hip)
+  kron_quad_x3.py                                  ... with its products on the bf16 matrix cores at fp32 grade (psgd_kron_quad_x3.hip)
   kron_quad_diag.py                                ... with one diagonal side, for embedding-scale layers (psgd_kron_qdiag.hip)
   multi_tail.py                                    the multi-tensor (list) kernels of its step tail as functions
   sharded.py                                       row-sharded multi-GPU UVd (torch.distributed / RCCL)

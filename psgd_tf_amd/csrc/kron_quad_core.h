@@ -312,12 +312,9 @@ struct StepSide {
   float t2;
 };
 
-// tile b (row-major over nb x nb) of P1 = Q - c (T Q - t2 Q)
-__device__ __forceinline__ void p1_tile(const StepSide& s, int b, float c1, float* lds) {
+// acc = the tile (m0, n0) of T Q: the tile of P1 = Q - c (T Q - t2 Q) is stored
+__device__ __forceinline__ void p1_store(const StepSide& s, float c1, int m0, int n0, const f32x4 (&acc)[2][2]) {
   const int n = s.n;
-  const int m0 = (b / s.nb) * kTile, n0 = (b % s.nb) * kTile;
-  f32x4 acc[2][2];
-  product(Opnd{s.T, n, 1, n}, Opnd{s.Q, 1, n, n}, n, m0, n0, lds, acc);
   each_elem([&](int i, int j, int e, int r, int c) {
     if (m0 + r < n && n0 + c < n) {
       const long at = (long)(m0 + r) * n + (n0 + c);
@@ -327,10 +324,18 @@ __device__ __forceinline__ void p1_tile(const StepSide& s, int b, float c1, floa
   });
 }
 
-// the tile (m0, n0) of P2 = P1 - c (P1 T - t2 P1), zero outside the matrix
-__device__ __forceinline__ void p2_tile(const StepSide& s, float c1, int m0, int n0, float* lds, f32x4 (&acc)[2][2]) {
+// tile b (row-major over nb x nb) of P1 = Q - c (T Q - t2 Q)
+__device__ __forceinline__ void p1_tile(const StepSide& s, int b, float c1, float* lds) {
   const int n = s.n;
-  product(Opnd{s.P1, n, 1, n}, Opnd{s.T, 1, n, n}, n, m0, n0, lds, acc);
+  const int m0 = (b / s.nb) * kTile, n0 = (b % s.nb) * kTile;
+  f32x4 acc[2][2];
+  product(Opnd{s.T, n, 1, n}, Opnd{s.Q, 1, n, n}, n, m0, n0, lds, acc);
+  p1_store(s, c1, m0, n0, acc);
+}
+
+// acc = the tile (m0, n0) of P1 T on entry, of P2 = P1 - c (P1 T - t2 P1) on return, zero outside the matrix
+__device__ __forceinline__ void p2_finish(const StepSide& s, float c1, int m0, int n0, f32x4 (&acc)[2][2]) {
+  const int n = s.n;
   each_elem([&](int i, int j, int e, int r, int c) {
     float v = 0.f;
     if (m0 + r < n && n0 + c < n) {
@@ -341,17 +346,17 @@ __device__ __forceinline__ void p2_tile(const StepSide& s, float c1, int m0, int
   });
 }
 
-// Q <- (P2 + P2') / 2 on upper tile u: P2 is formed on (ti, tj) AND on (tj, ti), the second transposed through LDS, the two
-// averaged, and both tiles of Q written -- Q[i,j] and Q[j,i] are one value written twice
-__device__ __forceinline__ void p2_sym_tiles(const StepSide& s, int u, float c1, float* lds) {
-  int ti, tj;
-  upper_tile(u, s.nb, ti, tj);
-  const int m0 = ti * kTile, n0 = tj * kTile;
-  const bool diag = ti == tj;
-  f32x4 up[2][2], lo[2][2];
-  p2_tile(s, c1, m0, n0, lds, up);
+// the tile (m0, n0) of P2
+__device__ __forceinline__ void p2_tile(const StepSide& s, float c1, int m0, int n0, float* lds, f32x4 (&acc)[2][2]) {
+  product(Opnd{s.P1, s.n, 1, s.n}, Opnd{s.T, 1, s.n, s.n}, s.n, m0, n0, lds, acc);
+  p2_finish(s, c1, m0, n0, acc);
+}
+
+// up = the tile (m0, n0) of P2, lo = the tile (n0, m0) (diag: not read): (up + lo') / 2, the transpose through LDS (free on
+// entry), is written to the tile (m0, n0) of Q and, off the diagonal, transposed to (n0, m0).  Ends without a barrier.
+__device__ __forceinline__ void p2_sym_store(const StepSide& s, int m0, int n0, bool diag, f32x4 (&up)[2][2], const f32x4 (&lo)[2][2],
+                                             float* lds) {
   if (!diag) {
-    p2_tile(s, c1, n0, m0, lds, lo);
     each_elem([&](int i, int j, int e, int r, int c) { lds[r * kSP + c] = lo[i][j][e]; });   // local (r, c) of tile (tj, ti)
   } else {
     each_elem([&](int i, int j, int e, int r, int c) { lds[r * kSP + c] = up[i][j][e]; });
@@ -363,6 +368,19 @@ __device__ __forceinline__ void p2_sym_tiles(const StepSide& s, int u, float c1,
   __syncthreads();
   store_tile(s.Q, s.n, m0, n0, lds, false, false);      // (a diagonal tile is symmetric already: a + b == b + a)
   if (!diag) store_tile(s.Q, s.n, m0, n0, lds, true, false);
+}
+
+// Q <- (P2 + P2') / 2 on upper tile u: P2 is formed on (ti, tj) AND on (tj, ti), the second transposed through LDS, the two
+// averaged, and both tiles of Q written -- Q[i,j] and Q[j,i] are one value written twice
+__device__ __forceinline__ void p2_sym_tiles(const StepSide& s, int u, float c1, float* lds) {
+  int ti, tj;
+  upper_tile(u, s.nb, ti, tj);
+  const int m0 = ti * kTile, n0 = tj * kTile;
+  const bool diag = ti == tj;
+  f32x4 up[2][2], lo[2][2];
+  p2_tile(s, c1, m0, n0, lds, up);
+  if (!diag) p2_tile(s, c1, n0, m0, lds, lo);
+  p2_sym_store(s, m0, n0, diag, up, lo, lds);
 }
 
 // --------------------------------------------------------------------------------------------------------------- the host

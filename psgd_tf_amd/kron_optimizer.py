@@ -20,6 +20,7 @@ import torch
 from . import kron as _kron
 from . import kron_quad as _quad
 from . import kron_quad_list as _qlist
+from . import kron_quad_x3 as _qx3
 from . import preconditioned_stochastic_gradient_descent as _psgd
 from .multi_tail import MultiTailPlan, _lists, _f32, _TINY, _HALF, _MIXED, _DTYPE_NAMES  # noqa: F401
 from .multi_tail import multi_sumsq, multi_param_update, multi_diff_scale, multi_blend, multi_scale_check  # noqa: F401
@@ -425,6 +426,16 @@ class Kron(_psgd._StepFeatures):
     Every layer's factors, L and preconditioned gradient have the bits of the "layer" route.  The route is not part of
     state_dict(): a state saved under one route resumes under the other, bit-identically.
 
+    quad_products="fp32" (keyword-only, the default: not a launch, a bit or a checkpoint byte changes) or "bf16x3" (any other
+    value, "bf16x3" without preconditioner_update="quad" and "bf16x3" with quad_route="list" are ValueErrors before a device is
+    touched): with "bf16x3" the (dense, dense) quad layers whose short side is >= quad_products_min_dim (opt.quad_x3_layers) run
+    steps 4 and 5 with products="bf16x3" -- every product on the bf16 matrix cores at fp32 grade (kron_quad_x3.py,
+    include/psgd_kron_quad_x3_hip.h).  Smaller layers and the layers quad_diagonal=True brings in stay on the fp32 per-layer
+    calls.  quad_products_min_dim defaults to kron_quad_x3.QUAD_X3_MIN_DIM, the smallest square size of
+    profiles/kron_quad_x3_timing.txt at which update + apply on the new route beat the fp32 route outside the spread.
+    state_dict() carries 'quad_products' only when it is not "fp32"; the state itself is route-independent and loads across
+    the switch.
+
     Out of scope: mixed dtypes with the switch off, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale),
     float16 stochastic rounding."""
 
@@ -434,7 +445,8 @@ class Kron(_psgd._StepFeatures):
                  momentum=0.0, weight_decay=0.0, nonfinite="propagate", loss_scale=None, loss_scale_growth_interval=2000,
                  any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM,
                  param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None,
-                 param_groups=None, mixed_dtypes=False, preconditioner_update="triangular", quad_diagonal=False, quad_route="layer"):
+                 param_groups=None, mixed_dtypes=False, preconditioner_update="triangular", quad_diagonal=False, quad_route="layer",
+                 quad_products="fp32", quad_products_min_dim=_qx3.QUAD_X3_MIN_DIM):
         _psgd._mixed_dtypes_switch("Kron", mixed_dtypes)
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
@@ -456,6 +468,14 @@ class Kron(_psgd._StepFeatures):
         if quad_route == "list" and preconditioner_update != "quad":
             raise ValueError("Kron: quad_route='list' groups the launches of preconditioner_update='quad': it needs "
                              "preconditioner_update='quad', got %r" % (preconditioner_update,))
+        if quad_products not in _qx3.PRODUCTS:
+            raise ValueError("Kron: quad_products must be 'fp32' or 'bf16x3', got %r" % (quad_products,))
+        if quad_products == "bf16x3" and preconditioner_update != "quad":
+            raise ValueError("Kron: quad_products='bf16x3' chooses the product core of preconditioner_update='quad': it needs "
+                             "preconditioner_update='quad', got %r" % (preconditioner_update,))
+        if quad_products == "bf16x3" and quad_route == "list":
+            raise ValueError("Kron: quad_products='bf16x3' runs per-layer calls; quad_route='list' (grouped launches) is fp32 only")
+        self._quad_products, self._quad_products_min_dim = quad_products, int(quad_products_min_dim)
         if vector_route not in ("list", "layer"):
             raise ValueError("Kron: vector_route must be 'list' or 'layer', got %r" % (vector_route,))
         any_rank = bool(any_rank)
@@ -533,6 +553,10 @@ class Kron(_psgd._StepFeatures):
         # side (quad_diagonal) stay in self._quad_layer, on the per-layer calls, like all of them with quad_route="layer"
         self._quad_listed = [i for i in self._quad if quad_route == "list" and self._formats[i] == ("dense", "dense")]
         self._quad_layer = [i for i in self._quad if i not in set(self._quad_listed)]
+        # quad_products="bf16x3": the (dense, dense) quad layers at or above the threshold take products="bf16x3" in both calls
+        self._quad_x3 = [i for i in self._quad_layer if self._quad_products == "bf16x3" and self._formats[i] == ("dense", "dense")
+                         and min(self._layer_shapes[i]) >= self._quad_products_min_dim]
+        self._quad_kw = {i: dict(products="bf16x3") if i in set(self._quad_x3) else {} for i in self._quad_layer}
         self._quad_plan, self._quad_out = None, None
         if self._quad_listed:
             self._quad_plan = _qlist.KronQuadListPlan([self._layer_shapes[i] for i in self._quad_listed], dev)
@@ -595,6 +619,11 @@ class Kron(_psgd._StepFeatures):
         return list(self._quad)
 
     @property
+    def quad_x3_layers(self):
+        """the indices (parameter order) of the quad layers that run products="bf16x3" (none with quad_products="fp32")"""
+        return list(self._quad_x3)
+
+    @property
     def quad_L(self):
         """{layer index: L}, L = [Ll, Lr] the float32 Lipschitz estimates of a quad layer, updated in place"""
         return self._quad_L
@@ -625,6 +654,8 @@ class Kron(_psgd._StepFeatures):
             sd["quad_L"] = [self._quad_L[i].detach().to("cpu", copy=True) for i in self._quad]
         if self._quad_diagonal:
             sd["quad_diagonal"] = True
+        if self._quad_products != "fp32":
+            sd["quad_products"] = self._quad_products
         return self._groups_encode(_probe_encode(sd, self._whiten, self._probe_seed0, self._probe_step))
 
     def load_state_dict(self, sd):
@@ -850,7 +881,7 @@ class Kron(_psgd._StepFeatures):
             for i, x, g in zip(ops, bX, bG):
                 Qs[i] = list(_psgd.update_precond_kron(Qs[i][0], Qs[i][1], x, g, lr_q))
         for i in self._quad_layer:                          # in place, outside the block; dG is the raw gradient, the probe unused
-            _quad.update_precond_kron_quad_(Qs[i][0], Qs[i][1], self._quad_L[i], dGs[i], lr_q)
+            _quad.update_precond_kron_quad_(Qs[i][0], Qs[i][1], self._quad_L[i], dGs[i], lr_q, **self._quad_kw[i])
         ql = self._quad_listed
         if ql:                                              # quad_route="list": six launches per group of the plan, in place
             _qlist.update_precond_kron_quad_list_([Qs[i][0] for i in ql], [Qs[i][1] for i in ql], [self._quad_L[i] for i in ql],
@@ -890,7 +921,7 @@ class Kron(_psgd._StepFeatures):
             for i, g in zip(ops, bg):
                 pre[i] = _psgd.precond_grad_kron(Qs[i][0], Qs[i][1], g)
         for i in self._quad_layer:
-            pre[i] = _quad.precond_grad_kron_quad(Qs[i][0], Qs[i][1], grads[i])
+            pre[i] = _quad.precond_grad_kron_quad(Qs[i][0], Qs[i][1], grads[i], **self._quad_kw[i])
         ql = self._quad_listed
         if ql:
             _qlist.precond_grad_kron_quad_list([Qs[i][0] for i in ql], [Qs[i][1] for i in ql], [grads[i].contiguous() for i in ql],

@@ -16,6 +16,10 @@ the HIP device only; no fallback.  class Kron(preconditioner_fit="whitening", pr
 One factor may be diagonal instead: a scale factor of shape [1, n], n >= 2, facing a square one sends both functions to
 kron_quad_diag.py (psgd_kron_qdiag.hip, include/psgd_kron_quad_diag_hip.h); kron_quad_initial_state(formats=("scale", "dense"))
 makes such a state.  Two scale factors are a ValueError.
+
+products="fp32" (the default: not a launch or a bit moves) or "bf16x3" on both functions: "bf16x3" sends (dense, dense) factors
+to kron_quad_x3.py (psgd_kron_quad_x3.hip, include/psgd_kron_quad_x3_hip.h): the same update with every product on the bf16 matrix
+cores at fp32 grade.  Any other value, and "bf16x3" with a scale factor, is a ValueError.
 """
 import ctypes
 
@@ -23,6 +27,7 @@ import torch
 
 from . import _lib
 from . import kron_quad_diag as _diag
+from . import kron_quad_x3 as _x3
 from . import preconditioned_stochastic_gradient_descent as _psgd
 
 KRON_QUAD_TILE = 64          # PSGD_KRON_QUAD_TILE: edge of the output tile one workgroup owns
@@ -91,13 +96,17 @@ def kron_quad_initial_state(M, N, scale=1.0, device=None, formats=("dense", "den
     return make(formats[0], M) * float(scale), make(formats[1], N), torch.zeros(2, dtype=torch.float32, device=device)
 
 
-def precond_grad_kron_quad(Ql, Qr, G, out=None):
+def precond_grad_kron_quad(Ql, Qr, G, out=None, products="fp32"):
     """out = Ql (Ql G Qr) Qr, four chained products.  out (made when None) must not be G, Ql or Qr.  With one scale factor
-    [1, n]: out = diag(ql o ql) ((G Qr) Qr) or its mirror, two launches (kron_quad_diag.py)."""
+    [1, n]: out = diag(ql o ql) ((G Qr) Qr) or its mirror, two launches (kron_quad_diag.py).  products="bf16x3": the four
+    products on the bf16 matrix cores at fp32 grade (kron_quad_x3.py), dense factors only."""
     G = _psgd._c(G)
     side = _diag.diag_side("precond_grad_kron_quad", Ql, Qr)
+    _x3.check_products("precond_grad_kron_quad", products, side)
     if side is not None:
         return _diag.apply(side, Ql, Qr, G, out)
+    if products == "bf16x3":
+        return _x3.apply(_operands, Ql, Qr, G, out)
     more = {} if out is None else {"out": (out, tuple(G.shape) if isinstance(G, torch.Tensor) else ())}
     dev, M, N = _operands("precond_grad_kron_quad", Ql, Qr, G, **more)
     if out is None:
@@ -109,13 +118,17 @@ def precond_grad_kron_quad(Ql, Qr, G, out=None):
     return out
 
 
-def update_precond_kron_quad_(Ql, Qr, L, G, step, decay=0.95):
+def update_precond_kron_quad_(Ql, Qr, L, G, step, decay=0.95, products="fp32"):
     """Ql, Qr, L <- the QUAD step on the gradient G, in place, six launches; the host reads nothing.  Returns None.  With one
-    scale factor [1, n] that side takes the diagonal rule (kron_quad_diag.py)."""
+    scale factor [1, n] that side takes the diagonal rule (kron_quad_diag.py).  products="bf16x3": every product on the bf16
+    matrix cores at fp32 grade (kron_quad_x3.py), dense factors only."""
     G = _psgd._c(G)
     side = _diag.diag_side("update_precond_kron_quad_", Ql, Qr)
+    _x3.check_products("update_precond_kron_quad_", products, side)
     if side is not None:
         return _diag.update(side, Ql, Qr, L, G, step, decay)
+    if products == "bf16x3":
+        return _x3.update(_operands, Ql, Qr, L, G, step, decay)
     dev, M, N = _operands("update_precond_kron_quad_", Ql, Qr, G, L=(L, (2,)))
     ws = _workspace(dev, M, N)
     rc = load().psgd_kron_quad_update_f32(Ql.data_ptr(), Qr.data_ptr(), L.data_ptr(), G.data_ptr(), M, N, float(step), float(decay),
