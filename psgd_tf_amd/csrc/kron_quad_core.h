@@ -127,6 +127,57 @@ __device__ __forceinline__ void product(const Opnd& a, const Opnd& b, int K, int
   }
 }
 
+// product() for operands of any two types that bring their own g2r() / r2s() overloads (found by argument type at the point of
+// instantiation): the same schedule, the same MFMA loop, the same K order.  With two Opnd it is product() itself; a unit with an
+// addressing that Opnd cannot express (psgd_kron_qnd.hip: a K index made of two tensor modes) defines the operand and its two
+// fetch halves and calls this.
+template <class OA, class OB>
+__device__ __forceinline__ void product_of(const OA& a, const OB& b, int K, int m0, int n0, float* lds, f32x4 (&acc)[2][2]) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wm = w >> 1, wn = w & 1;
+  float* LA = lds;
+  float* LB = lds + 2 * kGK * kPitch;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int nk = (K + kGK - 1) / kGK;
+  float ra[4], rb[4];
+  g2r(a, m0, 0, K, ra);
+  g2r(b, n0, 0, K, rb);
+  __syncthreads();
+  r2s(a, ra, LA);
+  r2s(b, rb, LB);
+  __syncthreads();
+  for (int t = 0; t < nk; ++t) {
+    const int buf = t & 1;
+    const bool more = t + 1 < nk;
+    if (more) {
+      g2r(a, m0, (t + 1) * kGK, K, ra);
+      g2r(b, n0, (t + 1) * kGK, K, rb);
+    }
+    const float* A = LA + buf * kGK * kPitch;
+    const float* B = LB + buf * kGK * kPitch;
+#pragma unroll
+    for (int kk = 0; kk < kGK / 4; ++kk) {
+      const int kr = kk * 4 + (lane >> 4);
+      float av[2], bv[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) av[i] = A[kr * kPitch + wm * 32 + i * 16 + (lane & 15)];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) bv[j] = B[kr * kPitch + wn * 32 + j * 16 + (lane & 15)];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+    }
+    if (more) {
+      r2s(a, ra, LA + (buf ^ 1) * kGK * kPitch);
+      r2s(b, rb, LB + (buf ^ 1) * kGK * kPitch);
+    }
+    __syncthreads();
+  }
+}
+
 // f(i, j, e, r, c) over this thread's 16 elements, (r, c) inside the tile
 template <class F>
 __device__ __forceinline__ void each_elem(F&& f) {

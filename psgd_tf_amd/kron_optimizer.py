@@ -20,6 +20,7 @@ import torch
 from . import kron as _kron
 from . import kron_quad as _quad
 from . import kron_quad_list as _qlist
+from . import kron_quad_nd as _qnd
 from . import kron_quad_x3 as _qx3
 from . import preconditioned_stochastic_gradient_descent as _psgd
 from .multi_tail import MultiTailPlan, _lists, _f32, _TINY, _HALF, _MIXED, _DTYPE_NAMES  # noqa: F401
@@ -114,7 +115,7 @@ def _factor_shape(side, n):
 VECTOR_FORMAT = ("dense", "scale")      # a vector of length n is the reference's [1, n] layer in this format (psgd.py:87-88, :129-130)
 
 
-def kron_layers(shapes, preconditioner_formats="dense", any_rank=False):
+def kron_layers(shapes, preconditioner_formats="dense", any_rank=False, quad_tensor=False):
     """How class Kron(any_rank=...) lays parameters of these shapes out as layers: one (kind, (M, N), (left, right)) per parameter.
         rank 2                     "matrix", the shape itself, the format asked for
         rank >= 3                  "matrix", (shape[0], prod(shape[1:])): the usual folding of a conv kernel
@@ -122,7 +123,10 @@ def kron_layers(shapes, preconditioner_formats="dense", any_rank=False):
         rank 0, rank 1 length 1    "scalar", (1, 1), ("dense", "dense"): a scaling side of length 1 does not exist
     One format given for all parameters applies to the matrix layers only.  In a per-parameter list the entry of a vector must be
     ("dense", "scale") or the default name "dense", that of a scalar ("dense", "dense") or "dense"; anything else is a ValueError
-    that names the parameter.  With any_rank off, or when every shape has rank 2, this is kron_formats on the shapes as they are."""
+    that names the parameter.  With any_rank off, or when every shape has rank 2, this is kron_formats on the shapes as they are.
+    quad_tensor=True (class Kron(quad_tensor=True); off by default: nothing changes): a parameter of rank >= 3 whose format is
+    ("dense", "dense") is a "tensor" layer instead, (kind, (A, B, C), format) with (A, B, C) = (shape[0], shape[1],
+    prod(shape[2:])): three dense factors, one per mode (kron_quad_nd.py)."""
     shapes = [tuple(int(n) for n in s) for s in shapes]
     k = len(shapes)
     if not any_rank or all(len(s) == 2 for s in shapes):
@@ -153,7 +157,11 @@ def kron_layers(shapes, preconditioner_formats="dense", any_rank=False):
     for i, (s, e) in enumerate(zip(shapes, entries)):
         if len(s) >= 2:
             shape2d = s if len(s) == 2 else (s[0], int(np.prod(s[1:], dtype=np.int64)))
-            out.append(("matrix", shape2d, matrix_pair if e is None else _format_pair(e, "Kron (parameter %d)" % i)))
+            pair = matrix_pair if e is None else _format_pair(e, "Kron (parameter %d)" % i)
+            if quad_tensor and len(s) >= 3 and pair == ("dense", "dense"):
+                out.append(("tensor", (s[0], s[1], int(np.prod(s[2:], dtype=np.int64))), pair))
+            else:
+                out.append(("matrix", shape2d, pair))
         elif len(s) == 1 and s[0] >= 2:
             out.append(("vector", (1, s[0]), fixed(i, e, "vector", VECTOR_FORMAT)))
         else:
@@ -242,7 +250,14 @@ def _decode_state(sd, formats, shapes, layer_shapes=None):
     factors = need("factors")
     if len(factors) != len(shapes):
         raise ValueError("%s: 'factors' holds %d pairs for %d parameters" % (name, len(factors), len(shapes)))
-    for i, (pair, fmt, (M, N)) in enumerate(zip(factors, formats, layer_shapes)):
+    for i, (pair, fmt, shape) in enumerate(zip(factors, formats, layer_shapes)):
+        if len(shape) == 3:                                  # a tensor layer (quad_tensor): three dense factors, one per mode
+            want = tuple((int(n), int(n)) for n in shape)
+            if len(pair) != 3 or any(not isinstance(q, torch.Tensor) or q.dtype != _f32 or tuple(q.shape) != w
+                                     for q, w in zip(pair, want)):
+                raise ValueError("%s: 'factors'[%d] must be three float32 tensors of shapes %s, %s and %s" % ((name, i) + want))
+            continue
+        M, N = shape
         want = (_factor_shape(fmt[0], M), _factor_shape(fmt[1], N))
         if len(pair) != 2 or any(not isinstance(q, torch.Tensor) or q.dtype != _f32 or tuple(q.shape) != w
                                  for q, w in zip(pair, want)):
@@ -436,6 +451,16 @@ class Kron(_psgd._StepFeatures):
     state_dict() carries 'quad_products' only when it is not "fp32"; the state itself is route-independent and loads across
     the switch.
 
+    quad_tensor=True (keyword-only; False by default: not a launch, a bit or a checkpoint byte changes; True without
+    preconditioner_update="quad" or without any_rank=True is a ValueError before a device is touched): every parameter of rank
+    >= 3 whose format is ("dense", "dense") is a TENSOR LAYER on the contiguous view [s0, s1, prod(s2:)] instead of the folded
+    matrix [s0, prod(s1:)]: three symmetric factors, one per mode (a conv kernel: output channels, input channels, filter taps),
+    three Lipschitz estimates in opt.quad_L, steps 4 and 5 through update_precond_kron_quad_nd_ and precond_grad_kron_quad_nd
+    (kron_quad_nd.py, include/psgd_kron_quad_nd_hip.h).  These layers are listed in opt.quad_layers and opt.quad_tensor_layers
+    and stay on per-layer calls: quad_route="list" and quad_products="bf16x3" concern the matrix layers only.  'factors' of
+    state_dict() holds three tensors for such a layer, and the dict carries 'quad_tensor' only when the switch is on;
+    load_state_dict refuses a dict whose 'quad_tensor' differs from this optimizer's.
+
     Out of scope: mixed dtypes with the switch off, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale),
     float16 stochastic rounding."""
 
@@ -446,7 +471,7 @@ class Kron(_psgd._StepFeatures):
                  any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM,
                  param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None,
                  param_groups=None, mixed_dtypes=False, preconditioner_update="triangular", quad_diagonal=False, quad_route="layer",
-                 quad_products="fp32", quad_products_min_dim=_qx3.QUAD_X3_MIN_DIM):
+                 quad_products="fp32", quad_products_min_dim=_qx3.QUAD_X3_MIN_DIM, quad_tensor=False):
         _psgd._mixed_dtypes_switch("Kron", mixed_dtypes)
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
@@ -479,6 +504,12 @@ class Kron(_psgd._StepFeatures):
         if vector_route not in ("list", "layer"):
             raise ValueError("Kron: vector_route must be 'list' or 'layer', got %r" % (vector_route,))
         any_rank = bool(any_rank)
+        if quad_tensor and preconditioner_update != "quad":
+            raise ValueError("Kron: quad_tensor=True gives the parameters of rank >= 3 one factor per mode under preconditioner_update="
+                             "'quad': it needs preconditioner_update='quad', got %r" % (preconditioner_update,))
+        if quad_tensor and not any_rank:
+            raise ValueError("Kron: quad_tensor=True concerns parameters of rank >= 3: it needs any_rank=True")
+        self._quad_tensor_on = bool(quad_tensor)
         # momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval: the switches of class UVd with their meaning
         # there (see step()); all off by default, and checked before anything touches a device
         self._init_features(momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval)
@@ -510,9 +541,9 @@ class Kron(_psgd._StepFeatures):
         self._params = params
         self._init_groups(param_groups)
         self._shapes = [tuple(int(s) for s in p.shape) for p in params]
-        layers = kron_layers(self._shapes, preconditioner_formats, any_rank)
+        layers = kron_layers(self._shapes, preconditioner_formats, any_rank, self._quad_tensor_on)
         self._formats = [f for _, _, f in layers]
-        # the (M, N) of every layer; _reshape: some parameter is not its own layer (any_rank), so what the preconditioner calls take
+        # the (M, N) of every layer ((A, B, C) of a tensor layer of quad_tensor); _reshape: some parameter is not its own layer (any_rank), so what the preconditioner calls take
         # and return is brought to the layers' shapes and back
         self._layer_shapes = [s for _, s, _ in layers]
         self._reshape = self._layer_shapes != self._shapes
@@ -530,8 +561,9 @@ class Kron(_psgd._StepFeatures):
         if self._mixed:           # one perturbation scale and one floor for all tensors: the largest over the dtypes present
             self._tiny, self._delta = _psgd.mixed_dtype_constants(self._dtypes)
             self._fd_inv = float(np.float32(1.0) / np.float32(self._delta))
-        self._Qs = [kron_initial_factors(s, f, preconditioner_init_scale, dev, "parameter %d" % i)
-                    for i, (s, f) in enumerate(zip(self._layer_shapes, self._formats))]
+        self._Qs = [_qnd.kron_quad_nd_initial_state(s, preconditioner_init_scale, dev)[0] if kind == "tensor"
+                    else kron_initial_factors(s, f, preconditioner_init_scale, dev, "parameter %d" % i)
+                    for i, (kind, s, f) in enumerate(layers)]
         # the vector layers of the list route (none with any_rank off or vector_route="layer") and all other layers; the applies of
         # the vectors write into buffers made once: the pointers of their table never move
         self._vec = [i for i, (kind, _, _) in enumerate(layers) if kind == "vector" and vector_route == "list"]
@@ -544,15 +576,19 @@ class Kron(_psgd._StepFeatures):
         # those with one scale side; each keeps its pair of Lipschitz estimates L, and leaves self._f32 for
         # update_precond_kron_quad_ / precond_grad_kron_quad
         quad_formats = (("dense", "dense"),) + ((("dense", "scale"), ("scale", "dense")) if self._quad_diagonal else ())
-        self._quad = [i for i in self._mat if preconditioner_update == "quad" and layers[i][0] == "matrix"
-                      and self._formats[i] in quad_formats]
-        self._quad_L = {i: torch.zeros(2, dtype=_f32, device=dev) for i in self._quad}
+        # quad_tensor: the tensor layers (rank >= 3, three factors, kron_quad_nd.py) are quad layers too, each with three estimates;
+        # they keep per-layer calls of their own, whatever quad_route and quad_products say of the matrix layers
+        self._quad_tensor = [i for i in self._mat if layers[i][0] == "tensor"]
+        self._quad = [i for i in self._mat if preconditioner_update == "quad" and (layers[i][0] == "tensor" or (
+            layers[i][0] == "matrix" and self._formats[i] in quad_formats))]
+        self._quad_L = {i: torch.zeros(3 if layers[i][0] == "tensor" else 2, dtype=_f32, device=dev) for i in self._quad}
         self._f32 = [i for i in self._f32 if i not in set(self._quad)]
         # quad_route="list": the (dense, dense) quad layers share ONE plan (kron_quad_list.py), made here from their shapes, and the
         # buffers their grouped apply writes, made once so that the pointers of its table never move; the quad layers with a scale
         # side (quad_diagonal) stay in self._quad_layer, on the per-layer calls, like all of them with quad_route="layer"
-        self._quad_listed = [i for i in self._quad if quad_route == "list" and self._formats[i] == ("dense", "dense")]
-        self._quad_layer = [i for i in self._quad if i not in set(self._quad_listed)]
+        self._quad_listed = [i for i in self._quad if quad_route == "list" and self._formats[i] == ("dense", "dense")
+                             and layers[i][0] == "matrix"]
+        self._quad_layer = [i for i in self._quad if i not in set(self._quad_listed) and layers[i][0] == "matrix"]
         # quad_products="bf16x3": the (dense, dense) quad layers at or above the threshold take products="bf16x3" in both calls
         self._quad_x3 = [i for i in self._quad_layer if self._quad_products == "bf16x3" and self._formats[i] == ("dense", "dense")
                          and min(self._layer_shapes[i]) >= self._quad_products_min_dim]
@@ -619,13 +655,20 @@ class Kron(_psgd._StepFeatures):
         return list(self._quad)
 
     @property
+    def quad_tensor_layers(self):
+        """the indices (parameter order) of the quad layers with three factors, one per mode of [s0, s1, prod(s2:)] (none with
+        quad_tensor=False)"""
+        return list(self._quad_tensor)
+
+    @property
     def quad_x3_layers(self):
         """the indices (parameter order) of the quad layers that run products="bf16x3" (none with quad_products="fp32")"""
         return list(self._quad_x3)
 
     @property
     def quad_L(self):
-        """{layer index: L}, L = [Ll, Lr] the float32 Lipschitz estimates of a quad layer, updated in place"""
+        """{layer index: L}, L = [Ll, Lr] ([La, Lb, Lc] of a tensor layer) the float32 Lipschitz estimates of a quad layer, updated in
+        place"""
         return self._quad_L
 
     @property
@@ -656,6 +699,8 @@ class Kron(_psgd._StepFeatures):
             sd["quad_diagonal"] = True
         if self._quad_products != "fp32":
             sd["quad_products"] = self._quad_products
+        if self._quad_tensor_on:
+            sd["quad_tensor"] = True
         return self._groups_encode(_probe_encode(sd, self._whiten, self._probe_seed0, self._probe_step))
 
     def load_state_dict(self, sd):
@@ -669,6 +714,9 @@ class Kron(_psgd._StepFeatures):
         leaves this object's seed and sets the counter to 0; a nearest optimizer ignores them.
         preconditioner_fit="whitening": probe_seed0 / probe_step likewise -- restored where the dict has them, this object's seed
         and a counter of 0 where it has not (a dict of a hessian-fit optimizer); a hessian-fit optimizer ignores them."""
+        if bool(sd.get("quad_tensor", False)) != self._quad_tensor_on:       # first: it decides how many factors a layer has
+            raise ValueError("Kron.load_state_dict: 'quad_tensor' of the state dict is %r, this optimizer's is %r"
+                             % (sd.get("quad_tensor", False), self._quad_tensor_on))
         factors, hyper, rng = _decode_state(sd, self._formats, self._shapes, self._layer_shapes)
         bufs, m_step = _decode_features(sd, self._shapes)
         sr_state = _psgd._param_rounding_decode("Kron.load_state_dict", sd, self._param_sr, self._param_round_seed0)
@@ -679,9 +727,11 @@ class Kron(_psgd._StepFeatures):
                              % (sd.get("quad_diagonal", False), self._quad_diagonal))
         quad_L = sd.get("quad_L") if self._quad else None
         if self._quad and (sd.get("preconditioner_update") != "quad" or not isinstance(quad_L, (list, tuple)) or len(quad_L) != len(self._quad)
-                           or any(not isinstance(t, torch.Tensor) or t.dtype != _f32 or tuple(t.shape) != (2,) for t in quad_L)):
+                           or any(not isinstance(t, torch.Tensor) or t.dtype != _f32 or tuple(t.shape) != tuple(self._quad_L[i].shape)
+                                  for i, t in zip(self._quad, quad_L))):
             raise ValueError("Kron.load_state_dict: this optimizer runs preconditioner_update='quad': the state dict must carry "
-                             "'preconditioner_update' == 'quad' and 'quad_L', one float32 tensor of shape (2,) per quad layer")
+                             "'preconditioner_update' == 'quad' and 'quad_L', one float32 tensor of shape (2,) per quad layer "
+                             "((3,) for a tensor layer of quad_tensor)")
         try:
             self._coin_generator().set_state(rng)
         except (RuntimeError, TypeError) as e:
@@ -882,6 +932,8 @@ class Kron(_psgd._StepFeatures):
                 Qs[i] = list(_psgd.update_precond_kron(Qs[i][0], Qs[i][1], x, g, lr_q))
         for i in self._quad_layer:                          # in place, outside the block; dG is the raw gradient, the probe unused
             _quad.update_precond_kron_quad_(Qs[i][0], Qs[i][1], self._quad_L[i], dGs[i], lr_q, **self._quad_kw[i])
+        for i in self._quad_tensor:                         # quad_tensor: three factors, seven launches, in place
+            _qnd.update_precond_kron_quad_nd_(Qs[i], self._quad_L[i], dGs[i], lr_q)
         ql = self._quad_listed
         if ql:                                              # quad_route="list": six launches per group of the plan, in place
             _qlist.update_precond_kron_quad_list_([Qs[i][0] for i in ql], [Qs[i][1] for i in ql], [self._quad_L[i] for i in ql],
@@ -922,6 +974,8 @@ class Kron(_psgd._StepFeatures):
                 pre[i] = _psgd.precond_grad_kron(Qs[i][0], Qs[i][1], g)
         for i in self._quad_layer:
             pre[i] = _quad.precond_grad_kron_quad(Qs[i][0], Qs[i][1], grads[i], **self._quad_kw[i])
+        for i in self._quad_tensor:
+            pre[i] = _qnd.precond_grad_kron_quad_nd(Qs[i], grads[i])
         ql = self._quad_listed
         if ql:
             _qlist.precond_grad_kron_quad_list([Qs[i][0] for i in ql], [Qs[i][1] for i in ql], [grads[i].contiguous() for i in ql],
