@@ -12,4 +12,5 @@ from psgd_tf_amd.preconditioned_stochastic_gradient_descent import (  # noqa: F4
     multi_narrow, kron_operand_layers, SPLU, splu_initial_factors, Dense, dense_initial_factor, XMat, xmat_initial_state, update_precond_Xmat_math_,
     precond_grad_Xmat_math, update_precond_grad_Xmat_math_, kron_quad_initial_state, update_precond_kron_quad_,
     precond_grad_kron_quad, KronQuadListPlan, update_precond_kron_quad_list_, precond_grad_kron_quad_list,
-    kron_quad_nd_initial_state, update_precond_kron_quad_nd_, precond_grad_kron_quad_nd)
+    kron_quad_nd_initial_state, update_precond_kron_quad_nd_, precond_grad_kron_quad_nd,
+    KronQuadTensorListPlan, update_precond_kron_quad_nd_list_, precond_grad_kron_quad_nd_list)

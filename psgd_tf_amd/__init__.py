@@ -13,6 +13,7 @@ Contents (only what the hot path needs):
   kron_quad_x3.py                                  ... with its products on the bf16 matrix cores at fp32 grade (psgd_kron_quad_x3.hip)
   kron_quad_diag.py                                ... with one diagonal side, for embedding-scale layers (psgd_kron_qdiag.hip)
   kron_quad_nd.py                                  ... on order-3 tensors with three symmetric factors (psgd_kron_qnd.hip)
+  kron_quad_nd_list.py                             ... on a list of them: grouped launches, a Gram split along K (psgd_kron_qtlist.hip)
   multi_tail.py                                    the multi-tensor (list) kernels of its step tail as functions
   sharded.py                                       row-sharded multi-GPU UVd (torch.distributed / RCCL)
 """

@@ -11,7 +11,7 @@
 //
 // Gram over the middle mode.  T_b[b, b'] = sum_{a, c} X[a, b, c] X[a, b', c]: the summed index is the PAIR (a, c), at address
 // a BC + c, which no (xs, ks) pair of an Opnd expresses, and a transposed copy of X would cost 8 A B C bytes of traffic and
-// 4 A B C bytes of workspace more.  SegOpnd is the operand with a SEGMENTED K: k -> (k / C) BC + (k % C), K = A C, a outer and
+// 4 A B C bytes of workspace more.  SegOpnd (kron_quad_seg.h) is the operand with a SEGMENTED K: k -> (k / C) BC + (k % C), K = A C, a outer and
 // c inner, so the order of the sum is that of the addresses.  Its fetch is the k-contiguous half of g2r(): thread t owns x = t & 63 and four consecutive k
 // from (t >> 6) 4; one integer division per thread and step gives (a, c) of the first, the other three follow by increment and
 // wrap.  When C % 4 == 0 and the base is 16-byte aligned, four consecutive k that start at a multiple of 4 lie in one segment
@@ -32,46 +32,8 @@
 // Determinism: no atomics; every output element and every partial has one writer, every fold a fixed order.
 #include <hip/hip_runtime.h>
 #include "kron_quad_core.h"
+#include "kron_quad_seg.h"
 #include "psgd_kron_quad_nd_hip.h"
-
-namespace psgdq {
-
-// an operand whose summed index runs over two tensor modes: element (x, k) = p[(k / C) BC + x C + (k % C)], x in [0, X)
-struct SegOpnd {
-  const float* p;
-  long BC;
-  int C, X;
-};
-
-// this thread's four elements of the step [x0, x0 + kTile) x [k0, k0 + kGK), zero outside [0, X) x [0, K): x = t & 63, four k
-// from (t >> 6) * 4, as the k-contiguous half of g2r(const Opnd&)
-__device__ __forceinline__ void g2r(const SegOpnd& o, int x0, int k0, int K, float (&r)[4]) {
-  const int t = threadIdx.x;
-  const int x = x0 + (t & 63), k = k0 + (t >> 6) * 4;
-  int a = k / o.C, c = k - a * o.C;
-  const bool wide = x0 + kTile <= o.X && k0 + kGK <= K && (o.C & 3) == 0 && (reinterpret_cast<uintptr_t>(o.p) & 15) == 0;
-  if (wide) {                                           // k % 4 == 0 and C % 4 == 0: one segment, a 16-byte aligned address
-    const f32x4 v = *reinterpret_cast<const f32x4*>(o.p + (long)a * o.BC + (long)x * o.C + c);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = v[e];
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      r[e] = (x < o.X && k + e < K) ? o.p[(long)a * o.BC + (long)x * o.C + c] : 0.f;
-      if (++c == o.C) {                                 // the next k opens the next slab
-        c = 0;
-        ++a;
-      }
-    }
-  }
-}
-__device__ __forceinline__ void r2s(const SegOpnd&, const float (&r)[4], float* S) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) S[((t >> 6) * 4 + e) * kPitch + (t & 63)] = r[e];
-}
-
-}  // namespace psgdq
 
 namespace psgdqn {
 using namespace psgdq;

@@ -21,6 +21,7 @@ from . import kron as _kron
 from . import kron_quad as _quad
 from . import kron_quad_list as _qlist
 from . import kron_quad_nd as _qnd
+from . import kron_quad_nd_list as _qtl
 from . import kron_quad_x3 as _qx3
 from . import preconditioned_stochastic_gradient_descent as _psgd
 from .multi_tail import MultiTailPlan, _lists, _f32, _TINY, _HALF, _MIXED, _DTYPE_NAMES  # noqa: F401
@@ -457,9 +458,20 @@ class Kron(_psgd._StepFeatures):
     matrix [s0, prod(s1:)]: three symmetric factors, one per mode (a conv kernel: output channels, input channels, filter taps),
     three Lipschitz estimates in opt.quad_L, steps 4 and 5 through update_precond_kron_quad_nd_ and precond_grad_kron_quad_nd
     (kron_quad_nd.py, include/psgd_kron_quad_nd_hip.h).  These layers are listed in opt.quad_layers and opt.quad_tensor_layers
-    and stay on per-layer calls: quad_route="list" and quad_products="bf16x3" concern the matrix layers only.  'factors' of
+    and stay on per-layer calls by default: quad_route="list" and quad_products="bf16x3" concern the matrix layers only (the
+    tensor layers have a list route of their own, quad_tensor_route below).  'factors' of
     state_dict() holds three tensors for such a layer, and the dict carries 'quad_tensor' only when the switch is on;
     load_state_dict refuses a dict whose 'quad_tensor' differs from this optimizer's.
+
+    quad_tensor_route="layer" (keyword-only, the default: not a launch, a bit or a checkpoint byte changes) or "list" (any other
+    value, and "list" without quad_tensor=True, are ValueErrors before a device is touched): with "list" all tensor layers go
+    through ONE KronQuadTensorListPlan made at construction -- one update_precond_kron_quad_nd_list_ call in step 4 and one
+    precond_grad_kron_quad_nd_list call in step 5, at most eight and six launches per group of layers instead of seven and six
+    per layer (kron_quad_nd_list.py, include/psgd_kron_quad_nd_list_hip.h).  The Gram of a side with few tiles and a long sum (the
+    filter-tap side of a wide conv kernel) is split along K and folded in fp64: such a side's T differs from the per-layer one by
+    the rounding of its sum; a layer without a split side (opt.quad_tensor_plan.slices) has the bits of the "layer" route, and
+    the preconditioned gradient always has.  The route is not part of state_dict(): a state saved under one route loads under
+    the other.  quad_route and quad_products keep their meaning for the matrix layers.
 
     Out of scope: mixed dtypes with the switch off, a narrow (bfloat16) factor state, a format for vectors other than the reference's (dense, scale),
     float16 stochastic rounding."""
@@ -471,7 +483,8 @@ class Kron(_psgd._StepFeatures):
                  any_rank=False, vector_route="list", operands=None, operand_min_dim=OPERAND_MIN_DIM,
                  param_rounding="nearest", param_rounding_seed=None, preconditioner_fit="hessian", probe_seed=None,
                  param_groups=None, mixed_dtypes=False, preconditioner_update="triangular", quad_diagonal=False, quad_route="layer",
-                 quad_products="fp32", quad_products_min_dim=_qx3.QUAD_X3_MIN_DIM, quad_tensor=False):
+                 quad_products="fp32", quad_products_min_dim=_qx3.QUAD_X3_MIN_DIM, quad_tensor=False,
+                 quad_tensor_route="layer"):
         _psgd._mixed_dtypes_switch("Kron", mixed_dtypes)
         if step_tail not in ("torch", "fused"):
             raise ValueError("Kron: step_tail must be 'torch' or 'fused', got %r" % (step_tail,))
@@ -510,6 +523,10 @@ class Kron(_psgd._StepFeatures):
         if quad_tensor and not any_rank:
             raise ValueError("Kron: quad_tensor=True concerns parameters of rank >= 3: it needs any_rank=True")
         self._quad_tensor_on = bool(quad_tensor)
+        if quad_tensor_route not in ("layer", "list"):
+            raise ValueError("Kron: quad_tensor_route must be 'layer' or 'list', got %r" % (quad_tensor_route,))
+        if quad_tensor_route == "list" and not quad_tensor:
+            raise ValueError("Kron: quad_tensor_route='list' groups the launches of the tensor layers: it needs quad_tensor=True")
         # momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval: the switches of class UVd with their meaning
         # there (see step()); all off by default, and checked before anything touches a device
         self._init_features(momentum, weight_decay, nonfinite, loss_scale, loss_scale_growth_interval)
@@ -593,6 +610,13 @@ class Kron(_psgd._StepFeatures):
         self._quad_x3 = [i for i in self._quad_layer if self._quad_products == "bf16x3" and self._formats[i] == ("dense", "dense")
                          and min(self._layer_shapes[i]) >= self._quad_products_min_dim]
         self._quad_kw = {i: dict(products="bf16x3") if i in set(self._quad_x3) else {} for i in self._quad_layer}
+        # quad_tensor_route="list": the tensor layers share ONE plan (kron_quad_nd_list.py) and the buffers its apply writes
+        self._quad_tensor_listed = self._quad_tensor if quad_tensor_route == "list" else []
+        self._quad_tensor_layer = [] if quad_tensor_route == "list" else self._quad_tensor
+        self._quad_tensor_plan, self._quad_tensor_out = None, None
+        if self._quad_tensor_listed:
+            self._quad_tensor_plan = _qtl.KronQuadTensorListPlan([self._layer_shapes[i] for i in self._quad_tensor_listed], dev)
+            self._quad_tensor_out = [torch.empty(self._layer_shapes[i], dtype=_f32, device=dev) for i in self._quad_tensor_listed]
         self._quad_plan, self._quad_out = None, None
         if self._quad_listed:
             self._quad_plan = _qlist.KronQuadListPlan([self._layer_shapes[i] for i in self._quad_listed], dev)
@@ -659,6 +683,11 @@ class Kron(_psgd._StepFeatures):
         """the indices (parameter order) of the quad layers with three factors, one per mode of [s0, s1, prod(s2:)] (none with
         quad_tensor=False)"""
         return list(self._quad_tensor)
+
+    @property
+    def quad_tensor_plan(self):
+        """the KronQuadTensorListPlan of the tensor layers (None with quad_tensor_route="layer")"""
+        return self._quad_tensor_plan
 
     @property
     def quad_x3_layers(self):
@@ -932,8 +961,12 @@ class Kron(_psgd._StepFeatures):
                 Qs[i] = list(_psgd.update_precond_kron(Qs[i][0], Qs[i][1], x, g, lr_q))
         for i in self._quad_layer:                          # in place, outside the block; dG is the raw gradient, the probe unused
             _quad.update_precond_kron_quad_(Qs[i][0], Qs[i][1], self._quad_L[i], dGs[i], lr_q, **self._quad_kw[i])
-        for i in self._quad_tensor:                         # quad_tensor: three factors, seven launches, in place
+        for i in self._quad_tensor_layer:                   # quad_tensor: three factors, seven launches, in place
             _qnd.update_precond_kron_quad_nd_(Qs[i], self._quad_L[i], dGs[i], lr_q)
+        tl = self._quad_tensor_listed
+        if tl:                                              # quad_tensor_route="list": eight launches per group, in place
+            _qtl.update_precond_kron_quad_nd_list_([Qs[i] for i in tl], [self._quad_L[i] for i in tl],
+                                                   [dGs[i].contiguous() for i in tl], lr_q, plan=self._quad_tensor_plan)
         ql = self._quad_listed
         if ql:                                              # quad_route="list": six launches per group of the plan, in place
             _qlist.update_precond_kron_quad_list_([Qs[i][0] for i in ql], [Qs[i][1] for i in ql], [self._quad_L[i] for i in ql],
@@ -974,8 +1007,14 @@ class Kron(_psgd._StepFeatures):
                 pre[i] = _psgd.precond_grad_kron(Qs[i][0], Qs[i][1], g)
         for i in self._quad_layer:
             pre[i] = _quad.precond_grad_kron_quad(Qs[i][0], Qs[i][1], grads[i], **self._quad_kw[i])
-        for i in self._quad_tensor:
+        for i in self._quad_tensor_layer:
             pre[i] = _qnd.precond_grad_kron_quad_nd(Qs[i], grads[i])
+        tl = self._quad_tensor_listed
+        if tl:
+            _qtl.precond_grad_kron_quad_nd_list([Qs[i] for i in tl], [grads[i].contiguous() for i in tl], self._quad_tensor_out,
+                                                plan=self._quad_tensor_plan)
+            for i, g in zip(tl, self._quad_tensor_out):
+                pre[i] = g
         ql = self._quad_listed
         if ql:
             _qlist.precond_grad_kron_quad_list([Qs[i][0] for i in ql], [Qs[i][1] for i in ql], [grads[i].contiguous() for i in ql],

@@ -2484,3 +2484,5 @@ from .xmat import update_precond_grad_Xmat_math_  # noqa: E402,F401
 from .kron_quad import kron_quad_initial_state, update_precond_kron_quad_, precond_grad_kron_quad  # noqa: E402,F401
 from .kron_quad_list import KronQuadListPlan, update_precond_kron_quad_list_, precond_grad_kron_quad_list  # noqa: E402,F401
 from .kron_quad_nd import kron_quad_nd_initial_state, update_precond_kron_quad_nd_, precond_grad_kron_quad_nd  # noqa: E402,F401
+from .kron_quad_nd_list import KronQuadTensorListPlan, update_precond_kron_quad_nd_list_  # noqa: E402,F401
+from .kron_quad_nd_list import precond_grad_kron_quad_nd_list  # noqa: E402,F401
